@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: field-elements committed per second, Ligero commit of 2^26 Ft255
 coefficients (rho = 1/2, BLAKE3), BASELINE.json's metric, on N MI355X of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1 without WORLD_SIZE: bench.py starts its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      (N > 1 without WORLD_SIZE: bench.py starts its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1, what the driver does)
 
 A "step" is one full commit (pad -> row NTTs -> column BLAKE3 -> Merkle tree, lcpc-2d/src/lib.rs:622-671) of
@@ -19,6 +19,8 @@ Timing protocol (mirroring rough_bench, lcpc-ligero-pc/src/tests.r
 the timed region; W warm-up steps; K steps between barrier + synchronize brackets give `value` / `ms_per_step` (mean);
 HIP events between the same steps give `min_ms_per_step`; afterwards, untimed: one instrumented step (kernel-group
 events), the end-to-end figure from host memory (`e2e_host`, PCIe-inclusive, never `value`) and the CPU baseline.
+`--dump-outputs DIR` writes the commitment of the last timed step right after the timed region (dump_outputs): the inputs are
+the same on every run, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -31,7 +33,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak
 
 
 def kernel_sources():
@@ -57,6 +59,46 @@ INPUT_SEED = 0              # ChaCha20Rng::from_seed([INPUT_SEED; 32]), stream 0
 def job_coeffs(enc, n):
     """the job's coefficient vector on the encoder's device: n x Field::random from the fixed generator (module docstring)"""
     return enc.random_coeffs_device(n, seed=INPUT_SEED)
+
+
+DUMP_SEED = 0x5EED          # the fixed sample of the commitment that --dump-outputs writes
+DUMP_MAX_HASHES, DUMP_ROWS, DUMP_COMM_COLS, DUMP_COEFF_COLS = 1 << 19, 64, 2048, 1024
+
+
+def words_f32(a):
+    """32-byte values (BLAKE3 digests as (n, 32) uint8, or Ft255 elements as (n, 4) uint64 Montgomery limbs) -> (n, 16) float32:
+    the 16 little-endian 16-bit words of each value, exact in float32"""
+    import numpy as np
+    return np.ascontiguousarray(a).view("<u2").astype(np.float32)
+
+
+def dump_sample(n, k, rng):
+    """k distinct indices of range(n) drawn by `rng`, sorted; all of them when n <= k"""
+    import numpy as np
+    return np.arange(n) if n <= k else np.sort(rng.choice(n, k, replace=False))
+
+
+def dump_outputs(cm, rows, out_dir):
+    """--dump-outputs: what a caller of LcCommit::commit receives from the last timed step -- root, hashes, comm, coeffs -- as
+    out_dir/<name>.npy (words_f32 of each digest / field element).  hashes whole up to DUMP_MAX_HASHES; comm and coeffs as a
+    seeded sample of `rows` x columns.  The sampled indices are written beside them (*_index, float64).  At most ~51 MB in all."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    cm._refresh()
+    h = cm.hashes()
+    hi = dump_sample(len(h), DUMP_MAX_HASHES, rng)
+    out = {"root": words_f32(np.frombuffer(cm.get_root(), np.uint8).reshape(1, 32))[0], "hashes": words_f32(h[hi]), "hashes_index": hi}
+    r = np.asarray(rows)[dump_sample(len(rows), DUMP_ROWS, rng)]
+    cc = dump_sample(cm.n_cols, DUMP_COMM_COLS, rng)
+    pc = dump_sample(cm.n_per_row, DUMP_COEFF_COLS, rng)
+    if len(r):
+        out["comm"] = np.stack([words_f32(cm.comm(int(i), 1)[cc]) for i in r])          # (rows, columns, 16)
+        out["coeffs"] = np.stack([words_f32(cm.coeffs(int(i), 1)[pc]) for i in r])
+        out.update(rows_index=r, comm_cols_index=cc, coeffs_cols_index=pc)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if name.endswith("_index") else np.float32))
+    return sorted(out)
 
 
 def sample_power(step, torch, seconds=1.6):
@@ -365,9 +407,13 @@ def main():
                     "exchange overlaps commit k + 1's encode)")
     ap.add_argument("--check", action="store_true", help="(always on for N > 1 since round 3; kept so that older command lines still parse)")
     ap.add_argument("--no-check", action="store_true", help="N > 1: skip the untimed comparison of the sharded root with an unsharded commit of the same data")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the commitment the last one computed "
+                    "(root, hashes, a seeded sample of comm and coeffs; rank 0's rows for N > 1) as DIR/<name>.npy, float32")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         return self_launch(args)
 
@@ -532,6 +578,10 @@ def main():
         t = torch.tensor([min_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         min_ms = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:         # before any later step refills the objects the timed loop left
+        dumped = dump_outputs(engines[turn[0]].cm if async_loop else cm, range(rb, re) if distributed else range(n_rows_total),
+                              args.dump_outputs)
 
     # N > 1, native exchange, untimed region: what ONE run must tell about scaling
     red_dev = dev if args.dist_backend == "nccl" else "cpu"
@@ -781,6 +831,8 @@ def main():
                          "DEBUG: ranks share devices (--dist-backend %s%s)" % (args.dist_backend, "" if args.force_device is None else ", --force-device %d" % args.force_device)
     if distributed and exchange_note:
         out["exchange_fallback"] = exchange_note
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped}
 
     cfg_pub, cfg_priv = None, {}
     if world == 1 and not args.no_configs:

@@ -54,6 +54,17 @@ def mk_transcript(T, root, n_col_opens):
     return tr
 
 
+def load_dump(d):
+    """the arrays `bench.py --dump-outputs d` wrote, by name"""
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d) if f.endswith(".npy")}
+
+
+def dump_bytes(words):
+    """bench.words_f32 undone: (..., 16) float32 words -> (..., 32) uint8 digests / Montgomery limbs"""
+    assert words.dtype == np.float32 and (words == np.round(words)).all() and words.min() >= 0 and words.max() < 65536
+    return np.ascontiguousarray(words.astype("<u2")).view(np.uint8)
+
+
 def commit_bincode(oc):
     """bincode 1.3 of WrappedLcCommit (lcpc-2d/src/lib.rs:186-197) built from a commitment's fields (oracle or HIP object with
     comm() / coeffs() / hashes() / n_rows / n_cols / n_per_row): Vec<F> = u64 len + raw Montgomery limbs; usize = u64;

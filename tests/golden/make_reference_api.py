@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """tests/golden/make_reference_api.py -> tests/golden/reference_api.json
 
-The public signatures of the reference items the Rust wrapper crate (bindings/rust/lcpc-hip) mirrors, parsed from
-/root/reference: for each item the argument NAMES and TYPES in order and the return type -- data about the API surface, no source
-text.  tests/test_rust_bindings.py compares the crate's functions with this table (and, where /root/reference is present, checks that
-the table is current).
+The public signatures of the reference items the Rust wrapper crate (bindings/rust/lcpc-hip) mirrors, parsed from a checkout of
+conroi/lcpc named by $LCPC_REFERENCE: for each item the argument NAMES and TYPES in order and the return type -- data about the API
+surface, no source text.  tests/test_rust_bindings.py compares the crate's functions with this table (and, where $LCPC_REFERENCE names
+a checkout, checks that the table is current).
+
+  LCPC_REFERENCE=<checkout of conroi/lcpc> python tests/golden/make_reference_api.py
 
   LcCommit::{commit, prove, get_root, get_n_rows, get_n_per_row, get_n_cols}      lcpc-2d/src/lib.rs:270-312
   LcEvalProof::verify                                                             lcpc-2d/src/lib.rs:518-527
@@ -17,7 +19,7 @@ import os
 import re
 import sys
 
-REF = "/root/reference"
+REF = os.environ.get("LCPC_REFERENCE", "")
 ITEMS = [
     ("lcpc-2d/src/lib.rs", "LcCommit", ["commit", "prove", "get_root", "get_n_rows", "get_n_per_row", "get_n_cols"]),
     ("lcpc-2d/src/lib.rs", "LcEvalProof", ["verify"]),
@@ -90,6 +92,8 @@ def build(root=REF):
 
 
 if __name__ == "__main__":
+    if not os.path.isdir(REF):
+        raise SystemExit("LCPC_REFERENCE must name a checkout of conroi/lcpc")
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_api.json")
     api = build()
     with open(out, "w") as f:        # one item per line

@@ -1,5 +1,5 @@
 """The generated shifted-multiples multipliers (lcpc_amd/csrc/gen/gen_wmul_asm.py -> field_wmul_gen.h: the multiply by a wave-uniform
-twiddle of the row NTT, /root/reference/lcpc-ligero-pc/src/lib.rs:162-164 butterflies) run as Python integers: the generator's own
+twiddle of the row NTT, the reference's lcpc-ligero-pc/src/lib.rs:162-164 butterflies) run as Python integers: the generator's own
 instruction list, interpreted with the instructions' 32 / 64-bit wrap-around, must give x * w (mod p), normalised limbs and a value
 inside wmul_bounds() for every admissible input shape of the four test fields (lcpc-test-fields/src/lib.rs:13-59).  CPU only."""
 import os

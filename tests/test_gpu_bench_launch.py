@@ -131,6 +131,34 @@ def test_bench_n1_json_contract():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_oracle_commitment(oracle, tmp_path):
+    """`--dump-outputs DIR` after K timed steps: the result line counts K steps, and what the last one computed -- root, hashes and
+    the sampled comm / coeffs entries -- is the oracle's commitment of the same seeded input, entry for entry"""
+    from common import dump_bytes, load_dump
+    import numpy as np
+    d = str(tmp_path / "out")
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log-len", "20", "--lean", "--dump-outputs", d])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dumped_outputs"]["dir"] == d
+    cfg = out["config"]
+    oc = oracle.Commit.commit(oracle.random_elems(3, 1 << 20, 0), oracle.Encoding.ligero_from_dims(3, cfg["n_per_row"], cfg["n_cols"]))
+    got = load_dump(d)
+    assert sorted(got) == out["dumped_outputs"]["names"]
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+    hi, rows, cc, pc = (got[k].astype(np.int64) for k in ("hashes_index", "rows_index", "comm_cols_index", "coeffs_cols_index"))
+    assert len(hi) == oc.n_hashes and len(rows) == oc.n_rows        # at 2^20 every hash and every row is written
+    assert dump_bytes(got["root"]).tobytes() == oc.get_root()
+    assert (dump_bytes(got["hashes"]) == oc.hashes()).all()
+    comm = oc.comm().view(np.uint8).reshape(oc.n_rows, oc.n_cols, 32)
+    coeffs = oc.coeffs().view(np.uint8).reshape(oc.n_rows, oc.n_per_row, 32)
+    assert (dump_bytes(got["comm"]) == comm[rows][:, cc]).all()
+    assert (dump_bytes(got["coeffs"]) == coeffs[rows][:, pc]).all()
+
+
+@pytest.mark.gpu
 def test_bench_refuses_more_ranks_than_devices():
     n = torch.cuda.device_count() + 1
     r = _run(["--gpus", str(n), "--steps", "1", "--warmup", "0", "--log-len", "20"], timeout=300)

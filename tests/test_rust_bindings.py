@@ -312,13 +312,13 @@ def test_wrapper_signatures_equal_reference():
     """every public function of lcpc-hip that stands in for a reference item takes the reference's arguments -- same names, same
     order, same types after the three documented substitutions -- and returns the reference's type (lcpc-2d/src/lib.rs:270-312,
     518-527; lcpc-ligero-pc/src/lib.rs:121-148; lcpc-brakedown-pc/src/lib.rs:103-137).  The reference side is the committed
-    table tests/golden/reference_api.json (made by tests/golden/make_reference_api.py); where /root/reference is present the
-    table itself is re-derived and must be current."""
+    table tests/golden/reference_api.json (made by tests/golden/make_reference_api.py); where $LCPC_REFERENCE names a checkout of
+    the reference the table itself is re-derived and must be current."""
     import json
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_api.json")))
     ours, M = crate_functions()
     if os.path.isdir(M.REF):
-        assert M.build() == ref, "tests/golden/reference_api.json is stale: python tests/golden/make_reference_api.py"
+        assert M.build() == ref, "tests/golden/reference_api.json is stale: LCPC_REFERENCE=... python tests/golden/make_reference_api.py"
     for item, key in MIRRORS.items():
         assert key in ours, "lcpc-hip has no %s::%s" % key
         r, o = ref[item], ours[key]

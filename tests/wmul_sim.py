@@ -1,5 +1,5 @@
 """tests/wmul_sim.py -- the generated shifted-multiples multipliers of lcpc_amd/csrc/gen/gen_wmul_asm.py (field_wmul_gen.h: the multiply by a
-wave-uniform twiddle in the row NTT kernels, the butterflies of /root/reference/lcpc-ligero-pc/src/lib.rs:162-164) as Python integers:
+wave-uniform twiddle in the row NTT kernels, the butterflies of the reference's lcpc-ligero-pc/src/lib.rs:162-164) as Python integers:
 simulate() interprets the generator's own instruction list with 32 / 64-bit wrap-around, shifted_multiples() builds the table the
 kernels read, wmul_bounds() is the proved range of the result.  Test infrastructure (tests/test_gen_wmul.py)."""
 import os

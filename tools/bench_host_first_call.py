@@ -2,7 +2,7 @@
 """tools/bench_host_first_call.py -- what an encoder's FIRST lcpc_commit from pageable memory costs beside the steady state (the pinned
 bounce ring is allocated as its buffers are first used), with LCPC_HOST_STAGE=1 (ring) and =0 (the runtime's own path).  profiles/r05_host_path.jsonl."""
 import os, sys, time, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from lcpc_amd import LcCommit, LigeroEncoding
 n = 1 << 26

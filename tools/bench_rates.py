@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(sys.path[0], "tools"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(sys.path[0], "tools"))
 import bench_configs as B
 from lcpc_amd import LigeroEncoding
 for rho in ((1, 2), (1, 4), (3, 4)):

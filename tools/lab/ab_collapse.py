@@ -1,7 +1,7 @@
 """tools/lab/ab_collapse.py -- eval_outer (collapse_columns of 1 and 2 tensors, lcpc-2d/src/lib.rs:1095-1123) at the headline shape on two
 builds of the library, interleaved: device-side timing with HIP events through lcpc_collapse_device"""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 child = r'''
 import os, sys, time, ctypes as C
 sys.path[:0] = [%r]

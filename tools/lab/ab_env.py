@@ -1,7 +1,7 @@
 """tools/lab/ab_env.py VAR v1 v2 ... [-- log_cols rows] -- the current library with an environment switch at several values, interleaved,
 three rounds, a child process per run (the switches are read when a context is created): root prefix and ms per commit."""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(R, "tools", "lab"))
 import ab_shapes_child as ch
 args = sys.argv[1:]

@@ -1,6 +1,6 @@
 """tools/lab/ab_field_libs.py fid log_len name=path ... -- several builds on one Ligero commit of another field, interleaved (child of ab_fields.py)"""
 import os, sys, subprocess, re
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = open(os.path.join(R, "tools/lab/ab_fields.py")).read()
 child = src[src.index("child = r'''") + len("child = r'''"):src.index("''' % R")] % R
 fid, lg = sys.argv[1], sys.argv[2]

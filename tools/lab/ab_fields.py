@@ -3,7 +3,7 @@ test fields (K1n) and on Ft255's general kernel (LCPC_NTT_GENERAL=1): a child pr
 tools/lab/base/liblcpc_hip.so is the baseline build, lcpc_amd/lib/liblcpc_hip.so the current one.  Prints root prefix, ms per commit,
 encode ms."""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 child = r'''
 import os, sys, time
 sys.path[:0] = [%r]

@@ -1,6 +1,6 @@
 """tools/lab/ab_hash.py -- hash_ms (column hash: leaf chunks + fold) and total of the headline commit on two builds, interleaved"""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 child = r'''
 import os, sys, time
 sys.path[:0] = [%r]

@@ -1,5 +1,5 @@
 import os, sys, subprocess, json
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 child = r'''
 import os, sys, time
 sys.path[:0] = [%r]

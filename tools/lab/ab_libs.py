@@ -1,6 +1,6 @@
 """tools/lab/ab_libs.py name=path ... [-- log_cols rows] -- several builds of the library on one box, interleaved, three rounds (child per run)"""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(R, "tools", "lab"))
 import ab_shapes_child as ch
 args = sys.argv[1:]

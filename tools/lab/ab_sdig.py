@@ -1,6 +1,6 @@
 """tools/lab/ab_sdig.py -- two builds of the library on the Brakedown commit of 2^24 Ft255 coefficients (C3), one box, interleaved"""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 child = r'''
 import os, sys, time
 sys.path[:0] = [%r]

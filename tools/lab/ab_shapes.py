@@ -1,7 +1,7 @@
 """tools/lab/ab_shapes.py -- two builds of the library against each other on one box, interleaved: a child process per (library,
 shape); tools/lab/base/liblcpc_hip.so is the baseline build (copy one there), lcpc_amd/lib/liblcpc_hip.so the current one."""
 import os, sys, subprocess
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(R, "tools", "lab"))
 import ab_shapes_child
 child = ab_shapes_child.CHILD % R

@@ -1,6 +1,6 @@
 """K1s against the shelved lane = row kernel K1u (tools/lab/README.md): run as a script on the GPU box, never collected by pytest."""
 import os, sys, time
-sys.path[:0] = [os.environ.get("GRAFT_REPO_ROOT", "/root/repo")]
+sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
 import numpy as np, torch
 from lcpc_amd import LcCommit, LigeroEncoding
 

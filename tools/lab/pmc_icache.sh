@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/lab/pmc_icache.sh TAG -- instruction-cache and scalar-cache counters of the two headline NTT kernels (own --pmc passes)
 TAG=${1:-x}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/pmc_icache_$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

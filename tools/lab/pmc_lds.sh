@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/lab/pmc_lds.sh TAG -- the LDS counters of the two headline NTT kernels (separate --pmc pass, nothing else traced)
 TAG=${1:-x}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/pmc_lds_$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

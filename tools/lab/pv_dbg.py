@@ -1,5 +1,5 @@
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [R]
 os.environ["LCPC_DEBUG_TIMING"] = "1"
 import numpy as np, torch

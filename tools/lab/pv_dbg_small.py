@@ -1,6 +1,6 @@
 """tools/lab/pv_dbg_small.py [log_len] -- prove / verify phase times (LCPC_DEBUG_TIMING) at a mid size, ten repetitions: where does the spread sit?"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [R]
 os.environ["LCPC_DEBUG_TIMING"] = "1"
 import torch, bench

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_fields_pmc.sh -- SQ counters of the small-field NTT passes (tools/bench_fields.py, Ligero only): where K1n's time goes
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/prof_fields
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

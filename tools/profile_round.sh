@@ -8,7 +8,7 @@
 #   bench_rs.jsonl, small_trace.txt   the other BASELINE.json configs, fields, the reference's loops and cargo-bench matrix, small commits
 # Run on the MI355X box:  gpurun -- 'bash tools/profile_round.sh r01f'
 TAG=${1:-latest}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/sample_clocks.sh -- sample sclk / power with rocm-smi while the headline bench loops (is the NTT clock- or power-limited?)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 python $R/bench.py --steps 1500 --warmup 2 --no-cpu-baseline > $R/gpurun_out/clk_bench.log 2>&1 &
 BP=$!
 while kill -0 $BP 2>/dev/null; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/ubench_power.sh -- run each instruction mix of ubench_power for a few seconds and sample clock / power meanwhile
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 for k in mad mad_sgpr mad29 mix alignbit add lds; do
   $R/tools/ubench_power $k 4 > /tmp/up_$k.txt &
   BP=$!
