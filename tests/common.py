@@ -95,3 +95,90 @@ def run_with_test_hooks(body, env=None, timeout=600):
     r = subprocess.run([sys.executable, "-c", pre + body], capture_output=True, text=True, env=e, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     return r.stdout
+
+
+# ---- worst-case operands and Python-int arithmetic of the lazy-reduction tests (test_lazy_bounds, test_gpu_lazy_worst,
+# test_gpu_fullsize) ------------------------------------------------------------------------------------------------------------------
+FIELD_L = {0: 1, 1: 2, 2: 3, 3: 4}
+
+
+def field_p(fid):
+    import pyref as P
+    return P.FIELDS[fid].p
+
+
+def maximal_limbs(fid, W, n_low):
+    """the largest element < p whose n_low low W-bit limbs are all 2^W - 1"""
+    p, s = field_p(fid), W * n_low
+    return ((p >> s) << s) - 1
+
+
+def maxc(fid):
+    """the stored coefficient that makes the collapse's products largest: Ft255 splits it into 29-bit limbs (fe_to29: eight low
+    limbs of 2^29 - 1), the other fields multiply 32-bit words (Wide<NL>: every word but the top one all ones)"""
+    return maximal_limbs(fid, 29, 8) if fid == 3 else maximal_limbs(fid, 32, 2 * FIELD_L[fid] - 1)
+
+
+def maxt(fid):
+    """the stored tensor entry whose multiplied form is maxc: for Ft255 the kernel multiplies t * 2^5 mod p (to_r29_kernel)"""
+    p = field_p(fid)
+    return maxc(fid) * pow(32, -1, p) % p if fid == 3 else maxc(fid)
+
+
+def ntt_maxlimb(fid):
+    """the largest element < p whose low limbs in the row NTT's limb form are all ones (l9: 9 x 29 bits; ln: 3 x 26, 5 / 7 x 29)"""
+    W, N = {0: (26, 3), 1: (29, 5), 2: (29, 7), 3: (29, 9)}[fid]
+    return maximal_limbs(fid, W, N - 1)
+
+
+def to_limbs(vals, L):
+    """python ints -> (n, L) uint64 limbs"""
+    return np.array([[(v >> (64 * k)) & ((1 << 64) - 1) for k in range(L)] for v in vals], np.uint64).reshape(-1, L)
+
+
+def to_int(limbs):
+    return sum(int(x) << (64 * k) for k, x in enumerate(limbs))
+
+
+def ntt_root(fid, log_n):
+    """w = ROOT_OF_UNITY^(2^(S - log n)) (oracle/lcpc_oracle.c lo_roots_table), as a plain residue"""
+    import pyref as P
+    F = P.FIELDS[fid]
+    return pow(F.root_of_unity, 1 << (F.S - log_n), F.p)
+
+
+def _butterflies(x, n, gap, w, p, inverse):
+    """one DIF stage of a length-n transform (gap = n >> (k + 1), twiddle w^((n / 2 gap) idx)) over the blocks of 2 gap in x"""
+    step = n // (2 * gap)
+    tw = [pow(w, step * i, p) for i in range(gap)]
+    if inverse:
+        tw = [pow(t, -1, p) for t in tw]
+        half = pow(2, -1, p)
+    for off in range(0, len(x), 2 * gap):
+        for i in range(gap):
+            a, b = x[off + i], x[off + i + gap]
+            if inverse:
+                d = b * tw[i] % p
+                x[off + i], x[off + i + gap] = (a + d) * half % p, (a - d) * half % p
+            else:
+                x[off + i], x[off + i + gap] = (a + b) % p, (a - b) * tw[i] % p
+
+
+def dif_stage(x, k, w, p, inverse=False):
+    """stage k of the row NTT's radix-2 DIF (oracle/lcpc_oracle.c fft_io_L: natural in, bit-reversed out), in place on a list of
+    residues of length n: gap = n >> (k + 1); in every block of 2 gap, lo' = lo + hi, hi' = (lo - hi) w^((n / 2 gap) idx).  The
+    stored (Montgomery) values transform the same way, the twiddles being plain residues.  inverse: undo that stage."""
+    _butterflies(x, len(x), len(x) >> (k + 1), w, p, inverse)
+    return x
+
+
+def row_with_stage_input(fid, log_n, s, pattern):
+    """the n/2 free entries x of a rate-1/2 row (x, 0) whose values entering DIF stage s equal `pattern` on the first half of the
+    row.  Stage 0 maps (x, 0) to (x, x w^i); stages 1 .. s-1 work in blocks of at most n/2, so the first half enters them as x and
+    never meets the second half again: running the inverse of stages s-1 .. 1 on the pattern gives x."""
+    p, n = field_p(fid), 1 << log_n
+    w = ntt_root(fid, log_n)
+    x = [pattern[i % len(pattern)] for i in range(n // 2)]
+    for k in range(s - 1, 0, -1):
+        _butterflies(x, n, n >> (k + 1), w, p, True)
+    return x

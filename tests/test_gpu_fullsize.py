@@ -30,16 +30,10 @@ from lcpc_amd import LcCommit, LigeroEncoding, SdigEncoding, Transcript
 pytestmark = pytest.mark.gpu
 
 
-def device_random_coeffs(fid, n, seed):
-    """uniform-ish field elements generated on the GPU (top limb masked below the modulus' top limb, so every
-    value is < p); returned as a torch int64 CUDA tensor viewed as (n, L) limbs."""
-    L = lcpc_amd.FIELD_LIMBS[fid]
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.randint(-(1 << 63), (1 << 63) - 1, (n, L), dtype=torch.int64, device="cuda", generator=g)
-    top_bits = {0: 62, 1: 62, 2: 62, 3: 62}[fid]      # all four moduli have their top limb >= 2^62
-    t[:, L - 1] &= (1 << top_bits) - 1
-    return t
+def device_random_coeffs(enc, n, seed):
+    """n uniform field elements over the whole of [0, p), generated on the GPU by Field::random (lcpc_random_coeffs_device, the
+    bench's generator); a torch int64 CUDA tensor viewed as (n, L) limbs."""
+    return enc.random_coeffs_device(n, seed)
 
 
 def host_memory_available():
@@ -100,7 +94,7 @@ def run_ligero_fullsize(O, log_len, rho, dims, linearity):
     enc = LigeroEncoding.new(fid, n, rho=rho)
     nr, npr, nc = enc.get_dims(n)
     assert (nr, npr, nc) == dims
-    coeffs = device_random_coeffs(fid, n, 5)
+    coeffs = device_random_coeffs(enc, n, 5)
     c = LcCommit.commit_device(coeffs.data_ptr(), n, enc, torch.cuda.current_stream().cuda_stream)
     oenc = O.Encoding.ligero_from_dims(fid, npr, nc, rho=rho)
     rows = {}
@@ -146,10 +140,7 @@ def run_ligero_fullsize(O, log_len, rho, dims, linearity):
     va, _ = c.open_columns(cols)
     ab = torch.empty((2, n, 4), dtype=torch.int64, device="cuda")
     ab[0].copy_(coeffs)
-    g = torch.Generator(device="cuda")
-    g.manual_seed(6)
-    ab[1].random_(-(1 << 63), (1 << 63) - 1, generator=g)
-    ab[1, :, 3] &= (1 << 62) - 1
+    enc.random_coeffs_device(n, 6, out_ptr=ab[1].data_ptr())
     total = torch.empty((n, 4), dtype=torch.int64, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     enc._check(lcpc_amd._lib.lib().lcpc_field_sum_device(enc._h, C.c_void_p(ab.data_ptr()), 2, n, C.c_void_p(st), C.c_void_p(total.data_ptr())))
@@ -187,7 +178,7 @@ def test_brakedown_ft255_2e24(oracle):
     enc = SdigEncoding.new(fid, n, 0)
     nr, npr, nc = enc.get_dims(n)
     assert (nr, npr, nc) == (101, 166292, 252931)
-    coeffs = device_random_coeffs(fid, n, 8)
+    coeffs = device_random_coeffs(enc, n, 8)
     c = LcCommit.commit_device(coeffs.data_ptr(), n, enc, torch.cuda.current_stream().cuda_stream)
     oenc = O.Encoding.sdig_from_dims(fid, npr, nc, 0, 3)
     rows = {}
@@ -227,7 +218,7 @@ def test_c4_fullsize_row_sharded_emulated(oracle):
     enc = LigeroEncoding.new(fid, n)
     nr, npr, nc = enc.get_dims(n)
     assert (nr, npr, nc) == (1024, 262144, 524288)
-    coeffs = device_random_coeffs(fid, n, 9)
+    coeffs = device_random_coeffs(enc, n, 9)
     ref = LcCommit.commit_device(coeffs.data_ptr(), n, enc, torch.cuda.current_stream().cuda_stream, borrow=True)
     root, hashes = ref.get_root(), ref.hashes().copy()
     del ref, enc
@@ -242,3 +233,36 @@ def test_c4_fullsize_row_sharded_emulated(oracle):
         n_rows_seen = re
         assert (eng.cm.hashes() == hashes).all(), "rank %d" % g
     assert n_rows_seen == nr
+
+
+def test_ligero_ft255_2e26_maximal_operands(oracle):
+    """The headline shape (2^26 Ft255 Ligero, 512 x 131072 -> 262144) with every coefficient the maximal stored pattern MAXC, the
+    largest value < p whose eight low 29-bit limbs are all 2^29 - 1: every product of the row NTT's first round and of the collapse
+    (collapse29_kernel at 1 split of 512 rows: lazy29 REDC chunks of 60 rows, normalise every 6) is at its largest.  Whole tree ==
+    the oracle's commit; eval_outer of the tensor whose 2^261 form is MAXC == the Python-int sum 512 * t * MAXC / R mod p in every
+    column; the proof bytes == the oracle prover's."""
+    import pyref as P
+    from common import maxc, maxt, to_int
+    O, fid = oracle, 3
+    p = P.FIELDS[fid].p
+    n = 1 << 26
+    enc = LigeroEncoding.new(fid, n)
+    nr, npr, nc = enc.get_dims(n)
+    assert (nr, npr, nc) == (512, 131072, 262144)
+    limbs = [(maxc(fid) >> (64 * k)) & ((1 << 64) - 1) for k in range(4)]
+    row = torch.tensor(np.array(limbs, np.uint64).view(np.int64), device="cuda")
+    coeffs = row.expand(n, 4).contiguous()
+    c = LcCommit.commit_device(coeffs.data_ptr(), n, enc, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    oenc = O.Encoding.ligero_from_dims(fid, npr, nc)
+    oc = check_whole_tree(O, c, coeffs, oenc)
+    t = np.array([[(maxt(fid) >> (64 * k)) & ((1 << 64) - 1) for k in range(4)]] * nr, np.uint64)
+    poly = c.eval_outer(t)
+    want = nr * maxt(fid) * maxc(fid) * pow(1 << 256, -1, p) % p
+    assert to_int(poly[0]) == want
+    assert (poly == poly[0]).all()
+    root = c.get_root()
+    pf = c.prove(t, enc, mk_transcript(Transcript, root, enc.get_n_col_opens()))
+    opf, _ = oc.prove(t, oenc, mk_transcript(O.Transcript, root, oenc.get_n_col_opens()))
+    assert pf.to_bytes() == opf
+    del oc, opf
