@@ -20,9 +20,9 @@ void ctx_ref(lcpc_ctx* c) { c->refs.fetch_add(1); }
 static void ctx_free(lcpc_ctx* c) {
   (void)hipSetDevice(c->prm.device);
   comm_release(c);
-  dev_free(c->d_wq_w);
-  dev_free(c->d_pack[0]); dev_free(c->d_pack[1]); dev_free(c->d_pack[2]); dev_free(c->d_roots29s); dev_free(c->d_roots29cs); dev_free(c->d_rootsls); dev_free(c->d_rootslcs);
-  dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_roots); dev_free(c->d_roots29); dev_free(c->d_roots29c); dev_free(c->d_qp29); dev_free(c->d_r2);
+  for (const NttStep& s : c->ntt) dev_free(s.pack);
+  dev_free(c->d_wq_w); dev_free(c->d_rootsls); dev_free(c->d_rootslcs);
+  dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_roots); dev_free(c->d_r2);
   dev_free(c->ws.d_tmp); dev_free(c->ws.d_t); dev_free(c->ws.d_mid); dev_free(c->d_scratch);
   if (c->h_varena) (void)hipHostFree(c->h_varena);
   for (unsigned k = 0; k < lcpc_ctx::N_STAGE; k++) {
@@ -45,7 +45,7 @@ void ctx_unref(lcpc_ctx* c) {
 // LCPC_NTT_MID_MAX_MB=<MiB> forces it for every shape within that budget (A/B, tests), =0 turns it off.
 uint64_t ntt_mid_rows(const lcpc_ctx* c, uint64_t n_rows) {
   const bool ev = c->sw_ntt_mid_max_mb >= 0;                    // (read when the context was created)
-  if (!c->l9s || n_rows == 0) return 0;
+  if (c->ntt.size() != 2 || c->ntt[0].kernel != NttStep::K1S || n_rows == 0) return 0;
   if (!ev && c->log_n > 15) return 0;
   const uint64_t max_mb = ev ? (uint64_t)c->sw_ntt_mid_max_mb : 6144;
   if (max_mb == 0) return 0;
@@ -101,7 +101,47 @@ static int build_wq_w(lcpc_ctx* c, int N, int W) {
   return 0;
 }
 
+// the lazy-limb form of the context's field: N limbs of W bits, `stride` words per table entry (field_dev.h l9 / field_ln.h)
+struct LimbForm { int N, W, stride; };
+static LimbForm limb_form(const lcpc_ctx* c) {
+  if (c->L == 4) return {9, 29, 12};
+  return {ntt_lns_limbs(c->NL), ntt_lns_limb_bits(c->NL), ntt_lns_stride(c->NL)};
+}
+// (i - 24) * p for i < 64 as normalised signed limbs of the form (limbs 0..N-2 in [0, 2^W), the top limb two's complement): the
+// table behind l9::clamp / ln::clamp_* (QOFF in field_dev.h)
+static std::vector<uint32_t> clamp_table(const FieldDesc& f, const LimbForm& lf) {
+  std::vector<uint32_t> tab((size_t)64 * lf.stride, 0);
+  for (int i = 0; i < 64; i++) {
+    const int q = i - 24;
+    uint64_t mag[5] = {0, 0, 0, 0, 0};                      // |q| * p
+    unsigned __int128 cy = 0;
+    for (int w = 0; w < 5; w++) { cy += (unsigned __int128)(w < f.L ? f.p[w] : 0) * (uint64_t)(q < 0 ? -q : q); mag[w] = (uint64_t)cy; cy >>= 64; }
+    if (q < 0) {                                            // two's complement over 320 bits
+      unsigned __int128 c2 = 1;
+      for (int w = 0; w < 5; w++) { c2 += (unsigned __int128)(~mag[w]); mag[w] = (uint64_t)c2; c2 >>= 64; }
+    }
+    for (int l = 0; l < lf.N; l++) {
+      const int b = lf.W * l, w = b / 64, sh = b % 64;
+      uint64_t x = mag[w] >> sh;
+      if (sh && w + 1 < 5) x |= mag[w + 1] << (64 - sh);
+      tab[(size_t)i * lf.stride + l] = l + 1 < lf.N ? (uint32_t)(x & (((uint64_t)1 << lf.W) - 1)) : (uint32_t)x;   // top limb: sign-extended
+    }
+  }
+  return tab;
+}
+// d_qpl and d_wq_w in the context's limb form; `made` (may be null) collects the allocations
+static int limb_consts(lcpc_ctx* c, std::vector<uint32_t**>* made) {
+  const LimbForm lf = limb_form(c);
+  const std::vector<uint32_t> tab = clamp_table(*c->f, lf);
+  if (made) { made->push_back(&c->d_qpl); made->push_back(&c->d_wq_w); }
+  if (int rc = dev_alloc(&c->err, &c->d_qpl, tab.size() * 4)) return rc;
+  HIPCHK(c, hipMemcpy(c->d_qpl, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  return build_wq_w(c, lf.N, lf.W);
+}
+
 // ---- NTT pass plan (DESIGN.md "K1") ----------------------------------------------------------------
+// the general kernel's passes.  They read the lazy-limb tables that exist when this runs: Ft255's (non-null qp29 selects
+// ntt_pass_l9_kernel); none for the other fields, whose tables are made only with their K1n plan (build_limb_plan)
 static void plan_passes(lcpc_ctx* c) {
   const unsigned k = c->log_n;
   const int NL = c->NL;
@@ -109,19 +149,30 @@ static void plan_passes(lcpc_ctx* c) {
   const int lt_big = NL >= 6 ? 11 : 12;
   unsigned ltj_min = 0;                                          // >= 128 B contiguous runs in strided passes
   while (((size_t)NL * 4 << ltj_min) < 128) ltj_min++;
-  c->passes.clear();
+  c->ntt.clear();
+  auto add = [&](unsigned t0, unsigned s, unsigned log_tj, int lt) {
+    NttStep p;
+    p.log_tile = lt;
+    p.a.roots = c->d_roots; p.a.roots29 = c->d_rootsl; p.a.qp29 = c->d_qpl; p.a.wq_w = c->d_wq_w;
+    p.a.log_n = k; p.a.t0 = t0; p.a.s = s; p.a.log_tj = log_tj;
+    p.roots29c = c->d_rootslc;
+    // the trailing stages multiply by 1 only: a final radix-4 round leaves 4 elements per row unconverted, a final
+    // radix-2 stage 2 (ntt_pass_l9_kernel)
+    p.mont_prefix = t0 + s == k ? (k == 0 ? 1u : (s % 2 == 0 ? 4u : 2u)) : 0u;
+    c->ntt.push_back(p);
+  };
   if ((int)k <= lt_small) {
-    c->passes.push_back({0, k, 0, lt_small});
+    add(0, k, 0, lt_small);
     return;
   }
   int LT = lt_small;
   auto n_pass = [&](int lt) { unsigned per = lt - ltj_min, rest = k - lt; return 1 + (rest + per - 1) / per; };
-  if (c->d_qp29 && (k == 19 || k == 20) && !c->sw_ntt_general) {
+  if (c->L == 4 && (k == 19 || k == 20) && !c->sw_ntt_general) {
     // Ft255, 2^19 / 2^20 columns (C4's shape): still two passes on 1024-element tiles for the shape-specialised kernel,
     // whose first pass then moves 64- / 32-byte runs -- affordable because the tiles that share those cache lines run back
-    // to back on one XCD (ntt_tile_group below; measured: DESIGN.md section 4 K1s)
-    c->passes.push_back({0, k - 10, 20 - k, 10});
-    c->passes.push_back({k - 10, 10, 0u, 10});
+    // to back on one XCD (ntt_tile_group_of below; measured: DESIGN.md section 4 K1s)
+    add(0, k - 10, 20 - k, 10);
+    add(k - 10, 10, 0u, 10);
     return;
   }
   if (n_pass(lt_small) > 2 && n_pass(lt_big) < n_pass(lt_small)) LT = lt_big;
@@ -131,11 +182,11 @@ static void plan_passes(lcpc_ctx* c) {
   for (unsigned i = 0; i + 1 < P; i++) {
     const unsigned left = P - 1 - i;
     const unsigned s = (rem + left - 1) / left;
-    c->passes.push_back({t0, s, (uint32_t)LT - s, LT});
+    add(t0, s, (uint32_t)LT - s, LT);
     t0 += s;
     rem -= s;
   }
-  c->passes.push_back({t0, s_final, 0u, LT});
+  add(t0, s_final, 0u, LT);
 }
 
 // first pass of the shape-specialised two-pass kernels: how many neighbouring tiles of a row (log2) run as consecutive
@@ -150,13 +201,124 @@ static uint32_t ntt_tile_group_of(uint32_t log_n, int L, uint32_t log_tj) {
   uint32_t lg = run_log <= 5 ? 11 - run_log : (run_log < 10 ? 10 - run_log : 0);
   return std::min(std::min(lg, 6u), tiles_log - 3);
 }
-static uint32_t ntt_tile_group(const lcpc_ctx* c, const Pass& first) { return ntt_tile_group_of(c->log_n, c->L, first.log_tj); }
+
+// The lazy-limb plan of n_pass passes on 1024-element tiles: K1s (Ft255) or K1n (the other fields).  Two passes: s0 = log_n - 10
+// stages, then 10.  Three (2^21 .. 2^26 columns): s0 = log_n - 20 stages with the first-pass kernel over the whole rows (zero
+// padding, ragged tail and the coeffs copy live there), then every row is 2^s0 independent 2^20-point transforms: the two-pass
+// plan on n_rows << s0 sub-rows, in place, with sub-sampled tables.  Canonical output: after the first pass only sub-row 0 of
+// each row still holds never-multiplied elements ("block 0"), so only those sub-rows take the converting twiddles.
+// If the device cannot hold the tables (the first pack of a three-pass plan is ~2.3 x one row: 4.9 GB at 2^26 columns), everything
+// made here is freed and the general kernel's plan stays -- slower, not an error.  Ft255's d_rootsl / d_rootslc / d_qpl / d_wq_w
+// were made with d_roots and belong to that plan as well.
+static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
+  std::vector<uint32_t**> made;                                // what this function allocated
+  std::vector<NttStep> plan(n_pass);
+  const int rc = [&]() -> int {
+    const FieldDesc* f = c->f;
+    std::string* err = &c->err;
+    const bool k1s = c->L == 4;
+    const unsigned k = c->log_n, s0 = k - 10 * (n_pass - 1);
+    const LimbForm lf = limb_form(c);
+    auto alloc = [&](uint32_t** p, size_t bytes) { made.push_back(p); return dev_alloc(err, p, bytes); };
+    int r;
+    if (!k1s) {
+      // w^i R' mod p and w^i R' R^-1 = mont_mul(w^i R, R' R^-1) from d_roots, with R' = 2^(N W) mod p (a plain integer)
+      uint64_t rp[2 * MAXL] = {1, 0, 0, 0};                    // R', then R' R^-1
+      for (int i = 0; i < lf.N * lf.W; i++) h_add(*f, rp, rp, rp);
+      h_canon(*f, rp + f->L, rp);
+      const size_t n_roots = (size_t)1 << (k - 1);
+      uint32_t* d_rp = nullptr;
+      if ((r = dev_alloc(err, &d_rp, 16 * f->L))) return r;
+      if ((r = alloc(&c->d_rootsl, n_roots * lf.stride * 4)) || (r = alloc(&c->d_rootslc, n_roots * lf.stride * 4))) { dev_free(d_rp); return r; }
+      hipError_t he = hipMemcpy(d_rp, rp, 16 * f->L, hipMemcpyHostToDevice);
+      if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rp, c->d_rootsl, nullptr);
+      if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rp + 2 * f->L, c->d_rootslc, nullptr);
+      if (he == hipSuccess) he = hipDeviceSynchronize();
+      dev_free(d_rp);
+      if (he != hipSuccess) return fail_hip(err, he, "ntt_lns tables");
+      if ((r = limb_consts(c, &made))) return r;
+    }
+    if (n_pass == 3) {
+      const size_t n_sub = (size_t)1 << 19;
+      if ((r = alloc(&c->d_rootsls, n_sub * lf.stride * 4)) || (r = alloc(&c->d_rootslcs, n_sub * lf.stride * 4))) return r;
+      for (int i = 0; i < 2; i++) {
+        const uint32_t* tab = i ? c->d_rootslc : c->d_rootsl;
+        uint32_t* sub = i ? c->d_rootslcs : c->d_rootsls;
+        HIPCHK(c, k1s ? launch_ntt_l9s_subtable(tab, s0, n_sub, sub, nullptr) : launch_ntt_lns_subtable(c->NL, tab, s0, n_sub, sub, nullptr));
+      }
+    }
+    for (unsigned i = 0; i < n_pass; i++) {
+      NttStep& p = plan[i];
+      const bool sub = n_pass == 3 && i > 0, last = i + 1 == n_pass;   // sub: a pass of the 2^20-point transforms
+      p.kernel = k1s ? NttStep::K1S : NttStep::K1N;
+      p.first = !last;
+      p.a.roots = c->d_roots; p.a.roots29 = sub ? c->d_rootsls : c->d_rootsl; p.a.qp29 = c->d_qpl; p.a.wq_w = c->d_wq_w;
+      p.a.log_n = sub ? 20u : k;
+      p.a.t0 = last ? p.a.log_n - 10 : 0u;
+      p.a.s = i == 0 ? s0 : 10u;
+      p.a.log_tj = 10 - p.a.s;
+      p.a.tile_group = p.first ? ntt_tile_group_of(p.a.log_n, c->L, p.a.log_tj) : 0u;
+      p.a.canon_row_mask = sub ? (1u << (k - 20)) - 1 : 0u;
+      p.roots29c = sub ? c->d_rootslcs : c->d_rootslc;
+      // canonical output: the last pass ends with a radix-4 round (10 stages).  Ft63 reduces its 4-element never-multiplied prefix
+      // at the store; Ft127 / Ft191 / Ft255 have a uniform round in that pass and convert block 0 before it (ntt_l9s.hip,
+      // ntt_lns.hip), or already in the pass before if that has >= 8 stages: then the last pass sees canonical values only
+      p.mont_prefix = last && c->NL == 2 ? 4u : 0u;
+      p.blk0_gone = last && c->NL != 2 && plan[i - 1].a.s >= 8 ? 1u : 0u;
+      p.pack_info = k1s ? ntt_l9s_pack_info(p.a.s, p.first) : ntt_lns_pack_info(c->NL, p.a.s, p.first);
+      const uint32_t n_classes = p.first ? 1u << (p.a.log_n - 10) : 1u;  // first pass: one class per tile position
+#ifdef LCPC_TEST_HOOKS
+      if (n_pass == 3 && i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;   // (the fallback below)
+#endif
+      if ((r = alloc(&p.pack, (size_t)n_classes * p.pack_info.class_words * 4))) return r;
+      NttPassArgs pa{};
+      pa.roots29 = p.a.roots29; pa.roots29c = p.roots29c; pa.log_n = p.a.log_n; pa.t0 = p.a.t0; pa.s = p.a.s; pa.log_tj = p.a.log_tj;
+      HIPCHK(c, k1s ? launch_ntt_l9s_pack(pa, p.first, p.pack_info, n_classes, p.pack, nullptr)
+                    : launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
+    }
+    HIPCHK(c, hipDeviceSynchronize());
+    return 0;
+  }();
+  if (rc == 0) {
+    c->ntt = std::move(plan);
+    c->comm_canon = true;                                      // commits keep comm canonical on the device
+    return 0;
+  }
+  for (uint32_t** p : made) { dev_free(*p); *p = nullptr; }
+  if (rc != LCPC_ERR_NOMEM) return rc;
+  (void)hipGetLastError();                                     // the failed hipMalloc must not surface at the next launch check
+  c->err.clear();
+  return 0;
+}
 
 #define ECHK(call)                                                        \
   do {                                                                    \
     hipError_t e__ = (call);                                              \
     if (e__ != hipSuccess) return fail_hip(err, e__, #call);              \
   } while (0)
+
+// The level walk of a Brakedown encode (encode.rs:36-94) over the segments of a codeword: precodes down, the last one into ws->d_tmp,
+// the R-S base case from d_tmp, postcodes up.  mat(m, in_off, out_off, into_tmp) and rs(out_off, n_out) each launch one step.
+template <class Mat, class Rs> static int sdig_walk(const lcpc_ctx* c, Mat&& mat, Rs&& rs) {
+  const size_t t = c->d_pre.size();
+  const DevCsr& pl = c->d_pre[t - 1];
+  uint64_t in_start = 0;
+  for (size_t i = 0; i + 1 < t; i++) {
+    if (int rc = mat(c->d_pre[i], in_start, in_start + c->d_pre[i].n_in, false)) return rc;
+    in_start += c->d_pre[i].n_in;
+  }
+  if (int rc = mat(pl, in_start, 0, true)) return rc;
+  const uint64_t in_end = in_start + pl.n_in;
+  if (int rc = rs(in_end, c->d_post[t - 1].n_in)) return rc;
+  in_start = in_end + pl.n_out;
+  uint64_t out_start = in_end + c->d_post[t - 1].n_in;
+  for (size_t ii = t; ii-- > 0;) {
+    in_start -= c->d_pre[ii].n_out;
+    if (int rc = mat(c->d_post[ii], in_start, out_start, false)) return rc;
+    out_start += c->d_post[ii].n_out;
+  }
+  return 0;
+}
 
 // ---- encode rows: LcEncoding::encode, batched over rows -----------------------------------------------
 int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, std::string* err, uint32_t* launches) {
@@ -165,9 +327,9 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
   if (j.kept_t) *j.kept_t = false;
   const uint64_t n_rows = j.n_rows;
   if (n_rows == 0) return 0;
-  if (c->prm.encoding == LCPC_ENC_LIGERO && c->l9s) {
-    // the shape-specialised two-pass kernel; between the passes the rows live as 29-bit limbs in ws->d_mid (row batches
-    // sized by ntt_mid_rows), or -- if that buffer cannot be had -- packed in dst itself
+  if (c->prm.encoding == LCPC_ENC_LIGERO) {
+    // the planned passes (plan_passes, build_limb_plan).  The K1s two-pass plan keeps the rows between its passes as 29-bit limbs
+    // in ws->d_mid, in row batches sized by ntt_mid_rows, or -- if that buffer cannot be had -- packed in dst itself
     uint64_t rb = ws->mid_failed ? 0 : ntt_mid_rows(c, n_rows);
     if (rb) {
       std::string scratch_err;
@@ -180,149 +342,31 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
         ws->mid_failed = true; ws->mid_cap = 0; rb = 0;
       }
     }
-    const uint64_t step = rb ? rb : n_rows;
-    for (uint64_t r0 = 0; r0 < n_rows; r0 += step) {
-      const uint64_t nr = std::min(step, n_rows - r0);
-      for (int i = 0; i < 2; i++) {
-        const Pass& p = c->passes[i];
-        const bool first = i == 0;
-        NttPassArgs a{};
-        a.roots29c = j.canon_out ? c->d_roots29c : nullptr;
-        // (canonical output: the last pass has a uniform round and converts what is left of block 0 before it -- no Montgomery-form
-        // prefix reaches the store; a first pass of 8 to 10 stages has one too, and then the last pass sees canonical values only)
-        a.mont_prefix = 0u;
-        a.blk0_gone = (!first && j.canon_out && c->passes[0].s >= 8) ? 1u : 0u;
+    const uint64_t batch = rb ? rb : n_rows;
+    for (uint64_t r0 = 0; r0 < n_rows; r0 += batch) {
+      const uint64_t nr = std::min(batch, n_rows - r0), consumed = r0 * j.src_stride;
+      for (size_t i = 0; i < c->ntt.size(); i++) {
+        const NttStep& p = c->ntt[i];
+        const bool first = i == 0;                              // reads the job's source; the later steps work in dst
+        const uint64_t len = (uint64_t)1 << p.a.log_n;         // elements per (sub-)row
+        NttPassArgs a = p.a;
+        if (j.canon_out) { a.roots29c = p.roots29c; a.mont_prefix = p.mont_prefix; a.blk0_gone = p.blk0_gone; }
         a.dst = j.dst + r0 * c->n_cols * c->NL;
-        a.src = first ? j.src + r0 * j.src_stride * c->NL : a.dst;
-        a.roots = c->d_roots; a.roots29 = c->d_roots29; a.qp29 = c->d_qp29; a.wq_w = c->d_wq_w;
-        a.src_stride = first ? j.src_stride : c->n_cols;
-        a.dst_stride = c->n_cols;
-        a.n_valid = first ? j.n_valid : c->n_cols;
-        const uint64_t consumed = r0 * j.src_stride;
+        a.src = first ? j.src + consumed * c->NL : a.dst;
+        a.src_stride = first ? j.src_stride : len;
+        a.dst_stride = len;
+        a.n_valid = first ? j.n_valid : len;
         a.n_src_total = !first || j.n_src_total == ~(uint64_t)0 ? ~(uint64_t)0 : (j.n_src_total > consumed ? j.n_src_total - consumed : 0);
-        a.copy_dst = first && j.copy_dst ? j.copy_dst + r0 * j.src_stride * c->NL : nullptr;
-        a.n_rows = nr;
-        a.log_n = c->log_n; a.t0 = p.t0; a.s = p.s; a.log_tj = p.log_tj;
+        a.copy_dst = first && j.copy_dst ? j.copy_dst + consumed * c->NL : nullptr;
+        a.n_rows = nr << (c->log_n - p.a.log_n);
         a.mid = rb ? ws->d_mid : nullptr;
-        a.tile_group = first ? ntt_tile_group(c, p) : 0u;
-        ECHK(launch_ntt_pass_l9s(a, first, c->d_pack[i], c->pack_info[i], st));
+        switch (p.kernel) {
+          case NttStep::K1S: ECHK(launch_ntt_pass_l9s(a, p.first, p.pack, p.pack_info, st)); break;
+          case NttStep::K1N: ECHK(launch_ntt_pass_lns(c->NL, a, p.first, p.pack, p.pack_info, st)); break;
+          case NttStep::GENERAL: ECHK(launch_ntt_pass(c->NL, p.log_tile, a, st)); break;
+        }
         nl++;
       }
-    }
-    return 0;
-  }
-  if (c->prm.encoding == LCPC_ENC_LIGERO && c->l9s3) {
-    // 2^21 .. 2^26 columns: s0 stages with the first-pass kernel over the whole rows (zero padding, ragged tail and the coeffs
-    // copy live there), then every row is 2^s0 independent 2^20-point transforms: the two-pass plan on n_rows << s0 sub-rows, in
-    // place, with the sub-sampled tables.  Canonical output: after the first pass only sub-row 0 of each row still holds
-    // never-multiplied elements ("block 0"), so only those sub-rows take the converting twiddles / the prefix reduction
-    const uint32_t s0 = c->log_n - 20;
-    for (int i = 0; i < 3; i++) {
-      const Pass& p = c->passes[i];
-      const bool first = i == 0, sub = i > 0;
-      NttPassArgs a{};
-      a.dst = j.dst;
-      a.src = first ? j.src : j.dst;
-      a.roots = c->d_roots; a.qp29 = c->d_qp29; a.wq_w = c->d_wq_w;
-      a.roots29 = sub ? c->d_roots29s : c->d_roots29;
-      a.roots29c = j.canon_out ? (sub ? c->d_roots29cs : c->d_roots29c) : nullptr;
-      a.canon_row_mask = sub ? (1u << s0) - 1 : 0u;
-      a.mont_prefix = 0u;                                     // (as in the two-pass branch: pass 1 -- 10 stages -- has the uniform round)
-      a.blk0_gone = (i == 2 && j.canon_out) ? 1u : 0u;
-      a.src_stride = first ? j.src_stride : ((uint64_t)1 << 20);
-      a.dst_stride = first ? c->n_cols : ((uint64_t)1 << 20);
-      a.n_valid = first ? j.n_valid : ((uint64_t)1 << 20);
-      a.n_src_total = first ? j.n_src_total : ~(uint64_t)0;
-      a.copy_dst = first ? j.copy_dst : nullptr;
-      a.n_rows = first ? n_rows : n_rows << s0;
-      a.log_n = first ? c->log_n : 20u;
-      a.t0 = i == 2 ? 10u : 0u; a.s = p.s; a.log_tj = p.log_tj;
-      a.tile_group = i == 0 ? ntt_tile_group_of(c->log_n, c->L, p.log_tj) : (i == 1 ? ntt_tile_group_of(20, c->L, 0) : 0u);
-      ECHK(launch_ntt_pass_l9s(a, i < 2, c->d_pack[i], c->pack_info[i], st));
-      nl++;
-    }
-    return 0;
-  }
-  if (c->prm.encoding == LCPC_ENC_LIGERO && c->lns3) {        // the three-pass plan of the l9s3 branch above, on K1n
-    const uint32_t s0 = c->log_n - 20;
-    for (int i = 0; i < 3; i++) {
-      const Pass& p = c->passes[i];
-      const bool first = i == 0, sub = i > 0;
-      NttPassArgs a{};
-      a.dst = j.dst;
-      a.src = first ? j.src : j.dst;
-      a.roots = c->d_roots; a.qp29 = c->d_qpl; a.wq_w = c->d_wq_w;
-      a.roots29 = sub ? c->d_rootsls : c->d_rootsl;
-      a.roots29c = j.canon_out ? (sub ? c->d_rootslcs : c->d_rootslc) : nullptr;
-      a.canon_row_mask = sub ? (1u << s0) - 1 : 0u;
-      // (fields with a shifted-multiples multiply -- Ft127, Ft191 -- run uniform rounds in every 10-stage pass and convert block 0 before
-      // them: pass 1 leaves nothing in Montgomery form; Ft63 keeps the 4-element prefix of the last pass)
-      a.mont_prefix = (j.canon_out && i == 2 && c->NL == 2) ? 4u : 0u;
-      a.blk0_gone = (i == 2 && j.canon_out && c->NL != 2) ? 1u : 0u;
-      a.src_stride = first ? j.src_stride : ((uint64_t)1 << 20);
-      a.dst_stride = first ? c->n_cols : ((uint64_t)1 << 20);
-      a.n_valid = first ? j.n_valid : ((uint64_t)1 << 20);
-      a.n_src_total = first ? j.n_src_total : ~(uint64_t)0;
-      a.copy_dst = first ? j.copy_dst : nullptr;
-      a.n_rows = first ? n_rows : n_rows << s0;
-      a.log_n = first ? c->log_n : 20u;
-      a.t0 = i == 2 ? 10u : 0u; a.s = p.s; a.log_tj = p.log_tj;
-      a.tile_group = i == 0 ? ntt_tile_group_of(c->log_n, c->L, p.log_tj) : (i == 1 ? ntt_tile_group_of(20, c->L, 0) : 0u);
-      ECHK(launch_ntt_pass_lns(c->NL, a, i < 2, c->d_pack[i], c->pack_info[i], st));
-      nl++;
-    }
-    return 0;
-  }
-  if (c->prm.encoding == LCPC_ENC_LIGERO && c->lns) {
-    for (int i = 0; i < 2; i++) {
-      const Pass& p = c->passes[i];
-      const bool first = i == 0;
-      NttPassArgs a{};
-      a.src = first ? j.src : j.dst;
-      a.dst = j.dst;
-      a.roots = c->d_roots; a.roots29 = c->d_rootsl; a.qp29 = c->d_qpl; a.wq_w = c->d_wq_w;
-      a.roots29c = j.canon_out ? c->d_rootslc : nullptr;
-      // the last pass ends with a radix-4 round (10 stages): Ft63 reduces its 4-element never-multiplied prefix at the store; Ft127 /
-      // Ft191 have a uniform round in that pass and convert block 0 before it (ntt_lns.hip), or already in a first pass of >= 8 stages
-      a.mont_prefix = (j.canon_out && !first && c->NL == 2) ? 4u : 0u;
-      a.blk0_gone = (!first && j.canon_out && c->NL != 2 && c->passes[0].s >= 8) ? 1u : 0u;
-      a.src_stride = first ? j.src_stride : c->n_cols;
-      a.dst_stride = c->n_cols;
-      a.n_valid = first ? j.n_valid : c->n_cols;
-      a.n_src_total = first ? j.n_src_total : ~(uint64_t)0;
-      a.copy_dst = first ? j.copy_dst : nullptr;
-      a.n_rows = n_rows;
-      a.log_n = c->log_n; a.t0 = p.t0; a.s = p.s; a.log_tj = p.log_tj;
-      a.tile_group = first ? ntt_tile_group(c, p) : 0u;
-      ECHK(launch_ntt_pass_lns(c->NL, a, first, c->d_pack[i], c->pack_info[i], st));
-      nl++;
-    }
-    return 0;
-  }
-  if (c->prm.encoding == LCPC_ENC_LIGERO) {
-    bool first = true;
-    for (const Pass& p : c->passes) {
-      NttPassArgs a;
-      a.roots29c = j.canon_out ? c->d_roots29c : nullptr;
-      // the trailing stages multiply by 1 only: a final radix-4 round leaves 4 elements per row unconverted, a final
-      // radix-2 stage 2 (ntt_pass_l9_kernel)
-      a.mont_prefix = (j.canon_out && p.t0 + p.s == c->log_n) ? (c->log_n == 0 ? 1u : (p.s % 2 == 0 ? 4u : 2u)) : 0u;
-      a.src = first ? j.src : j.dst;
-      a.dst = j.dst;
-      a.roots = c->d_roots;
-      a.roots29 = c->d_roots29;
-      a.qp29 = c->d_qp29;
-      a.wq_w = c->d_wq_w;
-      a.src_stride = first ? j.src_stride : c->n_cols;
-      a.dst_stride = c->n_cols;
-      a.n_valid = first ? j.n_valid : c->n_cols;
-      a.n_src_total = first ? j.n_src_total : ~(uint64_t)0;
-      a.copy_dst = first ? j.copy_dst : nullptr;
-      a.n_rows = n_rows;
-      a.log_n = c->log_n; a.t0 = p.t0; a.s = p.s; a.log_tj = p.log_tj;
-      ECHK(launch_ntt_pass(c->NL, p.log_tile, a, st));
-      nl++;
-      first = false;
     }
     return 0;
   }
@@ -338,35 +382,21 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
     if (int rc = ensure_dev(err, &ws->d_t, &ws->t_cap, n_rows * c->n_cols * eb)) return rc;
     ECHK(launch_transpose_to_t(c->NL, j.src, j.src_stride, j.n_valid, n_rows, ws->d_t, st, j.n_src_total, j.copy_dst, j.canon_out && j.keep_t));
     nl++;
-    uint64_t in_start = 0;
     SpmmTArgs a{};
     a.t = ws->d_t; a.n_rows = n_rows;
-    auto set_mat = [&](const DevCsr& m) { a.rowptr = m.rowptr; a.colidx = m.colidx; a.vals = m.vals; a.vals29 = m.vals29; a.m = m.n_out; };
-    for (size_t i = 0; i + 1 < t; i++) {
-      const uint64_t in_end = in_start + c->d_pre[i].n_in;
-      a.out_alt = nullptr; a.in_off = in_start; a.out_off = in_end;
-      set_mat(c->d_pre[i]);
+    auto mat = [&](const DevCsr& m, uint64_t in_off, uint64_t out_off, bool to_tmp) -> int {
+      a.out_alt = to_tmp ? ws->d_tmp : nullptr; a.in_off = in_off; a.out_off = out_off;
+      a.rowptr = m.rowptr; a.colidx = m.colidx; a.vals = m.vals; a.vals29 = m.vals29; a.m = m.n_out;
       ECHK(launch_spmm_t(c->NL, a, st));
       nl++;
-      in_start = in_end;
-    }
-    const uint64_t in_end = in_start + pl.n_in;
-    a.out_alt = ws->d_tmp; a.in_off = in_start; a.out_off = 0;
-    set_mat(pl);
-    ECHK(launch_spmm_t(c->NL, a, st));
-    const uint64_t out_end = in_end + c->d_post[t - 1].n_in;
-    ECHK(launch_sdig_rs_t(c->NL, ws->d_tmp, (uint32_t)pl.n_out, ws->d_t, in_end, (uint32_t)c->d_post[t - 1].n_in, n_rows, c->d_r2, st));
-    nl += 2;
-    in_start = in_end + pl.n_out;
-    uint64_t out_start = out_end;
-    for (size_t ii = t; ii-- > 0;) {
-      in_start -= c->d_pre[ii].n_out;
-      a.out_alt = nullptr; a.in_off = in_start; a.out_off = out_start;
-      set_mat(c->d_post[ii]);
-      ECHK(launch_spmm_t(c->NL, a, st));
+      return 0;
+    };
+    auto rs = [&](uint64_t out_off, uint64_t n_out) -> int {
+      ECHK(launch_sdig_rs_t(c->NL, ws->d_tmp, (uint32_t)pl.n_out, ws->d_t, out_off, (uint32_t)n_out, n_rows, c->d_r2, st));
       nl++;
-      out_start += c->d_post[ii].n_out;
-    }
+      return 0;
+    };
+    if (int rc = sdig_walk(c, mat, rs)) return rc;
     if (j.keep_t) {               // commit: the position-major copy IS the commitment (hash_columns / open_column read it)
       if (j.kept_t) *j.kept_t = true;
       return 0;
@@ -380,36 +410,22 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
     ECHK(launch_pad_rows(c->NL, j.src, j.src_stride, j.dst, c->n_cols, j.n_valid, n_rows, st));
     nl++;
   }
-  uint64_t in_start = 0;
   SpmvArgs a{};
   a.mat = j.dst; a.stride = c->n_cols; a.n_rows = n_rows;
-  for (size_t i = 0; i + 1 < t; i++) {
-    const uint64_t in_end = in_start + c->d_pre[i].n_in;
-    a.out_alt = nullptr; a.in_off = in_start; a.out_off = in_end;
-    a.rowptr = c->d_pre[i].rowptr; a.colidx = c->d_pre[i].colidx; a.vals = c->d_pre[i].vals; a.vals29 = c->d_pre[i].vals29; a.m = c->d_pre[i].n_out;
+  auto mat = [&](const DevCsr& m, uint64_t in_off, uint64_t out_off, bool to_tmp) -> int {
+    a.out_alt = to_tmp ? ws->d_tmp : nullptr; a.in_off = in_off; a.out_off = out_off;
+    if (to_tmp) a.out_alt_stride = pl.n_out;
+    a.rowptr = m.rowptr; a.colidx = m.colidx; a.vals = m.vals; a.vals29 = m.vals29; a.m = m.n_out;
     ECHK(launch_spmv(c->NL, a, st));
     nl++;
-    in_start = in_end;
-  }
-  const uint64_t in_end = in_start + pl.n_in;
-  a.out_alt = ws->d_tmp; a.out_alt_stride = pl.n_out; a.in_off = in_start; a.out_off = 0;
-  a.rowptr = pl.rowptr; a.colidx = pl.colidx; a.vals = pl.vals; a.vals29 = pl.vals29; a.m = pl.n_out;
-  ECHK(launch_spmv(c->NL, a, st));
-  const uint64_t out_end = in_end + c->d_post[t - 1].n_in;
-  ECHK(launch_sdig_rs(c->NL, ws->d_tmp, pl.n_out, (uint32_t)pl.n_out, j.dst, c->n_cols, in_end,
-                      (uint32_t)c->d_post[t - 1].n_in, n_rows, c->d_r2, st));
-  nl += 2;
-  in_start = in_end + pl.n_out;
-  uint64_t out_start = out_end;
-  for (size_t ii = t; ii-- > 0;) {
-    in_start -= c->d_pre[ii].n_out;
-    a.out_alt = nullptr; a.in_off = in_start; a.out_off = out_start;
-    a.rowptr = c->d_post[ii].rowptr; a.colidx = c->d_post[ii].colidx; a.vals = c->d_post[ii].vals; a.vals29 = c->d_post[ii].vals29; a.m = c->d_post[ii].n_out;
-    ECHK(launch_spmv(c->NL, a, st));
+    return 0;
+  };
+  auto rs = [&](uint64_t out_off, uint64_t n_out) -> int {
+    ECHK(launch_sdig_rs(c->NL, ws->d_tmp, pl.n_out, (uint32_t)pl.n_out, j.dst, c->n_cols, out_off, (uint32_t)n_out, n_rows, c->d_r2, st));
     nl++;
-    out_start += c->d_post[ii].n_out;
-  }
-  return 0;
+    return 0;
+  };
+  return sdig_walk(c, mat, rs);
 }
 
 }  // namespace lcpc
@@ -527,202 +543,29 @@ static int ctx_build(lcpc_ctx* c, const lcpc_params* p) {
       uint32_t *d_pw = nullptr, *d_one = nullptr;
       if ((rc = dev_alloc(err, &d_pw, pw.size() * 8)) || (rc = dev_alloc(err, &d_one, 8 * f->L)) ||
           (rc = dev_alloc(err, &c->d_roots, n_roots * 8 * f->L)) ||
-          (f->L == 4 && (rc = dev_alloc(err, &c->d_roots29, n_roots * 48))) ||
-          (f->L == 4 && (rc = dev_alloc(err, &c->d_roots29c, n_roots * 48)))) {
+          (f->L == 4 && (rc = dev_alloc(err, &c->d_rootsl, n_roots * 48))) ||
+          (f->L == 4 && (rc = dev_alloc(err, &c->d_rootslc, n_roots * 48)))) {
         dev_free(d_pw); dev_free(d_one);
         return rc;
       }
       hipError_t he = hipMemcpy(d_pw, pw.data(), pw.size() * 8, hipMemcpyHostToDevice);
       if (he == hipSuccess) he = hipMemcpy(d_one, f->r, 8 * f->L, hipMemcpyHostToDevice);
-      if (he == hipSuccess) he = launch_roots(c->NL, d_pw, log_half, d_one, c->d_roots, c->d_roots29, c->d_roots29c, nullptr);
+      if (he == hipSuccess) he = launch_roots(c->NL, d_pw, log_half, d_one, c->d_roots, c->d_rootsl, c->d_rootslc, nullptr);
       if (he == hipSuccess) he = hipDeviceSynchronize();
       dev_free(d_pw); dev_free(d_one);
       if (he != hipSuccess) return fail_hip(err, he, "precomp_fft");
     }
-    if (f->L == 4) {
-      // (i - 24) * p for i < 64 as normalised signed 29-bit limbs (limbs 0..7 in [0, 2^29), limb 8 two's complement):
-      // the table behind l9::clamp (lazy-limb NTT kernel; QOFF in field_dev.h)
-      std::vector<uint32_t> tab(64 * 12, 0);
-      for (int i = 0; i < 64; i++) {
-        const int q = i - 24;
-        uint64_t mag[5] = {0, 0, 0, 0, 0};                      // |q| * p
-        unsigned __int128 cy = 0;
-        for (int w = 0; w < 5; w++) { cy += (unsigned __int128)(w < 4 ? f->p[w] : 0) * (uint64_t)(q < 0 ? -q : q); mag[w] = (uint64_t)cy; cy >>= 64; }
-        if (q < 0) {                                            // two's complement over 320 bits
-          unsigned __int128 c2 = 1;
-          for (int w = 0; w < 5; w++) { c2 += (unsigned __int128)(~mag[w]); mag[w] = (uint64_t)c2; c2 >>= 64; }
-        }
-        for (int k = 0; k < 9; k++) {
-          const int b = 29 * k, w = b / 64, sh = b % 64;
-          uint64_t x = mag[w] >> sh;
-          if (sh > 35) x |= mag[w + 1] << (64 - sh);
-          tab[i * 12 + k] = k < 8 ? (uint32_t)(x & ((1u << 29) - 1)) : (uint32_t)x;      // limb 8: bits 232..263, sign-extended
-        }
-      }
-      if ((rc = dev_alloc(err, &c->d_qp29, tab.size() * 4))) return rc;
-      HIPCHK(c, hipMemcpy(c->d_qp29, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-      if ((rc = build_wq_w(c, 9, 29))) return rc;
+    if (f->L == 4) {                                           // Ft255: the general kernel's lazy-limb variant reads them too
+      if ((rc = limb_consts(c, nullptr))) return rc;
       c->comm_canon = true;
     }
     if ((rc = dev_alloc(err, &c->d_r2, 8 * f->L))) return rc;
     HIPCHK(c, hipMemcpy(c->d_r2, f->r2, 8 * f->L, hipMemcpyHostToDevice));
     plan_passes(c);
-    if (c->d_qp29 && !c->sw_ntt_general && ntt_l9s_supported(c->log_n, (uint32_t)c->passes.size(), c->passes[0].log_tile)) {
-      // two passes on 1024-element tiles: the shape-specialised kernel with its lane-order twiddle packs
-      for (int i = 0; i < 2; i++) {
-        const Pass& ps = c->passes[i];
-        const bool first = i == 0;
-        NttPassArgs a{};
-        a.roots29 = c->d_roots29; a.roots29c = c->d_roots29c; a.log_n = c->log_n; a.t0 = ps.t0; a.s = ps.s; a.log_tj = ps.log_tj;
-        c->pack_info[i] = ntt_l9s_pack_info(ps.s, first);
-        const uint32_t n_classes = first ? 1u << (c->log_n - 10) : 1u;
-        if ((rc = dev_alloc(err, &c->d_pack[i], (size_t)n_classes * c->pack_info[i].class_words * 4))) return rc;
-        HIPCHK(c, launch_ntt_l9s_pack(a, first, c->pack_info[i], n_classes, c->d_pack[i], nullptr));
-      }
-      HIPCHK(c, hipDeviceSynchronize());
-      c->l9s = true;
-    } else if (c->d_qp29 && !c->sw_ntt_general && ntt_l9s3_supported(c->log_n)) {
-      // three passes of the shape-specialised kernel (kernels.h ntt_l9s3_supported): tables for the 2^20-point sub-transforms,
-      // pack 0 for the first pass over the whole rows (one class per tile position: 2^(log_n - 10)), packs 1 / 2 = those of a
-      // 2^20-column context
-      const unsigned k = c->log_n, s0 = k - 20;
-      const size_t n_sub = (size_t)1 << 19;
-      // the first pack is ~2.3 x one row (4.9 GB at 2^26 columns): if the device cannot hold the plan's tables, the general kernel's
-      // three passes (tables already built above) take the rows instead -- slower, not an error
-      const std::vector<Pass> general_plan = c->passes;
-      auto build = [&]() -> int {
-        int r;
-        if ((r = dev_alloc(err, &c->d_roots29s, n_sub * 48)) || (r = dev_alloc(err, &c->d_roots29cs, n_sub * 48))) return r;
-        HIPCHK(c, launch_ntt_l9s_subtable(c->d_roots29, s0, n_sub, c->d_roots29s, nullptr));
-        HIPCHK(c, launch_ntt_l9s_subtable(c->d_roots29c, s0, n_sub, c->d_roots29cs, nullptr));
-        c->passes.clear();
-        c->passes.push_back({0, s0, 10 - s0, 10});
-        c->passes.push_back({s0, 10, 0u, 10});
-        c->passes.push_back({s0 + 10, 10, 0u, 10});
-        for (int i = 0; i < 3; i++) {
-          const Pass& ps = c->passes[i];
-          const bool first = i < 2;                            // passes 0 and 1 run the first-pass kernel
-          NttPassArgs a{};
-          a.roots29 = i == 0 ? c->d_roots29 : c->d_roots29s; a.roots29c = i == 0 ? c->d_roots29c : c->d_roots29cs;
-          a.log_n = i == 0 ? k : 20u; a.t0 = i == 2 ? 10u : 0u; a.s = ps.s; a.log_tj = ps.log_tj;
-          c->pack_info[i] = ntt_l9s_pack_info(ps.s, first);
-          const uint32_t n_classes = i == 0 ? 1u << (k - 10) : (i == 1 ? 1024u : 1u);
-#ifdef LCPC_TEST_HOOKS
-          if (i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;       // (the fallback below)
-#endif
-          if ((r = dev_alloc(err, &c->d_pack[i], (size_t)n_classes * c->pack_info[i].class_words * 4))) return r;
-          HIPCHK(c, launch_ntt_l9s_pack(a, first, c->pack_info[i], n_classes, c->d_pack[i], nullptr));
-        }
-        HIPCHK(c, hipDeviceSynchronize());
-        return 0;
-      };
-      const int brc = build();
-      if (brc == 0) {
-        c->l9s3 = true;
-      } else if (brc == LCPC_ERR_NOMEM) {
-        for (auto& pk : c->d_pack) { dev_free(pk); pk = nullptr; }
-        dev_free(c->d_roots29s); dev_free(c->d_roots29cs);
-        c->d_roots29s = c->d_roots29cs = nullptr;
-        c->passes = general_plan;
-        (void)hipGetLastError();                               // the failed hipMalloc must not surface at the next launch check
-        err->clear();
-      } else {
-        return brc;
-      }
-    }
-    const bool lns3 = !c->d_qp29 && !c->sw_ntt_general && ntt_lns3_supported(c->NL, c->log_n);
-    if (!c->d_qp29 && c->passes.size() >= 2 && !c->sw_ntt_general && (ntt_lns_supported(c->NL, c->log_n) || lns3)) {
-      // Ft63 / Ft127 / Ft191 rows that need more than one pass: two passes on 1024-element tiles with the lazy-limb
-      // kernel (ntt_lns.hip), its twiddle table in limb form (w^i R' mod p), the clamp table and the lane-order packs
-      const std::vector<Pass> general_plan = c->passes;      // (if the tables do not fit the device: the general kernel, as for l9s3)
-      auto build = [&]() -> int {
-        int rc_ = 0;
-        const unsigned k = c->log_n;
-        c->passes.clear();
-        if (lns3) {                                              // three passes: s0 stages over the whole rows, then 10 + 10 per 2^20-element block
-          c->passes.push_back({0, k - 20, 30 - k, 10});
-          c->passes.push_back({k - 20, 10, 0u, 10});
-          c->passes.push_back({k - 10, 10, 0u, 10});
-        } else {
-          c->passes.push_back({0, k - 10, 20 - k, 10});
-          c->passes.push_back({k - 10, 10, 0u, 10});
-        }
-        const int N = ntt_lns_limbs(c->NL), W = ntt_lns_limb_bits(c->NL), stride = ntt_lns_stride(c->NL);
-        uint64_t rp[MAXL] = {1, 0, 0, 0};                        // R' = 2^(N W) mod p, a plain integer
-        for (int i = 0; i < N * W; i++) h_add(*f, rp, rp, rp);
-        std::vector<uint32_t> tab((size_t)64 * stride, 0);
-        for (int i = 0; i < 64; i++) {                           // (i - 24) * p as normalised signed limbs (two's complement top limb)
-          const int q = i - 24;
-          uint64_t mag[5] = {0, 0, 0, 0, 0};
-          unsigned __int128 cy = 0;
-          for (int w = 0; w < 5; w++) { cy += (unsigned __int128)(w < f->L ? f->p[w] : 0) * (uint64_t)(q < 0 ? -q : q); mag[w] = (uint64_t)cy; cy >>= 64; }
-          if (q < 0) {                                           // two's complement over 320 bits
-            unsigned __int128 c2 = 1;
-            for (int w = 0; w < 5; w++) { c2 += (unsigned __int128)(~mag[w]); mag[w] = (uint64_t)c2; c2 >>= 64; }
-          }
-          for (int l = 0; l < N; l++) {
-            const int b = W * l, w = b / 64, sh = b % 64;
-            uint64_t x = mag[w] >> sh;
-            if (sh) x |= mag[w + 1] << (64 - sh);
-            tab[(size_t)i * stride + l] = l + 1 < N ? (uint32_t)(x & (((uint64_t)1 << W) - 1)) : (uint32_t)x;   // top limb: sign-extended
-          }
-        }
-        const size_t n_roots = (size_t)1 << (k - 1);
-        uint64_t rpc[MAXL];
-        h_canon(*f, rpc, rp);                                    // R' R^-1 mod p: the converting table is w^i R' R^-1 = mont_mul(w^i R, R' R^-1)
-        uint32_t *d_rp = nullptr, *d_rpc = nullptr;
-        if ((rc_ = dev_alloc(err, &d_rp, 8 * f->L))) return rc_;
-        if ((rc_ = dev_alloc(err, &d_rpc, 8 * f->L))) { dev_free(d_rp); return rc_; }
-        if ((rc_ = dev_alloc(err, &c->d_rootsl, n_roots * stride * 4)) || (rc_ = dev_alloc(err, &c->d_rootslc, n_roots * stride * 4)) ||
-            (rc_ = dev_alloc(err, &c->d_qpl, tab.size() * 4))) { dev_free(d_rp); dev_free(d_rpc); return rc_; }
-        hipError_t he = hipMemcpy(d_rp, rp, 8 * f->L, hipMemcpyHostToDevice);
-        if (he == hipSuccess) he = hipMemcpy(d_rpc, rpc, 8 * f->L, hipMemcpyHostToDevice);
-        if (he == hipSuccess) he = hipMemcpy(c->d_qpl, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
-        if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rp, c->d_rootsl, nullptr);
-        if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rpc, c->d_rootslc, nullptr);
-        if (he == hipSuccess) he = hipDeviceSynchronize();
-        dev_free(d_rp); dev_free(d_rpc);
-        if (he != hipSuccess) return fail_hip(err, he, "ntt_lns tables");
-        if (!c->d_wq_w && (rc_ = build_wq_w(c, N, W))) return rc_;
-        if (lns3) {
-          const size_t n_sub = (size_t)1 << 19;
-          if ((rc_ = dev_alloc(err, &c->d_rootsls, n_sub * stride * 4)) || (rc_ = dev_alloc(err, &c->d_rootslcs, n_sub * stride * 4))) return rc_;
-          HIPCHK(c, launch_ntt_lns_subtable(c->NL, c->d_rootsl, k - 20, n_sub, c->d_rootsls, nullptr));
-          HIPCHK(c, launch_ntt_lns_subtable(c->NL, c->d_rootslc, k - 20, n_sub, c->d_rootslcs, nullptr));
-        }
-        for (int i = 0; i < (lns3 ? 3 : 2); i++) {
-          const Pass& ps = c->passes[i];
-          const bool first = lns3 ? i < 2 : i == 0;              // three-pass plans: passes 0 and 1 run the first-pass kernel
-          const bool sub = lns3 && i > 0;
-          NttPassArgs a{};
-          a.roots29 = sub ? c->d_rootsls : c->d_rootsl; a.roots29c = sub ? c->d_rootslcs : c->d_rootslc;
-          a.log_n = sub ? 20u : k; a.t0 = sub ? (i == 2 ? 10u : 0u) : ps.t0; a.s = ps.s; a.log_tj = ps.log_tj;
-          c->pack_info[i] = ntt_lns_pack_info(c->NL, ps.s, first);
-          const uint32_t n_classes = !first ? 1u : (sub ? 1024u : 1u << (k - 10));
-#ifdef LCPC_TEST_HOOKS
-          if (lns3 && i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;   // (the fallback below)
-#endif
-          if ((rc_ = dev_alloc(err, &c->d_pack[i], (size_t)n_classes * c->pack_info[i].class_words * 4))) return rc_;
-          HIPCHK(c, launch_ntt_lns_pack(c->NL, a, first, c->pack_info[i], n_classes, c->d_pack[i], nullptr));
-        }
-        HIPCHK(c, hipDeviceSynchronize());
-        return 0;
-      };
-      const int brc = build();
-      if (brc == LCPC_ERR_NOMEM) {
-        for (auto& pk : c->d_pack) { dev_free(pk); pk = nullptr; }
-        dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_rootsls); dev_free(c->d_rootslcs); dev_free(c->d_wq_w);
-        c->d_rootsl = c->d_rootslc = c->d_qpl = c->d_rootsls = c->d_rootslcs = c->d_wq_w = nullptr;
-        c->passes = general_plan;
-        (void)hipGetLastError();
-        err->clear();
-        return 0;
-      }
-      if (brc) return brc;
-      c->lns = !lns3;
-      c->lns3 = lns3;
-      c->comm_canon = true;                                    // commits keep comm canonical on the device, as for Ft255
-    }
+    if (c->sw_ntt_general) return 0;
+    const uint32_t np = (uint32_t)c->ntt.size();
+    if (c->L == 4 ? ntt_l9s_supported(c->log_n, np, c->ntt[0].log_tile) : np >= 2 && ntt_lns_supported(c->NL, c->log_n)) return build_limb_plan(c, 2);
+    if (c->L == 4 ? ntt_l9s3_supported(c->log_n) : np >= 2 && ntt_lns3_supported(c->NL, c->log_n)) return build_limb_plan(c, 3);
     return 0;
   }
   if (p->encoding != LCPC_ENC_SDIG) return LCPC_ERR_ARG;

@@ -33,7 +33,19 @@ struct DevCsr {
   uint32_t *rowptr = nullptr, *colidx = nullptr, *vals = nullptr;
   uint32_t* vals29 = nullptr;     // Ft255: values in the 29-bit-limb / 2^261 form (lazy29_mac)
 };
-struct Pass { uint32_t t0, s, log_tj; int log_tile; };
+// one pass of the Ligero row NTT as the context plans it (ctx.cpp plan_passes, build_limb_plan): everything about the pass that
+// does not depend on the job.  A step with a.log_n < the context's log_n runs on n_rows << (log_n - a.log_n) sub-rows.
+struct NttStep {
+  enum Kernel { GENERAL, K1S, K1N } kernel = GENERAL;   // kernels.hip launch_ntt_pass / ntt_l9s.hip (Ft255) / ntt_lns.hip
+  bool first = false;              // K1s / K1n: the first-pass kernel
+  int log_tile = 0;                // general kernel
+  NttPassArgs a{};                 // log_n, t0, s, log_tj of the (sub-)transform; the tables (roots, roots29, qp29, wq_w); tile_group,
+                                   // canon_row_mask
+  const uint32_t* roots29c = nullptr;   // canonical output only: the converting table, and what the pass leaves to convert
+  uint32_t mont_prefix = 0, blk0_gone = 0;
+  uint32_t* pack = nullptr;        // K1s / K1n: the lane-order twiddle pack (owned by the context)
+  NttPackInfo pack_info{};
+};
 
 // device working buffers of one Brakedown encode: owned by a commitment (where the position-major copy IS the
 // commitment matrix) or, for lcpc_encode_rows, by the encoder context
@@ -71,10 +83,10 @@ struct lcpc_ctx {
   bool sw_ntt_general = false;     // LCPC_NTT_GENERAL: every Ligero row on the general kernel (K1) instead of the shape-specialised plans
   int64_t sw_ntt_mid_max_mb = -1;  // LCPC_NTT_MID_MAX_MB: -1 = the default rule of ntt_mid_rows
   bool sw_debug_timing = false;    // LCPC_DEBUG_TIMING: phase times of construction / prove / verify on stderr
-#ifdef LCPC_TEST_HOOKS             // forced allocation failures, compiled only into lib/liblcpc_hip_testhooks.so (the tests' second build of ctx.cpp)
+  // forced allocation failures: set and read only in lib/liblcpc_hip_testhooks.so (the tests' second build of ctx.cpp, with
+  // LCPC_TEST_HOOKS); members in every build, so that all objects of that library see one layout of the struct
   bool sw_test_fail_3pass = false; // LCPC_TEST_FAIL=3pass: the three-pass plan's tables "do not fit" -> the general kernel's plan
   bool sw_test_fail_mid = false;   // LCPC_TEST_FAIL=mid: the K1s limb-intermediate allocation fails -> packed intermediate
-#endif
   const lcpc::FieldDesc* f = nullptr;
   int L = 0, NL = 0;
   uint64_t n_per_row = 0, n_cols = 0, np2 = 0;
@@ -82,29 +94,21 @@ struct lcpc_ctx {
   // Ligero
   unsigned log_n = 0;
   uint32_t* d_roots = nullptr;
-  uint32_t* d_roots29 = nullptr;   // Ft255: twiddles in radix-2^29 / R'=2^261 Montgomery form (field_dev.h fe_mul_r29)
-  uint32_t* d_qp29 = nullptr;      // Ft255: q*p as 29-bit limbs (l9::clamp); null = packed-form NTT kernel
-  uint32_t* d_roots29c = nullptr;  // Ft255 lazy-limb kernel: w^i * 2^5, the table that converts to canonical on the fly
-                                   // (Brakedown: the position-major commitment of a commit -- ws.d_t, >= SDIG_T_MIN_ROWS rows -- always holds
-                                   // canonical values: converted once in the input transpose, kept by every (linear) level)
+  // lazy-limb NTT tables, N limbs of W bits per entry: (N, W, stride) = (9, 29, 12 words) for Ft255, made with d_roots and read by
+  // the general kernel as well (ntt_pass_l9_kernel); ntt_lns_limbs / _limb_bits / _stride for Ft63 / Ft127 / Ft191, made only for a K1n plan
+  uint32_t* d_rootsl = nullptr;    // w^i R' mod p (Ft255: R' = 2^261, field_dev.h fe_mul_r29; the other fields: field_ln.h)
+  uint32_t* d_rootslc = nullptr;   // w^i R' R^-1 mod p (Ft255: w^i 2^5): the table that converts to canonical on the fly
+  uint32_t* d_qpl = nullptr;       // (i - 24) * p, i < 64, same form (l9::clamp, ln::clamp_*)
+  uint32_t* d_rootsls = nullptr;   // three-pass plans: the 2^20-point tables (every 2^(log_n - 20)-th entry of d_rootsl / d_rootslc)
+  uint32_t* d_rootslcs = nullptr;
+  uint32_t* d_wq_w = nullptr;      // the shifted multiples of the primitive 4th root w^(n/4) (the same element for every n), 96 words
+  // the row NTT: the general kernel's passes (K1, plan_passes), or a lazy-limb plan (build_limb_plan) -- two passes on 1024-element
+  // tiles, or for 2^21 .. 2^26 columns three: a first pass over the whole rows, then the 2^20-point two-pass plan per block
+  std::vector<lcpc::NttStep> ntt;
   bool comm_canon = false;         // d_comm of a commit holds canonical values (x * R^-1), not Montgomery form: the column
                                    // hash reads them as they are; every read-out (get_comm, open_columns) converts back
-  std::vector<lcpc::Pass> passes;
-  uint32_t* d_pack[3] = {nullptr, nullptr, nullptr};   // Ft255 two- / three-pass plans: lane-order twiddle packs of the specialised kernel (ntt_l9s.hip)
-  lcpc::NttPackInfo pack_info[3]{};
-  bool l9s = false;
-  uint32_t* d_wq_w = nullptr;      // Ft255: the shifted multiples of the primitive 4th root w^(n/4) (the same element for every n), 96 words
-  bool l9s3 = false;               // 2^21 .. 2^26 columns: first-pass kernel over the whole rows, then the 2^20-point two-pass plan per block
-  uint32_t* d_roots29s = nullptr;  // l9s3: the 2^20-point twiddle tables (every 2^(log_n - 20)-th entry of d_roots29 / d_roots29c)
-  uint32_t* d_roots29cs = nullptr;
-  // Ft63 / Ft127 / Ft191 two-pass plans: the lazy-limb kernel of ntt_lns.hip (packs in d_pack / pack_info as well)
-  bool lns = false;
-  bool lns3 = false;               // the same fields at 2^21 .. 2^26 columns: three passes (sub-sampled tables in d_rootsls / d_rootslcs)
-  uint32_t* d_rootsls = nullptr;
-  uint32_t* d_rootslcs = nullptr;
-  uint32_t* d_rootsl = nullptr;    // w^i * R' mod p as N limbs of W bits (field_ln.h), ntt_lns_stride words per entry
-  uint32_t* d_rootslc = nullptr;   // w^i * R' R^-1 mod p: the table that converts to canonical on the fly (canonical-output commits)
-  uint32_t* d_qpl = nullptr;       // (i - 24) * p, i < 64, same form (ln::clamp_*)
+                                   // (Brakedown: the position-major commitment of a commit -- ws.d_t, >= SDIG_T_MIN_ROWS rows -- always holds
+                                   // canonical values: converted once in the input transpose, kept by every (linear) level)
   // Brakedown
   lcpc::SdigSpec spec{};
   std::vector<lcpc::LevelDims> pre_dims, post_dims;

@@ -51,7 +51,7 @@ def test_commit_all_two_pass_shapes_small_fields(oracle, fid, log_n, rate):
 @pytest.mark.parametrize("rate", ["1/2", "38/39"])
 def test_commit_long_rows_small_fields(oracle, fid, log_n, rate):
     """2^19 / 2^20 columns: first passes of 9 / 10 stages whose runs are 2 / 1 elements (8 bytes for Ft63 at 2^20): the tiles
-    that share cache lines run back to back on one XCD (ctx.cpp ntt_tile_group), which keeps these ahead of the general
+    that share cache lines run back to back on one XCD (ctx.cpp ntt_tile_group_of), which keeps these ahead of the general
     kernel's three-pass plan"""
     O = oracle
     n_cols = 1 << log_n
