@@ -44,8 +44,20 @@ extern "C" {
 enum { LCPC_FT63 = 0, LCPC_FT127 = 1, LCPC_FT191 = 2, LCPC_FT255 = 3 };
 /* encodings: lcpc-ligero-pc/src/lib.rs:31-37 (LigeroEncodingRho), lcpc-brakedown-pc/src/lib.rs:41-47 (SdigEncodingS) */
 enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
-/* D: Digest -- every reference test/bench uses blake3::Hasher */
-enum { LCPC_HASH_BLAKE3 = 0 };
+/* D: Digest of LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184).  Every reference test uses blake3::Hasher; the reference also
+ * benchmarks sha3::Sha3_256.  Both have 32-byte outputs, so roots, paths and `hashes` keep their layout.
+ * LCPC_HASH_SHA3_256 (FIPS 202 SHA3-256 of the same leaf and node messages), at each entry point:
+ *  - lcpc_commit, lcpc_commit_device, lcpc_commit_from_parts, lcpc_commit_from_bincode: one Keccak sponge per column over the
+ *    whole leaf message (sha3.hip; one permutation per 17 limbs), then one permutation per tree node.  The host-memory
+ *    lcpc_commit hashes after the last row batch instead of behind each batch.  Measured on one MI355X at 2^26 Ft255
+ *    coefficients (512 x 262144): column hash 3.97 ms and tree 0.22 ms, against 1.52 / 0.03 ms for BLAKE3;
+ *  - lcpc_commit_from_bincode refuses (LCPC_ERR_COMMIT) a stream whose `hashes` were made with the other digest;
+ *  - lcpc_prove, lcpc_open_columns, lcpc_collapse: unchanged (the transcript never sees D);
+ *  - lcpc_verify: leaves and path folds with the encoder's digest; a proof made under the other digest fails with
+ *    LCPC_VERR_COLUMN_PATH;
+ *  - row sharding: lcpc_ctx_create returns LCPC_ERR_ARG for shard_count > 1 (a sponge cannot be split by rows), and the
+ *    sharded commit entry points return LCPC_ERR_ARG on a SHA3 encoder. */
+enum { LCPC_HASH_BLAKE3 = 0, LCPC_HASH_SHA3_256 = 1 };
 
 typedef enum {
   LCPC_OK = 0,
@@ -84,7 +96,7 @@ typedef struct lcpc_transcript lcpc_transcript;
 typedef struct {
   uint32_t field;        /* LCPC_FT* */
   uint32_t encoding;     /* LCPC_ENC_* */
-  uint32_t hash;         /* LCPC_HASH_BLAKE3 */
+  uint32_t hash;         /* LCPC_HASH_BLAKE3 or LCPC_HASH_SHA3_256 */
   uint32_t rho_num, rho_den;  /* Ligero rate Rn/Rd (default alias 1/2: ligero lib.rs:189) */
   uint32_t sdig_code;    /* 1..6 = SdigCode1..6 (codespec.rs:169-232); default 3 (brakedown lib.rs:19) */
   uint64_t seed;         /* Brakedown matgen seed (brakedown lib.rs:103) */

@@ -15,6 +15,8 @@ from ._lib import LcpcParams, LcpcTimings
 FT63, FT127, FT191, FT255 = 0, 1, 2, 3
 FIELD_LIMBS = {FT63: 1, FT127: 2, FT191: 3, FT255: 4}
 ENC_LIGERO, ENC_SDIG = 0, 1
+# D of LcCommit<D, E>: LCPC_HASH_BLAKE3 / LCPC_HASH_SHA3_256 (include/lcpc_hip.h)
+DIGESTS = {"blake3": 0, "sha3_256": 1}
 
 
 class LcpcError(RuntimeError):
@@ -82,6 +84,7 @@ class _Encoding:
             raise LcpcError(rc)
         self._h = h
         self.field = params.field
+        self.digest = {v: k for k, v in DIGESTS.items()}[params.hash]
         self.L = FIELD_LIMBS[params.field]
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _lib.lib().lcpc_get_dims(self._h, 1, C.byref(a), C.byref(b), C.byref(c))
@@ -136,9 +139,15 @@ class _Encoding:
             pass
 
 
+def _digest_id(digest):
+    if digest not in DIGESTS:
+        raise ValueError("digest must be one of %s, not %r" % (sorted(DIGESTS), digest))
+    return DIGESTS[digest]
+
+
 def _params(field, encoding, device, **kw):
     p = LcpcParams()
-    p.field, p.encoding, p.hash, p.device = field, encoding, 0, device
+    p.field, p.encoding, p.hash, p.device = field, encoding, _digest_id(kw.get("digest", "blake3")), device
     p.rho_num, p.rho_den = kw.get("rho", (1, 2))
     p.sdig_code, p.seed = kw.get("code", 3), kw.get("seed", 0)
     p.n_coeffs, p.n_per_row, p.n_cols = kw.get("n_coeffs", 0), kw.get("n_per_row", 0), kw.get("n_cols", 0)
@@ -170,8 +179,8 @@ def static_get_dims_ml(field, encoding, n_vars, rho=(1, 2), code=3):
 class LigeroEncoding(_Encoding):
     """LigeroEncodingRho<Ft, Rn, Rd> (lcpc-ligero-pc/src/lib.rs:31-186); default rate 1/2 (lib.rs:189)."""
 
-    def __init__(self, field, length=None, rho=(1, 2), device=0, shard=(0, 1), _dims=None):
-        kw = dict(rho=rho, shard=shard)
+    def __init__(self, field, length=None, rho=(1, 2), device=0, shard=(0, 1), _dims=None, digest="blake3"):
+        kw = dict(rho=rho, shard=shard, digest=digest)
         if _dims is not None:
             kw.update(n_per_row=_dims[0], n_cols=_dims[1])
         else:
@@ -179,25 +188,25 @@ class LigeroEncoding(_Encoding):
         super().__init__(_params(field, ENC_LIGERO, device, **kw))
 
     @classmethod
-    def new(cls, field, length, rho=(1, 2), device=0, shard=(0, 1)):
-        return cls(field, length, rho, device, shard)
+    def new(cls, field, length, rho=(1, 2), device=0, shard=(0, 1), digest="blake3"):
+        return cls(field, length, rho, device, shard, digest=digest)
 
     @classmethod
-    def new_ml(cls, field, n_vars, rho=(1, 2), device=0):
+    def new_ml(cls, field, n_vars, rho=(1, 2), device=0, digest="blake3"):
         """LigeroEncodingRho::new_ml (lib.rs:128-135)."""
         _, n_per_row, n_cols = static_get_dims_ml(field, ENC_LIGERO, n_vars, rho)
-        return cls.new_from_dims(field, n_per_row, n_cols, rho, device)
+        return cls.new_from_dims(field, n_per_row, n_cols, rho, device, digest=digest)
 
     @classmethod
-    def new_from_dims(cls, field, n_per_row, n_cols, rho=(1, 2), device=0, shard=(0, 1)):
-        return cls(field, None, rho, device, shard, _dims=(n_per_row, n_cols))
+    def new_from_dims(cls, field, n_per_row, n_cols, rho=(1, 2), device=0, shard=(0, 1), digest="blake3"):
+        return cls(field, None, rho, device, shard, _dims=(n_per_row, n_cols), digest=digest)
 
 
 class SdigEncoding(_Encoding):
     """SdigEncodingS<Ft, S> (lcpc-brakedown-pc/src/lib.rs:41-176); default code SdigCode3 (lib.rs:19)."""
 
-    def __init__(self, field, length=None, seed=0, code=3, device=0, shard=(0, 1), _dims=None):
-        kw = dict(seed=seed, code=code, shard=shard)
+    def __init__(self, field, length=None, seed=0, code=3, device=0, shard=(0, 1), _dims=None, digest="blake3"):
+        kw = dict(seed=seed, code=code, shard=shard, digest=digest)
         if _dims is not None:
             kw.update(n_per_row=_dims[0], n_cols=_dims[1])
         else:
@@ -205,18 +214,18 @@ class SdigEncoding(_Encoding):
         super().__init__(_params(field, ENC_SDIG, device, **kw))
 
     @classmethod
-    def new(cls, field, length, seed, code=3, device=0):
-        return cls(field, length, seed, code, device)
+    def new(cls, field, length, seed, code=3, device=0, digest="blake3"):
+        return cls(field, length, seed, code, device, digest=digest)
 
     @classmethod
-    def new_ml(cls, field, n_vars, seed, code=3, device=0):
+    def new_ml(cls, field, n_vars, seed, code=3, device=0, digest="blake3"):
         """SdigEncodingS::new_ml (lib.rs:114-123)."""
         _, n_per_row, n_cols = static_get_dims_ml(field, ENC_SDIG, n_vars, code=code)
-        return cls.new_from_dims(field, n_per_row, n_cols, seed, code, device)
+        return cls.new_from_dims(field, n_per_row, n_cols, seed, code, device, digest=digest)
 
     @classmethod
-    def new_from_dims(cls, field, n_per_row, n_cols, seed, code=3, device=0):
-        return cls(field, None, seed, code, device, _dims=(n_per_row, n_cols))
+    def new_from_dims(cls, field, n_per_row, n_cols, seed, code=3, device=0, digest="blake3"):
+        return cls(field, None, seed, code, device, _dims=(n_per_row, n_cols), digest=digest)
 
 
 BORROW_COEFFS = 1      # LCPC_COMMIT_BORROW_COEFFS
@@ -224,7 +233,7 @@ ASYNC_TAIL = 2         # LCPC_COMMIT_ASYNC_TAIL (lcpc_commit_sharded_device)
 
 
 class LcCommit:
-    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = BLAKE3: one lcpc_commit_t -- comm / coeffs / hashes
+    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = the encoder's digest (BLAKE3 or SHA3-256): one lcpc_commit_t -- comm / coeffs / hashes
     of ONE commitment, resident in HBM.  Any number of them may be live under one encoding object (lib.rs:299-311)."""
 
     def __init__(self, enc):

@@ -65,7 +65,8 @@ int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
       }
       if (!m->h_root) (void)hipGetLastError();   // the failed call's error must not surface at the next launch check
     }
-    HIPCHK(m, launch_merkle_tree_from(m->d_hashes, c->np2, levels_done, st, m->d_root_alias));
+    if (is_sha3(c)) HIPCHK(m, launch_sha3_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
+    else HIPCHK(m, launch_merkle_tree_from(m->d_hashes, c->np2, levels_done, st, m->d_root_alias));
     m->launches[2]++;
   }
   return 0;
@@ -89,6 +90,14 @@ static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const uint64_t n_chunks = leaf_chunks(c, m->n_rows);
   LeafArgs la = leaf_args(m);
   la.row_base = 0; la.chunk_begin = 0; la.n_chunks_local = (uint32_t)n_chunks; la.n_chunks_total = (uint32_t)n_chunks;
+  if (is_sha3(c)) {
+    // SHA3-256: one sponge per column over the whole leaf message (sha3.hip), then the tree
+    la.out = m->d_hashes;
+    HIPCHK(m, launch_sha3_leaves(c->NL, la, st));
+    m->launches[1]++;
+    if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
+    return merkle_top(m, st);
+  }
   if (leaf_tree_supported(la, c->np2)) {
     // small commitment: leaf digests and the first six levels of the tree in one launch (kernels.hip leaf_tree_kernel)
     HIPCHK(m, launch_leaf_tree(c->NL, la, m->d_hashes, c->np2, st));
@@ -600,7 +609,9 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   if (padded > n_coeffs)
     HIPCHK(m, hipMemsetAsync(reinterpret_cast<uint8_t*>(m->d_coeffs) + total_bytes, 0, (size_t)(padded - n_coeffs) * eb, m->s_copy));
   const uint64_t rows_per = (n_rows + NB - 1) / NB;
-  const uint64_t n_chunks = leaf_chunks(c, n_rows);
+  // SHA3-256: a column's sponge is one serial chain over all rows, so nothing is hashed behind the batches -- the whole column
+  // hash runs after the last one (merkleize_device)
+  const uint64_t n_chunks = is_sha3(c) ? 1 : leaf_chunks(c, n_rows);
   uint64_t chunks_hashed = 0;
   m->comm_t = false;                                        // (Ligero: row-major comm; leaf_args reads it)
   if (n_chunks > 1 && (rc = ensure_cvs(m, n_chunks))) return rc;

@@ -430,4 +430,25 @@ void blake3_host(const uint8_t* in, size_t len, uint8_t out[32]) {
   memcpy(out, cv, 32);
 }
 
+void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
+  constexpr size_t RATE = 136;
+  uint64_t a[25] = {0};
+  uint8_t blk[RATE];
+  for (;;) {
+    const size_t n = len < RATE ? len : RATE;
+    memcpy(blk, in, n);
+    const bool last = n < RATE;
+    if (last) {                                    // pad10*1 with the SHA3 domain bits
+      memset(blk + n, 0, RATE - n);
+      blk[n] ^= 0x06;
+      blk[RATE - 1] ^= 0x80;
+    }
+    for (int i = 0; i < 17; i++) { uint64_t w; memcpy(&w, blk + 8 * i, 8); a[i] ^= w; }
+    keccak_f1600(a);
+    if (last) break;
+    in += n; len -= n;
+  }
+  memcpy(out, a, 32);
+}
+
 }  // namespace lcpc

@@ -64,5 +64,7 @@ class ChaCha20Rng {
 
 // BLAKE3 (plain hash, 32-byte output) of a contiguous message
 void blake3_host(const uint8_t* in, size_t len, uint8_t out[32]);
+// SHA3-256 (FIPS 202) of a contiguous message, on keccak_f1600 (so LCPC_KECCAK selects its form as for the transcript)
+void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]);
 
 }  // namespace lcpc

@@ -248,6 +248,7 @@ template <typename T> int ensure_dev(std::string* err, T** p, uint64_t* cap, uin
 }
 
 inline size_t elem_bytes(const lcpc_ctx* c) { return (size_t)8 * c->L; }
+inline bool is_sha3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA3_256; }
 // leaf message = 32 + F * n_rows bytes -> BLAKE3 chunks of 1 KiB
 inline uint64_t leaf_chunks(const lcpc_ctx* c, uint64_t n_rows) { return (32 + elem_bytes(c) * n_rows + 1023) / 1024; }
 

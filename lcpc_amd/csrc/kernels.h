@@ -104,6 +104,12 @@ hipError_t launch_merkle_tree_from(uint32_t* hashes, uint64_t np2, uint32_t leve
 bool leaf_tree_supported(const LeafArgs& a, uint64_t np2);
 hipError_t launch_leaf_tree(int nl, const LeafArgs& a, uint32_t* hashes, uint64_t np2, hipStream_t st);
 
+// ---- SHA3-256 digest (sha3.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA3_256 ----
+// leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a sponge is not split); a.out = LcCommit.hashes
+hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);
+// the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
+hipError_t launch_sha3_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
+
 struct CollapseArgs {
   const uint32_t* coeffs;      // local rows x n_per_row
   const uint32_t* tensors;     // [n_tensors][n_rows_local]

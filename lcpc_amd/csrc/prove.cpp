@@ -231,14 +231,16 @@ struct Rd {
   uint64_t u64_() { uint64_t v = 0; if (pos + 8 > len) { bad = true; return 0; } memcpy(&v, p + pos, 8); pos += 8; return v; }
   const uint8_t* take(uint64_t n) { if (n > len - pos) { bad = true; return nullptr; } const uint8_t* q = p + pos; pos += n; return q; }
 };
-void hash_column_host(const FieldDesc& f, const uint64_t* col, uint64_t n_rows, uint8_t out[32]) {
+// D(0^32 || to_repr(col[0]) || ...) with the encoder's digest (lib.rs:719-735)
+void hash_column_host(const FieldDesc& f, bool sha3, const uint64_t* col, uint64_t n_rows, uint8_t out[32]) {
   std::vector<uint8_t> msg(32 + n_rows * 8 * f.L, 0);
   for (uint64_t r = 0; r < n_rows; r++) {
     uint64_t t[MAXL];
     h_canon(f, t, col + r * f.L);
     memcpy(&msg[32 + r * 8 * f.L], t, 8 * f.L);
   }
-  blake3_host(msg.data(), msg.size(), out);
+  if (sha3) sha3_256_host(msg.data(), msg.size(), out);
+  else blake3_host(msg.data(), msg.size(), out);
 }
 // every element of an untrusted vector must be a reduced Montgomery representative (< p): the device arithmetic
 // (lazy-limb NTT, lazy dot products) is only proven for reduced inputs.  The reference's derived Deserialize
@@ -286,6 +288,7 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   if (!c || !root || !outer || !inner || !proof || !trw || !eval_out) return LCPC_ERR_ARG;
   LCPC_TRY
   const FieldDesc& f = *c->f;
+  const bool sha3 = is_sha3(c);               // the leaf and node digest (verify_column_path lib.rs:955-982)
   const int L = f.L;
   const uint64_t F = 8 * L;
   Transcript& tr = trw->t;
@@ -439,7 +442,7 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
             for (uint64_t k = 0; k < n_rows; k++) { h_mul(f, t, tensor + k * L, cols[i].data() + k * L); h_add(f, acc, acc, t); }
             memcpy(&dots[(d * n_columns + i) * MAXL], acc, F);
           }
-          hash_column_host(f, cols[i].data(), n_rows, &leaf[i * 32]);
+          hash_column_host(f, sha3, cols[i].data(), n_rows, &leaf[i * 32]);
         }
       }, n_columns * n_rows > ((uint64_t)1 << 19) ? 64u : 15u);       // Brakedown opens 6593 columns: ~0.1 s of work single-threaded
       t_side = now_ms() - t0;
@@ -497,7 +500,8 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
       for (uint64_t k = 0; k < paths[i].n; k++) {
         const uint8_t* pk = paths[i].p + 40 * k + 8;
         if (cc % 2 == 0) { memcpy(blk, h, 32); memcpy(blk + 32, pk, 32); } else { memcpy(blk, pk, 32); memcpy(blk + 32, h, 32); }
-        blake3_host(blk, 64, h);
+        if (sha3) sha3_256_host(blk, 64, h);
+        else blake3_host(blk, 64, h);
         cc >>= 1;
       }
       const bool pth = memcmp(h, root, 32) == 0;
