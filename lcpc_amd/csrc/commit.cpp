@@ -21,8 +21,9 @@ int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks) {
   return rc;
 }
 
-// comm (unless the commitment will live position-major in ws.d_t), coeffs (unless borrowed), hashes
-int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs) {
+// comm (unless the commitment will live position-major in ws.d_t and nothing asks for the row-major one: comm_rows), coeffs
+// (unless borrowed), hashes
+int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows) {
   const lcpc_ctx* c = m->enc;
   const size_t eb = elem_bytes(c);
   const uint64_t rows = n_rows_local ? n_rows_local : 1;
@@ -32,7 +33,7 @@ int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coef
     if ((rc = dev_alloc(&m->err, &m->d_coeffs, (size_t)rows * c->n_per_row * eb))) return rc;
     m->cap_coeff_rows = rows;
   }
-  const bool need_comm = !(c->prm.encoding == LCPC_ENC_SDIG && n_rows_local >= SDIG_T_MIN_ROWS);   // else made on demand (lcpc_get_comm)
+  const bool need_comm = comm_rows || !(c->prm.encoding == LCPC_ENC_SDIG && n_rows_local >= SDIG_T_MIN_ROWS);   // else made on demand (lcpc_get_comm)
   if (need_comm && (rows > m->cap_comm_rows || !m->d_comm)) {
     dev_free(m->d_comm); m->d_comm = nullptr; m->cap_comm_rows = 0;
     if ((rc = dev_alloc(&m->err, &m->d_comm, (size_t)rows * c->n_cols * eb))) return rc;
@@ -42,13 +43,24 @@ int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coef
   return 0;
 }
 
+// the column hash of the object's rows and chunk range (begin_commit)
 static LeafArgs leaf_args(const lcpc_commit_t* m) {
   const lcpc_ctx* c = m->enc;
   LeafArgs la{};
   la.comm = m->d_comm; la.canon_in = c->comm_canon ? 1u : 0u; la.row_stride = c->n_cols; la.col_stride = 1; la.n_cols = c->n_cols;
   if (m->comm_t) { la.comm = m->ws.d_t; la.canon_in = 1u; la.row_stride = 1; la.col_stride = m->n_rows_local; }
-  la.n_rows_total = m->n_rows;
+  la.row_base = (int64_t)m->row_begin; la.n_rows_total = m->n_rows;
+  la.chunk_begin = (uint32_t)m->chunk_begin; la.n_chunks_local = (uint32_t)(m->chunk_end - m->chunk_begin);
+  la.n_chunks_total = (uint32_t)m->n_chunks;
   return la;
+}
+
+int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st) {
+  LeafArgs la = leaf_args(m);
+  la.chunk_begin = (uint32_t)a; la.n_chunks_local = (uint32_t)(b - a); la.out = out;
+  HIPCHK(m, launch_leaf_chunks(m->enc->NL, la, st));
+  m->launches[1]++;
+  return 0;
 }
 
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
@@ -72,7 +84,7 @@ int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
   return 0;
 }
 // the root of a commit that was just enqueued on `st`, on the host (synchronises the stream)
-int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
+static int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   const lcpc_ctx* c = m->enc;
   if (m->d_root_alias && c->np2 > 1) {
     HIPCHK(m, hipStreamSynchronize(st));
@@ -84,12 +96,21 @@ int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   return 0;
 }
 
+// the chunk chaining values of every column in d_cvs (n_chunks > 1) -> leaf digests; then the tree
+static int finish_leaves(lcpc_commit_t* m, hipStream_t st) {
+  const lcpc_ctx* c = m->enc;
+  if (m->n_chunks > 1) {
+    HIPCHK(m, launch_leaf_finish(m->d_cvs, (uint32_t)m->n_chunks, c->n_cols, m->d_hashes, st));
+    m->launches[1]++;
+  }
+  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
+  return merkle_top(m, st);
+}
+
 // hash_columns + merkle_tree on the local comm (unsharded) -- lib.rs:690-704
 static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
-  const uint64_t n_chunks = leaf_chunks(c, m->n_rows);
   LeafArgs la = leaf_args(m);
-  la.row_base = 0; la.chunk_begin = 0; la.n_chunks_local = (uint32_t)n_chunks; la.n_chunks_total = (uint32_t)n_chunks;
   if (is_sha3(c)) {
     // SHA3-256: one sponge per column over the whole leaf message (sha3.hip), then the tree
     la.out = m->d_hashes;
@@ -105,49 +126,49 @@ static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
     return merkle_top(m, st, 6);
   }
-  if (n_chunks == 1) {
-    la.out = m->d_hashes;
-    HIPCHK(m, launch_leaf_chunks(c->NL, la, st));
-    m->launches[1]++;
-  } else {
-    int rc = ensure_cvs(m, n_chunks);
-    if (rc) return rc;
-    la.out = m->d_cvs;
-    HIPCHK(m, launch_leaf_chunks(c->NL, la, st));
-    HIPCHK(m, launch_leaf_finish(m->d_cvs, (uint32_t)n_chunks, c->n_cols, m->d_hashes, st));
-    m->launches[1] += 2;
-  }
-  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
-  return merkle_top(m, st);
+  int rc = m->n_chunks > 1 ? ensure_cvs(m, m->n_chunks) : 0;
+  if (!rc) rc = hash_chunks(m, 0, m->n_chunks, m->n_chunks > 1 ? m->d_cvs : m->d_hashes, st);   // (one chunk: the digests themselves)
+  return rc ? rc : finish_leaves(m, st);
 }
 
-int finish_timing(lcpc_commit_t* m, hipStream_t st) {
-  if (!m->timing) return 0;
-  HIPCHK(m, hipEventRecord(m->ev[3], st));
-  HIPCHK(m, hipEventSynchronize(m->ev[3]));
-  (void)hipEventElapsedTime(&m->last.encode_ms, m->ev[0], m->ev[1]);
-  (void)hipEventElapsedTime(&m->last.hash_ms, m->ev[1], m->ev[2]);
-  (void)hipEventElapsedTime(&m->last.merkle_ms, m->ev[2], m->ev[3]);
-  (void)hipEventElapsedTime(&m->last.total_ms, m->ev[0], m->ev[3]);
-  m->last.encode_launches = m->launches[0];
-  m->last.hash_launches = m->launches[1];
-  m->last.merkle_launches = m->launches[2];
+int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
+  if (m->timing) {
+    HIPCHK(m, hipEventRecord(m->ev[3], st));
+    HIPCHK(m, hipEventSynchronize(m->ev[3]));
+    (void)hipEventElapsedTime(&m->last.encode_ms, m->ev[0], m->ev[1]);
+    (void)hipEventElapsedTime(&m->last.hash_ms, m->ev[1], m->ev[2]);
+    (void)hipEventElapsedTime(&m->last.merkle_ms, m->ev[2], m->ev[3]);   // (sharded: includes whatever of the exchange is exposed)
+    (void)hipEventElapsedTime(&m->last.total_ms, m->ev[0], m->ev[3]);
+    m->last.encode_launches = m->launches[0];
+    m->last.hash_launches = m->launches[1];
+    m->last.merkle_launches = m->launches[2];
+  }
+  m->committed = true;
+  // whatever reads the commitment next (prove, collapse, open, the getters, a sharded prove's own stream) and the next fill may run
+  // on another stream, and a caller's NON-BLOCKING stream is not implicitly ordered before those: they wait for this event
+  if (!m->ev_done) HIPCHK(m, hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming));
+  HIPCHK(m, hipEventRecord(m->ev_done, st));
+  if (root) return fetch_root(m, st, root);
   return 0;
 }
 
 // a new commit starts: whatever the object held is gone, and stays gone if anything below fails.  `st` -- the stream that
 // will rewrite the object's buffers -- is first ordered behind the commit that filled them last (which may still be running
 // on another, non-blocking stream of the caller: lcpc_commit_device only enqueues)
-static int begin_commit(lcpc_commit_t* m, hipStream_t st, uint64_t n_rows_total, uint64_t row_begin, uint64_t n_rows_local) {
+int begin_commit(lcpc_commit_t* m, hipStream_t st, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end, uint64_t chunk_begin,
+                 uint64_t chunk_end) {
   int rc = order_after_commit(m, st);
   if (rc) return rc;
   m->committed = false;
   m->comm_t = false;
   m->comm_rows_valid = false;
   m->coeffs_view = nullptr;
-  m->n_rows = n_rows_total; m->row_begin = row_begin; m->n_rows_local = n_rows_local;
+  m->n_rows = n_rows_total; m->row_begin = row_begin; m->n_rows_local = row_end - row_begin;
+  m->chunk_begin = chunk_begin; m->chunk_end = chunk_end; m->n_chunks = leaf_chunks(m->enc, n_rows_total);
   m->launches[0] = m->launches[1] = m->launches[2] = 0;
   m->last.staged_slices = 0;
+  m->last.exchange_exposed_ms = 0.f; m->last.exchange_wire_ms = 0.f;
+  m->shard_encoded = false;
   return 0;
 }
 
@@ -169,22 +190,41 @@ static int encode_commit(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src_t
   return 0;
 }
 
-// can the first encode pass write the coeffs copy on the fly?  (Ligero: fused into the first NTT pass; Brakedown with
-// >= SDIG_T_MIN_ROWS rows: fused into the input transpose)
-static bool fused_copy(const lcpc_ctx* c, uint64_t n_rows_local) { return c->prm.encoding == LCPC_ENC_LIGERO || n_rows_local >= SDIG_T_MIN_ROWS; }
+// the padding of LcCommit.coeffs behind the n_src elements a source filled reads as zero (nothing to do when the rows are whole)
+static int zero_coeffs_tail(lcpc_commit_t* m, uint64_t n_src, hipStream_t st) {
+  const uint64_t padded = m->n_rows_local * m->enc->n_per_row;
+  const size_t eb = elem_bytes(m->enc);
+  if (padded > n_src) HIPCHK(m, hipMemsetAsync(reinterpret_cast<uint8_t*>(m->d_coeffs) + (size_t)n_src * eb, 0, (size_t)(padded - n_src) * eb, st));
+  return 0;
+}
 
+int encode_coeffs(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src, bool borrow, hipStream_t st) {
+  const lcpc_ctx* c = m->enc;
+  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
+  int rc = 0;
+  if (m->n_rows_local == 0) {
+    // a shard without rows: nothing to encode
+  } else if (borrow) {
+    // LcCommit.coeffs IS the caller's buffer: nothing but comm and the digests is written
+    rc = encode_commit(m, src, n_src, false, st);
+  } else if (c->prm.encoding == LCPC_ENC_LIGERO || m->n_rows_local >= SDIG_T_MIN_ROWS) {
+    // the padded local copy of coeffs (lib.rs:636-645; LcCommit keeps it for prove) is written by the first
+    // NTT pass (Ligero) / the input transpose (Brakedown, position-major path) while it streams the caller's buffer
+    rc = encode_commit(m, src, n_src, true, st);
+  } else {
+    HIPCHK(m, hipMemcpyAsync(m->d_coeffs, src, (size_t)n_src * elem_bytes(c), hipMemcpyDeviceToDevice, st));
+    if (!(rc = zero_coeffs_tail(m, n_src, st))) rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, st);
+  }
+  if (rc) return rc;
+  m->coeffs_view = borrow ? src : m->d_coeffs;
+  return 0;
+}
+
+// hash + seal of an unsharded commit whose encode is enqueued on `st`
 static int commit_tail(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   if (m->timing) HIPCHK(m, hipEventRecord(m->ev[1], st));
-  int rc;
-  if ((rc = merkleize_device(m, st))) return rc;
-  if ((rc = finish_timing(m, st))) return rc;
-  m->committed = true;
-  // whatever reads the commitment next (prove, collapse, open, the getters) runs on another stream -- the null stream, or the
-  // sharded prover's own -- and a caller's NON-BLOCKING stream is not implicitly ordered before those: they wait for this event
-  if (!m->ev_done) HIPCHK(m, hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming));
-  HIPCHK(m, hipEventRecord(m->ev_done, st));
-  if (root) return fetch_root(m, st, root);
-  return 0;
+  int rc = merkleize_device(m, st);
+  return rc ? rc : seal_commit(m, st, root);
 }
 // order `st` behind the commit that filled this object (no-op when the commit ran on `st` itself or has long finished)
 int order_after_commit(lcpc_commit_t* m, hipStream_t st) {
@@ -445,30 +485,11 @@ int lcpc_commit_device(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_
   HIPCHK(m, hipSetDevice(c->prm.device));
   hipStream_t st = (hipStream_t)stream;
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;    // get_dims (ligero lib.rs:166-169)
-  int rc = begin_commit(m, st, n_rows, 0, n_rows);
+  int rc = begin_commit(m, st, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
-  const uint64_t padded = n_rows * c->n_per_row;
-  const bool borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && padded == n_coeffs;
-  if ((rc = ensure_commit_buffers(m, n_rows, !borrow))) return rc;
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(coeffs_dev);
-  const size_t eb = elem_bytes(c);
-  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
-  if (borrow) {
-    // LcCommit.coeffs IS the caller's buffer: nothing but comm and the digests is written
-    if ((rc = encode_commit(m, src, n_coeffs, false, st))) return rc;
-    m->coeffs_view = src;
-  } else if (fused_copy(c, n_rows)) {
-    // the padded local copy of coeffs (lib.rs:636-645; LcCommit keeps it for prove) is written by the first
-    // NTT pass (Ligero) / the input transpose (Brakedown, position-major path) while it streams the caller's buffer
-    if ((rc = encode_commit(m, src, n_coeffs, true, st))) return rc;
-    m->coeffs_view = m->d_coeffs;
-  } else {
-    HIPCHK(m, hipMemcpyAsync(m->d_coeffs, coeffs_dev, (size_t)n_coeffs * eb, hipMemcpyDeviceToDevice, st));
-    if (padded > n_coeffs)
-      HIPCHK(m, hipMemsetAsync(reinterpret_cast<uint8_t*>(m->d_coeffs) + (size_t)n_coeffs * eb, 0, (size_t)(padded - n_coeffs) * eb, st));
-    if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, st))) return rc;
-    m->coeffs_view = m->d_coeffs;
-  }
+  const bool borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && n_rows * c->n_per_row == n_coeffs;
+  if ((rc = ensure_commit_buffers(m, n_rows, !borrow, false))) return rc;
+  if ((rc = encode_coeffs(m, reinterpret_cast<const uint32_t*>(coeffs_dev), n_coeffs, borrow, st))) return rc;
   return commit_tail(m, st, root);
   LCPC_CATCH(m)
 }
@@ -573,11 +594,10 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
-  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows);
+  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
-  if ((rc = ensure_commit_buffers(m, n_rows, true))) return rc;
+  if ((rc = ensure_commit_buffers(m, n_rows, true, false))) return rc;
   const size_t eb = elem_bytes(c);
-  const uint64_t padded = n_rows * c->n_per_row;
   const size_t total_bytes = (size_t)n_coeffs * eb;
   // pageable source (a Rust Vec, malloc, numpy): staged through pinned bounce buffers by the host pool; small ones are not worth the ring
   const bool pinned = c->sw_host_stage == 0 || (c->sw_host_stage < 0 && (total_bytes < ((size_t)4 << 20) || host_ptr_is_pinned(coeffs))) ||
@@ -585,8 +605,7 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   // Small inputs, Brakedown (whole-matrix transposes) and timing runs: one copy, then the resident path.
   if (c->prm.encoding != LCPC_ENC_LIGERO || total_bytes < ((size_t)64 << 20) || n_rows < 16 || m->timing) {
     if ((rc = upload_host(m, m->d_coeffs, coeffs, total_bytes, total_bytes, nullptr, pinned))) return rc;
-    if (padded > n_coeffs)
-      HIPCHK(m, hipMemsetAsync(reinterpret_cast<uint8_t*>(m->d_coeffs) + total_bytes, 0, (size_t)(padded - n_coeffs) * eb, nullptr));
+    if ((rc = zero_coeffs_tail(m, n_coeffs, nullptr))) return rc;
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], nullptr));
     if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, nullptr))) return rc;
     m->coeffs_view = m->d_coeffs;
@@ -602,19 +621,24 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   constexpr int NB = 16;
   for (auto& e : m->ev_batch)
     if (!e) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  // One exit: whatever fails from here on, the copies from the caller's buffer and the work behind them have left both streams
+  // before lcpc_commit returns -- as on success
+  struct Drain {
+    lcpc_commit_t* m;
+    bool armed = true;
+    ~Drain() { if (armed) { (void)hipStreamSynchronize(m->s_copy); (void)hipStreamSynchronize(m->s_comp); } }
+  } drain{m};
   // Earlier work on this object's buffers: the last fill is ordered by its event (begin_commit put the null stream behind it;
   // the two streams of this path wait for it as well), and every host-pointer reader (prove, collapse, open, the getters) has
   // synchronised before it returned.  No device-wide synchronisation: other contexts and streams of the process keep running.
   if ((rc = order_after_commit(m, m->s_copy)) || (rc = order_after_commit(m, m->s_comp))) return rc;
-  if (padded > n_coeffs)
-    HIPCHK(m, hipMemsetAsync(reinterpret_cast<uint8_t*>(m->d_coeffs) + total_bytes, 0, (size_t)(padded - n_coeffs) * eb, m->s_copy));
+  if ((rc = zero_coeffs_tail(m, n_coeffs, m->s_copy))) return rc;
   const uint64_t rows_per = (n_rows + NB - 1) / NB;
   // SHA3-256: a column's sponge is one serial chain over all rows, so nothing is hashed behind the batches -- the whole column
   // hash runs after the last one (merkleize_device)
-  const uint64_t n_chunks = is_sha3(c) ? 1 : leaf_chunks(c, n_rows);
+  const bool per_batch = !is_sha3(c) && m->n_chunks > 1;
   uint64_t chunks_hashed = 0;
-  m->comm_t = false;                                        // (Ligero: row-major comm; leaf_args reads it)
-  if (n_chunks > 1 && (rc = ensure_cvs(m, n_chunks))) return rc;
+  if (per_batch && (rc = ensure_cvs(m, m->n_chunks))) return rc;
   for (int b = 0; b < NB; b++) {
     const uint64_t r0 = (uint64_t)b * rows_per;
     if (r0 >= n_rows) break;
@@ -632,29 +656,20 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
     // 1024 / F rows, lib.rs:719-735): the chunks the encoded rows complete are hashed now, under the upload of the next batches, and
     // only the last batch's chunks, the fold and the tree remain behind the bus -- the reference hashes after its encode loop
     // (lib.rs:648-671), same digests
-    if (n_chunks > 1) {
-      const uint64_t done = r1 == n_rows ? n_chunks : std::min<uint64_t>(n_chunks, (32 + (uint64_t)eb * r1) / 1024);
+    if (per_batch) {
+      const uint64_t done = r1 == n_rows ? m->n_chunks : std::min<uint64_t>(m->n_chunks, (32 + (uint64_t)eb * r1) / 1024);
       if (done > chunks_hashed) {
-        LeafArgs la = leaf_args(m);
-        la.row_base = 0; la.n_chunks_total = (uint32_t)n_chunks;
-        la.chunk_begin = (uint32_t)chunks_hashed; la.n_chunks_local = (uint32_t)(done - chunks_hashed);
-        la.out = m->d_cvs + chunks_hashed * c->n_cols * 8;
-        HIPCHK(m, launch_leaf_chunks(c->NL, la, m->s_comp));
-        m->launches[1]++;
+        if ((rc = hash_chunks(m, chunks_hashed, done, m->d_cvs + chunks_hashed * c->n_cols * 8, m->s_comp))) return rc;
         chunks_hashed = done;
       }
     }
   }
   m->coeffs_view = m->d_coeffs;
-  if (n_chunks > 1) {
-    HIPCHK(m, launch_leaf_finish(m->d_cvs, (uint32_t)n_chunks, c->n_cols, m->d_hashes, m->s_comp));
-    m->launches[1]++;
-    if ((rc = merkle_top(m, m->s_comp))) return rc;
-  } else if ((rc = merkleize_device(m, m->s_comp))) return rc;
-  if (root) HIPCHK(m, hipMemcpyAsync(root, m->d_hashes + (2 * c->np2 - 2) * 8, 32, hipMemcpyDeviceToHost, m->s_comp));
+  if ((rc = per_batch ? finish_leaves(m, m->s_comp) : merkleize_device(m, m->s_comp))) return rc;
+  if ((rc = seal_commit(m, m->s_comp, root))) return rc;
   HIPCHK(m, hipStreamSynchronize(m->s_comp));              // later calls use the null stream / caller streams
   HIPCHK(m, hipStreamSynchronize(m->s_copy));              // (the tail memset when no batch followed it)
-  m->committed = true;
+  drain.armed = false;
   return 0;
   LCPC_CATCH(m)
 }
@@ -665,15 +680,10 @@ int lcpc_commit_from_parts(lcpc_commit_t* m, const uint64_t* comm, const uint64_
   LCPC_TRY
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
-  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows);
+  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
   const size_t eb = elem_bytes(c);
-  if ((rc = ensure_commit_buffers(m, n_rows, true))) return rc;
-  if (!m->d_comm || m->cap_comm_rows < n_rows) {           // (Brakedown, position-major path: ensure_commit_buffers leaves comm for later)
-    dev_free(m->d_comm); m->d_comm = nullptr; m->cap_comm_rows = 0;
-    if ((rc = dev_alloc(&m->err, &m->d_comm, (size_t)n_rows * c->n_cols * eb))) return rc;
-    m->cap_comm_rows = n_rows;
-  }
+  if ((rc = ensure_commit_buffers(m, n_rows, true, true))) return rc;
   HIPCHK(m, hipMemcpy(m->d_comm, comm, (size_t)n_rows * c->n_cols * eb, hipMemcpyHostToDevice));
   if (c->comm_canon) HIPCHK(m, launch_to_canon(c->NL, m->d_comm, n_rows * c->n_cols, m->d_comm, nullptr));
   if (coeffs) HIPCHK(m, hipMemcpy(m->d_coeffs, coeffs, (size_t)n_rows * c->n_per_row * eb, hipMemcpyHostToDevice));
@@ -755,14 +765,9 @@ int lcpc_commit_from_bincode(lcpc_commit_t* m, lcpc_read_fn fn, void* user, uint
     HIPCHK(m, hipMemGetInfo(&free_b, &total_b));
     if (n_rows * (c->n_cols + c->n_per_row) > total_b / eb) return LCPC_ERR_COMMIT;
   }
-  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows);
+  int rc = begin_commit(m, nullptr, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
-  if ((rc = ensure_commit_buffers(m, n_rows, true))) return rc;
-  if (!m->d_comm || m->cap_comm_rows < n_rows) {           // (Brakedown, position-major path: ensure_commit_buffers leaves comm for later)
-    dev_free(m->d_comm); m->d_comm = nullptr; m->cap_comm_rows = 0;
-    if ((rc = dev_alloc(&m->err, &m->d_comm, (size_t)n_rows * c->n_cols * eb))) return rc;
-    m->cap_comm_rows = n_rows;
-  }
+  if ((rc = ensure_commit_buffers(m, n_rows, true, true))) return rc;
   std::vector<uint64_t> buf;
   // an element vector of the stream -> device, a piece at a time; untrusted limbs: nothing >= p reaches device arithmetic
   auto upload = [&](uint32_t* dst, uint64_t n_elems) -> int {
@@ -845,12 +850,8 @@ int lcpc_get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
   { int orc = order_after_commit(m, nullptr); if (orc) return orc; }
   const size_t eb = elem_bytes(c);
   if (m->comm_t && !m->comm_rows_valid) {      // Brakedown: the commitment is position-major; make the row-major view once
-    if (!m->d_comm || m->cap_comm_rows < m->n_rows_local) {
-      dev_free(m->d_comm); m->d_comm = nullptr; m->cap_comm_rows = 0;
-      int rc = dev_alloc(&m->err, &m->d_comm, (size_t)m->n_rows_local * c->n_cols * eb);
-      if (rc) return rc;
-      m->cap_comm_rows = m->n_rows_local;
-    }
+    int rc = ensure_commit_buffers(m, m->n_rows_local, false, true);
+    if (rc) return rc;
     HIPCHK(m, launch_transpose_from_t(c->NL, m->ws.d_t, c->n_cols, m->n_rows_local, m->d_comm, c->n_cols, nullptr));
     HIPCHK(m, hipStreamSynchronize(nullptr));
     m->comm_rows_valid = true;

@@ -182,7 +182,8 @@ struct lcpc_commit_s {
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // start | encoded | hashed | done; [4]: the commit's stream
                                    // has the leaf digests (sharded commit: behind the exchange); [5]: the exchange's collectives are done
   hipStream_t s_prove = nullptr;   // sharded prove: its device steps and the native exchange, ordered behind the commit by ev_done
-  hipEvent_t ev_done = nullptr;    // recorded on the commit's stream when a sharded commit has been enqueued completely
+  hipEvent_t ev_done = nullptr;    // recorded behind every fill, on the stream that completed it (seal_commit): readers, refills and
+                                   // the sharded prove's stream wait for it
   // native sharded commit (shard.cpp): the exchange stream of an async tail and its hand-over event
   hipStream_t s_xchg = nullptr;
   hipEvent_t ev_hashed = nullptr;  // recorded on the caller's stream behind the local column hash; s_xchg waits for it
@@ -279,11 +280,22 @@ int encode_msgs_host(lcpc_ctx* c, const uint64_t* const* msgs, uint64_t n_rows, 
 // ---- commit.cpp -------------------------------------------------------------------------------------
 int ensure_scratch(lcpc_commit_t* m, uint64_t bytes);
 int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks);
-int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs);
-int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);       // zero padding leaves + tree above the leaf digests (above level `levels_done`)
+// The stages of every commit entry point (unsharded: rows [0, n_rows), chunks [0, leaf_chunks(n_rows)); a row shard: its own ranges):
+//   begin_commit            st behind the previous fill; every per-commit field reset, the row / chunk range set
+//   ensure_commit_buffers   comm_rows: a row-major d_comm even where the commitment would live position-major (from_parts, bincode)
+//   encode_coeffs           device source src (n_src elements, the rest of the last row zero) -> comm; coeffs_view / comm_t.
+//                           LcCommit.coeffs is the caller's buffer (borrow), the copy the first pass writes, or a copy made first
+//   hash_chunks             leaf-message chunks [a, b) of every column -> chaining values out[b - a][n_cols] (one chunk in all: the digests)
+//   merkle_top              zero padding leaves + tree above the leaf digests (above level `levels_done`)
+//   seal_commit             timings, committed, ev_done; the root -> host when asked for (synchronises st)
+int begin_commit(lcpc_commit_t* m, hipStream_t st, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end, uint64_t chunk_begin,
+                 uint64_t chunk_end);
+int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows);
+int encode_coeffs(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src, bool borrow, hipStream_t st);
+int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st);
+int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);
+int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);
 int order_after_commit(lcpc_commit_t* m, hipStream_t st);          // st waits for the commit that filled m (event; cheap)
-int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root);   // root of the commit just enqueued on st -> host (synchronises)
-int finish_timing(lcpc_commit_t* m, hipStream_t st);
 int collapse_run(lcpc_commit_t* m, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys);
 size_t collapse_scratch_bytes(const lcpc_commit_t* m, uint32_t n_tensors);
 int collapse_host(lcpc_commit_t* m, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys, uint64_t* polys_canon);

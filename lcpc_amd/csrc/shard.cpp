@@ -263,47 +263,16 @@ int open_sharded(lcpc_commit_t* m, const ShardXchg& x, const uint64_t* cols, uin
 // (Round 4 could slice the middle two by column ranges so that one slice's exchange overlapped the next slice's hashing: measured
 // neutral to negative -- LABNOTES "exchange slicing" -- and removed in round 5 together with its four column-range entry points.)
 static int shard_encode_phase(lcpc_commit_t* m, const uint64_t* coeffs_local, uint64_t n_rows_total, hipStream_t st, uint32_t flags) {
-  const lcpc_ctx* c = m->enc;
   uint64_t rb, re, cb, ce, nch;
-  shard_layout_of(c, c->prm.shard_rank, n_rows_total, &rb, &re, &cb, &ce, &nch);
-  int rc = order_after_commit(m, st);      // a refill on another stream than the previous fill's: behind that fill
+  shard_layout_of(m->enc, m->enc->prm.shard_rank, n_rows_total, &rb, &re, &cb, &ce, &nch);
+  int rc = begin_commit(m, st, n_rows_total, rb, re, cb, ce);
   if (rc) return rc;
-  m->committed = false;
-  m->comm_t = false; m->comm_rows_valid = false; m->coeffs_view = nullptr;
-  m->n_rows = n_rows_total; m->row_begin = rb; m->n_rows_local = re - rb;
-  m->chunk_begin = cb; m->chunk_end = ce; m->n_chunks = nch;
-  m->launches[0] = m->launches[1] = m->launches[2] = 0;
-  m->last.exchange_exposed_ms = 0.f; m->last.exchange_wire_ms = 0.f;
-  m->shard_encoded = false;
-  const bool fused = c->prm.encoding == LCPC_ENC_LIGERO || m->n_rows_local >= SDIG_T_MIN_ROWS;
-  const bool borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) != 0 && m->n_rows_local > 0;   // local rows are always whole rows
-  rc = ensure_commit_buffers(m, m->n_rows_local, !borrow);
+  const bool borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) != 0 && m->n_rows_local > 0;
+  if ((rc = ensure_commit_buffers(m, m->n_rows_local, !borrow, false))) return rc;
+  if (m->n_rows_local && !coeffs_local) return LCPC_ERR_ARG;
+  // local rows are always whole rows: the source has n_rows_local * n_per_row elements
+  rc = encode_coeffs(m, reinterpret_cast<const uint32_t*>(coeffs_local), m->n_rows_local * m->enc->n_per_row, borrow, st);
   if (rc) return rc;
-  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
-  if (m->n_rows_local) {
-    if (!coeffs_local) return LCPC_ERR_ARG;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(coeffs_local);
-    EncodeJob j;
-    j.src_stride = c->n_per_row; j.n_valid = c->n_per_row; j.dst = m->d_comm; j.n_rows = m->n_rows_local;
-    j.canon_out = c->prm.encoding == LCPC_ENC_SDIG ? true : c->comm_canon; j.keep_t = true;
-    bool kept = false;
-    j.kept_t = &kept;
-    if (borrow) {
-      j.src = src;
-      m->coeffs_view = src;
-    } else if (fused) {
-      j.src = src; j.copy_dst = m->d_coeffs;       // coeffs copy fused into the first pass / the input transpose
-      m->coeffs_view = m->d_coeffs;
-    } else {
-      HIPCHK(m, hipMemcpyAsync(m->d_coeffs, coeffs_local, (size_t)m->n_rows_local * c->n_per_row * elem_bytes(c), hipMemcpyDeviceToDevice, st));
-      j.src = m->d_coeffs;
-      m->coeffs_view = m->d_coeffs;
-    }
-    if ((rc = encode_rows_device(c, &m->ws, j, st, &m->err, &m->launches[0]))) return rc;
-    m->comm_t = kept;
-  } else {
-    m->coeffs_view = m->d_coeffs;
-  }
   if (m->timing) HIPCHK(m, hipEventRecord(m->ev[1], st));
   if (ce > cb && (rc = ensure_cvs(m, ce - cb))) return rc;      // (all slices share it; sized once so that no slice reallocates)
   m->shard_encoded = true;
@@ -312,36 +281,22 @@ static int shard_encode_phase(lcpc_commit_t* m, const uint64_t* coeffs_local, ui
 
 // the columns of the local rows -> one chaining value per (local node, column): nodes_dev[k][n_cols][32 B]
 static int shard_hash_cols(lcpc_commit_t* m, hipStream_t st, uint8_t* nodes_dev) {
-  const lcpc_ctx* c = m->enc;
-  const uint64_t cb = m->chunk_begin, ce = m->chunk_end, w = c->n_cols;
+  const uint64_t cb = m->chunk_begin, ce = m->chunk_end, w = m->enc->n_cols;
   if (ce <= cb) return 0;
   uint64_t first[64];
   uint32_t lg[64];
   const int n_nodes = shard_nodes(cb, ce, first, lg);
   bool all_single = true;
   for (int k = 0; k < n_nodes; k++) all_single = all_single && lg[k] == 0;
-  LeafArgs la{};
-  la.comm = m->d_comm; la.canon_in = c->comm_canon ? 1u : 0u; la.row_stride = c->n_cols; la.col_stride = 1;
-  if (m->comm_t) { la.comm = m->ws.d_t; la.canon_in = 1u; la.row_stride = 1; la.col_stride = m->n_rows_local; }
-  la.n_cols = w; la.row_base = (int64_t)m->row_begin;
-  la.n_rows_total = m->n_rows; la.chunk_begin = (uint32_t)cb; la.n_chunks_local = (uint32_t)(ce - cb);
-  la.n_chunks_total = (uint32_t)m->n_chunks;
-  if (all_single) {                       // nothing to pre-merge: chunk CVs are the nodes
-    la.out = reinterpret_cast<uint32_t*>(nodes_dev);
-    HIPCHK(m, launch_leaf_chunks(c->NL, la, st));
-    m->launches[1]++;
-    return 0;
-  }
-  uint32_t* cvs = m->d_cvs;
-  la.out = cvs;
-  HIPCHK(m, launch_leaf_chunks(c->NL, la, st));
-  m->launches[1]++;
+  // nothing to pre-merge: chunk CVs are the nodes
+  int rc = hash_chunks(m, cb, ce, all_single ? reinterpret_cast<uint32_t*>(nodes_dev) : m->d_cvs, st);
+  if (rc || all_single) return rc;
   // a rank that owns the WHOLE message as one node (a power-of-two number of chunks and nobody else has any: world = 1, or an
   // Ft191 commitment too short for a cut) produces the digest itself -- the parent of the last merge is the tree's root and
   // takes the ROOT flag here; the finish step then only copies it, as for a single-chunk message
   const bool whole = n_nodes == 1 && cb == 0 && ce == m->n_chunks;
   for (int k = 0; k < n_nodes; k++) {   // one subtree CV per aligned block of chunks
-    uint32_t* blk = cvs + (first[k] - cb) * w * 8;
+    uint32_t* blk = m->d_cvs + (first[k] - cb) * w * 8;
     uint32_t* out = reinterpret_cast<uint32_t*>(nodes_dev) + (size_t)k * w * 8;
     HIPCHK(m, launch_leaf_finish_nodes(blk, nullptr, nullptr, 1u << lg[k], w, out, whole, st));
     m->launches[1]++;
@@ -418,22 +373,8 @@ static int shard_finish_cols(lcpc_commit_t* m, uint8_t* gathered, uint32_t slots
 static int shard_merkle_phase(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   int rc = merkle_top(m, st);
   if (rc) return rc;
-  if (m->timing) {
-    HIPCHK(m, hipEventRecord(m->ev[3], st));
-    HIPCHK(m, hipEventSynchronize(m->ev[3]));
-    (void)hipEventElapsedTime(&m->last.encode_ms, m->ev[0], m->ev[1]);
-    (void)hipEventElapsedTime(&m->last.hash_ms, m->ev[1], m->ev[2]);
-    (void)hipEventElapsedTime(&m->last.merkle_ms, m->ev[2], m->ev[3]);   // includes whatever of the exchange is exposed
-    (void)hipEventElapsedTime(&m->last.total_ms, m->ev[0], m->ev[3]);
-    m->last.encode_launches = m->launches[0]; m->last.hash_launches = m->launches[1]; m->last.merkle_launches = m->launches[2];
-  }
-  m->committed = true;
   m->shard_encoded = false;
-  // a prove on this commitment runs on its own stream: it waits for this point of the commit's stream
-  if (!m->ev_done) HIPCHK(m, hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming));
-  HIPCHK(m, hipEventRecord(m->ev_done, st));
-  if (root) return fetch_root(m, st, root);
-  return 0;
+  return seal_commit(m, st, root);
 }
 
 }  // namespace lcpc

@@ -225,7 +225,8 @@ def test_sharded_prove_equals_unsharded(oracle, kind, fid, n_rows, n_per_row, n_
 
 def test_split_phase_state_errors():
     """the finish step of the split-phase form refuses to run before its shard step (LCPC_ERR_STATE) and with another row count than
-    the shard step's (LCPC_ERR_ARG); after a finish the commit is done: a second finish is refused again"""
+    the shard step's (LCPC_ERR_ARG); after a finish the commit is done: a second finish is refused again.  A commit through another
+    entry point in between replaces the pending one: its finish is refused and leaves the new commitment's digests alone"""
     import ctypes as C
     lib = lcpc_amd._lib.lib()
     eng = HipShardEngine(LigeroEncoding.new_from_dims(3, 64, 128, shard=(0, 2)))
@@ -237,3 +238,8 @@ def test_split_phase_state_errors():
     assert lib.lcpc_commit_finish_device(eng.cm._h, p, 41, 1, None, None) == lcpc_amd.ERR_ARG
     assert lib.lcpc_commit_finish_device(eng.cm._h, p, 40, 2, None, None) == 0
     assert lib.lcpc_commit_finish_device(eng.cm._h, p, 40, 2, None, None) == lcpc_amd.ERR_STATE
+    eng.commit_shard(torch.zeros(((re - rb) * 64, 4), dtype=torch.int64, device="cuda"), 40)
+    LcCommit.from_parts(eng.enc, np.zeros((40 * 128, 4), np.uint64), None, 40, into=eng.cm)
+    hashes = eng.cm.hashes()
+    assert lib.lcpc_commit_finish_device(eng.cm._h, p, 40, 2, None, None) == lcpc_amd.ERR_STATE
+    assert (eng.cm.hashes() == hashes).all()
