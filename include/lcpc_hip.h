@@ -18,7 +18,17 @@
  *    usable from several host threads at once, like a `Sync` encoder), and `lcpc_commit_t` is an
  *    LcCommit<D, E> (lib.rs:172-184): comm / coeffs / hashes of ONE commitment, resident in HBM, created by
  *    commit() and consumed by prove / open_column / collapse_columns.  Many commitments may be live under
- *    one encoder (lib.rs:299-311); each is used by one host thread at a time;
+ *    one encoder (lib.rs:299-311);
+ *  - threads: any number of host threads may call lcpc_prove, lcpc_collapse, lcpc_open_columns and the
+ *    lcpc_get_* copies on ONE lcpc_commit_t at once, and lcpc_verify under ONE lcpc_ctx at once
+ *    (LcCommit::prove(&self), LcEvalProof::verify(.., &E, ..), lib.rs:304-311, 518-527).  Such calls run side by
+ *    side, each in a working set of its own (up to 8 per object, made on first need and kept; a 9th caller
+ *    waits for one), and each returns exactly what it returns alone.  A refill of the object (the commit
+ *    entry points, lcpc_commit_from_parts, lcpc_commit_from_bincode) waits until the readers in flight are
+ *    done, and a reader that arrives meanwhile waits for the refill.  Sharded proves (lcpc_prove_sharded*)
+ *    of one commitment stay one at a time: every rank must submit its collectives in the same order.
+ *    After concurrent failures on one object, lcpc_last_error / lcpc_commit_last_error hold the detail of
+ *    one of them; the returned pointer stays valid while the object lives;
  *  - the caller owns every host buffer; device memory belongs to the handle that allocated it;
  *  - `*_device` entry points take HIP device pointers + a hipStream_t (passed as void*), so a host
  *    runtime (torch, or a Rust hip-sys binding) can keep inputs resident in HBM.

@@ -12,7 +12,33 @@ using namespace lcpc;
 
 namespace lcpc {
 
-int ensure_scratch(lcpc_commit_t* m, uint64_t bytes) { return ensure_dev(&m->err, &m->d_scratch, &m->scratch_cap, bytes); }
+int ensure_scratch(lcpc_commit_t* m, DevScratch* sc, uint64_t bytes) { return ensure_dev(&m->err, &sc->d, &sc->cap, bytes); }
+
+int CallSet::make() {
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return LCPC_ERR_HIP;
+  for (auto& e : ev_slice)
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return LCPC_ERR_HIP;
+  return 0;
+}
+CallSet::~CallSet() {
+  if (st) (void)hipStreamSynchronize(st);
+  sc.release();
+  for (auto& e : ev_slice) if (e) (void)hipEventDestroy(e);
+  if (st) (void)hipStreamDestroy(st);
+  if (h_pin) (void)hipHostFree(h_pin);
+}
+
+// a working set for one host-entry reader (m->fill_mu held shared): its stream is put behind the commit that filled the object
+int take_call_set(lcpc_commit_t* m, uint64_t pin_bytes, CallSet** ws) {
+  HIPCHK(m, hipSetDevice(m->enc->prm.device));    // (a new set's stream and arena belong to the encoder's device)
+  int rc = m->sets.take(pin_bytes, ws);
+  if (rc) {
+    if (rc == LCPC_ERR_NOMEM) m->err = "hipHostMalloc: no pinned host memory for a prove working set";
+    else if (rc == LCPC_ERR_HIP) m->err = "hipStreamCreateWithFlags / hipEventCreateWithFlags: working set";
+    return rc;
+  }
+  return order_after_commit(m, (*ws)->st);
+}
 
 int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks) {
   uint64_t cap_b = m->cap_cvs * 32;
@@ -245,7 +271,7 @@ size_t collapse_scratch_bytes(const lcpc_commit_t* m, uint32_t n_tensors) {
 // ([n_tensors][n_per_row] elements); `a` arrives with coeffs / tensors / tensors29 / n_rows / n_per_row / n_tensors filled in.  A range
 // narrower than the whole polynomial (prove's first slice) takes only one tensor and splits its rows further, so that it still fills
 // the chip: the partials never exceed the reserved collapse_scratch_bytes(m, 2)
-static int collapse_range(lcpc_commit_t* m, CollapseArgs a, uint64_t j0, uint64_t j1, hipStream_t st, uint32_t* d_out) {
+static int collapse_range(lcpc_commit_t* m, const DevScratch* sc, CollapseArgs a, uint64_t j0, uint64_t j1, hipStream_t st, uint32_t* d_out) {
   const lcpc_ctx* c = m->enc;
   const uint64_t len = j1 - j0;
   uint32_t n_splits = collapse_splits(m);
@@ -263,69 +289,69 @@ static int collapse_range(lcpc_commit_t* m, CollapseArgs a, uint64_t j0, uint64_
   }
   const size_t part_bytes = (size_t)n_splits * a.n_tensors * len * elem_bytes(c);
   // partials live at the end of scratch (callers reserve it; scratch_cap is a multiple of 256, part_bytes of 16)
-  uint32_t* d_part = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(m->d_scratch) + m->scratch_cap - ((part_bytes + 255) & ~(size_t)255));
+  uint32_t* d_part = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(sc->d) + sc->cap - ((part_bytes + 255) & ~(size_t)255));
   a.out = d_part; a.out_stride = len;
   HIPCHK(m, launch_collapse(c->NL, a, st));
   // (whole: flat over [n_tensors][n_per_row]; a range: one tensor, its outputs start at element j0)
   HIPCHK(m, launch_field_sum(c->NL, d_part, n_splits, (uint64_t)a.n_tensors * len, d_out + j0 * c->NL, st));
   return 0;
 }
-static int collapse_prepare(lcpc_commit_t* m, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, CollapseArgs* a) {
+static int collapse_prepare(lcpc_commit_t* m, DevScratch* sc, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, CollapseArgs* a) {
   const lcpc_ctx* c = m->enc;
   *a = CollapseArgs{};
   a->coeffs = m->coeffs_view; a->tensors = d_tensors; a->n_rows = m->n_rows_local; a->n_per_row = c->n_per_row;
   a->n_tensors = n_tensors;
   if (c->NL == 8) {
     const uint64_t ne = (uint64_t)n_tensors * m->n_rows_local;
-    int rc = ensure_dev(&m->err, &m->d_t29, &m->t29_cap, ne * 48);
+    int rc = ensure_dev(&m->err, &sc->t29, &sc->t29_cap, ne * 48);
     if (rc) return rc;
-    HIPCHK(m, launch_to_r29(d_tensors, ne, m->d_t29, st));
-    a->tensors29 = m->d_t29;
+    HIPCHK(m, launch_to_r29(d_tensors, ne, sc->t29, st));
+    a->tensors29 = sc->t29;
   }
   return 0;
 }
-static int collapse_local(lcpc_commit_t* m, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_out) {
+static int collapse_local(lcpc_commit_t* m, DevScratch* sc, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_out) {
   CollapseArgs a;
-  int rc = collapse_prepare(m, d_tensors, n_tensors, st, &a);
+  int rc = collapse_prepare(m, sc, d_tensors, n_tensors, st, &a);
   if (rc) return rc;
-  return collapse_range(m, a, 0, m->enc->n_per_row, st, d_out);
+  return collapse_range(m, sc, a, 0, m->enc->n_per_row, st, d_out);
 }
 // scratch layout for collapse: [tensors (host entry only)] [polys (host entry only)] ... [partials at the end]
-int collapse_run(lcpc_commit_t* m, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys) {
+int collapse_run(lcpc_commit_t* m, DevScratch* sc, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys) {
   const lcpc_ctx* c = m->enc;
   for (uint32_t t = 0; t < n_tensors; t += 2) {
     const uint32_t nt = (n_tensors - t) >= 2 ? 2 : 1;
-    int rc = collapse_local(m, d_tensors + (size_t)t * m->n_rows_local * c->NL, nt, st, d_polys + (size_t)t * c->n_per_row * c->NL);
+    int rc = collapse_local(m, sc, d_tensors + (size_t)t * m->n_rows_local * c->NL, nt, st, d_polys + (size_t)t * c->n_per_row * c->NL);
     if (rc) return rc;
   }
   return 0;
 }
 
 // collapse_columns for tensors in host memory; polys_canon (optional): the same polynomials as canonical values
-// (PrimeField::to_repr limbs, what the transcript absorbs, lib.rs:47-57), converted on the device
-int collapse_host(lcpc_commit_t* m, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys, uint64_t* polys_canon) {
+// (PrimeField::to_repr limbs, what the transcript absorbs, lib.rs:47-57), converted on the device.  Runs in the caller's working set
+// (prove: also from its helper thread, while the main thread only waits for slice events of the same set)
+int collapse_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys, uint64_t* polys_canon) {
   if (!m || !tensors || !polys || n_tensors == 0) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   const lcpc_ctx* c = m->enc;
-  std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const size_t eb = elem_bytes(c);
   const size_t tb = ((size_t)n_tensors * m->n_rows_local * eb + 255) & ~(size_t)255;
   const size_t pbytes = (size_t)n_tensors * c->n_per_row * eb;
   const size_t pb = (pbytes + 255) & ~(size_t)255;
-  int rc = ensure_scratch(m, tb + 2 * pb + collapse_scratch_bytes(m, 2) + 512);
+  int rc = ensure_scratch(m, &ws->sc, tb + 2 * pb + collapse_scratch_bytes(m, 2) + 512);
   if (rc) return rc;
-  uint8_t* base = reinterpret_cast<uint8_t*>(m->d_scratch);
+  uint8_t* base = reinterpret_cast<uint8_t*>(ws->sc.d);
   uint32_t* d_t = reinterpret_cast<uint32_t*>(base);
   uint32_t* d_p = reinterpret_cast<uint32_t*>(base + tb);
   uint32_t* d_pc = reinterpret_cast<uint32_t*>(base + tb + pb);
-  if ((rc = order_after_commit(m, nullptr))) return rc;
-  HIPCHK(m, hipMemcpyAsync(d_t, tensors, (size_t)n_tensors * m->n_rows_local * eb, hipMemcpyHostToDevice, nullptr));
-  if ((rc = collapse_run(m, d_t, n_tensors, nullptr, d_p))) return rc;
-  if (polys_canon) HIPCHK(m, launch_to_canon(c->NL, d_p, (uint64_t)n_tensors * c->n_per_row, d_pc, nullptr));
-  HIPCHK(m, hipMemcpyAsync(polys, d_p, pbytes, hipMemcpyDeviceToHost, nullptr));
-  if (polys_canon) HIPCHK(m, hipMemcpyAsync(polys_canon, d_pc, pbytes, hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(m, hipStreamSynchronize(nullptr));
+  hipStream_t st = ws->st;
+  HIPCHK(m, hipMemcpyAsync(d_t, tensors, (size_t)n_tensors * m->n_rows_local * eb, hipMemcpyHostToDevice, st));
+  if ((rc = collapse_run(m, &ws->sc, d_t, n_tensors, st, d_p))) return rc;
+  if (polys_canon) HIPCHK(m, launch_to_canon(c->NL, d_p, (uint64_t)n_tensors * c->n_per_row, d_pc, st));
+  HIPCHK(m, hipMemcpyAsync(polys, d_p, pbytes, hipMemcpyDeviceToHost, st));
+  if (polys_canon) HIPCHK(m, hipMemcpyAsync(polys_canon, d_pc, pbytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(m, hipStreamSynchronize(st));
   return 0;
 }
 
@@ -333,12 +359,11 @@ int collapse_host(lcpc_commit_t* m, const uint64_t* tensors, uint32_t n_tensors,
 // [cut, n_per_row), cut = *cut_out -- each followed by its device-to-host copies (Montgomery form and canonical values) and an event:
 // the transcript absorbs the first range (lib.rs:1045-1047 is serial, ~50 ns per coefficient) while the second is still being
 // computed, so that of the collapse only the first eighth stays on the prover's critical path.  The caller waits for ev[0] / ev[1]
-// (collapse_wait_slice); everything is on the null stream, so later work of this commitment queues up behind it.
-int collapse_host_sliced(lcpc_commit_t* m, const uint64_t* tensor, uint64_t* polys, uint64_t* polys_canon, uint64_t* cut_out) {
+// (collapse_wait_slice); everything is on the working set's stream, so later work of this call queues up behind it.
+int collapse_host_sliced(lcpc_commit_t* m, CallSet* ws, const uint64_t* tensor, uint64_t* polys, uint64_t* polys_canon, uint64_t* cut_out) {
   if (!m || !tensor || !polys || !polys_canon || !cut_out) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   const lcpc_ctx* c = m->enc;
-  std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const size_t eb = elem_bytes(c);
   const uint64_t np = c->n_per_row;
@@ -346,32 +371,30 @@ int collapse_host_sliced(lcpc_commit_t* m, const uint64_t* tensor, uint64_t* pol
   if (cut == 0 || cut >= np) return LCPC_ERR_ARG;
   const size_t tb = ((size_t)m->n_rows_local * eb + 255) & ~(size_t)255;
   const size_t pb = ((size_t)np * eb + 255) & ~(size_t)255;
-  int rc = ensure_scratch(m, tb + 2 * pb + collapse_scratch_bytes(m, 2) + 512);
+  int rc = ensure_scratch(m, &ws->sc, tb + 2 * pb + collapse_scratch_bytes(m, 2) + 512);
   if (rc) return rc;
-  for (auto& e : m->ev_slice)
-    if (!e) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  uint8_t* base = reinterpret_cast<uint8_t*>(m->d_scratch);
+  uint8_t* base = reinterpret_cast<uint8_t*>(ws->sc.d);
   uint32_t* d_t = reinterpret_cast<uint32_t*>(base);
   uint32_t* d_p = reinterpret_cast<uint32_t*>(base + tb);
   uint32_t* d_pc = reinterpret_cast<uint32_t*>(base + tb + pb);
-  if ((rc = order_after_commit(m, nullptr))) return rc;
-  HIPCHK(m, hipMemcpyAsync(d_t, tensor, (size_t)m->n_rows_local * eb, hipMemcpyHostToDevice, nullptr));
+  hipStream_t st = ws->st;
+  HIPCHK(m, hipMemcpyAsync(d_t, tensor, (size_t)m->n_rows_local * eb, hipMemcpyHostToDevice, st));
   CollapseArgs a;
-  if ((rc = collapse_prepare(m, d_t, 1, nullptr, &a))) return rc;
+  if ((rc = collapse_prepare(m, &ws->sc, d_t, 1, st, &a))) return rc;
   const uint64_t lim[3] = {0, cut, np};
   for (int s = 0; s < 2; s++) {
     const uint64_t j0 = lim[s], len = lim[s + 1] - lim[s];
-    if ((rc = collapse_range(m, a, j0, j0 + len, nullptr, d_p))) return rc;
-    HIPCHK(m, launch_to_canon(c->NL, d_p + j0 * c->NL, len, d_pc + j0 * c->NL, nullptr));
-    HIPCHK(m, hipMemcpyAsync(reinterpret_cast<uint8_t*>(polys_canon) + j0 * eb, reinterpret_cast<uint8_t*>(d_pc) + j0 * eb, len * eb, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(m, hipMemcpyAsync(reinterpret_cast<uint8_t*>(polys) + j0 * eb, reinterpret_cast<uint8_t*>(d_p) + j0 * eb, len * eb, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(m, hipEventRecord(m->ev_slice[s], nullptr));
+    if ((rc = collapse_range(m, &ws->sc, a, j0, j0 + len, st, d_p))) return rc;
+    HIPCHK(m, launch_to_canon(c->NL, d_p + j0 * c->NL, len, d_pc + j0 * c->NL, st));
+    HIPCHK(m, hipMemcpyAsync(reinterpret_cast<uint8_t*>(polys_canon) + j0 * eb, reinterpret_cast<uint8_t*>(d_pc) + j0 * eb, len * eb, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, hipMemcpyAsync(reinterpret_cast<uint8_t*>(polys) + j0 * eb, reinterpret_cast<uint8_t*>(d_p) + j0 * eb, len * eb, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, hipEventRecord(ws->ev_slice[s], st));
   }
   *cut_out = cut;
   return 0;
 }
-int collapse_wait_slice(lcpc_commit_t* m, int s) {
-  HIPCHK(m, hipEventSynchronize(m->ev_slice[s]));
+int collapse_wait_slice(lcpc_commit_t* m, CallSet* ws, int s) {
+  HIPCHK(m, hipEventSynchronize(ws->ev_slice[s]));
   return 0;
 }
 
@@ -389,47 +412,35 @@ int open_columns_device(lcpc_commit_t* m, const uint64_t* d_cols, uint32_t n, ui
 
 // open_column (lib.rs:788-825) for n columns into host memory.  vals_pitch: bytes between the values of consecutive
 // columns (0 = packed, n_rows * F): prove lets the device-to-host copy drop them straight into the bincode layout
-int open_columns_host(lcpc_commit_t* m, const uint64_t* cols, uint32_t n, uint64_t* col_vals, size_t vals_pitch, uint8_t* paths) {
+int open_columns_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* cols, uint32_t n, uint64_t* col_vals, size_t vals_pitch, uint8_t* paths) {
   if (!m || !cols || (!col_vals && !paths)) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   const lcpc_ctx* c = m->enc;
   for (uint32_t i = 0; i < n; i++)
     if (cols[i] >= c->n_cols) return LCPC_ERR_COLUMN_NUMBER;        // lib.rs:797-799
   if (n == 0) return 0;
-  std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const size_t eb = elem_bytes(c);
   const size_t col_b = (size_t)m->n_rows_local * eb;
   const size_t vb = (((size_t)n * col_b) + 255) & ~(size_t)255, pb = (((size_t)n * c->path_len * 32) + 255) & ~(size_t)255;
   const size_t cb = (((size_t)n * 8) + 255) & ~(size_t)255;
-  int rc = ensure_scratch(m, vb + pb + cb);
+  int rc = ensure_scratch(m, &ws->sc, vb + pb + cb);
   if (rc) return rc;
-  uint8_t* base = reinterpret_cast<uint8_t*>(m->d_scratch);
+  uint8_t* base = reinterpret_cast<uint8_t*>(ws->sc.d);
   uint64_t* d_cols = reinterpret_cast<uint64_t*>(base);
   uint32_t* d_vals = reinterpret_cast<uint32_t*>(base + cb);
   uint32_t* d_paths = reinterpret_cast<uint32_t*>(base + cb + vb);
-  if ((rc = order_after_commit(m, nullptr))) return rc;
-  HIPCHK(m, hipMemcpyAsync(d_cols, cols, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
-  if ((rc = open_columns_device(m, d_cols, n, col_vals ? d_vals : nullptr, paths ? d_paths : nullptr, nullptr))) return rc;
+  hipStream_t st = ws->st;
+  HIPCHK(m, hipMemcpyAsync(d_cols, cols, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  if ((rc = open_columns_device(m, d_cols, n, col_vals ? d_vals : nullptr, paths ? d_paths : nullptr, st))) return rc;
   if (col_vals && m->n_rows_local) {
     if (vals_pitch == 0 || vals_pitch == col_b)
-      HIPCHK(m, hipMemcpyAsync(col_vals, d_vals, (size_t)n * col_b, hipMemcpyDeviceToHost, nullptr));
+      HIPCHK(m, hipMemcpyAsync(col_vals, d_vals, (size_t)n * col_b, hipMemcpyDeviceToHost, st));
     else
-      HIPCHK(m, hipMemcpy2DAsync(col_vals, vals_pitch, d_vals, col_b, col_b, n, hipMemcpyDeviceToHost, nullptr));
+      HIPCHK(m, hipMemcpy2DAsync(col_vals, vals_pitch, d_vals, col_b, col_b, n, hipMemcpyDeviceToHost, st));
   }
-  if (paths && c->path_len) HIPCHK(m, hipMemcpyAsync(paths, d_paths, (size_t)n * c->path_len * 32, hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(m, hipStreamSynchronize(nullptr));
-  return 0;
-}
-
-// pinned host memory that lives with the commitment (prove's tensors / polynomials: no page faults, full-speed D2H)
-int ensure_pinned(lcpc_commit_t* m, uint64_t bytes) {
-  if (bytes > m->h_pin_cap || !m->h_pin) {
-    if (m->h_pin) (void)hipHostFree(m->h_pin);
-    m->h_pin = nullptr; m->h_pin_cap = 0;
-    HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), (size_t)bytes, hipHostMallocDefault));
-    m->h_pin_cap = bytes;
-  }
+  if (paths && c->path_len) HIPCHK(m, hipMemcpyAsync(paths, d_paths, (size_t)n * c->path_len * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(m, hipStreamSynchronize(st));
   return 0;
 }
 
@@ -457,13 +468,13 @@ int lcpc_commit_create(lcpc_ctx* enc, lcpc_commit_t** out) {
 void lcpc_commit_destroy(lcpc_commit_t* m) {
   if (!m) return;
   (void)hipSetDevice(m->enc->prm.device);
-  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs); dev_free(m->d_scratch);
+  m->sets.clear();
+  m->sc.release();
+  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs);
   for (auto& t : m->node_tabs) dev_free(t.d);
-  dev_free(m->d_t29); dev_free(m->ws.d_tmp); dev_free(m->ws.d_t); dev_free(m->ws.d_mid); dev_free(m->d_gather); dev_free(m->d_xsend); dev_free(m->d_xrecv);
+  dev_free(m->ws.d_tmp); dev_free(m->ws.d_t); dev_free(m->ws.d_mid); dev_free(m->d_gather); dev_free(m->d_xsend); dev_free(m->d_xrecv);
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : m->ev_batch) if (e) (void)hipEventDestroy(e);
-  for (auto& e : m->ev_slice) if (e) (void)hipEventDestroy(e);
-  if (m->h_pin) (void)hipHostFree(m->h_pin);
   if (m->h_root) (void)hipHostFree(m->h_root);
   if (m->s_prove) (void)hipStreamDestroy(m->s_prove);
   if (m->s_xchg) (void)hipStreamDestroy(m->s_xchg);
@@ -474,13 +485,14 @@ void lcpc_commit_destroy(lcpc_commit_t* m) {
   ctx_unref(m->enc);
   delete m;
 }
-const char* lcpc_commit_last_error(const lcpc_commit_t* m) { return m ? m->err.c_str() : ""; }
+const char* lcpc_commit_last_error(const lcpc_commit_t* m) { return m ? m->err.c_str() : ""; }   // (ErrText: stable while m lives)
 
 int lcpc_commit_device(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_coeffs, void* stream, uint32_t flags, uint8_t* root) {
   if (!m || !coeffs_dev || n_coeffs == 0) return LCPC_ERR_ARG;
   const lcpc_ctx* c = m->enc;
   if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   hipStream_t st = (hipStream_t)stream;
@@ -591,6 +603,7 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   lcpc_ctx* c = m->enc;
   if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
@@ -678,6 +691,7 @@ int lcpc_commit_from_parts(lcpc_commit_t* m, const uint64_t* comm, const uint64_
   if (!m || !comm || n_rows == 0) return LCPC_ERR_ARG;
   const lcpc_ctx* c = m->enc;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   int rc = begin_commit(m, nullptr, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
@@ -695,8 +709,13 @@ int lcpc_commit_from_parts(lcpc_commit_t* m, const uint64_t* comm, const uint64_
 }
 
 // ---- serde of LcCommit (lib.rs:186-268), bincode 1.3 ---------------------------------------------------------------
+static int get_hashes(lcpc_commit_t* m, uint8_t* hashes);
+static int get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out);
+static int get_coeffs(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out);
 uint64_t lcpc_commit_bincode_size(const lcpc_commit_t* m) {
-  if (!m || !m->committed || m->enc->prm.shard_count > 1) return 0;
+  if (!m) return 0;
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (!m->committed || m->enc->prm.shard_count > 1) return 0;
   const lcpc_ctx* c = m->enc;
   const uint64_t eb = elem_bytes(c);
   return 8 + m->n_rows * c->n_cols * eb + 8 + m->n_rows * c->n_per_row * eb + 24 + 8 + (2 * c->np2 - 1) * 40;
@@ -704,15 +723,16 @@ uint64_t lcpc_commit_bincode_size(const lcpc_commit_t* m) {
 
 int lcpc_commit_bincode_write(lcpc_commit_t* m, lcpc_write_fn fn, void* user) {
   if (!m || !fn) return LCPC_ERR_ARG;
-  if (!m->committed || m->enc->prm.shard_count > 1) return LCPC_ERR_STATE;
   const lcpc_ctx* c = m->enc;
   LCPC_TRY
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (!m->committed || m->enc->prm.shard_count > 1) return LCPC_ERR_STATE;
   const uint64_t eb = elem_bytes(c);
   auto put64 = [&](uint64_t v) { return fn(user, reinterpret_cast<const uint8_t*>(&v), 8); };
   // comm, then coeffs: row batches of <= 64 MiB through one staging buffer (lcpc_get_comm converts a canonical device copy
   // back to Montgomery form and materialises Brakedown's row-major view)
   struct Part { uint64_t per_row; int (*get)(lcpc_commit_t*, uint64_t, uint64_t, uint64_t*); };
-  const Part parts[2] = {{c->n_cols, lcpc_get_comm}, {c->n_per_row, lcpc_get_coeffs}};
+  const Part parts[2] = {{c->n_cols, get_comm}, {c->n_per_row, get_coeffs}};
   for (const Part& p : parts) {
     if (put64(m->n_rows * p.per_row)) return LCPC_ERR_ARG;
     const uint64_t row_b = p.per_row * eb;
@@ -729,7 +749,7 @@ int lcpc_commit_bincode_write(lcpc_commit_t* m, lcpc_write_fn fn, void* user) {
   if (put64(m->n_rows) || put64(c->n_cols) || put64(c->n_per_row)) return LCPC_ERR_ARG;
   const uint64_t nh = 2 * c->np2 - 1;
   std::vector<uint8_t> h((size_t)nh * 32), w((size_t)nh * 40);
-  int rc = lcpc_get_hashes(m, h.data());
+  int rc = get_hashes(m, h.data());
   if (rc) return rc;
   for (uint64_t i = 0; i < nh; i++) {
     const uint64_t l = 32;
@@ -748,6 +768,7 @@ int lcpc_commit_from_bincode(lcpc_commit_t* m, lcpc_read_fn fn, void* user, uint
   const lcpc_ctx* c = m->enc;
   if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   const FieldDesc& f = *c->f;
@@ -816,6 +837,7 @@ int lcpc_commit_from_bincode(lcpc_commit_t* m, lcpc_read_fn fn, void* user, uint
 
 int lcpc_get_root(lcpc_commit_t* m, uint8_t root[32]) {
   if (!m || !root) return LCPC_ERR_ARG;
+  std::shared_lock<FillLock> rd(m->fill_mu);
   if (!m->committed) return LCPC_ERR_STATE;
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
   { int orc = order_after_commit(m, nullptr); if (orc) return orc; }
@@ -824,6 +846,7 @@ int lcpc_get_root(lcpc_commit_t* m, uint8_t root[32]) {
 }
 int lcpc_commit_dims(const lcpc_commit_t* m, uint64_t* nr, uint64_t* np, uint64_t* nc, uint64_t* nh) {
   if (!m) return LCPC_ERR_ARG;
+  std::shared_lock<FillLock> rd(m->fill_mu);
   if (!m->committed) return LCPC_ERR_STATE;
   if (nr) *nr = m->n_rows;
   if (np) *np = m->enc->n_per_row;
@@ -831,7 +854,8 @@ int lcpc_commit_dims(const lcpc_commit_t* m, uint64_t* nr, uint64_t* np, uint64_
   if (nh) *nh = 2 * m->enc->np2 - 1;
   return 0;
 }
-int lcpc_get_hashes(lcpc_commit_t* m, uint8_t* hashes) {
+// the getters' bodies (the caller holds m->fill_mu shared: lcpc_get_*, lcpc_commit_bincode_write)
+static int get_hashes(lcpc_commit_t* m, uint8_t* hashes) {
   if (!m || !hashes) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
@@ -839,7 +863,7 @@ int lcpc_get_hashes(lcpc_commit_t* m, uint8_t* hashes) {
   HIPCHK(m, hipMemcpy(hashes, m->d_hashes, (size_t)(2 * m->enc->np2 - 1) * 32, hipMemcpyDeviceToHost));
   return 0;
 }
-int lcpc_get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
+static int get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
   if (!m || !out) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   if (row0 < m->row_begin || row0 + n > m->row_begin + m->n_rows_local) return LCPC_ERR_ARG;
@@ -877,7 +901,7 @@ int lcpc_get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
   return 0;
   LCPC_CATCH(m)
 }
-int lcpc_get_coeffs(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
+static int get_coeffs(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
   if (!m || !out) return LCPC_ERR_ARG;
   if (!m->committed) return LCPC_ERR_STATE;
   if (row0 < m->row_begin || row0 + n > m->row_begin + m->n_rows_local) return LCPC_ERR_ARG;
@@ -889,31 +913,62 @@ int lcpc_get_coeffs(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) 
                       (size_t)n * c->n_per_row * eb, hipMemcpyDeviceToHost));
   return 0;
 }
+int lcpc_get_hashes(lcpc_commit_t* m, uint8_t* hashes) {
+  if (!m) return LCPC_ERR_ARG;
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  return get_hashes(m, hashes);
+}
+int lcpc_get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
+  if (!m) return LCPC_ERR_ARG;
+  LCPC_TRY
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  return get_comm(m, row0, n, out);
+  LCPC_CATCH(m)
+}
+int lcpc_get_coeffs(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {
+  if (!m) return LCPC_ERR_ARG;
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  return get_coeffs(m, row0, n, out);
+}
 
 // ---- collapse / open ---------------------------------------------------------------------------------
 int lcpc_collapse_device(lcpc_commit_t* m, const uint64_t* tensors_dev, uint32_t n_tensors, void* stream, uint64_t* polys_dev) {
   if (!m || !tensors_dev || !polys_dev || n_tensors == 0) return LCPC_ERR_ARG;
-  if (!m->committed) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (!m->committed) return LCPC_ERR_STATE;
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
-  int rc = ensure_scratch(m, collapse_scratch_bytes(m, 2) + 256);
+  int rc = ensure_scratch(m, &m->sc, collapse_scratch_bytes(m, 2) + 256);
   if (rc) return rc;
   if ((rc = order_after_commit(m, (hipStream_t)stream))) return rc;
-  return collapse_run(m, reinterpret_cast<const uint32_t*>(tensors_dev), n_tensors, (hipStream_t)stream,
+  return collapse_run(m, &m->sc, reinterpret_cast<const uint32_t*>(tensors_dev), n_tensors, (hipStream_t)stream,
                       reinterpret_cast<uint32_t*>(polys_dev));
   LCPC_CATCH(m)
 }
 
 int lcpc_collapse(lcpc_commit_t* m, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys) {
+  if (!m || !tensors || !polys || n_tensors == 0) return LCPC_ERR_ARG;
   LCPC_TRY
-  return collapse_host(m, tensors, n_tensors, polys, nullptr);
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (!m->committed) return LCPC_ERR_STATE;
+  SetLease<CallSet> lease{m->sets};
+  int rc = take_call_set(m, 0, &lease.s);
+  return rc ? rc : collapse_host(m, lease.s, tensors, n_tensors, polys, nullptr);
   LCPC_CATCH(m)
 }
 
 int lcpc_open_columns(lcpc_commit_t* m, const uint64_t* cols, uint32_t n, uint64_t* col_vals, uint8_t* paths) {
+  if (!m || !cols || (!col_vals && !paths)) return LCPC_ERR_ARG;
   LCPC_TRY
-  return open_columns_host(m, cols, n, col_vals, 0, paths);
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (!m->committed) return LCPC_ERR_STATE;
+  for (uint32_t i = 0; i < n; i++)
+    if (cols[i] >= m->enc->n_cols) return LCPC_ERR_COLUMN_NUMBER;      // (before a set is taken: lib.rs:797-799)
+  if (n == 0) return 0;
+  SetLease<CallSet> lease{m->sets};
+  int rc = take_call_set(m, 0, &lease.s);
+  return rc ? rc : open_columns_host(m, lease.s, cols, n, col_vals, 0, paths);
   LCPC_CATCH(m)
 }
 

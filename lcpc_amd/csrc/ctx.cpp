@@ -24,7 +24,8 @@ static void ctx_free(lcpc_ctx* c) {
   dev_free(c->d_wq_w); dev_free(c->d_rootsls); dev_free(c->d_rootslcs);
   dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_roots); dev_free(c->d_r2);
   dev_free(c->ws.d_tmp); dev_free(c->ws.d_t); dev_free(c->ws.d_mid); dev_free(c->d_scratch);
-  if (c->h_varena) (void)hipHostFree(c->h_varena);
+  c->verify_sets.clear();
+  if (c->s_verify) (void)hipStreamDestroy(c->s_verify);
   for (unsigned k = 0; k < lcpc_ctx::N_STAGE; k++) {
     if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
     if (c->ev_stage[k]) (void)hipEventDestroy(c->ev_stage[k]);
@@ -215,7 +216,7 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
   std::vector<NttStep> plan(n_pass);
   const int rc = [&]() -> int {
     const FieldDesc* f = c->f;
-    std::string* err = &c->err;
+    ErrText* err = &c->err;
     const bool k1s = c->L == 4;
     const unsigned k = c->log_n, s0 = k - 10 * (n_pass - 1);
     const LimbForm lf = limb_form(c);
@@ -321,7 +322,7 @@ template <class Mat, class Rs> static int sdig_walk(const lcpc_ctx* c, Mat&& mat
 }
 
 // ---- encode rows: LcEncoding::encode, batched over rows -----------------------------------------------
-int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, std::string* err, uint32_t* launches) {
+int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, ErrText* err, uint32_t* launches) {
   uint32_t dummy = 0;
   uint32_t& nl = launches ? *launches : dummy;
   if (j.kept_t) *j.kept_t = false;
@@ -332,7 +333,7 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
     // in ws->d_mid, in row batches sized by ntt_mid_rows, or -- if that buffer cannot be had -- packed in dst itself
     uint64_t rb = ws->mid_failed ? 0 : ntt_mid_rows(c, n_rows);
     if (rb) {
-      std::string scratch_err;
+      ErrText scratch_err;
       uint64_t want = rb * c->n_cols * 36;
 #ifdef LCPC_TEST_HOOKS
       if (c->sw_test_fail_mid) want = (uint64_t)1 << 62;      // an allocation no device can satisfy, so that the real failure path runs
@@ -520,7 +521,7 @@ int lcpc_static_get_dims_ml(const lcpc_params* p, uint32_t n_vars, uint64_t* nr,
 
 static int ctx_build(lcpc_ctx* c, const lcpc_params* p) {
   const FieldDesc* f = c->f;
-  std::string* err = &c->err;
+  ErrText* err = &c->err;
   int rc = 0;
   if (p->encoding == LCPC_ENC_LIGERO) {
     if (p->rho_num == 0 || p->rho_num >= p->rho_den) return LCPC_ERR_ARG;
@@ -727,22 +728,28 @@ namespace lcpc {
 // LcEncoding::encode for messages given WITHOUT their zero padding (msgs[i] = n_per_row elements): the padding is
 // produced on the device (fused into the first NTT pass / the Brakedown input copy), only n_per_row elements per row
 // cross PCIe.  out: n_rows x n_cols.  The verifier's 1 + n_degree_tests row encodes (lib.rs:886, 918).
+// (lcpc_verify's row encodes, from its helper thread: the encoder's scratch is held only for this small encode, never across a
+// transcript, and the work runs on the encoder's own non-blocking stream -- nothing waits for other threads' streams)
 int encode_msgs_host(lcpc_ctx* c, const uint64_t* const* msgs, uint64_t n_rows, uint64_t* out) {
   if (n_rows == 0) return 0;
   std::lock_guard<std::mutex> g(c->mu);
   HIPCHK(c, hipSetDevice(c->prm.device));
+  if (!c->s_verify) HIPCHK(c, hipStreamCreateWithFlags(&c->s_verify, hipStreamNonBlocking));
+  hipStream_t st = c->s_verify;
+  struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (a failure half-way: nothing left writing to out)
   const size_t eb = elem_bytes(c);
   const size_t in_b = ((size_t)n_rows * c->n_per_row * eb + 255) & ~(size_t)255, out_b = (size_t)n_rows * c->n_cols * eb;
   int rc = ensure_dev(&c->err, &c->d_scratch, &c->scratch_cap, in_b + out_b);
   if (rc) return rc;
   uint8_t* base = reinterpret_cast<uint8_t*>(c->d_scratch);
   for (uint64_t i = 0; i < n_rows; i++)
-    HIPCHK(c, hipMemcpyAsync(base + i * c->n_per_row * eb, msgs[i], c->n_per_row * eb, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(c, hipMemcpyAsync(base + i * c->n_per_row * eb, msgs[i], c->n_per_row * eb, hipMemcpyHostToDevice, st));
   EncodeJob j;
   j.src = reinterpret_cast<uint32_t*>(base); j.src_stride = c->n_per_row; j.n_valid = c->n_per_row;
   j.dst = reinterpret_cast<uint32_t*>(base + in_b); j.n_rows = n_rows;
-  if ((rc = encode_rows_device(c, &c->ws, j, nullptr, &c->err, nullptr))) return rc;
-  HIPCHK(c, hipMemcpy(out, base + in_b, out_b, hipMemcpyDeviceToHost));
+  if ((rc = encode_rows_device(c, &c->ws, j, st, &c->err, nullptr))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, base + in_b, out_b, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return 0;
 }
 }  // namespace lcpc

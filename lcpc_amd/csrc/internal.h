@@ -15,8 +15,11 @@
 #include <string.h>
 #include <algorithm>
 #include <atomic>
+#include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
+#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -68,6 +71,160 @@ constexpr uint64_t SDIG_T_MIN_ROWS = 24;
 // proof buffers (prove.cpp): lcpc_free hands them back; one is kept for the next proof
 void* proof_buf_alloc(size_t n);
 void proof_buf_free(void* p);
+
+// The detail text of an object's last failure (lcpc_last_error, lcpc_commit_last_error).  Calls on one object may fail on several
+// threads at once, so a failure writes its text under a lock of its own into the next of four fixed buffers and then publishes
+// that buffer: the pointer a getter returned stays valid for the object's lifetime, and after concurrent failures the text is
+// that of one of them.  (Its own lock, not the object's `mu`: a failure is often reported from inside a `mu` section.)
+class ErrText {
+ public:
+  ErrText& operator=(const std::string& s) { set(s.c_str()); return *this; }
+  ErrText& operator=(const char* s) { set(s); return *this; }
+  void clear() { set(""); }
+  const char* c_str() const { return buf_[cur_.load(std::memory_order_acquire)]; }
+ private:
+  void set(const char* s) {
+    std::lock_guard<std::mutex> g(mu_);
+    const unsigned k = (cur_.load(std::memory_order_relaxed) + 1) % 4;
+    snprintf(buf_[k], sizeof buf_[k], "%s", s ? s : "");
+    cur_.store(k, std::memory_order_release);
+  }
+  std::mutex mu_;
+  std::atomic<unsigned> cur_{0};
+  char buf_[4][512] = {};
+};
+
+// The shared / exclusive lock of a commitment's contents (lcpc_commit_s::fill_mu).  A waiting fill goes before readers that
+// arrive after it: glibc's std::shared_mutex prefers readers, and a loop of proves on one thread could hold a refill off for good.
+// Not recursive in either mode (a reader that re-locked behind a waiting fill would deadlock): the entry points lock, internals don't.
+class FillLock {
+ public:
+  void lock() {
+    std::unique_lock<std::mutex> g(mu_);
+    ++fills_waiting_;
+    cv_.wait(g, [&] { return !filling_ && readers_ == 0; });
+    --fills_waiting_;
+    filling_ = true;
+  }
+  void unlock() {
+    { std::lock_guard<std::mutex> g(mu_); filling_ = false; }
+    cv_.notify_all();
+  }
+  void lock_shared() {
+    std::unique_lock<std::mutex> g(mu_);
+    cv_.wait(g, [&] { return !filling_ && fills_waiting_ == 0; });
+    ++readers_;
+  }
+  void unlock_shared() {
+    bool last;
+    { std::lock_guard<std::mutex> g(mu_); last = --readers_ == 0; }
+    if (last) cv_.notify_all();
+  }
+ private:
+  std::mutex mu_;
+  std::condition_variable cv_;
+  unsigned readers_ = 0, fills_waiting_ = 0;
+  bool filling_ = false;
+};
+
+// device scratch of collapse / open: the working buffers of one call at a time (a commitment's own, or a working set's)
+struct DevScratch {
+  uint32_t* d = nullptr;           // [tensors][polys][canonical polys] ... [collapse partials at the end]; open: [cols][vals][paths]
+  uint64_t cap = 0;                // bytes
+  uint32_t* t29 = nullptr;         // collapse: tensors in the 29-bit-limb form
+  uint64_t t29_cap = 0;
+  void release() { if (d) (void)hipFree(d); if (t29) (void)hipFree(t29); d = t29 = nullptr; cap = t29_cap = 0; }
+};
+
+// What one prove / collapse / open call on a commitment works in, so that calls on one commitment run side by side: its own
+// non-blocking stream (ordered behind the commit that filled the object when the set is taken), the slice events of prove's
+// collapse, device scratch, and prove's pinned arena (tensors, polynomials, their canonical forms).
+struct CallSet {
+  bool busy = false;
+  uint8_t* h_pin = nullptr;
+  uint64_t h_pin_cap = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev_slice[2] = {nullptr, nullptr};   // arrival of the two column ranges of p_random on the host (collapse_host_sliced)
+  DevScratch sc;
+  int make();                      // stream and events (on the current device)
+  void quiesce() { (void)hipStreamSynchronize(st); }   // (a call that failed half-way may have left work on the stream)
+  ~CallSet();
+};
+// lcpc_verify's host working set (encoded rows as they come back, to_repr of the polynomials): pinned, kept between calls
+// (a fresh 150 MB of pageable memory costs ~20 ms in first-touch faults and munmap at Brakedown 2^27)
+struct VerifySet {
+  bool busy = false;
+  uint8_t* h_pin = nullptr;
+  uint64_t h_pin_cap = 0;
+  int make() { return 0; }
+  void quiesce() {}
+  ~VerifySet() { if (h_pin) (void)hipHostFree(h_pin); }
+};
+
+// Working sets of concurrent calls on one object.  A call takes a set on entry (take) and hands it back on exit (SetLease).
+// Sets are made on first need and kept with the object, at most MAX_SETS of them: a caller beyond that waits for a set to come
+// back.  take() also sizes the set's pinned arena; when that allocation fails while the object has another set whose arena is
+// large enough, the caller waits for that one instead of failing.  `mu` guards only this bookkeeping.
+template <typename S> class SetPool {
+ public:
+  static constexpr size_t MAX_SETS = 8;
+  // the device of the object must be current (a new set's stream is made on it); 0, LCPC_ERR_NOMEM or a HIP error code
+  int take(uint64_t pin_bytes, S** out) {
+    *out = nullptr;
+    std::unique_lock<std::mutex> lk(mu_);
+    bool reuse_only = false;       // a pinned allocation failed: only a set that already holds pin_bytes will do
+    for (;;) {
+      S* pick = nullptr;
+      for (auto& s : sets_) if (!s->busy && s->h_pin_cap >= pin_bytes) { pick = s.get(); break; }
+      if (!pick && !reuse_only) {
+        for (auto& s : sets_) if (!s->busy) { pick = s.get(); break; }
+        if (!pick && sets_.size() < MAX_SETS) {
+          std::unique_ptr<S> s(new S());
+          if (int rc = s->make()) return rc;
+          sets_.push_back(std::move(s));
+          pick = sets_.back().get();
+        }
+      }
+      if (!pick) {
+        if (reuse_only && !any_holds(pin_bytes)) return LCPC_ERR_NOMEM;
+        cv_.wait(lk);
+        continue;
+      }
+      pick->busy = true;
+      if (pick->h_pin_cap >= pin_bytes) { *out = pick; return 0; }
+      lk.unlock();                 // (the set is this caller's: pinning runs outside the bookkeeping lock)
+      if (pick->h_pin) (void)hipHostFree(pick->h_pin);
+      pick->h_pin = nullptr; pick->h_pin_cap = 0;
+      void* hp = nullptr;
+      const bool ok = hipHostMalloc(&hp, (size_t)pin_bytes, hipHostMallocDefault) == hipSuccess;
+      if (!ok) (void)hipGetLastError();
+      lk.lock();
+      if (ok) { pick->h_pin = static_cast<uint8_t*>(hp); pick->h_pin_cap = pin_bytes; *out = pick; return 0; }
+      pick->busy = false;
+      if (!any_holds(pin_bytes)) return LCPC_ERR_NOMEM;
+      reuse_only = true;
+    }
+  }
+  void give(S* s) {
+    { std::lock_guard<std::mutex> g(mu_); s->busy = false; }
+    cv_.notify_all();
+  }
+  void clear() { sets_.clear(); }  // (destroy: no call is running)
+ private:
+  bool any_holds(uint64_t pin_bytes) const {
+    for (auto& s : sets_) if (s->h_pin_cap >= pin_bytes) return true;
+    return false;
+  }
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<S>> sets_;
+};
+// a taken set, handed back on every exit path -- with nothing of its call left in flight
+template <typename S> struct SetLease {
+  SetPool<S>& pool;
+  S* s = nullptr;
+  ~SetLease() { if (s) { s->quiesce(); pool.give(s); } }
+};
 
 }  // namespace lcpc
 
@@ -125,13 +282,12 @@ struct lcpc_ctx {
                                    // collectives of one communicator run in submission order whatever streams they are enqueued on
                                    // (two commitments' exchange streams, a prove stream) -- under xchg_mu
   std::atomic<int> refs{1};        // the handle itself + one per live lcpc_commit
-  std::string err;
+  lcpc::ErrText err;
   std::mutex mu;
-  // lcpc_verify's host working set (encoded rows as they come back, to_repr of the polynomials): pinned, kept between
-  // calls (a fresh 150 MB of pageable memory costs ~20 ms in first-touch faults and munmap at Brakedown 2^27)
-  std::mutex verify_mu;            // held for a whole lcpc_verify call
-  uint8_t* h_varena = nullptr;
-  size_t h_varena_cap = 0;
+  // lcpc_verify: one pinned host working set per running call (verifies under one encoder run side by side); the row encodes of a
+  // verify run on s_verify under `mu` (ws / d_scratch above), which is held only around that encode's enqueue and synchronisation
+  lcpc::SetPool<lcpc::VerifySet> verify_sets;
+  hipStream_t s_verify = nullptr;  // non-blocking
   // lcpc_commit from PAGEABLE host memory (commit.cpp upload_host): a ring of pinned bounce buffers the host pool fills while
   // the previous slices cross the bus.  stage_mu is held per upload call (one row batch of one commit); the buffers are kept between commits
   // (up to 4 x 64 MiB of pinned host memory per encoder that has taken a pageable source; LCPC_HOST_STAGE=1 pins the first two at lcpc_ctx_create).
@@ -168,15 +324,11 @@ struct lcpc_commit_s {
   uint64_t gather_cap = 0;
   uint8_t *d_xsend = nullptr, *d_xrecv = nullptr;   // native sharded prove: exchange buffers
   uint64_t xchg_cap = 0;
-  // scratch for prove / collapse / open
-  uint32_t* d_scratch = nullptr;
-  uint64_t scratch_cap = 0;
-  uint32_t* d_t29 = nullptr;       // collapse: tensors in the 29-bit-limb form
-  uint64_t t29_cap = 0;
+  // scratch of the device-entry collapse (lcpc_collapse_device) and of the sharded prove; the host-entry prove / collapse / open
+  // work in a set of `sets`
+  lcpc::DevScratch sc;
   uint32_t* h_root = nullptr;      // pinned, device-mapped: the Merkle kernel that produces the root writes it here as well
   uint32_t* d_root_alias = nullptr;  // ... through this device address (null: no mapping, the root is copied out)
-  uint8_t* h_pin = nullptr;        // pinned host arena of prove (tensors, polynomials, their canonical forms)
-  uint64_t h_pin_cap = 0;
   // timing
   bool timing = false;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // start | encoded | hashed | done; [4]: the commit's stream
@@ -190,19 +342,24 @@ struct lcpc_commit_s {
   bool shard_encoded = false;      // split phases: the encode step of a sharded commit has been enqueued, hash / finish / merkle may follow
   hipStream_t s_copy = nullptr, s_comp = nullptr;   // lcpc_commit (host pointer): H2D of row batch b+1 overlaps the NTTs of batch b
   hipEvent_t ev_batch[16] = {nullptr};
-  std::mutex prove_mu;             // held for a whole prove on this commitment: the pinned arena, the slice events and the scratch layout are
-                                   // per object (LcCommit::prove takes &self: concurrent proves on ONE commitment queue up, on different ones run side by side)
-  hipEvent_t ev_slice[2] = {nullptr, nullptr};   // prove: arrival of the two column ranges of p_random on the host (collapse_host_sliced)
+  // Concurrency (include/lcpc_hip.h "Threads"): every fill (the commit entry points, from_parts, from_bincode) holds fill_mu
+  // exclusively; every reader (prove, collapse, open, the getters) holds it shared for its whole duration.  A refill therefore waits
+  // for the readers in flight, and no reader sees a half-filled object.  Lock order: fill_mu, then mu.
+  mutable lcpc::FillLock fill_mu;
+  lcpc::SetPool<lcpc::CallSet> sets;   // host-entry prove / collapse / open: one working set per running call
+  std::mutex shard_prove_mu;       // held for a whole SHARDED prove: its collectives go out on one communicator, and every rank must
+                                   // submit them in the same order -- two sharded proves of one commitment interleaving their
+                                   // exchanges differently on two ranks would pair the wrong buffers (or hang)
   lcpc_timings last{};
   uint32_t launches[3] = {0, 0, 0};
-  std::string err;
-  std::mutex mu;
+  lcpc::ErrText err;
+  std::mutex mu;                   // short sections: lazy allocation, the sharded and device-entry paths' scratch
 };
 
 namespace lcpc {
 
 // ---- error plumbing ---------------------------------------------------------------------------------
-inline int fail_hip(std::string* err, hipError_t e, const char* what) {
+inline int fail_hip(ErrText* err, hipError_t e, const char* what) {
   if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
   return e == hipErrorOutOfMemory ? LCPC_ERR_NOMEM : LCPC_ERR_HIP;
 }
@@ -226,7 +383,7 @@ inline int fail_hip(std::string* err, hipError_t e, const char* what) {
     return LCPC_ERR_STATE;                                                \
   }
 
-template <typename T> int dev_alloc(std::string* err, T** p, size_t bytes) {
+template <typename T> int dev_alloc(ErrText* err, T** p, size_t bytes) {
   *p = nullptr;
   if (bytes == 0) bytes = 16;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
@@ -236,7 +393,7 @@ template <typename T> int dev_alloc(std::string* err, T** p, size_t bytes) {
 inline void dev_free(void* p) { if (p) (void)hipFree(p); }
 // grow-only device buffer; the requested size is rounded up to 256 bytes so that offsets computed from the capacity
 // (collapse partials at the end of scratch) stay 16-byte aligned for the uint4 element accesses
-template <typename T> int ensure_dev(std::string* err, T** p, uint64_t* cap, uint64_t bytes) {
+template <typename T> int ensure_dev(ErrText* err, T** p, uint64_t* cap, uint64_t bytes) {
   bytes = (bytes + 255) & ~(uint64_t)255;
   if (bytes > *cap || !*p) {
     dev_free(*p);
@@ -273,12 +430,12 @@ struct EncodeJob {
   bool keep_t = false;             // Brakedown: leave the result position-major in ws->d_t (the commit path); *kept_t reports it
   bool* kept_t = nullptr;
 };
-int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, std::string* err, uint32_t* launches);
+int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, ErrText* err, uint32_t* launches);
 
 int encode_msgs_host(lcpc_ctx* c, const uint64_t* const* msgs, uint64_t n_rows, uint64_t* out);
 
 // ---- commit.cpp -------------------------------------------------------------------------------------
-int ensure_scratch(lcpc_commit_t* m, uint64_t bytes);
+int ensure_scratch(lcpc_commit_t* m, DevScratch* sc, uint64_t bytes);
 int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks);
 // The stages of every commit entry point (unsharded: rows [0, n_rows), chunks [0, leaf_chunks(n_rows)); a row shard: its own ranges):
 //   begin_commit            st behind the previous fill; every per-commit field reset, the row / chunk range set
@@ -296,14 +453,16 @@ int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStre
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);
 int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);
 int order_after_commit(lcpc_commit_t* m, hipStream_t st);          // st waits for the commit that filled m (event; cheap)
-int collapse_run(lcpc_commit_t* m, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys);
+int collapse_run(lcpc_commit_t* m, DevScratch* sc, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys);
 size_t collapse_scratch_bytes(const lcpc_commit_t* m, uint32_t n_tensors);
-int collapse_host(lcpc_commit_t* m, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys, uint64_t* polys_canon);
-int collapse_host_sliced(lcpc_commit_t* m, const uint64_t* tensor, uint64_t* polys, uint64_t* polys_canon, uint64_t* cut_out);
-int collapse_wait_slice(lcpc_commit_t* m, int s);
+// the host-entry readers (prove, lcpc_collapse, lcpc_open_columns) run in a working set `ws` of m->sets, taken by take_call_set
+// (the caller holds m->fill_mu shared): everything on ws->st, synchronised on that stream or its events
+int take_call_set(lcpc_commit_t* m, uint64_t pin_bytes, CallSet** ws);
+int collapse_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* tensors, uint32_t n_tensors, uint64_t* polys, uint64_t* polys_canon);
+int collapse_host_sliced(lcpc_commit_t* m, CallSet* ws, const uint64_t* tensor, uint64_t* polys, uint64_t* polys_canon, uint64_t* cut_out);
+int collapse_wait_slice(lcpc_commit_t* m, CallSet* ws, int s);
+int open_columns_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* cols, uint32_t n, uint64_t* col_vals, size_t vals_pitch, uint8_t* paths);
 // open_column values / paths into device buffers (either may be null)
-int open_columns_host(lcpc_commit_t* m, const uint64_t* cols, uint32_t n, uint64_t* col_vals, size_t vals_pitch, uint8_t* paths);
-int ensure_pinned(lcpc_commit_t* m, uint64_t bytes);
 int open_columns_device(lcpc_commit_t* m, const uint64_t* d_cols, uint32_t n, uint32_t* d_vals, uint32_t* d_paths, hipStream_t st);
 
 // ---- shard.cpp --------------------------------------------------------------------------------------

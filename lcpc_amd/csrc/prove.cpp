@@ -74,18 +74,20 @@ void proof_buf_free(void* p) {
   free(drop);
 }
 
+// The caller holds m->fill_mu shared (and, sharded, m->shard_prove_mu).  Everything of this call -- pinned arena, slice events,
+// device scratch, stream -- is in a working set of m->sets, so unsharded proves of one commitment run side by side.
 int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_transcript* trw, uint8_t** proof, uint64_t* proof_len,
                uint64_t* cols_opened, const ShardXchg* xchg) {
   if (!m || !outer || !trw || !proof || !proof_len) return LCPC_ERR_ARG;
-  std::lock_guard<std::mutex> prove_lock(m->prove_mu);
   if (!m->committed) return LCPC_ERR_STATE;
   lcpc_ctx* c = m->enc;
   if (c->prm.shard_count > 1 && !xchg) return LCPC_ERR_STATE;   // sharded commitments prove through lcpc_prove_sharded*
   const FieldDesc& f = *c->f;
   const int L = f.L;
+  SetLease<CallSet> ws{m->sets};
   // polynomials in Montgomery form (what the proof carries) and as canonical values (what the transcript absorbs)
   auto collapse = [&](const uint64_t* tensors, uint32_t nt, uint64_t* polys, uint64_t* canon) -> int {
-    if (!xchg) return collapse_host(m, tensors, nt, polys, canon);
+    if (!xchg) return collapse_host(m, ws.s, tensors, nt, polys, canon);
     return collapse_sharded(m, *xchg, tensors, nt, polys, canon);
   };
   if (!lcpc_dims_ok(c, c->n_per_row, c->n_cols)) return LCPC_ERR_COMMIT;      // check_comm lib.rs:1015
@@ -107,15 +109,13 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   struct Buf { uint8_t* p = nullptr; ~Buf() { proof_buf_free(p); } } out;
   out.p = static_cast<uint8_t*>(proof_buf_alloc(total ? total : 1));
   if (!out.p) return LCPC_ERR_NOMEM;
-  // pinned arena that stays with the commitment: [tensors 2 nr][polys 2 np][canon 2 np] elements
+  // the working set's pinned arena: [tensors 2 nr][polys 2 np][canon 2 np] elements
   const size_t a_t = 2 * nr * L, a_p = 2 * np * L;
   {
-    std::lock_guard<std::mutex> g(m->mu);
-    HIPCHK(m, hipSetDevice(c->prm.device));      // the pinned arena belongs to the encoder's device, whatever this thread used last
-    int rc = ensure_pinned(m, (a_t + 2 * a_p) * 8);
+    int rc = take_call_set(m, (a_t + 2 * a_p) * 8, &ws.s);
     if (rc) return rc;
   }
-  uint64_t* tensors = reinterpret_cast<uint64_t*>(m->h_pin);
+  uint64_t* tensors = reinterpret_cast<uint64_t*>(ws.s->h_pin);
   uint64_t* polys = tensors + a_t;
   uint64_t* canon = polys + a_p;
   std::vector<uint64_t> p_eval_canon;                                         // only when the eval tensor could not be fused
@@ -145,20 +145,20 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
     // (serial STROBE, ~50 ns per coefficient) hides the computation of the second (commit.cpp collapse_host_sliced)
     const bool sliced = xchg == nullptr && nt == 1 && np >= 32768;
     uint64_t cut = np;
-    int rc = sliced ? collapse_host_sliced(m, tensors, polys, canon, &cut) : collapse(tensors, nt, polys, canon);
+    int rc = sliced ? collapse_host_sliced(m, ws.s, tensors, polys, canon, &cut) : collapse(tensors, nt, polys, canon);
     if (rc) return rc;
-    if (sliced && (rc = collapse_wait_slice(m, 0))) return rc;
+    if (sliced && (rc = collapse_wait_slice(m, ws.s, 0))) return rc;
     t_collapse += now_ms() - t0;
     if (eval_here) have_eval = true;
     if (nt == 2 && n_deg > 1) p_eval_canon.assign(canon + np * L, canon + 2 * np * L);
     // the helper copies this round's polynomial(s) into the proof (and thereby faults the fresh pages in) meanwhile
-    filler = std::thread([=, &out, &eval_rc, &p_eval_canon, &collapse] {
+    filler = std::thread([=, &out, &eval_rc, &p_eval_canon, &collapse, &ws] {
       if (eval_beside) {
         eval_rc = collapse(tensors + nr * L, 1, polys + np * L, canon + np * L);   // (queues up behind p_random's second range)
         if (eval_rc) return;
         if (n_deg > 1) p_eval_canon.assign(canon + np * L, canon + 2 * np * L);
       }
-      if (sliced && (eval_rc = collapse_wait_slice(m, 1))) return;              // all of p_random is on the host before it is copied
+      if (sliced && (eval_rc = collapse_wait_slice(m, ws.s, 1))) return;              // all of p_random is on the host before it is copied
       memcpy(out.p + off_rand0 + i * (8 + pbytes), polys, pbytes);
       if (eval_here) memcpy(out.p + off_eval, polys + np * L, pbytes);
       if (i + 1 == n_deg) memset(out.p + head, 0, total - head);              // touch the column area before the copies land in it
@@ -166,7 +166,7 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
     t0 = now_ms();
     absorb_canon(tr, LBL_PR, f, canon, cut);
     if (sliced) {
-      if ((rc = collapse_wait_slice(m, 1))) return rc;
+      if ((rc = collapse_wait_slice(m, ws.s, 1))) return rc;
       absorb_canon(tr, LBL_PR, f, canon + cut * L, np - cut);
     }
     t_absorb += now_ms() - t0;
@@ -198,7 +198,7 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   if (xchg) {
     rc = open_sharded(m, *xchg, cols.data(), (uint32_t)n_open, vals0, col_bytes, paths.get());   // straight into the bincode slots
   } else {
-    rc = open_columns_host(m, cols.data(), (uint32_t)n_open, vals0, col_bytes, paths.get());      // lib.rs:1081-1084
+    rc = open_columns_host(m, ws.s, cols.data(), (uint32_t)n_open, vals0, col_bytes, paths.get());      // lib.rs:1081-1084
   }
   if (rc) return rc;
   tp[4] = now_ms();
@@ -277,7 +277,9 @@ void lcpc_transcript_free(lcpc_transcript* t) { delete t; }
 
 int lcpc_prove(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_transcript* trw, uint8_t** proof, uint64_t* proof_len,
                uint64_t* cols_opened) {
+  if (!m) return LCPC_ERR_ARG;
   LCPC_TRY
+  std::shared_lock<FillLock> rd(m->fill_mu);      // a refill of m waits for this prove; proves run side by side
   return prove_impl(m, outer, n_outer, trw, proof, proof_len, cols_opened, nullptr);
   LCPC_CATCH(m)
 }
@@ -363,19 +365,14 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   //                columns, and the part of step 3 (lib.rs:923-944) that does not depend on WHICH columns were drawn:
   //                the tensor . column dot products and the leaf hash of every opened column, and <inner, p_eval>.
   const size_t enc_words = (size_t)(n_deg + 1) * n_cols * L, canon_words = (size_t)(n_deg + 1) * n_per_row * L;
-  std::lock_guard<std::mutex> arena_lock(c->verify_mu);
+  // this call's pinned working set (verifies under one encoder run side by side, each in its own)
+  SetLease<VerifySet> arena{c->verify_sets};
   {
-    const size_t need = (enc_words + canon_words) * 8 + 256;
-    if (c->h_varena_cap < need) {
-      if (hipSetDevice(c->prm.device) != hipSuccess) return LCPC_ERR_HIP;
-      if (c->h_varena) (void)hipHostFree(c->h_varena);
-      c->h_varena = nullptr; c->h_varena_cap = 0;
-      void* hp = nullptr;
-      if (hipHostMalloc(&hp, need + need / 4, hipHostMallocDefault) != hipSuccess) return LCPC_ERR_NOMEM;
-      c->h_varena = static_cast<uint8_t*>(hp); c->h_varena_cap = need + need / 4;
-    }
+    if (hipSetDevice(c->prm.device) != hipSuccess) return LCPC_ERR_HIP;
+    const int rc = c->verify_sets.take((enc_words + canon_words) * 8 + 256, &arena.s);
+    if (rc) return rc;
   }
-  uint64_t* const enc = reinterpret_cast<uint64_t*>(c->h_varena);
+  uint64_t* const enc = reinterpret_cast<uint64_t*>(arena.s->h_pin);
   uint64_t* const vcanon = enc + ((enc_words + 31) & ~(size_t)31);
   std::vector<const uint64_t*> enc_msgs(n_deg + 1);
   for (uint64_t i = 0; i < n_deg; i++) enc_msgs[i] = p_random[i].data();

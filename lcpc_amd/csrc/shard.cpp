@@ -121,7 +121,7 @@ Rccl& rccl() {
   return r;
 }
 constexpr int NCCL_UINT8 = 1;      // ncclUint8 (rccl.h)
-int fail_nccl(std::string* err, int rc, const char* what) {
+int fail_nccl(ErrText* err, int rc, const char* what) {
   if (err) *err = std::string(what) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(rc) : "nccl error") ;
   return LCPC_ERR_XCHG;
 }
@@ -175,16 +175,16 @@ int collapse_sharded(lcpc_commit_t* m, const ShardXchg& x, const uint64_t* tenso
     if (rc) return rc;
     const size_t row_b = m->n_rows_local * eb;
     const size_t tb = ((size_t)nt * row_b + 255) & ~(size_t)255, pb = (bytes + 255) & ~(size_t)255;
-    if ((rc = ensure_scratch(m, tb + pb + collapse_scratch_bytes(m, 2) + 512))) return rc;
-    uint32_t* d_t = m->d_scratch;
-    d_canon = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(m->d_scratch) + tb);
+    if ((rc = ensure_scratch(m, &m->sc, tb + pb + collapse_scratch_bytes(m, 2) + 512))) return rc;
+    uint32_t* d_t = m->sc.d;
+    d_canon = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(m->sc.d) + tb);
     if (m->n_rows_local == 0) {
       HIPCHK(m, hipMemsetAsync(x.send_dev, 0, bytes, st));
     } else {
       for (uint32_t t = 0; t < nt; t++)      // this rank's slice of every tensor, straight from the caller's buffer
         HIPCHK(m, hipMemcpyAsync(reinterpret_cast<uint8_t*>(d_t) + (size_t)t * row_b, tensors_full + ((size_t)t * m->n_rows + m->row_begin) * L, row_b,
                                  hipMemcpyHostToDevice, st));
-      if ((rc = collapse_run(m, d_t, nt, st, reinterpret_cast<uint32_t*>(x.send_dev)))) return rc;
+      if ((rc = collapse_run(m, &m->sc, d_t, nt, st, reinterpret_cast<uint32_t*>(x.send_dev)))) return rc;
     }
     if (!x.stream_ordered) HIPCHK(m, hipStreamSynchronize(st));       // a host-driven exchange reads send_dev next
   }
@@ -232,8 +232,8 @@ int open_sharded(lcpc_commit_t* m, const ShardXchg& x, const uint64_t* cols, uin
     if (rc) return rc;
     const size_t cb = (((size_t)n * 8) + 255) & ~(size_t)255, pb = (((size_t)n * c->path_len * 32) + 255) & ~(size_t)255;
     const size_t rbb = (((size_t)(G + 1) * 8) + 255) & ~(size_t)255, ob = (((size_t)n * col_b) + 255) & ~(size_t)255;
-    if ((rc = ensure_scratch(m, cb + pb + rbb + ob))) return rc;
-    uint8_t* base = reinterpret_cast<uint8_t*>(m->d_scratch);
+    if ((rc = ensure_scratch(m, &m->sc, cb + pb + rbb + ob))) return rc;
+    uint8_t* base = reinterpret_cast<uint8_t*>(m->sc.d);
     uint64_t* d_cols = reinterpret_cast<uint64_t*>(base);
     uint32_t* d_paths = reinterpret_cast<uint32_t*>(base + cb);
     d_rb = reinterpret_cast<uint64_t*>(base + cb + pb);
@@ -414,6 +414,7 @@ int lcpc_commit_shard_device(lcpc_commit_t* m, const uint64_t* coeffs_local, uin
                              uint8_t* nodes_dev) {
   if (!m || n_rows_total == 0 || !nodes_dev || is_sha3(m->enc)) return LCPC_ERR_ARG;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
   hipStream_t st = (hipStream_t)stream;
@@ -428,6 +429,7 @@ int lcpc_commit_shard_device(lcpc_commit_t* m, const uint64_t* coeffs_local, uin
 int lcpc_commit_finish_device(lcpc_commit_t* m, uint8_t* gathered, uint64_t n_rows_total, uint32_t slots_per_rank, void* stream, uint8_t* root) {
   if (!m || !gathered || is_sha3(m->enc)) return LCPC_ERR_ARG;
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   if (n_rows_total != m->n_rows) return LCPC_ERR_ARG;
   if (!m->shard_encoded) return LCPC_ERR_STATE;             // (read under the lock: the encode step may run on another host thread)
@@ -544,6 +546,7 @@ int lcpc_commit_sharded_device(lcpc_commit_t* m, const uint64_t* coeffs_local, u
   lcpc_ctx* c = m->enc;
   if (!c->comm) return LCPC_ERR_STATE;             // lcpc_comm_init first
   LCPC_TRY
+  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
   hipStream_t st = (hipStream_t)stream;
@@ -596,6 +599,7 @@ int lcpc_shard_exchange_probe(lcpc_commit_t* m, void* stream, uint64_t* bytes_in
   lcpc_ctx* c = m->enc;
   if (!c->comm) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::shared_lock<FillLock> rd(m->fill_mu);
   std::lock_guard<std::mutex> g(m->mu);
   if (!m->committed || !m->d_gather) return LCPC_ERR_STATE;
   HIPCHK(m, hipSetDevice(c->prm.device));
@@ -637,8 +641,10 @@ int lcpc_prove_sharded(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer
                        uint64_t* cols_opened) {
   if (!m || !send_dev || !recv_dev || !fn) return LCPC_ERR_ARG;
   if (m->enc->prm.shard_count <= 1) return LCPC_ERR_STATE;
-  if (m->committed && max_bytes < lcpc_prove_sharded_bytes(m->enc, m->n_rows)) return LCPC_ERR_ARG;
   LCPC_TRY
+  std::lock_guard<std::mutex> whole(m->shard_prove_mu);      // sharded proves of one commitment are serial (internal.h)
+  std::shared_lock<FillLock> rd(m->fill_mu);
+  if (m->committed && max_bytes < lcpc_prove_sharded_bytes(m->enc, m->n_rows)) return LCPC_ERR_ARG;
   const ShardXchg x{send_dev, recv_dev, max_bytes, fn, user};
   return prove_impl(m, outer, n_outer, trw, proof, proof_len, cols_opened, &x);
   LCPC_CATCH(m)
@@ -648,8 +654,10 @@ int lcpc_prove_sharded_rccl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_
                             uint64_t* proof_len, uint64_t* cols_opened) {
   if (!m) return LCPC_ERR_ARG;
   lcpc_ctx* c = m->enc;
-  if (!c->comm || !m->committed) return LCPC_ERR_STATE;
   LCPC_TRY
+  std::lock_guard<std::mutex> whole(m->shard_prove_mu);      // sharded proves of one commitment are serial (internal.h); the exchange
+  std::shared_lock<FillLock> rd(m->fill_mu);                 // buffers below are this call's until it returns
+  if (!c->comm || !m->committed) return LCPC_ERR_STATE;
   const uint64_t nb = lcpc_prove_sharded_bytes(c, m->n_rows);
   {
     std::lock_guard<std::mutex> g(m->mu);
