@@ -102,16 +102,10 @@ static int build_wq_w(lcpc_ctx* c, int N, int W) {
   return 0;
 }
 
-// the lazy-limb form of the context's field: N limbs of W bits, `stride` words per table entry (field_dev.h l9 / field_ln.h)
-struct LimbForm { int N, W, stride; };
-static LimbForm limb_form(const lcpc_ctx* c) {
-  if (c->L == 4) return {9, 29, 12};
-  return {ntt_lns_limbs(c->NL), ntt_lns_limb_bits(c->NL), ntt_lns_stride(c->NL)};
-}
-// (i - 24) * p for i < 64 as normalised signed limbs of the form (limbs 0..N-2 in [0, 2^W), the top limb two's complement): the
-// table behind l9::clamp / ln::clamp_* (QOFF in field_dev.h)
-static std::vector<uint32_t> clamp_table(const FieldDesc& f, const LimbForm& lf) {
-  std::vector<uint32_t> tab((size_t)64 * lf.stride, 0);
+// (i - 24) * p for i < 64 as normalised signed limbs of the field's lazy-limb form (N limbs of W bits, `stride` words per entry;
+// limbs 0..N-2 in [0, 2^W), the top limb two's complement): the table behind ln::clamp / ln::clamp_* (QOFF in field_ln.h)
+static std::vector<uint32_t> clamp_table(const FieldDesc& f, int N, int W, int stride) {
+  std::vector<uint32_t> tab((size_t)64 * stride, 0);
   for (int i = 0; i < 64; i++) {
     const int q = i - 24;
     uint64_t mag[5] = {0, 0, 0, 0, 0};                      // |q| * p
@@ -121,23 +115,23 @@ static std::vector<uint32_t> clamp_table(const FieldDesc& f, const LimbForm& lf)
       unsigned __int128 c2 = 1;
       for (int w = 0; w < 5; w++) { c2 += (unsigned __int128)(~mag[w]); mag[w] = (uint64_t)c2; c2 >>= 64; }
     }
-    for (int l = 0; l < lf.N; l++) {
-      const int b = lf.W * l, w = b / 64, sh = b % 64;
+    for (int l = 0; l < N; l++) {
+      const int b = W * l, w = b / 64, sh = b % 64;
       uint64_t x = mag[w] >> sh;
       if (sh && w + 1 < 5) x |= mag[w + 1] << (64 - sh);
-      tab[(size_t)i * lf.stride + l] = l + 1 < lf.N ? (uint32_t)(x & (((uint64_t)1 << lf.W) - 1)) : (uint32_t)x;   // top limb: sign-extended
+      tab[(size_t)i * stride + l] = l + 1 < N ? (uint32_t)(x & (((uint64_t)1 << W) - 1)) : (uint32_t)x;   // top limb: sign-extended
     }
   }
   return tab;
 }
 // d_qpl and d_wq_w in the context's limb form; `made` (may be null) collects the allocations
 static int limb_consts(lcpc_ctx* c, std::vector<uint32_t**>* made) {
-  const LimbForm lf = limb_form(c);
-  const std::vector<uint32_t> tab = clamp_table(*c->f, lf);
+  const int N = ntt_lns_limbs(c->NL), W = ntt_lns_limb_bits(c->NL);
+  const std::vector<uint32_t> tab = clamp_table(*c->f, N, W, ntt_lns_stride(c->NL));
   if (made) { made->push_back(&c->d_qpl); made->push_back(&c->d_wq_w); }
   if (int rc = dev_alloc(&c->err, &c->d_qpl, tab.size() * 4)) return rc;
   HIPCHK(c, hipMemcpy(c->d_qpl, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-  return build_wq_w(c, lf.N, lf.W);
+  return build_wq_w(c, N, W);
 }
 
 // ---- NTT pass plan (DESIGN.md "K1") ----------------------------------------------------------------
@@ -217,20 +211,19 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
   const int rc = [&]() -> int {
     const FieldDesc* f = c->f;
     ErrText* err = &c->err;
-    const bool k1s = c->L == 4;
     const unsigned k = c->log_n, s0 = k - 10 * (n_pass - 1);
-    const LimbForm lf = limb_form(c);
+    const size_t stride = (size_t)ntt_lns_stride(c->NL);
     auto alloc = [&](uint32_t** p, size_t bytes) { made.push_back(p); return dev_alloc(err, p, bytes); };
     int r;
-    if (!k1s) {
+    if (c->L != 4) {                                           // (Ft255's tables were made with d_roots)
       // w^i R' mod p and w^i R' R^-1 = mont_mul(w^i R, R' R^-1) from d_roots, with R' = 2^(N W) mod p (a plain integer)
       uint64_t rp[2 * MAXL] = {1, 0, 0, 0};                    // R', then R' R^-1
-      for (int i = 0; i < lf.N * lf.W; i++) h_add(*f, rp, rp, rp);
+      for (int i = 0; i < ntt_lns_limbs(c->NL) * ntt_lns_limb_bits(c->NL); i++) h_add(*f, rp, rp, rp);
       h_canon(*f, rp + f->L, rp);
       const size_t n_roots = (size_t)1 << (k - 1);
       uint32_t* d_rp = nullptr;
       if ((r = dev_alloc(err, &d_rp, 16 * f->L))) return r;
-      if ((r = alloc(&c->d_rootsl, n_roots * lf.stride * 4)) || (r = alloc(&c->d_rootslc, n_roots * lf.stride * 4))) { dev_free(d_rp); return r; }
+      if ((r = alloc(&c->d_rootsl, n_roots * stride * 4)) || (r = alloc(&c->d_rootslc, n_roots * stride * 4))) { dev_free(d_rp); return r; }
       hipError_t he = hipMemcpy(d_rp, rp, 16 * f->L, hipMemcpyHostToDevice);
       if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rp, c->d_rootsl, nullptr);
       if (he == hipSuccess) he = launch_ntt_lns_roots(c->NL, c->d_roots, n_roots, d_rp + 2 * f->L, c->d_rootslc, nullptr);
@@ -241,17 +234,17 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
     }
     if (n_pass == 3) {
       const size_t n_sub = (size_t)1 << 19;
-      if ((r = alloc(&c->d_rootsls, n_sub * lf.stride * 4)) || (r = alloc(&c->d_rootslcs, n_sub * lf.stride * 4))) return r;
+      if ((r = alloc(&c->d_rootsls, n_sub * stride * 4)) || (r = alloc(&c->d_rootslcs, n_sub * stride * 4))) return r;
       for (int i = 0; i < 2; i++) {
         const uint32_t* tab = i ? c->d_rootslc : c->d_rootsl;
         uint32_t* sub = i ? c->d_rootslcs : c->d_rootsls;
-        HIPCHK(c, k1s ? launch_ntt_l9s_subtable(tab, s0, n_sub, sub, nullptr) : launch_ntt_lns_subtable(c->NL, tab, s0, n_sub, sub, nullptr));
+        HIPCHK(c, launch_ntt_lns_subtable(c->NL, tab, s0, n_sub, sub, nullptr));
       }
     }
     for (unsigned i = 0; i < n_pass; i++) {
       NttStep& p = plan[i];
       const bool sub = n_pass == 3 && i > 0, last = i + 1 == n_pass;   // sub: a pass of the 2^20-point transforms
-      p.kernel = k1s ? NttStep::K1S : NttStep::K1N;
+      p.kernel = c->L == 4 ? NttStep::K1S : NttStep::K1N;
       p.first = !last;
       p.a.roots = c->d_roots; p.a.roots29 = sub ? c->d_rootsls : c->d_rootsl; p.a.qp29 = c->d_qpl; p.a.wq_w = c->d_wq_w;
       p.a.log_n = sub ? 20u : k;
@@ -266,7 +259,7 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
       // ntt_lns.hip), or already in the pass before if that has >= 8 stages: then the last pass sees canonical values only
       p.mont_prefix = last && c->NL == 2 ? 4u : 0u;
       p.blk0_gone = last && c->NL != 2 && plan[i - 1].a.s >= 8 ? 1u : 0u;
-      p.pack_info = k1s ? ntt_l9s_pack_info(p.a.s, p.first) : ntt_lns_pack_info(c->NL, p.a.s, p.first);
+      p.pack_info = ntt_lns_pack_info(c->NL, p.a.s, p.first);
       const uint32_t n_classes = p.first ? 1u << (p.a.log_n - 10) : 1u;  // first pass: one class per tile position
 #ifdef LCPC_TEST_HOOKS
       if (n_pass == 3 && i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;   // (the fallback below)
@@ -274,8 +267,7 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
       if ((r = alloc(&p.pack, (size_t)n_classes * p.pack_info.class_words * 4))) return r;
       NttPassArgs pa{};
       pa.roots29 = p.a.roots29; pa.roots29c = p.roots29c; pa.log_n = p.a.log_n; pa.t0 = p.a.t0; pa.s = p.a.s; pa.log_tj = p.a.log_tj;
-      HIPCHK(c, k1s ? launch_ntt_l9s_pack(pa, p.first, p.pack_info, n_classes, p.pack, nullptr)
-                    : launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
+      HIPCHK(c, launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
     }
     HIPCHK(c, hipDeviceSynchronize());
     return 0;
@@ -601,7 +593,7 @@ static int ctx_build(lcpc_ctx* c, const lcpc_params* p) {
     HIPCHK(c, hipMemcpy(d.rowptr, m.rowptr.data(), m.rowptr.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d.colidx, m.colidx.data(), m.colidx.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d.vals, m.vals.data(), m.vals.size() * 8, hipMemcpyHostToDevice));
-    if (f->L == 4) {      // the 29-bit-limb / 2^261 form of the values (lazy29_mac) is derived on the device from the uploaded copy
+    if (f->L == 4) {      // the 29-bit-limb / 2^261 form of the values (ln::lazy_mac) is derived on the device from the uploaded copy
       const size_t nnz = m.colidx.size();
       if ((r = dev_alloc(err, &d.vals29, (nnz + 1) * 48))) return r;
       HIPCHK(c, launch_to_r29(d.vals, nnz, d.vals29, nullptr));

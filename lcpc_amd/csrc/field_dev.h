@@ -220,8 +220,26 @@ template <> LCPC_DEV Fe<8> fe_sub<8>(const Fe<8>& a, const Fe<8>& b) {
       : "vcc");
   return r;
 }
-// t (8 limbs) in [0, 2p) -> [0, p): the 8-limb specialisation of fe_reduce_once with top == 0
-LCPC_DEV Fe<8> fe_reduce_once8(const u32* t) {
+// conditional final subtraction: t (NL limbs + top word) in [0, 2p) -> [0, p)
+template <int NL> LCPC_DEV Fe<NL> fe_reduce_once(const u32* t, u32 top) {
+  Fe<NL> d, r;
+  u32 br = 0;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    u64 x = (u64)t[i] - Mod<NL>::P[i] - br;
+    d.v[i] = (u32)x;
+    br = (u32)(x >> 63);
+  }
+  const bool ge = (top != 0) | (br == 0);
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.v[i] = ge ? d.v[i] : t[i];
+  return r;
+}
+
+// t (NL limbs) in [0, 2p) -> [0, p)
+template <int NL> LCPC_DEV Fe<NL> fe_reduce_once(const u32* t) { return fe_reduce_once<NL>(t, 0u); }
+// Ft255: the same as one carry chain
+template <> LCPC_DEV Fe<8> fe_reduce_once<8>(const u32* t) {
   Fe<8> r;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.v[i] = t[i];
@@ -246,22 +264,6 @@ LCPC_DEV Fe<8> fe_reduce_once8(const u32* t) {
         "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(d4), "=&v"(d5), "=&v"(d6), "=&v"(d7)
       : "v"(Mod<8>::P[1]), "v"(Mod<8>::P[2]), "v"(Mod<8>::P[3]), "v"(Mod<8>::P[4]), "v"(Mod<8>::P[5]), "v"(Mod<8>::P[6]), "v"(Mod<8>::P[7])
       : "vcc");
-  return r;
-}
-
-// conditional final subtraction: t (NL limbs + top word) in [0, 2p) -> [0, p)
-template <int NL> LCPC_DEV Fe<NL> fe_reduce_once(const u32* t, u32 top) {
-  Fe<NL> d, r;
-  u32 br = 0;
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    u64 x = (u64)t[i] - Mod<NL>::P[i] - br;
-    d.v[i] = (u32)x;
-    br = (u32)(x >> 63);
-  }
-  const bool ge = (top != 0) | (br == 0);
-#pragma unroll
-  for (int i = 0; i < NL; i++) r.v[i] = ge ? d.v[i] : t[i];
   return r;
 }
 
@@ -322,296 +324,6 @@ template <int NL> LCPC_DEV Fe<NL> fe_canon(const Fe<NL>& a) {
   return fe_reduce_once<NL>(t, t[NL]);
 }
 
-
-// ---- reduced-radix Montgomery multiply for Ft255 (the headline field) --------------------------
-// Measured on gfx950 (profiles/r01_ubench_valu.txt): v_mad_u64_u32 issues at ~half the f32-FMA rate,
-// but every carry-propagating add after it costs about as much again, and the 32-bit-limb CIOS above
-// spends >2/3 of its instructions on 64-bit carry emulation.  With 9 limbs of 29 bits a whole Comba
-// column (<= 9 products < 2^58 plus <= 8 reduction products) fits one 64-bit accumulator, so the
-// product AND the Montgomery reduction are a pure chain of 153 v_mad_u64_u32 with no carry handling.
-// p == 1 mod 2^29, hence -p^-1 == -1 mod 2^29 and the quotient digit is a negate-and-mask.
-// The multiplier (a twiddle) is pre-converted on the host to the radix-2^261 Montgomery form
-// w * 2^261 mod p, so  REDC_261( a*R * w*2^261 ) = (a*w)*R : data stays in ff_derive's R = 2^256 form.
-struct P29 {
-  static constexpr u32 M = (1u << 29) - 1;
-  static constexpr u32 limb(int k) {   // k-th 29-bit limb of the Ft255 modulus
-    const int b = 29 * k, w = b / 32, sh = b % 32;
-    u64 lo = Mod<8>::P[w];
-    u64 hi = (w + 1 < 8) ? Mod<8>::P[w + 1] : 0;
-    return (u32)(((lo | (hi << 32)) >> sh) & M);
-  }
-};
-struct Fe29 {
-  u32 v[9];
-};
-// packed 8x32 -> 9x29 (value unchanged, limbs < 2^29)
-LCPC_DEV Fe29 fe_to29(const Fe<8>& a) {
-  Fe29 r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const int b = 29 * k, w = b / 32, sh = b % 32;
-    u32 x;
-    if (sh == 0) x = a.v[w];
-    else if (w + 1 < 8) x = __builtin_amdgcn_alignbit(a.v[w + 1], a.v[w], sh);
-    else x = a.v[w] >> sh;
-    r.v[k] = x & P29::M;
-  }
-  return r;
-}
-// 9x29 (limbs < 2^29, value < 2^256) -> packed 8x32
-LCPC_DEV void fe_from29(u32 out[8], const u32 l[9]) {
-#pragma unroll
-  for (int w = 0; w < 8; w++) {
-    const int b = 32 * w, k = b / 29, s = b % 29;      // word w starts at bit s of limb k
-    u32 x = l[k] >> s;
-    x |= l[k + 1] << (29 - s);
-    if (58 - s < 32 && k + 2 < 9) x |= l[k + 2] << (58 - s);
-    out[w] = x;
-  }
-}
-#include "field_r29_gen.h"   // r29_columns(): the 153-mad Comba/Montgomery chain as generated asm blocks
-#include "field_wmul_gen.h"  // wmul_u(): x * w mod p for a WAVE-UNIFORM w given as its nine shifted multiples (scalar operands)
-
-// r = a * b29 * 2^-261 mod p, fully reduced, packed.  a: packed element < p; b29: 9 limbs < 2^29.
-LCPC_DEV Fe<8> fe_mul_r29(const Fe<8>& a, const Fe29& b) {
-  const Fe29 x = fe_to29(a);
-  u32 m[9], r[9];
-  r29_columns(x.v, b.v, m, r);
-  u32 t[8];
-  fe_from29(t, r);
-  return fe_reduce_once8(t);           // REDC output < 2p < 2^256
-}
-
-
-// =================================================================================================
-// Lazy 9 x 29-bit-limb arithmetic for the Ft255 NTT (ntt_pass_l9_kernel).
-//
-// Measured issue costs on gfx950 (profiles/r01_ubench_valu.txt): plain v_add/v_sub/v_and/v_xor 2.4 cycles per
-// wave64 instruction, but v_addc/v_subb (carry chains), v_alignbit, v_add3, 64-bit adds AND v_mad_u64_u32 all
-// ~4.3-4.5.  In the packed 8x32 representation a butterfly spends ~25 % of its cycles on carry-chain add/sub and
-// on packed<->29-bit conversions around the multiply.  Here an element stays in the multiplier's own format
-// between stages: 9 limbs, SIGNED (two's complement) and only loosely reduced:
-//     invariant I ("normalised"):  limbs 0..7 in [0, 2^29), limb 8 signed;  |value| < 4p;  value == true value (mod p).
-// add and sub are 9 plain limb operations each (differences simply go negative: no bias constants, no borrows);
-// the Montgomery multiply (r29_mul1s: v_mad_i64_i32 column chain with negative quotient digits) accepts limbs in
-// (-2^30, 2^30), |value| < 16p, and returns a normalised value in (-1.2p, 0.2p]; a "clamp" (quotient estimate from
-// the signed top limb, subtract q*p from a table) brings the only growing path (sums of sums) back into [0, 1.01p).
-// Exact reduction to [0,p) and packing happen once per element per pass, at the tile store.  Bounds are stated at
-// every step below and in the kernel; tests/test_gpu_edges.py::test_lazy_limb_ntt_range_stress pushes them.
-// =================================================================================================
-struct L9 {
-  u32 v[9];       // two's complement; limb 8 (and un-normalised intermediates) may be negative
-};
-
-namespace l9 {
-constexpr u32 M = P29::M;
-constexpr int QOFF = 24;          // clamp table: entry i = (i - QOFF) * p, i in [0, 64)
-constexpr int QBIAS = 40;         // subtracted from the top limb before the quotient estimate (keeps remainders >= 0)
-
-LCPC_DEV L9 from_packed(const Fe<8>& a) {           // value in [0, p), normalised
-  const Fe29 t = fe_to29(a);
-  L9 r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) r.v[k] = t.v[k];
-  return r;
-}
-LCPC_DEV L9 add(const L9& a, const L9& b) {         // limb-wise, no carries
-  L9 r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) r.v[k] = a.v[k] + b.v[k];
-  return r;
-}
-LCPC_DEV L9 sub(const L9& a, const L9& b) {         // limb-wise, limbs may go negative
-  L9 r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) r.v[k] = a.v[k] - b.v[k];
-  return r;
-}
-// carry-propagate signed limbs (|limb| < 2^31): limbs 0..7 -> [0, 2^29), limb 8 takes what is left (signed)
-LCPC_DEV void normalize(L9& a) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    a.v[k + 1] += (u32)((int32_t)a.v[k] >> 29);     // floor division: arithmetic shift
-    a.v[k] &= M;
-  }
-}
-// a: normalised, |value| < 16p  ->  normalised, value in [0, p + 2^239) (== a mod p).  qp[i] = (i - QOFF) * p as
-// normalised signed limbs (12-word stride).  With t the signed top limb, V = t * 2^232 + low, 0 <= low < 2^232, and
-// q = floor((t - QBIAS) / (ptop + 1)), ptop = floor(p / 2^232):  t - QBIAS = q (ptop + 1) + rem, so
-// V - q p = q (2^232 - plow) + (rem + QBIAS) 2^232 + low  with plow = p mod 2^232:  >= (QBIAS - |q|) 2^232 >= 0 for
-// |q| <= 17 + 1 and < (ptop + 1 + QBIAS + |q| + 1) 2^232 < p + 2^239.
-LCPC_DEV void clamp(L9& a, const u32* qp) {
-  constexpr u32 PTOP1 = (u32)(P29::limb(8)) + 1;                         // floor(p / 2^232) + 1 (23 bits)
-  constexpr u64 MAGIC = (((u64)1 << 52) + PTOP1 - 1) / PTOP1;            // ceil(2^52 / PTOP1) < 2^30
-  const u32 n = a.v[8] + (u32)(QOFF * PTOP1 - QBIAS);                    // in [0, 2^29) for |value| < 16p
-  const u32 q = (u32)(((u64)n * MAGIC) >> 52);                           // exact floor(n / PTOP1) for n < 2^29
-  const u32* t = qp + q * 12;
-  int32_t d[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) d[k] = (int32_t)(a.v[k] - t[k]);
-#pragma unroll
-  for (int k = 0; k < 8; k++) {                                         // borrow-propagate
-    d[k + 1] += d[k] >> 31;                                             // -1 if limb k went negative
-    a.v[k] = (u32)d[k] & M;                                             // + 2^29 in that case
-  }
-  a.v[8] = (u32)d[8];
-}
-// ---- normalise + clamp in ONE carry pass (ntt_pass_l9s_kernel) ----------------------------------------------------
-// The pure-sum output of a radix-4 butterfly, c0 = x0 + x1 + x2 + x3 of four normalised values, has limbs 0..7 in
-// [0, 2^31 - 4] and a signed top limb; |value| < 16p.  clamp_q() estimates the quotient from that UN-normalised top limb
-// (the carries still sitting in the lower limbs, at most 3 units of 2^232, are not in it yet), the row q*p is fetched from
-// the NEGATED table nqp[i] = -(i - QOFF) * p (limb-wise; the kernel negates the l9::clamp table when it copies it to
-// LDS), and clamp_apply() adds row and carries in one sweep.  With t' = t - c (c in [0, 3] the unseen carry) the
-// derivation above l9::clamp gives  V - q p = q (2^232 - plow) + (rem + QBIAS + c) 2^232 + low:  still >= 0 and
-// < (ptop + 1 + QBIAS + |q| + 1 + 3) 2^232 < p + 2^239.  Per limb: d = a_k - t_k + carry in (-2^29 - 1, 2^31) fits i32.
-struct Row9 {
-  u32 v[9];
-};
-LCPC_DEV u32 clamp_q(u32 top) {
-  constexpr u32 PTOP1 = (u32)(P29::limb(8)) + 1;
-  constexpr u64 MAGIC = (((u64)1 << 52) + PTOP1 - 1) / PTOP1;
-  const u32 n = top + (u32)(QOFF * PTOP1 - QBIAS);                       // in [0, 2^29) for |value| < 16p
-  return (u32)(((u64)n * MAGIC) >> 52);
-}
-LCPC_DEV Row9 clamp_row(const u32* nqp, u32 q) {
-  const uint4 a = *reinterpret_cast<const uint4*>(nqp + q * 12), b = *reinterpret_cast<const uint4*>(nqp + q * 12 + 4);
-  Row9 r;
-  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-  r.v[8] = nqp[q * 12 + 8];
-  return r;
-}
-LCPC_DEV void clamp_apply(L9& a, const Row9& nt) {
-  int32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int32_t d = (int32_t)(a.v[k] + nt.v[k] + (u32)c);
-    a.v[k] = (u32)d & M;
-    c = d >> 29;
-  }
-  a.v[8] = a.v[8] + nt.v[8] + (u32)c;
-}
-// (a * w) * 2^-261 mod p, loosely: a limbs in (-2^30, 2^30), |value| < 16p; w normalised, in [0, p) (2^261-Montgomery
-// form).  Column sums stay inside i64: 9 * 2^59 + 8 * 2^58 + 2^34 < 2^63.  Result: normalised, in (-1.2p, 0.2p].
-LCPC_DEV L9 mul(const L9& a, const Fe29& w) {
-  L9 r;
-  r29_mul1s(a.v, w.v, r.v);       // one asm statement (field_r29_gen.h)
-  return r;
-}
-// a * w mod p for a wave-uniform w: wt = the 81 words t = 9 k + j of its shifted multiples W_j = balanced(w 2^(29 j) mod p), limb k
-// (host: ctx.cpp wmul_table).  a: limbs of a difference of two normalised values (sum |limb| < 9 * 2^29).  Result: normalised,
-// in (-2p, 2.7p).  119 instructions against mul()'s 188 (tools/lab, profiles/r05_ubench_wmul.jsonl: 1.6-1.8 x per second).
-LCPC_DEV L9 mul_u(const L9& a, const u32* wt) {
-  u32 np2[9];
-#pragma unroll
-  for (int j = 0; j < 9; j++) np2[j] = 0u - 2u * (u32)P29::limb(j);        // the limbs of -2p (the quotient counts units of 2p)
-  L9 r;
-  wmul_u(a.v, np2, wt, r.v);
-  return r;
-}
-// exact: normalised |value| < 16p -> packed, fully reduced
-LCPC_DEV Fe<8> to_packed_reduced(L9 a, const u32* qp) {
-  clamp(a, qp);                   // [0, p + 2^239) < 2^256
-  u32 t[8];
-  fe_from29(t, a.v);
-  return fe_reduce_once8(t);
-}
-}  // namespace l9
-
-// Montgomery form (R = 2^256) -> canonical value for Ft255, reduction only: a * 2^-256 = REDC_261(a * 2^5).
-// The "product" a << 5 needs no multiplies; the 9-step reduction is 72 v_mad_u64_u32, carry-free.
-LCPC_DEV Fe<8> fe_canon_r29(const Fe<8>& a) {
-  // limbs of (a << 5): bit b of the shifted value is bit b-5 of a
-  u32 x[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const int b = 29 * k - 5;            // first source bit of limb k (negative for k = 0)
-    u32 v;
-    if (k == 0) v = (a.v[0] << 5);
-    else {
-      const int w = b / 32, sh = b % 32;
-      if (sh == 0) v = a.v[w];
-      else if (w + 1 < 8) v = __builtin_amdgcn_alignbit(a.v[w + 1], a.v[w], sh);
-      else v = a.v[w] >> sh;
-    }
-    x[k] = v & P29::M;
-  }
-  u32 m[9], r[9];
-  u64 acc = 0;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    if (k < 9) acc += x[k];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (i < k && j >= 1 && j < 9) acc += (u64)m[i] * P29::limb(j);
-    }
-    if (k < 9) {
-      m[k] = (0u - (u32)acc) & P29::M;
-      acc += m[k];
-      acc >>= 29;
-    } else {
-      r[k - 9] = (u32)acc & P29::M;
-      acc >>= 29;
-    }
-  }
-  r[8] = (u32)acc;
-  u32 t[8];
-  fe_from29(t, r);
-  return fe_reduce_once8(t);
-}
-
-
-// ---- carry-free lazy dot product for Ft255 (Brakedown SpMM, collapse) ---------------------------
-// acc += x * v with x, v as 9 x 29-bit limbs: 81 v_mad_u64_u32 into 18 u64 columns, no carries.
-// A column receives <= 9 products < 2^58 per term, so up to 7 terms fit before lazy29_normalize()
-// must move the excess up; the value is Montgomery-reduced once per dot product (lazy29_reduce).
-struct Lazy29 {
-  u64 c[18];
-};
-LCPC_DEV void lazy29_zero(Lazy29& a) {
-#pragma unroll
-  for (int k = 0; k < 18; k++) a.c[k] = 0;
-}
-LCPC_DEV void lazy29_mac(Lazy29& a, const Fe29& x, const Fe29& v) {
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) a.c[i + j] += (u64)x.v[i] * v.v[j];
-}
-LCPC_DEV void lazy29_normalize(Lazy29& a) {
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    a.c[k + 1] += a.c[k] >> 29;
-    a.c[k] &= P29::M;
-  }
-}
-// value * 2^-261 mod p, fully reduced, packed.  Requires value < 64 * p^2 (<= 64 terms of (x < p) * (v < p)),
-// so that the REDC output is < 2p.  v operands must be in the 2^261-Montgomery form (like the NTT twiddles).
-LCPC_DEV Fe<8> lazy29_reduce(Lazy29& a) {
-  lazy29_normalize(a);
-  u32 m[9], r[9];
-  u64 acc = 0;
-#pragma unroll
-  for (int k = 0; k < 18; k++) {
-    acc += a.c[k];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (i < k && j >= 1 && j < 9) acc += (u64)m[i] * P29::limb(j);
-    }
-    if (k < 9) {
-      m[k] = (0u - (u32)acc) & P29::M;
-      acc += m[k];
-      acc >>= 29;
-    } else {
-      r[k - 9] = (u32)acc & P29::M;
-      acc >>= 29;
-    }
-  }
-  u32 t[8];
-  fe_from29(t, r);
-  return fe_reduce_once8(t);
-}
 
 // ---- lazy (unreduced) accumulation: sum of products, one Montgomery reduction at the end -------
 // Used by collapse_columns and the expander SpMV: acc += a*b as a plain 2NL(+1)-limb integer.

@@ -1,48 +1,60 @@
-// lcpc_amd/csrc/field_ln.h -- lazy signed reduced-radix arithmetic for Ft63 / Ft127 / Ft191 (the row NTT of
-// ntt_lns.hip): the scheme of field_dev.h's namespace l9 (Ft255: 9 limbs of 29 bits) for the other three test fields of
-// /root/reference/lcpc-test-fields/src/lib.rs:18-58 (ff_derive [3P]: Montgomery form, R = 2^(64 L)).
+// lcpc_amd/csrc/field_ln.h -- lazy signed reduced-radix arithmetic for the four test fields of
+// /root/reference/lcpc-test-fields/src/lib.rs:13-59 (ff_derive [3P]: Montgomery form, R = 2^(64 L)): the row NTTs (ntt_l9s.hip for
+// Ft255, ntt_lns.hip for the others, kernels.hip ntt_pass_l9_kernel), the carry-free lazy dot products (collapse, SpMV, SpMM).
 //
 //   field   N limbs x W bits   R' = 2^(N W)   spare bits N W - log2 p   top limb of p (PTOP)
 //   Ft63    3 x 26             2^78           15.9                      0x46d     (p >> 52)
 //   Ft127   5 x 29             2^145          18.2                      0x6e7     (p >> 116)
 //   Ft191   7 x 29             2^203          12.9                      0x8a6e    (p >> 174)
+//   Ft255   9 x 29             2^261           6.3                      0x663c79  (p >> 232)
 // (26-bit limbs for Ft63: with 29 the top limb of p would be 17, too coarse for the quotient estimate of the clamp.)
 //
-// An element between stages: N limbs, limbs 0..N-2 in [0, 2^W), top limb two's complement; |value| < 4p; value == the true
-// value (mod p) ("invariant I", as in l9).  add / sub are N plain limb operations; the Montgomery multiply
-// (field_ln_gen.h: ONE asm statement, N^2 + N(N-1) v_mad_i64_i32 on a single 64-bit accumulator, negative quotient
-// digits) accepts limbs in (-2^(W+1), 2^(W+1)), |value| < 16p, and returns a normalised value in (-p - eps, eps],
-// eps = 16 p^2 / R' < p / 400; sums of sums are brought back to [0, p + 64 B), B = 2^(W(N-1)), by the quotient-estimate
-// clamp.  Data stays in ff_derive's R = 2^(32 NL) form in HBM: the twiddles are pre-scaled to w^i * R' mod p, so that
-// REDC_R'(a R * w R') = (a w) R.  Exact reduction to [0, p) happens once per element, at the last pass's store.
+// Why limbs (measured issue costs on gfx950, profiles/r01_ubench_valu.txt): plain v_add/v_sub/v_and/v_xor cost 2.4 cycles per wave64
+// instruction, but v_addc/v_subb (carry chains), v_alignbit, v_add3, 64-bit adds AND v_mad_u64_u32 all ~4.3-4.5.  In the packed 32-bit
+// representation a butterfly spends ~25 % of its cycles on carry-chain add/sub and on conversions around the multiply; with W-bit limbs
+// a whole Comba column of the Montgomery multiply fits one 64-bit accumulator (a pure chain of mads, no carry handling), and an element
+// stays in the multiplier's own format between stages:
+//     invariant I ("normalised"):  limbs 0..N-2 in [0, 2^W), top limb two's complement;  |value| < 4p;  value == true value (mod p).
+// add / sub are N plain limb operations (differences simply go negative: no bias constants, no borrows); the Montgomery multiply
+// (field_ln_gen.h / field_r29_gen.h: ONE asm statement, N^2 + N(N-1) v_mad_i64_i32 on a single 64-bit accumulator, negative quotient
+// digits; p == 1 mod 2^W, so the quotient digit is a negate-and-mask) accepts limbs in (-2^(W+1), 2^(W+1)), |value| < 16p, and returns
+// a normalised value in (-p - eps, eps], eps = 16 p^2 / R' (Ft255: (-1.2p, 0.2p]); sums of sums are brought back to [0, p + 64 B),
+// B = 2^(W(N-1)), by the quotient-estimate clamp.  Data stays in ff_derive's R = 2^(32 NL) form in HBM: the twiddles are pre-scaled
+// to w^i R' mod p, so that REDC_R'(a R * w R') = (a w) R.  Exact reduction to [0, p) happens once per element, at the last pass's
+// store.  Bounds are stated at every step here and in the kernels; tests/test_gpu_edges.py and tests/test_gpu_lazy_worst.py push them.
 #pragma once
 #include "field_dev.h"
 
 namespace lcpc {
 
+// k-th W-bit limb of the modulus of NL 32-bit words
+template <int NL, int W> constexpr u32 mod_limb(int k) {
+  const int b = W * k, w = b / 32, sh = b % 32;
+  const u64 lo = Mod<NL>::P[w], hi = (w + 1 < NL) ? Mod<NL>::P[w + 1] : 0;
+  return (u32)(((lo | (hi << 32)) >> sh) & ((1u << W) - 1));
+}
+// WAVES: the occupancy the row NTT of the field is built for; STRIDE: words per entry of the limb-form tables (twiddles, q*p rows)
 template <int FID> struct LnField;
 template <> struct LnField<FT63> {
   static constexpr int FID = FT63, N = 3, W = 26, NL = 2, WAVES = 8, STRIDE = 4;
-  static constexpr u32 limb(int k) { return (u32)(((((u64)Mod<2>::P[1] << 32) | Mod<2>::P[0]) >> (26 * k)) & ((1u << 26) - 1)); }
+  static constexpr u32 limb(int k) { return mod_limb<NL, W>(k); }
 };
 template <> struct LnField<FT127> {
   static constexpr int FID = FT127, N = 5, W = 29, NL = 4, WAVES = 7, STRIDE = 8;
-  static constexpr u32 limb(int k) {
-    const int b = 29 * k, w = b / 32, sh = b % 32;
-    const u64 lo = Mod<4>::P[w], hi = (w + 1 < 4) ? Mod<4>::P[w + 1] : 0;
-    return (u32)(((lo | (hi << 32)) >> sh) & ((1u << 29) - 1));
-  }
+  static constexpr u32 limb(int k) { return mod_limb<NL, W>(k); }
 };
 template <> struct LnField<FT191> {
   static constexpr int FID = FT191, N = 7, W = 29, NL = 6, WAVES = 5, STRIDE = 8;
-  static constexpr u32 limb(int k) {
-    const int b = 29 * k, w = b / 32, sh = b % 32;
-    const u64 lo = Mod<6>::P[w], hi = (w + 1 < 6) ? Mod<6>::P[w + 1] : 0;
-    return (u32)(((lo | (hi << 32)) >> sh) & ((1u << 29) - 1));
-  }
+  static constexpr u32 limb(int k) { return mod_limb<NL, W>(k); }
+};
+template <> struct LnField<FT255> {
+  static constexpr int FID = FT255, N = 9, W = 29, NL = 8, WAVES = 4, STRIDE = 12;
+  static constexpr u32 limb(int k) { return mod_limb<NL, W>(k); }
 };
 
-#include "field_ln_gen.h"   // ln_mul1s_ft63 / _ft127 / _ft191
+#include "field_ln_gen.h"    // ln_mul1s_ft63 / _ft127 / _ft191
+#include "field_r29_gen.h"   // Ft255: r29_columns (fe_mul_r29's Comba/Montgomery chain as asm blocks), r29_mul1s
+#include "field_wmul_gen.h"  // wmul_u / _ft127 / _ft191: x * w mod p for a WAVE-UNIFORM w given as its shifted multiples (scalar operands)
 
 template <int N> struct LN {
   u32 v[N];       // two's complement; the top limb (and un-normalised intermediates) may be negative
@@ -53,7 +65,7 @@ constexpr int QOFF = 24;          // clamp table: entry i = (i - QOFF) * p, i in
 constexpr int QBIAS = 40;         // subtracted from the top limb before the quotient estimate (keeps remainders >= 0)
 
 // packed NL x 32 (value < 2^(32 NL)) -> N x W, normalised, non-negative.  The top limb takes every bit from W (N - 1) up:
-// 12 bits for Ft63 / Ft127, 18 for Ft191.
+// 12 bits for Ft63 / Ft127, 18 for Ft191, 24 for Ft255.
 template <class FT> LCPC_DEV LN<FT::N> from_packed(const Fe<FT::NL>& a) {
   constexpr int N = FT::N, W = FT::W, NL = FT::NL;
   LN<N> r;
@@ -83,6 +95,22 @@ template <class FT> LCPC_DEV void to_packed(u32* out, const u32* l) {
     out[w] = x;
   }
 }
+// N consecutive words (16-byte aligned) as uint4 / uint2 / u32 loads: limbs 0-3 (N >= 5) and 4-7 (N = 9) as uint4, a uint2 for
+// limbs 0-1 (N = 3) or 4-5 (N = 7), then the top limb
+template <int N> LCPC_DEV LN<N> load_limbs(const u32* t) {
+  LN<N> r;
+  if constexpr (N == 3) {
+    const uint2 a = *reinterpret_cast<const uint2*>(t);
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = t[2];
+  } else {
+    const uint4 a = *reinterpret_cast<const uint4*>(t);
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+    if constexpr (N == 5) r.v[4] = t[4];
+    else if constexpr (N == 7) { const uint2 b = *reinterpret_cast<const uint2*>(t + 4); r.v[4] = b.x; r.v[5] = b.y; r.v[6] = t[6]; }
+    else { const uint4 b = *reinterpret_cast<const uint4*>(t + 4); r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w; r.v[8] = t[8]; }
+  }
+  return r;
+}
 template <int N> LCPC_DEV LN<N> add(const LN<N>& a, const LN<N>& b) {
   LN<N> r;
 #pragma unroll
@@ -103,7 +131,7 @@ template <class FT> LCPC_DEV void normalize(LN<FT::N>& a) {
     a.v[k] &= (1u << FT::W) - 1;
   }
 }
-// ---- normalise + clamp in ONE carry pass (l9::clamp_q / clamp_row / clamp_apply for N limbs of W bits) -------------
+// ---- normalise + clamp in ONE carry pass -----------------------------------------------------------------------------------------
 // a: limbs 0..N-2 in [0, 2^31 - 4] (the sum of four normalised values), top limb signed, |value| < 16p.  With
 // B = 2^(W(N-1)), V = t B + low, q = floor((t - QBIAS) / (PTOP + 1)) estimated from the UN-normalised top limb (the
 // carries still in the lower limbs, c in [0, 3], are not in it yet):
@@ -119,21 +147,7 @@ template <class FT> LCPC_DEV u32 clamp_q(u32 top) {
   const u32 n = top + (u32)(QOFF * PTOP1 - QBIAS);                       // in [0, 64 PTOP1) for |value| < 16p
   return __umulhi(n, MAGIC) >> SH;
 }
-template <class FT> LCPC_DEV LN<FT::N> clamp_row(const u32* nqp, u32 q) {
-  constexpr int N = FT::N;
-  const u32* t = nqp + q * FT::STRIDE;
-  LN<N> r;
-  if constexpr (N == 3) {
-    const uint2 a = *reinterpret_cast<const uint2*>(t);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = t[2];
-  } else {
-    const uint4 a = *reinterpret_cast<const uint4*>(t);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    if constexpr (N == 5) r.v[4] = t[4];
-    else { const uint2 b = *reinterpret_cast<const uint2*>(t + 4); r.v[4] = b.x; r.v[5] = b.y; r.v[6] = t[6]; }
-  }
-  return r;
-}
+template <class FT> LCPC_DEV LN<FT::N> clamp_row(const u32* nqp, u32 q) { return load_limbs<FT::N>(nqp + q * FT::STRIDE); }
 template <class FT> LCPC_DEV void clamp_apply(LN<FT::N>& a, const LN<FT::N>& nt) {
   int32_t c = 0;
 #pragma unroll
@@ -144,30 +158,41 @@ template <class FT> LCPC_DEV void clamp_apply(LN<FT::N>& a, const LN<FT::N>& nt)
   }
   a.v[FT::N - 1] = a.v[FT::N - 1] + nt.v[FT::N - 1] + (u32)c;
 }
+// (a * w) / R' mod p, loosely: a limbs in (-2^(W+1), 2^(W+1)), |value| < 16p; w normalised, in [0, p) (R'-Montgomery form).
+// Ft255: column sums stay inside i64 (9 * 2^59 + 8 * 2^58 + 2^34 < 2^63); result normalised, in (-1.2p, 0.2p].
 template <class FT> LCPC_DEV LN<FT::N> mul(const LN<FT::N>& a, const LN<FT::N>& w) {
   LN<FT::N> r;
   if constexpr (FT::FID == FT63) ln_mul1s_ft63(a.v, w.v, r.v);
   else if constexpr (FT::FID == FT127) ln_mul1s_ft127(a.v, w.v, r.v);
-  else ln_mul1s_ft191(a.v, w.v, r.v);
+  else if constexpr (FT::FID == FT191) ln_mul1s_ft191(a.v, w.v, r.v);
+  else r29_mul1s(a.v, w.v, r.v);
   return r;
 }
 // a * w mod p for a wave-uniform w given as its N shifted multiples W_j = balanced(w 2^(W j) mod p) (N^2 words t = N k + j, host:
 // ctx.cpp wmul_table; field_wmul_gen.h).  a: limbs of a normalised value or of a difference of two (sum |limb| < N 2^W).  Result:
-// normalised, in (-2.5p, 1.6p) (gen_wmul_asm.py wmul_bounds).  Ft127: 50 instructions against mul()'s 64, Ft191: 80 against 118.
+// normalised, in (-2.5p, 1.6p) (gen_wmul_asm.py wmul_bounds; Ft255: (-2p, 2.7p)).  Ft127: 50 instructions against mul()'s 64, Ft191:
+// 80 against 118, Ft255: 119 against 188 (tools/lab, profiles/r05_ubench_wmul.jsonl: 1.6-1.8 x per second).
 // Ft63 has no such form: at 3 limbs the Montgomery multiply (22 instructions) is the shorter one (28).
 template <class FT> constexpr bool has_mul_u = FT::N >= 5;
 template <class FT> LCPC_DEV LN<FT::N> mul_u(const LN<FT::N>& a, const u32* wt) {
   static_assert(has_mul_u<FT>, "no shifted-multiples multiply for this field");
   LN<FT::N> r;
   if constexpr (FT::FID == FT127) wmul_u_ft127(a.v, wt, r.v);
-  else wmul_u_ft191(a.v, wt, r.v);
+  else if constexpr (FT::FID == FT191) wmul_u_ft191(a.v, wt, r.v);
+  else {
+    u32 np2[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) np2[j] = 0u - 2u * FT::limb(j);           // the limbs of -2p (the quotient counts units of 2p)
+    wmul_u(a.v, np2, wt, r.v);
+  }
   return r;
 }
-// ---- carry-free lazy dot product (Brakedown SpMM for Ft127 / Ft191): field_dev.h's lazy29_* for N limbs of W bits ------
-// acc += x * v with x, v as N unsigned W-bit limbs (x: a packed element < p split by from_packed; v: a matrix value in the
+// ---- carry-free lazy dot product (collapse, SpMV, SpMM) -----------------------------------------------------------------------------
+// acc += x * v with x, v as N unsigned W-bit limbs (x: a packed element < p split by from_packed; v: a matrix / tensor value in the
 // R'-Montgomery form, v R' mod p): N^2 v_mad_u64_u32 into 2N u64 columns, no carries.  A column receives <= N products
-// < 2^(2W) per term: 6 terms fit (6 * 7 * 2^58 < 2^64) before lazy_normalize() must move the excess up; the value is
-// Montgomery-reduced once per <= 60 terms: (sum + m p) / R' < 60 p^2 / R' + p < 2p since R' / p > 2^12.
+// < 2^(2W) per term: 6 terms fit (6 * 9 * 2^58 < 2^64) before lazy_normalize() must move the excess up; the value is
+// Montgomery-reduced once per <= 60 terms: (sum + m p) / R' < 60 p^2 / R' + p < 2p since R' / p > 2^6 (Ft255: value < 64 p^2;
+// tests/test_lazy_bounds.py derives the limits).
 template <class FT> struct LazyN {
   u64 c[2 * FT::N];
 };
@@ -214,8 +239,94 @@ template <class FT> LCPC_DEV Fe<FT::NL> lazy_reduce(LazyN<FT>& a) {
   }
   u32 t[FT::NL];
   to_packed<FT>(t, r);
-  return fe_reduce_once<FT::NL>(t, 0u);    // < 2p < 2^(32 NL)
+  return fe_reduce_once<FT::NL>(t);        // < 2p < 2^(32 NL)
+}
+
+// ---- Ft255 only: the general row NTT (kernels.hip ntt_pass_l9_kernel) and its canonical store ----------------------------------------
+// a: normalised, |value| < 16p  ->  normalised, value in [0, p + 2^239) (== a mod p).  qp[i] = (i - QOFF) * p as normalised signed
+// limbs (12-word stride).  With t the signed top limb, V = t * 2^232 + low, 0 <= low < 2^232, and q = floor((t - QBIAS) / (ptop + 1)),
+// ptop = floor(p / 2^232):  t - QBIAS = q (ptop + 1) + rem, so  V - q p = q (2^232 - plow) + (rem + QBIAS) 2^232 + low  with
+// plow = p mod 2^232:  >= (QBIAS - |q|) 2^232 >= 0 for |q| <= 17 + 1 and < (ptop + 1 + QBIAS + |q| + 1) 2^232 < p + 2^239.
+LCPC_DEV void clamp(LN<9>& a, const u32* qp) {
+  constexpr u32 M = (1u << 29) - 1;
+  constexpr u32 PTOP1 = LnField<FT255>::limb(8) + 1;                     // floor(p / 2^232) + 1 (23 bits)
+  constexpr u64 MAGIC = (((u64)1 << 52) + PTOP1 - 1) / PTOP1;            // ceil(2^52 / PTOP1) < 2^30
+  const u32 n = a.v[8] + (u32)(QOFF * PTOP1 - QBIAS);                    // in [0, 2^29) for |value| < 16p
+  const u32 q = (u32)(((u64)n * MAGIC) >> 52);                           // exact floor(n / PTOP1) for n < 2^29
+  const u32* t = qp + q * 12;
+  int32_t d[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) d[k] = (int32_t)(a.v[k] - t[k]);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {                                         // borrow-propagate
+    d[k + 1] += d[k] >> 31;                                             // -1 if limb k went negative
+    a.v[k] = (u32)d[k] & M;                                             // + 2^29 in that case
+  }
+  a.v[8] = (u32)d[8];
+}
+// exact: normalised |value| < 16p -> packed, fully reduced
+LCPC_DEV Fe<8> to_packed_reduced(LN<9> a, const u32* qp) {
+  clamp(a, qp);                   // [0, p + 2^239) < 2^256
+  u32 t[8];
+  to_packed<LnField<FT255>>(t, a.v);
+  return fe_reduce_once<8>(t);
 }
 }  // namespace ln
+
+// r = a * b * 2^-261 mod p, fully reduced, packed.  a: packed element < p; b: 9 limbs < 2^29 (a table entry, w 2^261 mod p, so that
+// REDC_261(a R * w 2^261) = (a w) R).  The product and the reduction are one pure chain of 153 v_mad_u64_u32 (field_r29_gen.h).
+LCPC_DEV Fe<8> fe_mul_r29(const Fe<8>& a, const LN<9>& b) {
+  const LN<9> x = ln::from_packed<LnField<FT255>>(a);
+  u32 m[9], r[9];
+  r29_columns(x.v, b.v, m, r);
+  u32 t[8];
+  ln::to_packed<LnField<FT255>>(t, r);
+  return fe_reduce_once<8>(t);         // REDC output < 2p < 2^256
+}
+
+// Montgomery form (R = 2^256) -> canonical value for Ft255, reduction only: a * 2^-256 = REDC_261(a * 2^5).
+// The "product" a << 5 needs no multiplies; the 9-step reduction is 72 v_mad_u64_u32, carry-free.
+LCPC_DEV Fe<8> fe_canon_r29(const Fe<8>& a) {
+  using FT = LnField<FT255>;
+  constexpr u32 M = (1u << 29) - 1;
+  // limbs of (a << 5): bit b of the shifted value is bit b-5 of a
+  u32 x[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const int b = 29 * k - 5;            // first source bit of limb k (negative for k = 0)
+    u32 v;
+    if (k == 0) v = (a.v[0] << 5);
+    else {
+      const int w = b / 32, sh = b % 32;
+      if (sh == 0) v = a.v[w];
+      else if (w + 1 < 8) v = __builtin_amdgcn_alignbit(a.v[w + 1], a.v[w], sh);
+      else v = a.v[w] >> sh;
+    }
+    x[k] = v & M;
+  }
+  u32 m[9], r[9];
+  u64 acc = 0;
+#pragma unroll
+  for (int k = 0; k < 17; k++) {
+    if (k < 9) acc += x[k];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      const int j = k - i;
+      if (i < k && j >= 1 && j < 9) acc += (u64)m[i] * FT::limb(j);
+    }
+    if (k < 9) {
+      m[k] = (0u - (u32)acc) & M;
+      acc += m[k];
+      acc >>= 29;
+    } else {
+      r[k - 9] = (u32)acc & M;
+      acc >>= 29;
+    }
+  }
+  r[8] = (u32)acc;
+  u32 t[8];
+  ln::to_packed<FT>(t, r);
+  return fe_reduce_once<8>(t);
+}
 
 }  // namespace lcpc

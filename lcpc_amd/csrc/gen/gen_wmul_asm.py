@@ -3,8 +3,8 @@
 
 The "shifted multiples" multiply of the row NTT kernels (ntt_l9s.hip, ntt_lns.hip): x * w mod p for a WAVE-UNIFORM w whose N constants
 W_j = balanced(w * 2^(W j) mod p), j = 0..N-1, sit in memory as N^2 dwords t = N k + j (limb k of W_j; limbs 0..N-2 in [0, 2^W), the top
-limb signed), for the four test fields of /root/reference/lcpc-test-fields/src/lib.rs:13-59 in the limb forms of field_dev.h (Ft255:
-9 x 29 bits) and field_ln.h (Ft63 3 x 26, Ft127 5 x 29, Ft191 7 x 29):
+limb signed), for the four test fields of /root/reference/lcpc-test-fields/src/lib.rs:13-59 in the limb forms of field_ln.h (Ft63
+3 x 26, Ft127 5 x 29, Ft191 7 x 29, Ft255 9 x 29):
 
     z = sum_j x_j * W_j                       N^2 v_mad_i64_i32, the W limbs as SGPR operands (s_load inside the statement)
     q' ~ z / 2p from the two top columns      5 instructions

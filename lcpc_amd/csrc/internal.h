@@ -34,7 +34,7 @@ namespace lcpc {
 struct DevCsr {
   uint64_t n_in = 0, n_out = 0;
   uint32_t *rowptr = nullptr, *colidx = nullptr, *vals = nullptr;
-  uint32_t* vals29 = nullptr;     // Ft255: values in the 29-bit-limb / 2^261 form (lazy29_mac)
+  uint32_t* vals29 = nullptr;     // Ft255: values in the 29-bit-limb / 2^261 form (ln::lazy_mac)
 };
 // one pass of the Ligero row NTT as the context plans it (ctx.cpp plan_passes, build_limb_plan): everything about the pass that
 // does not depend on the job.  A step with a.log_n < the context's log_n runs on n_rows << (log_n - a.log_n) sub-rows.
@@ -251,11 +251,12 @@ struct lcpc_ctx {
   // Ligero
   unsigned log_n = 0;
   uint32_t* d_roots = nullptr;
-  // lazy-limb NTT tables, N limbs of W bits per entry: (N, W, stride) = (9, 29, 12 words) for Ft255, made with d_roots and read by
-  // the general kernel as well (ntt_pass_l9_kernel); ntt_lns_limbs / _limb_bits / _stride for Ft63 / Ft127 / Ft191, made only for a K1n plan
-  uint32_t* d_rootsl = nullptr;    // w^i R' mod p (Ft255: R' = 2^261, field_dev.h fe_mul_r29; the other fields: field_ln.h)
+  // lazy-limb NTT tables, N limbs of W bits per entry, `stride` words (ntt_lns_limbs / _limb_bits / _stride; field_ln.h LnField):
+  // Ft255's (9, 29, 12) are made with d_roots and read by the general kernel as well (ntt_pass_l9_kernel); those of Ft63 / Ft127 /
+  // Ft191 are made only for a K1n plan
+  uint32_t* d_rootsl = nullptr;    // w^i R' mod p (Ft255: R' = 2^261, field_ln.h fe_mul_r29; R' = 2^(N W))
   uint32_t* d_rootslc = nullptr;   // w^i R' R^-1 mod p (Ft255: w^i 2^5): the table that converts to canonical on the fly
-  uint32_t* d_qpl = nullptr;       // (i - 24) * p, i < 64, same form (l9::clamp, ln::clamp_*)
+  uint32_t* d_qpl = nullptr;       // (i - 24) * p, i < 64, same form (ln::clamp, ln::clamp_*)
   uint32_t* d_rootsls = nullptr;   // three-pass plans: the 2^20-point tables (every 2^(log_n - 20)-th entry of d_rootsl / d_rootslc)
   uint32_t* d_rootslcs = nullptr;
   uint32_t* d_wq_w = nullptr;      // the shifted multiples of the primitive 4th root w^(n/4) (the same element for every n), 96 words

@@ -39,22 +39,18 @@ struct NttPassArgs {
 hipError_t launch_ntt_pass(int nl, int log_tile, const NttPassArgs& a, hipStream_t st);
 
 // ---- shape-specialised Ft255 NTT for two-pass plans on 1024-element tiles (ntt_l9s.hip) ----
-// twiddle pack of one pass: per tile class, per round, the table entries in lane order (layout: ntt_l9s.hip)
+// twiddle pack of one pass: per tile class, per round, the table entries in lane order (layout: ntt_ln_dev.h; built by
+// launch_ntt_lns_pack for all four fields)
 struct NttPackInfo {
   uint32_t round_off[8];    // word offset of round slot r inside a class block
   uint32_t class_words;     // words per tile class
-  uint32_t u_off;           // passes with a uniform round (ntt_l9s.hip Shape::RU): word offset of its 4 x 3 shifted-multiples tables
+  uint32_t u_off;           // passes with a uniform round (ntt_ln_dev.h Shape::RU): word offset of its 4 x 3 shifted-multiples tables
 };
 bool ntt_l9s_supported(uint32_t log_n, uint32_t n_passes, int log_tile);
 // three passes for 2^21 .. 2^26 columns: s0 = log_n - 20 stages with the first-pass kernel on the whole rows (element stride 2^20),
 // then the two-pass plan of a 2^20-point transform on each of the 2^s0 contiguous blocks of every row (DIF: after s0 stages the
 // blocks are independent transforms with the root w^(2^s0)), from a sub-sampled twiddle table
 bool ntt_l9s3_supported(uint32_t log_n);
-// sub[i] = tab[i << shift], 12-word entries, i < n
-hipError_t launch_ntt_l9s_subtable(const uint32_t* tab, uint32_t shift, uint64_t n, uint32_t* sub, hipStream_t st);
-NttPackInfo ntt_l9s_pack_info(uint32_t s, bool first);
-// a: the pass (log_n, t0, s, log_tj, roots29, roots29c); first pass: n_classes = tiles per row, last pass: 1
-hipError_t launch_ntt_l9s_pack(const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st);
 hipError_t launch_ntt_pass_l9s(const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st);
 
 // ---- shape-specialised lazy-limb NTT for Ft63 / Ft127 / Ft191, two-pass plans on 1024-element tiles (ntt_lns.hip) ----
@@ -64,14 +60,17 @@ bool ntt_lns_supported(int nl, uint32_t log_n);
 // three passes for 2^21 .. 2^26 columns, built like ntt_l9s3_supported's plan (first-pass kernel over the whole rows, then the
 // 2^20-point two-pass plan per block from sub-sampled tables)
 bool ntt_lns3_supported(int nl, uint32_t log_n);
+hipError_t launch_ntt_pass_lns(int nl, const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st);
+// the table side of both plan families, nl = 2 / 4 / 6 / 8 (Ft255: N = 9, W = 29, 12-word entries):
+int ntt_lns_limbs(int nl);          // N
+int ntt_lns_limb_bits(int nl);      // W
+int ntt_lns_stride(int nl);         // words per table entry
+// sub[i] = tab[i << shift], i < n
 hipError_t launch_ntt_lns_subtable(int nl, const uint32_t* tab, uint32_t shift, uint64_t n, uint32_t* sub, hipStream_t st);
-int ntt_lns_limbs(int nl);
-int ntt_lns_limb_bits(int nl);
-int ntt_lns_stride(int nl);
 NttPackInfo ntt_lns_pack_info(int nl, uint32_t s, bool first);
 hipError_t launch_ntt_lns_roots(int nl, const uint32_t* roots, uint64_t n, const uint32_t* rprime, uint32_t* out, hipStream_t st);
+// a: the pass (log_n, t0, s, log_tj, roots29, roots29c); first pass: n_classes = tiles per row, last pass: 1
 hipError_t launch_ntt_lns_pack(int nl, const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st);
-hipError_t launch_ntt_pass_lns(int nl, const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st);
 
 // device-side precomp_fft: roots[i] = w^i (i < 2^log_half) from pw[j] = w^(2^j); roots29 (Ft255) may be null
 hipError_t launch_roots(int nl, const uint32_t* pw, uint32_t log_half, const uint32_t* one, uint32_t* roots, uint32_t* roots29,

@@ -13,12 +13,14 @@
 // fully-reduced results; the kernels are free to re-associate (multi-pass NTT, split sums).
 #include "kernels.h"
 #include "field_dev.h"
-#include "ntt_l9_dev.h"
-#include "field_ln.h"
+#include "ntt_ln_dev.h"
 #include "blake3_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace lcpc {
+
+using L255 = LnField<FT255>;                     // Ft255's lazy-limb form (field_ln.h)
 
 // limb count (runtime) -> template parameter
 #define LCPC_DISPATCH_NL(nl, CALL)                 \
@@ -82,31 +84,16 @@ template <int NL> struct Tw {
   Fe<NL> w;
 };
 template <> struct Tw<8> {
-  Fe29 w;
+  LN<9> w;
 };
 template <int NL>
 __device__ __forceinline__ Tw<NL> tw_load(const NttPassArgs& a, u32 widx) {
   Tw<NL> t;
-  if constexpr (NL == 8) {
-    const uint4* wp = reinterpret_cast<const uint4*>(a.roots29 + (size_t)widx * 12);
-    const uint4 w0 = wp[0], w1 = wp[1];
-    const u32 w8 = a.roots29[(size_t)widx * 12 + 8];
-    t.w.v[0] = w0.x; t.w.v[1] = w0.y; t.w.v[2] = w0.z; t.w.v[3] = w0.w;
-    t.w.v[4] = w1.x; t.w.v[5] = w1.y; t.w.v[6] = w1.z; t.w.v[7] = w1.w; t.w.v[8] = w8;
-  } else {
-    t.w = fe_load<NL>(a.roots + (size_t)widx * NL);
-  }
+  if constexpr (NL == 8) t.w = tab_entry<L255>(a.roots29, widx);
+  else t.w = fe_load<NL>(a.roots + (size_t)widx * NL);
   return t;
 }
-__device__ __forceinline__ Tw<8> tw_load29(const u32* tab, u32 widx) {
-  Tw<8> t;
-  const uint4* wp = reinterpret_cast<const uint4*>(tab + (size_t)widx * 12);
-  const uint4 w0 = wp[0], w1 = wp[1];
-  const u32 w8 = tab[(size_t)widx * 12 + 8];
-  t.w.v[0] = w0.x; t.w.v[1] = w0.y; t.w.v[2] = w0.z; t.w.v[3] = w0.w;
-  t.w.v[4] = w1.x; t.w.v[5] = w1.y; t.w.v[6] = w1.z; t.w.v[7] = w1.w; t.w.v[8] = w8;
-  return t;
-}
+__device__ __forceinline__ Tw<8> tw_load29(const u32* tab, u32 widx) { return Tw<8>{tab_entry<L255>(tab, widx)}; }
 template <int NL>
 __device__ __forceinline__ Fe<NL> tw_mul(const Fe<NL>& d, const Tw<NL>& t) {
   if constexpr (NL == 8) return fe_mul_r29(d, t.w);
@@ -229,9 +216,9 @@ __global__ void __launch_bounds__(BS) ntt_pass_kernel(NttPassArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// Ft255 variant on lazy signed 9 x 29-bit limbs (field_dev.h, namespace l9): same tiling, rounds and twiddle indexing
+// Ft255 variant on lazy signed 9 x 29-bit limbs (field_ln.h, LnField<FT255>): same tiling, rounds and twiddle indexing
 // as ntt_pass_kernel, but the tile lives in LDS in the multiplier's own limb format (36 B per element), add/sub are
-// plain limb operations and exact reduction + packing happen once, at the tile store.  Bounds: see l9.
+// plain limb operations and exact reduction + packing happen once, at the tile store.  Bounds: see field_ln.h.
 //
 // Canonical output (a.roots29c != null; the Ligero commit): hash_columns needs to_repr(x) = x * R^-1 of every
 // codeword element, one Montgomery reduction each (2^27 of them at the headline, 0.7 ms inside the hash kernel).
@@ -245,8 +232,8 @@ __global__ void __launch_bounds__(BS) ntt_pass_kernel(NttPassArgs a) {
 // loads, stays in Montgomery form); the hash kernel reads them as they are.
 // -------------------------------------------------------------------------------------------------
 // m == ~0: -x, m == 0: x, limb-wise (per-lane choice without a select)
-__device__ __forceinline__ L9 l9_neg_if(const L9& x, u32 m) {
-  L9 r;
+__device__ __forceinline__ LN<9> l9_neg_if(const LN<9>& x, u32 m) {
+  LN<9> r;
 #pragma unroll
   for (int i = 0; i < 9; i++) r.v[i] = (x.v[i] ^ m) - m;
   return r;
@@ -255,7 +242,8 @@ template <int LT>
 __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
   constexpr int NL = 8;
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
-  u32* qp = lds + (size_t)Lds9<LT>::T * 9;                   // q*p table copy
+  const std::integral_constant<u32, 1u << LT> TP;           // LDS planes of 2^LT slots (a tile may use fewer)
+  u32* qp = lds + (size_t)TP * 9;                            // q*p table copy
   const u32 k = a.log_n, t0 = a.t0, s = a.s, ltj = a.log_tj;
   const u32 lb = k - t0 - s;
   const u32 lbt = lb < ltj ? lb : ltj;
@@ -289,7 +277,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
   for (u32 e = tid; e < T; e += 256) {
     const u32 g = gindex(e);
     const Fe<NL> v = (g < a.n_valid && row * a.src_stride + g < a.n_src_total) ? fe_load<NL>(src + (size_t)g * NL) : fe_zero<NL>();
-    lds9_put<LT>(lds, e, l9::from_packed(v));
+    planes_put<L255>(lds, TP, e, ln::from_packed<L255>(v));
     if (a.copy_dst != nullptr && g < a.n_valid) fe_store<NL>(a.copy_dst + (row * a.src_stride + g) * NL, v);
   }
   __syncthreads();
@@ -320,40 +308,40 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
         const Tw<NL> w0 = tw_load29(tc, ex), w2 = tw_load29(tc, 2 * ex), w3 = tw_load29(tc, (3 * ex) & half_mask);
         const u32 ng = 3 * ex > half_mask ? ~0u : 0u;
         if (zero_3q) {           // rate <= 1/4: x1 is zero too; c0 = x0 stays where it is, three multiplies
-          const L9 x0 = lds9_get<LT>(lds, e0);
-          lds9_put<LT>(lds, e0 + dq, l9::mul(x0, w2.w));
-          lds9_put<LT>(lds, e0 + 2 * dq, l9::mul(x0, w0.w));
-          lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(l9_neg_if(x0, ng), w3.w));
+          const LN<9> x0 = planes_get<L255>(lds, TP, e0);
+          planes_put<L255>(lds, TP, e0 + dq, ln::mul<L255>(x0, w2.w));
+          planes_put<L255>(lds, TP, e0 + 2 * dq, ln::mul<L255>(x0, w0.w));
+          planes_put<L255>(lds, TP, e0 + 3 * dq, ln::mul<L255>(l9_neg_if(x0, ng), w3.w));
           continue;
         }
-        const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-        L9 c0 = l9::add(x0, x1);                                                           // [0, 2p)
-        l9::normalize(c0);
-        lds9_put<LT>(lds, e0, c0);
-        lds9_put<LT>(lds, e0 + dq, l9::mul(l9::sub(x0, x1), w2.w));
-        const L9 tI = l9::mul_u(x1, a.wq_w);                                               // x1 I (ntt_l9s.hip: the true radix-4 form)
-        lds9_put<LT>(lds, e0 + 2 * dq, l9::mul(l9::add(x0, tI), w0.w));
-        lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(l9_neg_if(l9::sub(x0, tI), ng), w3.w));
+        const LN<9> x0 = planes_get<L255>(lds, TP, e0), x1 = planes_get<L255>(lds, TP, e0 + dq);
+        LN<9> c0 = ln::add(x0, x1);                                                           // [0, 2p)
+        ln::normalize<L255>(c0);
+        planes_put<L255>(lds, TP, e0, c0);
+        planes_put<L255>(lds, TP, e0 + dq, ln::mul<L255>(ln::sub(x0, x1), w2.w));
+        const LN<9> tI = ln::mul_u<L255>(x1, a.wq_w);                                               // x1 I (ntt_l9s.hip: the true radix-4 form)
+        planes_put<L255>(lds, TP, e0 + 2 * dq, ln::mul<L255>(ln::add(x0, tI), w0.w));
+        planes_put<L255>(lds, TP, e0 + 3 * dq, ln::mul<L255>(l9_neg_if(ln::sub(x0, tI), ng), w3.w));
         continue;
       }
-      const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-      const L9 x2 = lds9_get<LT>(lds, e0 + 2 * dq), x3 = lds9_get<LT>(lds, e0 + 3 * dq);   // I: normalised, |value| < 4p
+      const LN<9> x0 = planes_get<L255>(lds, TP, e0), x1 = planes_get<L255>(lds, TP, e0 + dq);
+      const LN<9> x2 = planes_get<L255>(lds, TP, e0 + 2 * dq), x3 = planes_get<L255>(lds, TP, e0 + 3 * dq);   // I: normalised, |value| < 4p
       mem_phase(false);
-      const L9 b0 = l9::add(x0, x2), b1 = l9::add(x1, x3);                                 // limbs [0, 2^30), |value| < 8p
-      L9 c0 = l9::add(b0, b1);                                                             // limbs [0, 2^31), |value| < 16p
-      l9::normalize(c0);
+      const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);                                 // limbs [0, 2^30), |value| < 8p
+      LN<9> c0 = ln::add(b0, b1);                                                             // limbs [0, 2^31), |value| < 16p
+      ln::normalize<L255>(c0);
       if (last_two) {
         // stages k-2, k-1: twiddles 1, w^(n/4), 1 -- outputs go straight to the store path (normalised, |value| < 16p)
-        L9 c1 = l9::sub(b0, b1);                                                           // |value| < 16p
-        const L9 b2 = l9::sub(x0, x2);                                                     // limbs (-2^29, 2^29), |value| < 8p
-        const L9 b3 = l9::mul_u(l9::sub(x1, x3), a.wq_w);                                  // normalised, (-2.2p, 1.5p)
-        L9 c2 = l9::add(b2, b3);                                                           // |value| < 9.2p
-        L9 c3 = l9::sub(b2, b3);                                                           // |value| < 9.2p
-        l9::normalize(c1); l9::normalize(c2); l9::normalize(c3);
-        lds9_put<LT>(lds, e0, c0);
-        lds9_put<LT>(lds, e0 + dq, c1);
-        lds9_put<LT>(lds, e0 + 2 * dq, c2);
-        lds9_put<LT>(lds, e0 + 3 * dq, c3);
+        LN<9> c1 = ln::sub(b0, b1);                                                           // |value| < 16p
+        const LN<9> b2 = ln::sub(x0, x2);                                                     // limbs (-2^29, 2^29), |value| < 8p
+        const LN<9> b3 = ln::mul_u<L255>(ln::sub(x1, x3), a.wq_w);                                  // normalised, (-2.2p, 1.5p)
+        LN<9> c2 = ln::add(b2, b3);                                                           // |value| < 9.2p
+        LN<9> c3 = ln::sub(b2, b3);                                                           // |value| < 9.2p
+        ln::normalize<L255>(c1); ln::normalize<L255>(c2); ln::normalize<L255>(c3);
+        planes_put<L255>(lds, TP, e0, c0);
+        planes_put<L255>(lds, TP, e0 + dq, c1);
+        planes_put<L255>(lds, TP, e0 + 2 * dq, c2);
+        planes_put<L255>(lds, TP, e0 + 3 * dq, c3);
       } else {
         // block 0 of stages t, t+1 with canonical output (inputs still in Montgomery form): the three multiplies that
         // leave block 0 take the converting table; c0 stays a pure sum; c3's inputs b2, b3 are already canonical
@@ -364,13 +352,13 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
         const u32 ex = (g0 & gm0) << t;
         const Tw<NL> w0 = tw_load29(t01, ex), w2 = tw_load29(t01, 2 * ex), w3 = tw_load29(t01, (3 * ex) & half_mask);
         const u32 ng = 3 * ex > half_mask ? ~0u : 0u;
-        l9::clamp(c0, qp);                                                                 // [0, 1.01p)
-        lds9_put<LT>(lds, e0, c0);
-        lds9_put<LT>(lds, e0 + dq, l9::mul(l9::sub(b0, b1), w2.w));                        // normalised, (-1.2p, 0.2p]
-        const L9 tI = l9::mul_u(l9::sub(x1, x3), a.wq_w);                                  // normalised, (-2.2p, 1.5p)
-        const L9 e2 = l9::sub(x0, x2);                                                     // limbs (-2^29, 2^29), |value| < 8p
-        lds9_put<LT>(lds, e0 + 2 * dq, l9::mul(l9::add(e2, tI), w0.w));
-        lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(l9_neg_if(l9::sub(e2, tI), ng), w3.w));
+        ln::clamp(c0, qp);                                                                 // [0, 1.01p)
+        planes_put<L255>(lds, TP, e0, c0);
+        planes_put<L255>(lds, TP, e0 + dq, ln::mul<L255>(ln::sub(b0, b1), w2.w));                        // normalised, (-1.2p, 0.2p]
+        const LN<9> tI = ln::mul_u<L255>(ln::sub(x1, x3), a.wq_w);                                  // normalised, (-2.2p, 1.5p)
+        const LN<9> e2 = ln::sub(x0, x2);                                                     // limbs (-2^29, 2^29), |value| < 8p
+        planes_put<L255>(lds, TP, e0 + 2 * dq, ln::mul<L255>(ln::add(e2, tI), w0.w));
+        planes_put<L255>(lds, TP, e0 + 3 * dq, ln::mul<L255>(l9_neg_if(ln::sub(e2, tI), ng), w3.w));
       }
       mem_phase(true);                                       // the next quad's reads, or the barrier and the next round's
     }
@@ -389,18 +377,18 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
       const u32 e2 = e1 + (1u << (hb + lbt));
       const u32 g1 = gindex(e1);
       const u32 widx = (g1 & gm) << t;
-      const L9 x = lds9_get<LT>(lds, e1), y = lds9_get<LT>(lds, e2);
-      L9 sum = l9::add(x, y);                                                              // |value| < 8p
-      l9::normalize(sum);
-      l9::clamp(sum, qp);                                                                  // [0, 1.01p)
-      lds9_put<LT>(lds, e1, sum);
-      L9 d = l9::sub(x, y);                                                                // |value| < 8p
+      const LN<9> x = planes_get<L255>(lds, TP, e1), y = planes_get<L255>(lds, TP, e2);
+      LN<9> sum = ln::add(x, y);                                                              // |value| < 8p
+      ln::normalize<L255>(sum);
+      ln::clamp(sum, qp);                                                                  // [0, 1.01p)
+      planes_put<L255>(lds, TP, e1, sum);
+      LN<9> d = ln::sub(x, y);                                                                // |value| < 8p
       if (t + 1 == k) {
-        l9::normalize(d);                                                                  // last stage: twiddle 1
-        lds9_put<LT>(lds, e2, d);
+        ln::normalize<L255>(d);                                                                  // last stage: twiddle 1
+        planes_put<L255>(lds, TP, e2, d);
       } else {
         const Tw<NL> w = tw_load29((canon && g1 <= gm) ? a.roots29c : a.roots29, widx);   // block 0 of stage t converts
-        lds9_put<LT>(lds, e2, l9::mul(d, w.w));
+        planes_put<L255>(lds, TP, e2, ln::mul<L255>(d, w.w));
       }
     }
     __syncthreads();
@@ -409,7 +397,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
   u32* dst = a.dst + row * a.dst_stride * NL;
   for (u32 e = tid; e < T; e += 256) {
     const u32 g = gindex(e);
-    Fe<NL> v = l9::to_packed_reduced(lds9_get<LT>(lds, e), qp);
+    Fe<NL> v = ln::to_packed_reduced(planes_get<L255>(lds, TP, e), qp);
     if (g < a.mont_prefix) v = fe_canon_r29(v);              // canonical output, final pass: the never-multiplied prefix
     fe_store<NL>(dst + (size_t)g * NL, v);
   }
@@ -418,7 +406,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9_kernel(NttPassArgs a) {
 template <int LT>
 static hipError_t launch_ntt_pass_l9_t(const NttPassArgs& a, hipStream_t st) {
   const u64 tiles = ((u64)1 << (a.log_n - a.s - a.log_tj)) * a.n_rows;
-  const size_t lds_bytes = (size_t)Lds9<LT>::WORDS * 4;
+  const size_t lds_bytes = (((size_t)1 << LT) * 9 + 64 * L255::STRIDE) * 4;
   // (idempotent and cheap; set on every launch rather than cached in an unsynchronised static)
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_l9_kernel<LT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds_bytes);
@@ -897,7 +885,7 @@ __global__ void __launch_bounds__(256) collapse_kernel(CollapseArgs a) {
 #pragma unroll
   for (int t = 0; t < NT; t++) fe_store<NL>(a.out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * NL, acc[t]);
 }
-// Ft255: carry-free lazy dot products (lazy29_mac); the tensor entry is wave-uniform, so its nine 29-bit limbs
+// Ft255: carry-free lazy dot products (ln::lazy_mac); the tensor entry is wave-uniform, so its nine 29-bit limbs
 // (pre-converted to the 2^261 form, a.tensors29) are scalar operands of the 81 v_mad_u64_u32 per term.
 template <int NT>
 __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
@@ -912,9 +900,9 @@ __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
   for (int t = 0; t < NT; t++) acc[t] = fe_zero<8>();
   for (u64 rb = r0; rb < r1; rb += 60) {
     const u64 re = (rb + 60 < r1) ? rb + 60 : r1;
-    Lazy29 w[NT];
+    ln::LazyN<L255> w[NT];
 #pragma unroll
-    for (int t = 0; t < NT; t++) lazy29_zero(w[t]);
+    for (int t = 0; t < NT; t++) ln::lazy_zero(w[t]);
     u32 since = 0;
     Fe<8> c = fe_load<8>(a.coeffs + (rb * a.n_per_row + j) * 8);
     for (u64 r = rb; r < re; r++) {
@@ -924,23 +912,23 @@ __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
       if constexpr (NT == 1) mem_phase(true);
       if (r + 1 < re) cn = fe_load<8>(a.coeffs + ((r + 1) * a.n_per_row + j) * 8);     // next row in flight
       if constexpr (NT == 1) mem_phase(false);
-      const Fe29 x = fe_to29(c);
+      const LN<9> x = ln::from_packed<L255>(c);
 #pragma unroll
       for (int t = 0; t < NT; t++) {
-        Fe29 v;
+        LN<9> v;
 #pragma unroll
         for (int i = 0; i < 9; i++) v.v[i] = __builtin_amdgcn_readfirstlane(a.tensors29[((u64)t * a.n_rows + r) * 12 + i]);
-        lazy29_mac(w[t], x, v);
+        ln::lazy_mac(w[t], x, v);
       }
       if (++since == 6) {
 #pragma unroll
-        for (int t = 0; t < NT; t++) lazy29_normalize(w[t]);
+        for (int t = 0; t < NT; t++) ln::lazy_normalize(w[t]);
         since = 0;
       }
       c = cn;
     }
 #pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = fe_add<8>(acc[t], lazy29_reduce(w[t]));
+    for (int t = 0; t < NT; t++) acc[t] = fe_add<8>(acc[t], ln::lazy_reduce(w[t]));
   }
 #pragma unroll
   for (int t = 0; t < NT; t++) fe_store<8>(a.out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * 8, acc[t]);
@@ -952,7 +940,7 @@ __global__ void __launch_bounds__(256) to_r29_kernel(const u32* in, u64 n, u32* 
   Fe<8> t = fe_load<8>(in + i * 8);
 #pragma unroll
   for (int d = 0; d < 5; d++) t = fe_add<8>(t, t);
-  const Fe29 x = fe_to29(t);
+  const LN<9> x = ln::from_packed<L255>(t);
 #pragma unroll
   for (int k = 0; k < 9; k++) out[i * 12 + k] = x.v[k];
   out[i * 12 + 9] = out[i * 12 + 10] = out[i * 12 + 11] = 0;
@@ -1139,20 +1127,20 @@ __global__ void __launch_bounds__(256) spmv_kernel(SpmvArgs a) {
   Fe<NL> acc = fe_zero<NL>();
   bool lazy = false;
   if constexpr (NL == 8) {
-    lazy = a.vals29 != nullptr && k1 - k0 <= 60 * SL;  // lazy29_reduce takes <= 60 terms: a lane sees ceil((k1 - k0) / SL)
+    lazy = a.vals29 != nullptr && k1 - k0 <= 60 * SL;  // ln::lazy_reduce takes <= 60 terms: a lane sees ceil((k1 - k0) / SL)
     if (lazy) {
       // the carry-free 29-bit-limb dot product of the position-major kernels
-      Lazy29 l;
-      lazy29_zero(l);
+      ln::LazyN<L255> l;
+      ln::lazy_zero(l);
       u32 since = 0;
       for (u32 k = k0 + sl; k < k1; k += SL) {
-        Fe29 v;
+        LN<9> v;
 #pragma unroll
         for (int i = 0; i < 9; i++) v.v[i] = a.vals29[(size_t)k * 12 + i];
-        lazy29_mac(l, fe_to29(fe_load<NL>(x + (u64)a.colidx[k] * NL)), v);
-        if (++since == 6) { lazy29_normalize(l); since = 0; }
+        ln::lazy_mac(l, ln::from_packed<L255>(fe_load<NL>(x + (u64)a.colidx[k] * NL)), v);
+        if (++since == 6) { ln::lazy_normalize(l); since = 0; }
       }
-      acc = lazy29_reduce(l);
+      acc = ln::lazy_reduce(l);
     }
   }
   if (!lazy) {
@@ -1312,16 +1300,16 @@ __device__ __forceinline__ Fe<NL> spmm_t_terms(const SpmmTArgs& a, const u32* xi
     // into SGPRs, which the multiplier takes directly) instead of vector loads + readfirstlane (-10 VALU per term).
     const ConstU32* cidx = (const ConstU32*)a.colidx;
     const ConstU32* cv29 = (const ConstU32*)a.vals29;
-    for (u32 kb = k0; kb < k1; kb += 60) {         // <= 60 terms per Montgomery reduction (lazy29_reduce bound)
+    for (u32 kb = k0; kb < k1; kb += 60) {         // <= 60 terms per Montgomery reduction (ln::lazy_reduce bound)
       const u32 ke = kb + 60 < k1 ? kb + 60 : k1;
-      Lazy29 acc;
-      lazy29_zero(acc);
+      ln::LazyN<L255> acc;
+      ln::lazy_zero(acc);
       u32 since = 0;
       // the column index is fetched two terms ahead, the gathered operand and the matrix value one term ahead (indices
       // clamped to the chunk: the redundant scalar loads at its end stay in bounds)
       Fe<NL> x = fe_load<NL>(xin + (size_t)cidx[kb] * pstride);
       u32 cn = cidx[kb + 1 < ke ? kb + 1 : kb];
-      Fe29 v;
+      LN<9> v;
 #pragma unroll
       for (int i = 0; i < 9; i++) v.v[i] = cv29[(size_t)kb * 12 + i];
       for (u32 k = kb; k < ke; k++) {
@@ -1330,16 +1318,16 @@ __device__ __forceinline__ Fe<NL> spmm_t_terms(const SpmmTArgs& a, const u32* xi
         if (k + 1 < ke) xn = fe_load<NL>(xin + (size_t)cn * pstride);
         const u32 kn = k + 1 < ke ? k + 1 : k, kn2 = k + 2 < ke ? k + 2 : k;
         cn = cidx[kn2];
-        Fe29 vn;
+        LN<9> vn;
 #pragma unroll
         for (int i = 0; i < 9; i++) vn.v[i] = cv29[(size_t)kn * 12 + i];
         mem_phase(false);
-        lazy29_mac(acc, fe_to29(x), v);
+        ln::lazy_mac(acc, ln::from_packed<L255>(x), v);
         v = vn;
-        if (++since == 6) { lazy29_normalize(acc); since = 0; }
+        if (++since == 6) { ln::lazy_normalize(acc); since = 0; }
         x = xn;
       }
-      res = fe_add<NL>(res, lazy29_reduce(acc));
+      res = fe_add<NL>(res, ln::lazy_reduce(acc));
     }
   } else {
     bool done = false;
@@ -1443,7 +1431,7 @@ __global__ void __launch_bounds__(256) spmm_t_tail_kernel(SpmmTArgs a, u32 n_mai
   const u32* xin = a.t + (a.in_off * a.n_rows + row) * NL;
   const size_t pstride = (size_t)a.n_rows * NL;
   auto load_v = [&](u32 k) {
-    Fe29 v;
+    LN<9> v;
     const uint4* p = reinterpret_cast<const uint4*>(a.vals29 + (size_t)k * 12);
     const uint4 lo = p[0], hi = p[1];
     v.v[0] = lo.x; v.v[1] = lo.y; v.v[2] = lo.z; v.v[3] = lo.w; v.v[4] = hi.x; v.v[5] = hi.y; v.v[6] = hi.z; v.v[7] = hi.w;
@@ -1452,26 +1440,26 @@ __global__ void __launch_bounds__(256) spmm_t_tail_kernel(SpmmTArgs a, u32 n_mai
   };
   Fe<NL> res = fe_zero<NL>();
   Fe<NL> x = fe_zero<NL>();
-  Fe29 v;
+  LN<9> v;
 #pragma unroll
   for (int i = 0; i < 9; i++) v.v[i] = 0;
   if (len) { x = fe_load<NL>(xin + (size_t)a.colidx[k0] * pstride); v = load_v(k0); }
   for (u32 ib = 0; ib < maxlen; ib += 60) {
     const u32 ie = ib + 60 < maxlen ? ib + 60 : maxlen;
-    Lazy29 acc;
-    lazy29_zero(acc);
+    ln::LazyN<L255> acc;
+    ln::lazy_zero(acc);
     u32 since = 0;
     for (u32 i = ib; i < ie; i++) {
       Fe<NL> xn = x;
-      Fe29 vn = v;
+      LN<9> vn = v;
       mem_phase(true);
       if (i + 1 < len) { xn = fe_load<NL>(xin + (size_t)a.colidx[k0 + i + 1] * pstride); vn = load_v(k0 + i + 1); }
       mem_phase(false);
-      if (i < len) lazy29_mac(acc, fe_to29(x), v);
-      if (++since == 6) { lazy29_normalize(acc); since = 0; }
+      if (i < len) ln::lazy_mac(acc, ln::from_packed<L255>(x), v);
+      if (++since == 6) { ln::lazy_normalize(acc); since = 0; }
       x = xn; v = vn;
     }
-    res = fe_add<NL>(res, lazy29_reduce(acc));
+    res = fe_add<NL>(res, ln::lazy_reduce(acc));
   }
   if (live) {
     u32* dst = a.out_alt ? a.out_alt + (o * a.n_rows + row) * NL : a.t + ((a.out_off + o) * a.n_rows + row) * NL;
@@ -1587,7 +1575,7 @@ __global__ void __launch_bounds__(256) roots_kernel(const u32* pw, u32 log_half,
       Fe<8> t = acc;
 #pragma unroll
       for (int d = 0; d < 5; d++) t = fe_add<8>(t, t);          // * 2^5: R = 2^256 -> 2^261
-      const Fe29 x = fe_to29(t);
+      const LN<9> x = ln::from_packed<L255>(t);
 #pragma unroll
       for (int k = 0; k < 9; k++) roots29[i * 12 + k] = x.v[k];
       roots29[i * 12 + 9] = roots29[i * 12 + 10] = roots29[i * 12 + 11] = 0;
@@ -1596,7 +1584,7 @@ __global__ void __launch_bounds__(256) roots_kernel(const u32* pw, u32 log_half,
       Fe<8> t = fe_canon<8>(acc);
 #pragma unroll
       for (int d = 0; d < 5; d++) t = fe_add<8>(t, t);
-      const Fe29 x = fe_to29(t);
+      const LN<9> x = ln::from_packed<L255>(t);
 #pragma unroll
       for (int k = 0; k < 9; k++) roots29c[i * 12 + k] = x.v[k];
       roots29c[i * 12 + 9] = roots29c[i * 12 + 10] = roots29c[i * 12 + 11] = 0;

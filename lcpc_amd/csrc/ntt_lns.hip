@@ -24,74 +24,19 @@
 // Exact modular arithmetic: any stage grouping gives the same fully-reduced bits as the reference's radix-2 loop.
 // The general kernel (kernels.hip ntt_pass_kernel) remains for one-pass rows, plans whose tables do not fit and as the A/B reference
 // (LCPC_NTT_GENERAL=1; tests/test_gpu_ntt_shapes.py).
+// The table side here -- twiddle packs, the uniform rounds' shifted multiples, sub-sampled tables -- serves K1s too: all four fields.
 #include "kernels.h"
-#include "field_ln.h"
+#include "ntt_ln_dev.h"
 
 namespace lcpc {
 
 namespace {
-
-// ---- an array of `cnt` elements in planes: limbs 0-3 as uint4 (N >= 5), then a uint2 plane (N = 3: limbs 0-1; N = 7:
-//      limbs 4-5), then the top limb as u32.  Used for the LDS tile (cnt = 1024: unit-stride lanes are conflict-free in
-//      every plane) and for the twiddle packs (cnt = variants x period) -------------------------------------------------
-template <class FT> LCPC_DEV LN<FT::N> planes_get(const u32* base, u32 cnt, u32 e) {
-  constexpr int N = FT::N;
-  LN<N> r;
-  if constexpr (N == 3) {
-    const uint2 a = *reinterpret_cast<const uint2*>(base + (size_t)e * 2);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = base[(size_t)cnt * 2 + e];
-  } else {
-    const uint4 a = *reinterpret_cast<const uint4*>(base + (size_t)e * 4);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    if constexpr (N == 5) r.v[4] = base[(size_t)cnt * 4 + e];
-    else {
-      const uint2 b = *reinterpret_cast<const uint2*>(base + (size_t)cnt * 4 + (size_t)e * 2);
-      r.v[4] = b.x; r.v[5] = b.y; r.v[6] = base[(size_t)cnt * 6 + e];
-    }
-  }
-  return r;
-}
-template <class FT> LCPC_DEV void planes_put(u32* base, u32 cnt, u32 e, const LN<FT::N>& x) {
-  constexpr int N = FT::N;
-  if constexpr (N == 3) {
-    *reinterpret_cast<uint2*>(base + (size_t)e * 2) = make_uint2(x.v[0], x.v[1]);
-    base[(size_t)cnt * 2 + e] = x.v[2];
-  } else {
-    *reinterpret_cast<uint4*>(base + (size_t)e * 4) = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-    if constexpr (N == 5) base[(size_t)cnt * 4 + e] = x.v[4];
-    else {
-      *reinterpret_cast<uint2*>(base + (size_t)cnt * 4 + (size_t)e * 2) = make_uint2(x.v[4], x.v[5]);
-      base[(size_t)cnt * 6 + e] = x.v[6];
-    }
-  }
-}
-// one entry of the limb-form twiddle table / of the q*p table (STRIDE words per entry)
-template <class FT> LCPC_DEV LN<FT::N> tab_entry(const u32* tab, u32 idx) {
-  LN<FT::N> t;
-#pragma unroll
-  for (int k = 0; k < FT::N; k++) t.v[k] = tab[(size_t)idx * FT::STRIDE + k];
-  return t;
-}
 
 // x * I, I = w^(n/4): a.wq_w = its shifted multiples (ctx.cpp build_wq_w); Ft63: the table entry w^(n/4) R' itself (wave-uniform load)
 template <class FT> LCPC_DEV LN<FT::N> mul_i(const LN<FT::N>& x, const NttPassArgs& a) {
   if constexpr (ln::has_mul_u<FT>) return ln::mul_u<FT>(x, a.wq_w);
   else return ln::mul<FT>(x, tab_entry<FT>(a.roots29, 1u << (a.log_n - 2)));
 }
-
-// round structure of a pass with S stages on tiles of 2^S x 2^LBT slots (as in ntt_l9s.hip)
-template <int S, int LBT> struct Shape {
-  static constexpr int U0 = S & 1;
-  static constexpr int NR4 = S / 2;
-  static constexpr u32 period2 = 1u << (S - 1 + LBT);
-  static constexpr u32 period4(int r) { return 1u << (S - U0 - 2 * r - 2 + LBT); }
-  // the uniform rounds of ntt_l9s.hip (Shape::RU there): from the radix-4 round whose twiddle period is 4 on, wave w takes the quads
-  // q = w mod 4 and all its lanes multiply by the same three twiddles -- scalar operands of ln::mul_u (fields that have one)
-  static constexpr int RU = NR4 >= 4 ? 3 : -1;
-  static constexpr int NRU = RU < 0 ? 0 : NR4 - RU;
-};
-// words per shifted-multiples table in the packs: N^2 = 25 / 49 used
-template <class FT> constexpr u32 U_SLOT = FT::N == 5 ? 32u : 64u;
 
 constexpr u32 TILE = 1024;
 
@@ -174,7 +119,7 @@ __global__ void __launch_bounds__(256, FT::WAVES) ntt_pass_lns_kernel(NttPassArg
 #pragma unroll
     for (u32 pp = 0; pp < 2; pp++) {
       const u32 e1 = tid + 256u * pp;                        // slots with the top stage bit clear are [0, half)
-      const E w = planes_get<FT>(blk, 2 * SH::period2, (canon ? SH::period2 : 0u) + e1);   // stage 0 is all block 0
+      const E w = pack_get<FT, 2>(blk, SH::period2, canon ? 1u : 0u, e1);              // stage 0 is all block 0
       const E x = xin[pp];
       if (pp == 0) mem_phase(false);
       if (zero_hi) {
@@ -240,8 +185,8 @@ __global__ void __launch_bounds__(256, FT::WAVES) ntt_pass_lns_kernel(NttPassArg
       // zero-padded first round (rate <= 1/2): x2 = x3 = 0, the stage-0 butterflies are (x, x w); inputs < 4p; everything
       // is block 0, so with canonical output the three multiplies leaving it (w0, w3, and w2 for c1) take the converting set
       const u32 vb = canon ? 3u : 0u;
-      const E w0 = planes_get<FT>(blk, 6 * period, (vb + 0) * period + jl), w2 = planes_get<FT>(blk, 6 * period, (vb + 2) * period + jl);
-      const E w3 = planes_get<FT>(blk, 6 * period, (vb + 1) * period + jl);
+      const E w0 = pack_get<FT, 6>(blk, period, vb + 0, jl), w2 = pack_get<FT, 6>(blk, period, vb + 2, jl);
+      const E w3 = pack_get<FT, 6>(blk, period, vb + 1, jl);
       mem_phase(false);
       if (a.n_valid <= (1ull << (k - 2))) {                  // rate <= 1/4: x1 is zero too
         const E x0 = xin[0];
@@ -323,11 +268,11 @@ __global__ void __launch_bounds__(256, FT::WAVES) ntt_pass_lns_kernel(NttPassArg
         }
       }
       const u32 vb = blk0c ? 3u : 0u;
-      const E w2 = planes_get<FT>(blk, 6 * period, (vb + 2) * period + jl);
+      const E w2 = pack_get<FT, 6>(blk, period, vb + 2, jl);
       planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(ln::sub(b0, b1), w2));                          // in: |value| < 16p
       const E t = mul_i<FT>(ln::sub(x1, x3), a);                                                  // normalised, (-2.5p, 1.6p)
       const E e2 = ln::sub(x0, x2);                                                               // limbs (-2^W, 2^W), |value| < 8p
-      const E w0 = planes_get<FT>(blk, 6 * period, (vb + 0) * period + jl), w3 = planes_get<FT>(blk, 6 * period, (vb + 1) * period + jl);
+      const E w0 = pack_get<FT, 6>(blk, period, vb + 0, jl), w3 = pack_get<FT, 6>(blk, period, vb + 1, jl);
       planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(ln::add(e2, t), w0));                       // in: limbs (-2^W, 2^(W+1)), |value| < 10.5p
       planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), ln::mul<FT>(ln::sub(e2, t), w3));
     }
@@ -357,6 +302,7 @@ __global__ void __launch_bounds__(256, FT::WAVES) ntt_pass_lns_kernel(NttPassArg
   }
 }
 
+// ---- the twiddle packs of both pass kernels (K1s: Ft255, ntt_l9s.hip; K1n: here), in the layout of ntt_ln_dev.h pack_put ----------
 // one thread per (class, round slot, position): copies the table entries a quad / pair will ask for into lane order
 template <class FT, int S, int LBT>
 __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
@@ -374,8 +320,8 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
       const u32 lp = jl & ((1u << LBT) - 1), i = jl >> LBT;
       const u32 g1 = (i << lb) | lo | lp;
       const u32 gm = (1u << (k - t0 - 1)) - 1;
-      planes_put<FT>(blk, 2 * SH::period2, jl, tab_entry<FT>(a.roots29, (g1 & gm) << t0));
-      planes_put<FT>(blk, 2 * SH::period2, SH::period2 + jl, tab_entry<FT>(a.roots29c, (g1 & gm) << t0));
+      pack_put<FT, 2>(blk, SH::period2, 0, jl, tab_entry<FT>(a.roots29, (g1 & gm) << t0));
+      pack_put<FT, 2>(blk, SH::period2, 1, jl, tab_entry<FT>(a.roots29c, (g1 & gm) << t0));
       continue;
     }
     const u32 r = slot - SH::U0, u = SH::U0 + 2 * r, hb = S - u - 1, period = 1u << (hb - 1 + LBT);
@@ -385,8 +331,8 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
     const u32 lp = jl & ((1u << LBT) - 1), j = jl >> LBT;
     const u32 i0 = ((j >> (hb - 1)) << (hb + 1)) | (j & ((1u << (hb - 1)) - 1));
     const u32 g0 = (i0 << lb) | lo | lp;                     // (last pass: the tile's high bits do not reach these twiddles)
-    // w0 = w^e, w3 = w^(3 e), w2 = w^(2 e), e = (g0 & gm0) << t < n / 4; the tables hold w^i for i < n / 2 and w^(n/2) = -1: past
-    // that, the negated entry (ntt_l9s.hip ntt_pack_kernel)
+    // w0 = w^e, w3 = w^(3 e), w2 = w^(2 e), e = (g0 & gm0) << t < n / 4 (g0 has the quarter bit clear; the pass kernels'
+    // w1 = w^(e + n/4) = I w0 is never read).  The tables hold w^i for i < n / 2 and w^(n/2) = -1: past that, the negated entry
     const u32 ex = (g0 & gm0) << t, half_n = 1u << (k - 1);
     const u32 idx[3] = {ex, 3 * ex, 2 * ex};
     for (u32 v = 0; v < 6; v++) {
@@ -401,15 +347,16 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
           m.v[z] = z + 1 < FT::N ? (u32)d & ((1u << FT::W) - 1) : (u32)d;
         }
       }
-      planes_put<FT>(blk, 6 * period, v * period + jl, m);
+      pack_put<FT, 6>(blk, period, v, jl, m);
     }
   }
 }
 
-// the uniform rounds' constants (ntt_l9s.hip ntt_upack_kernel for N limbs of W bits): per class, for jl = 0..3 and the round's three
-// twiddles w0, w1 = I w0, w2 (plain: block 0 is gone by then), the N shifted multiples W_j = balanced(w 2^(W j) mod p) as N^2 words
-// t = N k + j (limb k of W_j; ln::mul_u / field_wmul_gen.h).  The table entry is w R' mod p: ln::mul(2^(W j), entry) = w 2^(W j),
-// lazily reduced in (-p - eps, eps]; + p where that lies below -(p - 1) / 2.
+// the uniform rounds' constants: per class, for jl = 0..3 and the round's three twiddles w0, w1 = I w0, w2 (plain: block 0 is gone by
+// then), the N shifted multiples W_j = balanced(w 2^(W j) mod p) as N^2 words t = N k + j (limb k of W_j, the top limb sign-extended;
+// ln::mul_u / field_wmul_gen.h).  The table entry is w R' mod p: ln::mul(2^(W j), entry) = w 2^(W j), lazily reduced in
+// (-p - eps, eps] (Ft255: (-1.2p, 0.2p]); + p where that lies below -(p - 1) / 2.  Since the multiplier's range lies inside
+// (-1.5p, 0.5p), that one conditional + p lands every value on its unique representative in [-(p - 1) / 2, (p - 1) / 2].
 template <class FT, int S, int LBT>
 __global__ void __launch_bounds__(64) ntt_lns_upack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
   using SH = Shape<S, LBT>;
@@ -464,7 +411,7 @@ template <class FT, int S, int LBT> NttPackInfo pack_info_t() {
   // radix-2 slot: variants (plain, converting); radix-4 slots: w0, w3 = w0 w2, w2 plain, then the same from the converting table
   if (SH::U0) { pi.round_off[slot++] = off; off += 2 * SH::period2 * FT::N; off = (off + 3) & ~3u; }
   for (int r = 0; r < SH::NR4; r++) { pi.round_off[slot++] = off; off += 6 * SH::period4(r) * FT::N; off = (off + 3) & ~3u; }
-  if (ln::has_mul_u<FT> && SH::RU >= 0) { off = (off + 15) & ~15u; pi.u_off = off; off += SH::NRU * 4 * 3 * U_SLOT<FT>; }
+  if (ln::has_mul_u<FT> && SH::RU >= 0) { off = (off + U_ALIGN<FT> - 1) & ~(U_ALIGN<FT> - 1); pi.u_off = off; off += SH::NRU * 4 * 3 * U_SLOT<FT>; }
   pi.class_words = off;
   return pi;
 }
@@ -536,11 +483,13 @@ template <class FT> hipError_t launch_pass_f(const NttPassArgs& a, bool first, c
 
 }  // namespace
 
+// the table side serves all four fields (Ft255's pass kernel is K1s, ntt_l9s.hip)
 #define LNS_DISPATCH(nl, EXPR)                         \
   switch (nl) {                                        \
     case 2: { using FT = LnField<FT63>; EXPR; }        \
     case 4: { using FT = LnField<FT127>; EXPR; }       \
     case 6: { using FT = LnField<FT191>; EXPR; }       \
+    case 8: { using FT = LnField<FT255>; EXPR; }       \
     default: break;                                    \
   }
 
@@ -560,9 +509,9 @@ hipError_t launch_ntt_lns_subtable(int nl, const uint32_t* tab, uint32_t shift, 
   hipLaunchKernelGGL(lns_subtable_kernel, dim3(2048), dim3(256), 0, st, tab, shift, n, (u32)ntt_lns_stride(nl), sub);
   return hipGetLastError();
 }
-int ntt_lns_limbs(int nl) { return nl == 2 ? 3 : (nl == 4 ? 5 : (nl == 6 ? 7 : 0)); }
-int ntt_lns_limb_bits(int nl) { return nl == 2 ? 26 : 29; }
-int ntt_lns_stride(int nl) { return nl == 2 ? 4 : 8; }
+int ntt_lns_limbs(int nl) { LNS_DISPATCH(nl, return FT::N) return 0; }
+int ntt_lns_limb_bits(int nl) { LNS_DISPATCH(nl, return FT::W) return 0; }
+int ntt_lns_stride(int nl) { LNS_DISPATCH(nl, return FT::STRIDE) return 0; }
 
 NttPackInfo ntt_lns_pack_info(int nl, uint32_t s, bool first) {
   LNS_DISPATCH(nl, return pack_info_f<FT>(s, first))
@@ -579,7 +528,11 @@ hipError_t launch_ntt_lns_pack(int nl, const NttPassArgs& a, bool first, const N
 }
 hipError_t launch_ntt_pass_lns(int nl, const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st) {
   if (a.tile_group && (!first || ((1u << (a.log_n - 10)) >> a.tile_group) < 8)) return hipErrorInvalidValue;
-  LNS_DISPATCH(nl, return launch_pass_f<FT>(a, first, pack, pi, st))
+  switch (nl) {
+    case 2: return launch_pass_f<LnField<FT63>>(a, first, pack, pi, st);
+    case 4: return launch_pass_f<LnField<FT127>>(a, first, pack, pi, st);
+    case 6: return launch_pass_f<LnField<FT191>>(a, first, pack, pi, st);
+  }
   return hipErrorInvalidValue;
 }
 

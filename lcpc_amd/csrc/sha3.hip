@@ -8,7 +8,7 @@
 // chain per column, so the grid is one lane per column and nothing else.  L blocks (17 L words) hold exactly 17 elements,
 // so the kernel walks the message in groups of L blocks whose word -> (row, limb) map is a compile-time table.
 #include "kernels.h"
-#include "field_dev.h"
+#include "field_ln.h"
 #include "keccak_dev.h"
 
 namespace lcpc {

@@ -114,7 +114,7 @@ def maximal_limbs(fid, W, n_low):
 
 
 def maxc(fid):
-    """the stored coefficient that makes the collapse's products largest: Ft255 splits it into 29-bit limbs (fe_to29: eight low
+    """the stored coefficient that makes the collapse's products largest: Ft255 splits it into 29-bit limbs (ln::from_packed: eight low
     limbs of 2^29 - 1), the other fields multiply 32-bit words (Wide<NL>: every word but the top one all ones)"""
     return maximal_limbs(fid, 29, 8) if fid == 3 else maximal_limbs(fid, 32, 2 * FIELD_L[fid] - 1)
 

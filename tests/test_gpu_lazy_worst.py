@@ -2,7 +2,7 @@
 
 Operands are chosen by their stored Montgomery limbs, so that what the kernel multiplies is maximal:
   * coefficients: MAXC, the largest value < p whose low limbs are all ones -- eight 29-bit limbs for Ft255 (collapse29_kernel's
-    fe_to29 split), all but the top 32-bit word for Ft63 / Ft127 / Ft191 (collapse_kernel's Wide<NL> words) -- and p - 1;
+    ln::from_packed split), all but the top 32-bit word for Ft63 / Ft127 / Ft191 (collapse_kernel's Wide<NL> words) -- and p - 1;
   * tensors: for Ft255 the value whose 2^261 form (to_r29_kernel: t * 2^5 mod p) is MAXC, i.e. MAXC / 32 mod p; for the other fields
     MAXC itself;
   * a sprinkle of random rows / entries between the extremes, so that a wrong row order or a wrong batch boundary shows too.
@@ -109,8 +109,8 @@ def test_collapse_shapes_reach_every_split_count():
 @pytest.mark.parametrize("fid", [3, 0, 1, 2])
 @pytest.mark.parametrize("shape", COLLAPSE_SHAPES, ids=_shape_id)
 def test_eval_outer_worst_operands(oracle, fid, shape):
-    """eval_outer (lcpc_collapse -> collapse_run): Ft255 runs collapse29_kernel<NT> (lazy29_mac, normalise every 6 rows, one
-    lazy29_reduce per <= 60 rows: REDC input < 60 p^2, output < 2p), the other fields collapse_kernel<NL, NT> (Wide<NL>, reduced every 8
+    """eval_outer (lcpc_collapse -> collapse_run): Ft255 runs collapse29_kernel<NT> (ln::lazy_mac, normalise every 6 rows, one
+    ln::lazy_reduce per <= 60 rows: REDC input < 60 p^2, output < 2p), the other fields collapse_kernel<NL, NT> (Wide<NL>, reduced every 8
     rows); with more than one split, field_sum_kernel adds the per-split partials.  NT = 1 (one tensor) and NT = 2 (a stack of two),
     MAXC / p - 1 / random coefficient rows against MAXT / p - 1 / random tensor entries, against Python ints at sampled columns
     (the first and last of each 256-column block, the ragged block's last, random ones)."""

@@ -590,7 +590,7 @@ def test_matgen_encode_full_length_input(oracle, n_rows):
 @pytest.mark.parametrize("fid,n_per_row,n_rows", [(1, 40000, 101), (2, 40000, 72), (1, 3000, 130), (2, 2500, 64)])
 def test_brakedown_limb_dot_product_small_fields(oracle, fid, n_per_row, n_rows):
     """Ft127 / Ft191 on the position-major path accumulate their dot products carry-free on 5 / 7 limbs of 29 bits
-    (field_ln.h lazy_mac, matrix values in the R'-Montgomery limb form) like Ft255's lazy29: a level wide enough for the
+    (field_ln.h lazy_mac, matrix values in the R'-Montgomery limb form) like Ft255's 9 limbs: a level wide enough for the
     4-outputs-per-workgroup kernel and sliced ones, random rows plus rows of all p-1 (every product at its largest), against
     the oracle."""
     import pyref as P

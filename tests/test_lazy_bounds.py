@@ -1,11 +1,10 @@
 """Range proofs for the lazy (unreduced) dot-product accumulators, as Python integers.  CPU only.
 
 Every fast dot product on the device skips reductions, and each skip rests on a range argument:
-  * lazy29_mac / lazy29_normalize / lazy29_reduce (field_dev.h, Ft255: 9 limbs of 29 bits, R' = 2^261), called by collapse29_kernel
-    (eval_outer / prove), spmv_kernel's lazy branch, spmm_t_terms and spmm_t_tail_kernel (Brakedown SpMM), all with a normalise
-    every 6 terms and one REDC per <= 60 terms;
-  * ln::lazy_mac / lazy_normalize / lazy_reduce (field_ln.h, Ft127 / Ft191: 5 / 7 limbs of 29 bits), the Brakedown SpMM of those
-    fields, at the same cadence;
+  * ln::lazy_mac / lazy_normalize / lazy_reduce (field_ln.h) for Ft255 (LnField<FT255>: 9 limbs of 29 bits, R' = 2^261), called by
+    collapse29_kernel (eval_outer / prove), spmv_kernel's lazy branch, spmm_t_terms and spmm_t_tail_kernel (Brakedown SpMM), all with
+    a normalise every 6 terms and one REDC per <= 60 terms ("lazy29" below);
+  * the same templates for Ft127 / Ft191 (5 / 7 limbs of 29 bits), the Brakedown SpMM of those fields, at the same cadence ("ln");
   * Wide<NL> (field_dev.h wide_mac / wide_reduce, carry-propagating 32-bit words), collapse_kernel and the non-lazy SpMV / SpMM,
     in batches of 8.
 Each accumulator is modelled column by column with upper bounds at the exact schedule its callers run (which limbs each operand can
@@ -84,7 +83,7 @@ def ln_params():
     """{fid: (N, W, NL)} from field_ln.h's LnField specialisations"""
     t = _src("field_ln.h")
     out = {}
-    for name, fid in (("FT63", 0), ("FT127", 1), ("FT191", 2)):
+    for name, fid in (("FT63", 0), ("FT127", 1), ("FT191", 2), ("FT255", 3)):
         m = re.search(r"struct LnField<%s> \{\s*static constexpr int FID = %s, N = (\d+), W = (\d+), NL = (\d+)" % (name, name), t)
         out[fid] = tuple(int(v) for v in m.groups())
     return out
@@ -92,7 +91,7 @@ def ln_params():
 
 # ---- the accumulators --------------------------------------------------------------------------------------------------------------
 class LimbAcc:
-    """lazy29_* (N = 9, W = 29, NL = 8) / ln::lazy_* : 2N u64 columns, acc[i + j] += x_i v_j, normalize carries columns 0..2N-2 up
+    """ln::lazy_* (Ft255: N = 9, W = 29, NL = 8): 2N u64 columns, acc[i + j] += x_i v_j, normalize carries columns 0..2N-2 up
     (the top column 2N-1 takes no products and is never masked), reduce = normalize + a column-wise REDC by R' = 2^(N W) with
     quotient digits m_k = -acc mod 2^W (p == 1 mod 2^W), whose N result limbs are masked to W bits and packed into NL words."""
 
@@ -224,7 +223,7 @@ class LimbAcc:
 
 
 def lazy29():
-    return LimbAcc(3, 9, 29, 8)
+    return ln_acc(3)
 
 
 def ln_acc(fid):
@@ -237,8 +236,8 @@ LIMB_ACCS = {"lazy29 (Ft255)": lazy29, "ln (Ft127)": lambda: ln_acc(1), "ln (Ft1
 # derived limits (max_safe): (largest normalise cadence at the largest REDC chunk, largest REDC chunk; 4096 = "at least").  The REDC
 # chunk is bound by "output < 2p": T (p - 1)^2 + (R' - 1) p < 2 p R', i.e. 80 terms for Ft255 (the comment's 64 p^2 is a round
 # number below it).  The normalise cadence is bound by the middle columns, which take N - 2 products of two full limbs and two with
-# the short top limb per term, plus what normalize leaves behind and the carry from below: 8 terms for lazy29 (field_dev.h's
-# comment says 7), and far more for Ft127, whose 12-bit top limb makes the columns short.
+# the short top limb per term, plus what normalize leaves behind and the carry from below: 8 terms for lazy29 (field_ln.h's
+# comment counts 6), and far more for Ft127, whose 12-bit top limb makes the columns short.
 DERIVED = {"lazy29 (Ft255)": (8, 80), "ln (Ft127)": (16, 4096), "ln (Ft191)": (10, 4096)}
 
 
@@ -253,12 +252,12 @@ def test_cadences_are_read_from_the_sources():
     wb = wide_batches()
     assert all(len(set(v)) == 1 for v in wb.values()) and {n: v[0] for n, v in wb.items()} == {
         "collapse_kernel": 8, "spmv_kernel (Wide)": 8, "spmm_t_terms (Wide)": 8}
-    assert ln_params() == {0: (3, 26, 2), 1: (5, 29, 4), 2: (7, 29, 6)}
+    assert ln_params() == {0: (3, 26, 2), 1: (5, 29, 4), 2: (7, 29, 6), 3: (9, 29, 8)}
 
 
 @pytest.mark.parametrize("name", list(LIMB_ACCS))
 def test_limb_accumulator_bounds_at_source_cadence(name):
-    """columns < 2^64 throughout, REDC input < 64 p^2 (lazy29_reduce's stated requirement) / < p R' (ln), REDC accumulator < 2^64,
+    """columns < 2^64 throughout, REDC input < 64 p^2 (Ft255, field_ln.h lazy_reduce) / < p R' (ln), REDC accumulator < 2^64,
     REDC output < 2p and inside NL words, at the cadence of every caller in kernels.hip"""
     a = LIMB_ACCS[name]()
     callers = {n: (v[0][0], v[1][0]) for n, v in lazy29_cadences().items() if ("(ln)" in n) == name.startswith("ln")}

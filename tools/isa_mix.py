@@ -7,7 +7,7 @@ stream issue": VERDICT r5 item 5.  Runs without a GPU (hipcc -S --cuda-device-on
 
 Classes and their measured cost in cycles per wave instruction per SIMD at the nominal 2.4 GHz (i.e. 1 / rate, whatever the clock did):
   mad64      v_mad_i64_i32 / v_mad_u64_u32, vector operands        4.79   (one accumulator or eight: the same)
-  mad64_s    the same with an SGPR multiplicand (l9::mul_u)        4.46
+  mad64_s    the same with an SGPR multiplicand (ln::mul_u)        4.46
   mul32      v_mul_lo_u32 / v_mul_hi_u32                           4.32
   vop3       every other 64-bit encoding (add3, alignbit, bfe, 64-bit shifts, lshl_add, carry adds, cndmask, lane moves)   4.30
   vop2       32-bit encodings, with or without a 32-bit literal    2.45

@@ -22,10 +22,9 @@
 // 9 x 29-bit limbs as K1s; exact modular arithmetic, so the fully reduced bits equal the reference's radix-2 loop.
 #include <algorithm>
 #include "kernels.h"
-#include "ntt_l9_dev.h"
+#include "ntt_ln_dev.h"
 
 namespace lcpc {
-#include "field_wmul_gen.h"   // wmul_u(): the one-statement shifted-multiples multiply
 
 namespace {
 
@@ -37,7 +36,7 @@ struct NttUArgs {
   const u32* src;         // pass 0: row-major (src_stride elements per row); passes 1, 2: mid
   u32* dst;               // passes 0, 1: mid; pass 2: row-major (dst_stride elements per row)
   const u32* pack;        // this pass's twiddle pack: [class][round][quad][slot][U_SLOT]
-  const u32* qp29;        // (i - 24) p table of l9::clamp
+  const u32* qp29;        // (i - 24) p table of ln::clamp
   u32* copy_dst;          // pass 0, may be null: padded copy of src (LcCommit.coeffs)
   u64 src_stride, dst_stride, n_valid, n_src_total, n_rows;
   u32 log_n, n_groups;
@@ -50,14 +49,14 @@ template <int R> LCPC_DEV u32 u_idx(u32 q, u32 c) {
   else return 4u * q + c;
 }
 
-LCPC_DEV L9 u_mul(const L9& x, const u32* np2, const u32* w) {
-  L9 r;
+LCPC_DEV LN<9> u_mul(const LN<9>& x, const u32* np2, const u32* w) {
+  LN<9> r;
   wmul_u(x.v, np2, w, r.v);
   return r;
 }
 
 // regroup the eight elements of a thread from round R's quads to round R + 1's through LDS, 4 + 4 + 1 limbs at a time
-template <int R> LCPC_DEV void u_exchange(L9 (&E)[2][4], u32* xch, const u32 (&qa)[2], u32 lane) {
+template <int R> LCPC_DEV void u_exchange(LN<9> (&E)[2][4], u32* xch, const u32 (&qa)[2], u32 lane) {
   uint4* x4 = reinterpret_cast<uint4*>(xch);
 #pragma unroll
   for (int half = 0; half < 2; half++) {
@@ -92,26 +91,26 @@ template <int R> LCPC_DEV void u_exchange(L9 (&E)[2][4], u32* xch, const u32 (&q
 // Value ranges (u_mul returns (-2p, 2.7p)): inputs |x| < 5.4p -> b < 10.8p, c0 < 21.6p (inside the clamp table's -24p .. 39p);
 // the difference b0 - b1 has limbs up to 2^30 and is normalised before its multiply (the quotient estimate wants sum |limb| <
 // 9 * 2^29); x0 - x2, x1 - x3 and b2 - b3 are differences of normalised values.
-template <bool LAST_TWO> LCPC_DEV void u_butterfly(L9 (&x)[4], const u32* np2, const u32* nqp, const u32* w) {
+template <bool LAST_TWO> LCPC_DEV void u_butterfly(LN<9> (&x)[4], const u32* np2, const u32* nqp, const u32* w) {
   if constexpr (LAST_TWO) {
     // stages k-2, k-1: twiddles 1, w^(n/4), 1 -- slot 1 holds w^(n/4)
-    const L9 b0 = l9::add(x[0], x[2]), b1 = l9::add(x[1], x[3]);
-    const L9 b2 = l9::sub(x[0], x[2]);
-    const L9 b3 = u_mul(l9::sub(x[1], x[3]), np2, w + U_SLOT);
-    x[0] = l9::add(b0, b1); x[1] = l9::sub(b0, b1); x[2] = l9::add(b2, b3); x[3] = l9::sub(b2, b3);
-    l9::normalize(x[0]); l9::normalize(x[1]); l9::normalize(x[2]); l9::normalize(x[3]);
+    const LN<9> b0 = ln::add(x[0], x[2]), b1 = ln::add(x[1], x[3]);
+    const LN<9> b2 = ln::sub(x[0], x[2]);
+    const LN<9> b3 = u_mul(ln::sub(x[1], x[3]), np2, w + U_SLOT);
+    x[0] = ln::add(b0, b1); x[1] = ln::sub(b0, b1); x[2] = ln::add(b2, b3); x[3] = ln::sub(b2, b3);
+    ln::normalize<LnField<FT255>>(x[0]); ln::normalize<LnField<FT255>>(x[1]); ln::normalize<LnField<FT255>>(x[2]); ln::normalize<LnField<FT255>>(x[3]);
   } else {
-    const L9 b0 = l9::add(x[0], x[2]), b1 = l9::add(x[1], x[3]);
-    L9 c0 = l9::add(b0, b1);
-    l9::clamp_apply(c0, l9::clamp_row(nqp, l9::clamp_q(c0.v[8])));                        // [0, p + 2^239)
-    L9 d1 = l9::sub(b0, b1);
-    l9::normalize(d1);
-    const L9 b2 = u_mul(l9::sub(x[0], x[2]), np2, w);
-    const L9 b3 = u_mul(l9::sub(x[1], x[3]), np2, w + U_SLOT);
-    const L9 c1 = u_mul(d1, np2, w + 3 * U_SLOT);
-    L9 c2 = l9::add(b2, b3);
-    l9::normalize(c2);
-    const L9 c3 = u_mul(l9::sub(b2, b3), np2, w + 2 * U_SLOT);
+    const LN<9> b0 = ln::add(x[0], x[2]), b1 = ln::add(x[1], x[3]);
+    LN<9> c0 = ln::add(b0, b1);
+    ln::clamp_apply<LnField<FT255>>(c0, ln::clamp_row<LnField<FT255>>(nqp, ln::clamp_q<LnField<FT255>>(c0.v[8])));                        // [0, p + 2^239)
+    LN<9> d1 = ln::sub(b0, b1);
+    ln::normalize<LnField<FT255>>(d1);
+    const LN<9> b2 = u_mul(ln::sub(x[0], x[2]), np2, w);
+    const LN<9> b3 = u_mul(ln::sub(x[1], x[3]), np2, w + U_SLOT);
+    const LN<9> c1 = u_mul(d1, np2, w + 3 * U_SLOT);
+    LN<9> c2 = ln::add(b2, b3);
+    ln::normalize<LnField<FT255>>(c2);
+    const LN<9> c3 = u_mul(ln::sub(b2, b3), np2, w + 2 * U_SLOT);
     x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
   }
 }
@@ -154,10 +153,10 @@ __global__ void __launch_bounds__(512, 4) ntt_u_kernel(NttUArgs a) {
 
   u32 np2[9];
 #pragma unroll
-  for (int j = 0; j < 9; j++) np2[j] = 0u - 2u * (u32)P29::limb(j);
+  for (int j = 0; j < 9; j++) np2[j] = 0u - 2u * LnField<FT255>::limb(j);
 
   // ---- load: the thread's two quads of round 0 ----
-  L9 E[2][4];
+  LN<9> E[2][4];
 #pragma unroll
   for (int q2 = 0; q2 < 2; q2++)
 #pragma unroll
@@ -175,7 +174,7 @@ __global__ void __launch_bounds__(512, 4) ntt_u_kernel(NttUArgs a) {
       } else {
         v = fe_load<8>(a.src + ((((u64)g << k) + pos) * 64 + lane) * 8);
       }
-      E[q2][c] = l9::from_packed(v);
+      E[q2][c] = ln::from_packed<LnField<FT255>>(v);
     }
   __syncthreads();                                           // nqp is in place
 
@@ -197,15 +196,15 @@ __global__ void __launch_bounds__(512, 4) ntt_u_kernel(NttUArgs a) {
     for (int c = 0; c < 4; c++) {
       const u32 i = u_idx<2>(qa[q2], c);
       const u32 pos = base + (i << stride_log);
-      L9 x = E[q2][c];                                                  // normalised, |value| < 22p
-      l9::clamp_apply(x, l9::clamp_row(nqp, l9::clamp_q(x.v[8])));      // [0, p + 2^239) < 2^256
+      LN<9> x = E[q2][c];                                                  // normalised, |value| < 22p
+      ln::clamp_apply<LnField<FT255>>(x, ln::clamp_row<LnField<FT255>>(nqp, ln::clamp_q<LnField<FT255>>(x.v[8])));      // [0, p + 2^239) < 2^256
       u32 w8[8];
-      fe_from29(w8, x.v);
+      ln::to_packed<LnField<FT255>>(w8, x.v);
       Fe<8> v;
 #pragma unroll
       for (int t = 0; t < 8; t++) v.v[t] = w8[t];
       if constexpr (PASS == 2) {
-        if (__any((int)(x.v[8] >= (u32)P29::limb(8)))) v = fe_reduce_once8(w8);   // -> [0, p): about one element in 2^17 needs it
+        if (__any((int)(x.v[8] >= LnField<FT255>::limb(8)))) v = fe_reduce_once<8>(w8);   // -> [0, p): about one element in 2^17 needs it
         if (hi == 0 && i < 4) v = fe_canon_r29(v);                        // the never-multiplied prefix of a row is still in Montgomery form
         if (live) fe_store<8>(a.dst + (row * a.dst_stride + pos) * 8, v);
       } else {
@@ -277,7 +276,7 @@ __global__ void __launch_bounds__(256) ntt_u_pack_kernel(const u32* roots, u32 l
         const u32 b = 29 * kk, wd = b / 32, shb = b % 32;
         u64 x = (u64)m[wd] >> shb;
         if (wd + 1 < 9) x |= (u64)m[wd + 1] << (32 - shb);
-        const u32 limb = kk < 8 ? (u32)(x & P29::M) : (u32)x;   // limb 8: bits 232 .. 263, i.e. sign-extended (m[8] is 0 or ~0)
+        const u32 limb = kk < 8 ? (u32)(x & ((1u << 29) - 1)) : (u32)x;   // limb 8: bits 232 .. 263, i.e. sign-extended (m[8] is 0 or ~0)
         out[9 * kk + j] = limb;
       }
     }

@@ -1,20 +1,19 @@
 // tools/ubench_wmul.hip -- LAB: what a WAVE-UNIFORM twiddle would buy the Ft255 row NTT (LABNOTES Part 0, "shifted multiples").
-//   A  today's multiply: l9::mul = r29_mul1s, 153 mads + 35, per-LANE twiddle (36 B per lane and multiply, coalesced)
+//   A  today's multiply: ln::mul = r29_mul1s, 153 mads + 35, per-LANE twiddle (36 B per lane and multiply, coalesced)
 //   B  x * w as sum_j x_j * W_j with the nine precomputed W_j = balanced(w 2^(29 j) mod p) of a wave-uniform w (81 dwords by
 //      scalar loads inside the statement) + one 32-bit quotient: 90 mads + 26  (lcpc_amd/csrc/gen/gen_wmul_asm.py)
 // Each thread runs a dependent chain x <- x * w_i of ITERS multiplies (one accumulator chain per wave and multiply, as in K1s);
 // occupancy by __launch_bounds__.  Results of B are checked on the host (r == x * prod w_i mod p, done by the caller script with
 // Python integers from the dumped values).
-// Build: python lcpc_amd/csrc/gen/gen_wmul_asm.py > tools/wmul_gen.h && hipcc --offload-arch=gfx950 -O3 -I lcpc_amd/csrc tools/ubench_wmul.hip -o tools/ubench_wmul
+// Build: hipcc --offload-arch=gfx950 -O3 -I lcpc_amd/csrc tools/ubench_wmul.hip -o tools/ubench_wmul
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "field_dev.h"
+#include "field_ln.h"
 using namespace lcpc;
-#include "wmul_gen.h"
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
 typedef unsigned __int128 u128;
@@ -42,15 +41,15 @@ static void wtable(const uint64_t w[4], uint32_t out[81]) {
 
 template <int OCC>
 __global__ void __launch_bounds__(256, OCC) k_permul(const u32* __restrict__ tw, u32 n_tw, u32 iters, u32* out) {
-  L9 x;
+  LN<9> x;
   for (int i = 0; i < 9; i++) x.v[i] = (threadIdx.x * 2654435761u + i * 40503u + blockIdx.x) & 0x0fffffffu;
   const u32 gid = blockIdx.x * 256 + threadIdx.x;
   for (u32 it = 0; it < iters; it++) {
     const u32 e = (gid + it * 8191u) % n_tw;                         // per-lane entries, consecutive lanes consecutive (as the packs are)
     const uint4* p = reinterpret_cast<const uint4*>(tw + (size_t)e * 12);
     const uint4 a = p[0], b = p[1];
-    Fe29 w; w.v[0] = a.x; w.v[1] = a.y; w.v[2] = a.z; w.v[3] = a.w; w.v[4] = b.x; w.v[5] = b.y; w.v[6] = b.z; w.v[7] = b.w; w.v[8] = tw[(size_t)e * 12 + 8];
-    x = l9::mul(x, w);
+    LN<9> w; w.v[0] = a.x; w.v[1] = a.y; w.v[2] = a.z; w.v[3] = a.w; w.v[4] = b.x; w.v[5] = b.y; w.v[6] = b.z; w.v[7] = b.w; w.v[8] = tw[(size_t)e * 12 + 8];
+    x = ln::mul<LnField<FT255>>(x, w);
   }
   u32 s = 0; for (int i = 0; i < 9; i++) s ^= x.v[i];
   out[gid] = s;
@@ -62,8 +61,8 @@ __global__ void __launch_bounds__(256, OCC) k_wmul(const u32* __restrict__ wt, u
   u32 x[9], np2[9];
   for (int i = 0; i < 9; i++) x[i] = (threadIdx.x * 2654435761u + i * 40503u + blockIdx.x) & 0x0fffffffu;
   // limbs of -2p as signed 32-bit values
-  np2[0] = (u32)(-(int)(2 * P29::limb(0)));
-  for (int k = 1; k < 9; k++) np2[k] = (u32)(-(int)(2 * P29::limb(k)));
+  np2[0] = (u32)(-(int)(2 * LnField<FT255>::limb(0)));
+  for (int k = 1; k < 9; k++) np2[k] = (u32)(-(int)(2 * LnField<FT255>::limb(k)));
   const u32 gid = blockIdx.x * 256 + threadIdx.x;
   const u32 wave = __builtin_amdgcn_readfirstlane(gid >> 6);
   if (dump && gid < 64) for (int i = 0; i < 9; i++) dump[gid * 18 + i] = x[i];

@@ -14,7 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "field_dev.h"
+#include "field_ln.h"
 #include "host_field.h"
 #include "kernels.h"
 
@@ -28,21 +28,21 @@ template <int LT> struct Lds9 {
   static constexpr u32 T = 1u << LT;
   static constexpr u32 WORDS = T * 9 + 64 * 12;
 };
-template <int LT> __device__ __forceinline__ L9 lds9_get(const u32* lds, u32 e) {
+template <int LT> __device__ __forceinline__ LN<9> lds9_get(const u32* lds, u32 e) {
   const uint4 a = *reinterpret_cast<const uint4*>(lds + (size_t)e * 4);
   const uint4 b = *reinterpret_cast<const uint4*>(lds + ((size_t)Lds9<LT>::T + e) * 4);
-  L9 r;
+  LN<9> r;
   r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
   r.v[8] = lds[(size_t)Lds9<LT>::T * 8 + e];
   return r;
 }
-template <int LT> __device__ __forceinline__ void lds9_put(u32* lds, u32 e, const L9& x) {
+template <int LT> __device__ __forceinline__ void lds9_put(u32* lds, u32 e, const LN<9>& x) {
   *reinterpret_cast<uint4*>(lds + (size_t)e * 4) = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
   *reinterpret_cast<uint4*>(lds + ((size_t)Lds9<LT>::T + e) * 4) = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
   lds[(size_t)Lds9<LT>::T * 8 + e] = x.v[8];
 }
-__device__ __forceinline__ Fe29 tw29(const u32* tab, u32 widx) {
-  Fe29 t;
+__device__ __forceinline__ LN<9> tw29(const u32* tab, u32 widx) {
+  LN<9> t;
   const uint4* wp = reinterpret_cast<const uint4*>(tab + (size_t)widx * 12);
   const uint4 w0 = wp[0], w1 = wp[1];
   const u32 w8 = tab[(size_t)widx * 12 + 8];
@@ -51,23 +51,23 @@ __device__ __forceinline__ Fe29 tw29(const u32* tab, u32 widx) {
   return t;
 }
 
-template <int V> __device__ __forceinline__ L9 vmul(const L9& a, const Fe29& w) {
+template <int V> __device__ __forceinline__ LN<9> vmul(const LN<9>& a, const LN<9>& w) {
   if constexpr (V & V_NOMUL) {
-    L9 r;
+    LN<9> r;
 #pragma unroll
-    for (int k = 0; k < 9; k++) r.v[k] = (a.v[k] + w.v[k]) & l9::M;
+    for (int k = 0; k < 9; k++) r.v[k] = (a.v[k] + w.v[k]) & ((1u << 29) - 1);
     return r;
   } else {
-    return l9::mul(a, w);
+    return ln::mul<LnField<FT255>>(a, w);
   }
 }
-template <int V> __device__ __forceinline__ void vnorm(L9& a) { if constexpr (!(V & V_NONORM)) l9::normalize(a); }
-template <int V> __device__ __forceinline__ void vclamp(L9& a, const u32* qp) { if constexpr (!(V & V_NONORM)) l9::clamp(a, qp); }
-template <int V> __device__ __forceinline__ Fe29 vtw(const u32* tab, u32 widx, u32 q) {
+template <int V> __device__ __forceinline__ void vnorm(LN<9>& a) { if constexpr (!(V & V_NONORM)) ln::normalize<LnField<FT255>>(a); }
+template <int V> __device__ __forceinline__ void vclamp(LN<9>& a, const u32* qp) { if constexpr (!(V & V_NONORM)) ln::clamp(a, qp); }
+template <int V> __device__ __forceinline__ LN<9> vtw(const u32* tab, u32 widx, u32 q) {
   if constexpr (V & V_NOTWLOAD) {
-    Fe29 t;
+    LN<9> t;
 #pragma unroll
-    for (int k = 0; k < 9; k++) t.v[k] = (widx * 2654435761u + k * 40503u) & l9::M;
+    for (int k = 0; k < 9; k++) t.v[k] = (widx * 2654435761u + k * 40503u) & ((1u << 29) - 1);
     return t;
   }
   if constexpr (V & V_TW_UNIFORM) return tw29(tab, widx & 1u);
@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(256, 4) lab_l9_kernel(NttPassArgs a, u32 stagg
     Fe<NL> v;
     if constexpr (V & V_NOGLOBAL) { v = fe_zero<NL>(); v.v[0] = g; v.v[3] = e * 77u; }
     else v = (g < a.n_valid && row * a.src_stride + g < a.n_src_total) ? fe_load<NL>(src + (size_t)g * NL) : fe_zero<NL>();
-    lds9_put<LT>(lds, e, l9::from_packed(v));
+    lds9_put<LT>(lds, e, ln::from_packed<LnField<FT255>>(v));
     if constexpr (!(V & V_NOGLOBAL))
       if (a.copy_dst != nullptr && g < a.n_valid) fe_store<NL>(a.copy_dst + (row * a.src_stride + g) * NL, v);
   }
@@ -160,42 +160,42 @@ __global__ void __launch_bounds__(256, 4) lab_l9_kernel(NttPassArgs a, u32 stagg
       const u32 g0 = gindex(e0), g1 = gindex(e0 + dq);
       if (zero_hi) {
         const u32* tc = canon ? a.roots29c : a.roots29;
-        const Fe29 w0 = vtw<V>(tc, g0 & gm0, q);
-        const Fe29 w2c = vtw<V>(tc, (g0 & gm1) << 1, q);
-        const Fe29 w2 = vtw<V>(a.roots29, (g0 & gm1) << 1, q);
+        const LN<9> w0 = vtw<V>(tc, g0 & gm0, q);
+        const LN<9> w2c = vtw<V>(tc, (g0 & gm1) << 1, q);
+        const LN<9> w2 = vtw<V>(a.roots29, (g0 & gm1) << 1, q);
         if (zero_3q) {
-          const L9 x0 = lds9_get<LT>(lds, e0);
+          const LN<9> x0 = lds9_get<LT>(lds, e0);
           lds9_put<LT>(lds, e0 + dq, vmul<V>(x0, w2c));
-          const L9 b2 = vmul<V>(x0, w0);
+          const LN<9> b2 = vmul<V>(x0, w0);
           lds9_put<LT>(lds, e0 + 2 * dq, b2);
           lds9_put<LT>(lds, e0 + 3 * dq, vmul<V>(b2, w2));
           continue;
         }
-        const Fe29 w1 = vtw<V>(tc, g1 & gm0, q);
-        const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-        L9 c0 = l9::add(x0, x1);
+        const LN<9> w1 = vtw<V>(tc, g1 & gm0, q);
+        const LN<9> x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
+        LN<9> c0 = ln::add(x0, x1);
         vnorm<V>(c0);
         lds9_put<LT>(lds, e0, c0);
-        lds9_put<LT>(lds, e0 + dq, vmul<V>(l9::sub(x0, x1), w2c));
-        const L9 b2 = vmul<V>(x0, w0), b3 = vmul<V>(x1, w1);
-        L9 c2 = l9::add(b2, b3);
+        lds9_put<LT>(lds, e0 + dq, vmul<V>(ln::sub(x0, x1), w2c));
+        const LN<9> b2 = vmul<V>(x0, w0), b3 = vmul<V>(x1, w1);
+        LN<9> c2 = ln::add(b2, b3);
         vnorm<V>(c2);
         lds9_put<LT>(lds, e0 + 2 * dq, c2);
-        lds9_put<LT>(lds, e0 + 3 * dq, vmul<V>(l9::sub(b2, b3), w2));
+        lds9_put<LT>(lds, e0 + 3 * dq, vmul<V>(ln::sub(b2, b3), w2));
         continue;
       }
-      const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-      const L9 x2 = lds9_get<LT>(lds, e0 + 2 * dq), x3 = lds9_get<LT>(lds, e0 + 3 * dq);
-      const L9 b0 = l9::add(x0, x2), b1 = l9::add(x1, x3);
-      L9 c0 = l9::add(b0, b1);
+      const LN<9> x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
+      const LN<9> x2 = lds9_get<LT>(lds, e0 + 2 * dq), x3 = lds9_get<LT>(lds, e0 + 3 * dq);
+      const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);
+      LN<9> c0 = ln::add(b0, b1);
       vnorm<V>(c0);
       if (last_two) {
-        const Fe29 wq = vtw<V>(a.roots29, 1u << (k - 2), q);
-        L9 c1 = l9::sub(b0, b1);
-        const L9 b2 = l9::sub(x0, x2);
-        const L9 b3 = vmul<V>(l9::sub(x1, x3), wq);
-        L9 c2 = l9::add(b2, b3);
-        L9 c3 = l9::sub(b2, b3);
+        const LN<9> wq = vtw<V>(a.roots29, 1u << (k - 2), q);
+        LN<9> c1 = ln::sub(b0, b1);
+        const LN<9> b2 = ln::sub(x0, x2);
+        const LN<9> b3 = vmul<V>(ln::sub(x1, x3), wq);
+        LN<9> c2 = ln::add(b2, b3);
+        LN<9> c3 = ln::sub(b2, b3);
         vnorm<V>(c1); vnorm<V>(c2); vnorm<V>(c3);
         lds9_put<LT>(lds, e0, c0);
         lds9_put<LT>(lds, e0 + dq, c1);
@@ -204,22 +204,22 @@ __global__ void __launch_bounds__(256, 4) lab_l9_kernel(NttPassArgs a, u32 stagg
       } else {
         const bool blk0c = canon && g0 <= gm1;
         const u32* t01 = blk0c ? a.roots29c : a.roots29;
-        const Fe29 w0 = vtw<V>(t01, (g0 & gm0) << t, q);
-        const Fe29 w1 = vtw<V>(t01, (g1 & gm0) << t, q);
-        const Fe29 w2 = vtw<V>(a.roots29, (g0 & gm1) << (t + 1), q);
+        const LN<9> w0 = vtw<V>(t01, (g0 & gm0) << t, q);
+        const LN<9> w1 = vtw<V>(t01, (g1 & gm0) << t, q);
+        const LN<9> w2 = vtw<V>(a.roots29, (g0 & gm1) << (t + 1), q);
         vclamp<V>(c0, qp);
         lds9_put<LT>(lds, e0, c0);
-        const L9 d1 = l9::sub(b0, b1);
-        L9 c1;
+        const LN<9> d1 = ln::sub(b0, b1);
+        LN<9> c1;
         if (blk0c) c1 = vmul<V>(d1, vtw<V>(a.roots29c, (g0 & gm1) << (t + 1), q));
         else c1 = vmul<V>(d1, w2);
         lds9_put<LT>(lds, e0 + dq, c1);
-        const L9 b2 = vmul<V>(l9::sub(x0, x2), w0);
-        const L9 b3 = vmul<V>(l9::sub(x1, x3), w1);
-        L9 c2 = l9::add(b2, b3);
+        const LN<9> b2 = vmul<V>(ln::sub(x0, x2), w0);
+        const LN<9> b3 = vmul<V>(ln::sub(x1, x3), w1);
+        LN<9> c2 = ln::add(b2, b3);
         vnorm<V>(c2);
         lds9_put<LT>(lds, e0 + 2 * dq, c2);
-        lds9_put<LT>(lds, e0 + 3 * dq, vmul<V>(l9::sub(b2, b3), w2));
+        lds9_put<LT>(lds, e0 + 3 * dq, vmul<V>(ln::sub(b2, b3), w2));
       }
     }
     __syncthreads();
@@ -227,7 +227,7 @@ __global__ void __launch_bounds__(256, 4) lab_l9_kernel(NttPassArgs a, u32 stagg
   u32* dst = a.dst + row * a.dst_stride * NL;
   for (u32 e = tid; e < T; e += 256) {
     const u32 g = gindex(e);
-    Fe<NL> v = l9::to_packed_reduced(lds9_get<LT>(lds, e), qp);
+    Fe<NL> v = ln::to_packed_reduced(lds9_get<LT>(lds, e), qp);
     if (g < a.mont_prefix) v = fe_canon_r29(v);
     if constexpr (V & V_NOGLOBAL) { if (v.v[0] == 0x12345u && v.v[5] == 77u) fe_store<NL>(dst + (size_t)g * NL, v); }
     else fe_store<NL>(dst + (size_t)g * NL, v);
@@ -258,11 +258,11 @@ template <int S, int LBT> struct PackShape {
   static constexpr u32 period(int r) { return 1u << (S - 2 * r - 2 + LBT); }     // hb - 1 + LBT, hb = S - 2r - 1
 };
 
-__device__ __forceinline__ Fe29 pk_load(const u32* blk, u32 period, u32 variant, u32 jl) {
+__device__ __forceinline__ LN<9> pk_load(const u32* blk, u32 period, u32 variant, u32 jl) {
   const uint4 a = *reinterpret_cast<const uint4*>(blk + ((size_t)(variant * 2 + 0) * period + jl) * 4);
   const uint4 b = *reinterpret_cast<const uint4*>(blk + ((size_t)(variant * 2 + 1) * period + jl) * 4);
   const u32 c = blk[(size_t)12 * period * 4 + (size_t)variant * period + jl];
-  Fe29 t;
+  LN<9> t;
   t.v[0] = a.x; t.v[1] = a.y; t.v[2] = a.z; t.v[3] = a.w; t.v[4] = b.x; t.v[5] = b.y; t.v[6] = b.z; t.v[7] = b.w; t.v[8] = c;
   return t;
 }
@@ -302,11 +302,11 @@ __global__ void pack_kernel(NttPassArgs a, PackInfo pi, u32 n_classes, u32* pack
 }
 
 namespace l9x {
-// quotient for the clamp from an UN-normalised top limb (carries from below still missing, <= 3): see l9::clamp
+// quotient for the clamp from an UN-normalised top limb (carries from below still missing, <= 3): see ln::clamp
 LCPC_DEV u32 clamp_q(u32 top) {
-  constexpr u32 PTOP1 = (u32)(P29::limb(8)) + 1;
+  constexpr u32 PTOP1 = (u32)(LnField<FT255>::limb(8)) + 1;
   constexpr u64 MAGIC = (((u64)1 << 52) + PTOP1 - 1) / PTOP1;
-  const u32 n = top + (u32)(l9::QOFF * PTOP1 - l9::QBIAS);
+  const u32 n = top + (u32)(ln::QOFF * PTOP1 - ln::QBIAS);
   return (u32)(((u64)n * MAGIC) >> 52);
 }
 struct Row { u32 v[9]; };
@@ -318,12 +318,12 @@ LCPC_DEV Row row_load(const u32* nqp, u32 q) {       // nqp: NEGATED q*p rows, 1
 }
 // a: limbs 0..7 in [0, 2^31) (sum of <= 4 normalised values), top signed; nt = -(q*p) limb-wise.  One carry pass:
 // limbs 0..7 -> [0, 2^29), value = a - q*p exactly, in [0, p + 2^239) (the carries the estimate did not see add < 4 * 2^232)
-LCPC_DEV void clamp_apply(L9& a, const Row& nt) {
+LCPC_DEV void clamp_apply(LN<9>& a, const Row& nt) {
   int32_t c = 0;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const int32_t d = (int32_t)(a.v[k] + nt.v[k] + (u32)c);
-    a.v[k] = (u32)d & l9::M;
+    a.v[k] = (u32)d & ((1u << 29) - 1);
     c = d >> 29;
   }
   a.v[8] = a.v[8] + nt.v[8] + (u32)c;
@@ -371,7 +371,7 @@ __global__ void __launch_bounds__(256, 4) v2_kernel(NttPassArgs a, const u32* __
     } else {
       v = fe_load<NL>(src + (size_t)g * NL);
     }
-    lds9_put<LT>(lds, e, l9::from_packed(v));
+    lds9_put<LT>(lds, e, ln::from_packed<LnField<FT255>>(v));
   }
   __syncthreads();
   const u32 q = tid;                                         // one quad per thread per round (T / 4 == 256)
@@ -393,42 +393,42 @@ __global__ void __launch_bounds__(256, 4) v2_kernel(NttPassArgs a, const u32* __
     if (FIRST && r == 0 && a.n_valid <= (1ull << (k - 1))) {
       // zero-padded first round (rate <= 1/2): x2 = x3 = 0; everything is block 0
       const u32 vb = canon ? 3u : 0u;
-      const Fe29 w0 = pk_load(blk, period, vb + 0, jl), w2c = pk_load(blk, period, vb + 2, jl), w2 = pk_load(blk, period, 2, jl);
+      const LN<9> w0 = pk_load(blk, period, vb + 0, jl), w2c = pk_load(blk, period, vb + 2, jl), w2 = pk_load(blk, period, 2, jl);
       if (a.n_valid <= (1ull << (k - 2))) {
-        const L9 x0 = lds9_get<LT>(lds, e0);
-        lds9_put<LT>(lds, e0 + dq, l9::mul(x0, w2c));
-        const L9 b2 = l9::mul(x0, w0);
+        const LN<9> x0 = lds9_get<LT>(lds, e0);
+        lds9_put<LT>(lds, e0 + dq, ln::mul<LnField<FT255>>(x0, w2c));
+        const LN<9> b2 = ln::mul<LnField<FT255>>(x0, w0);
         lds9_put<LT>(lds, e0 + 2 * dq, b2);
-        lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(b2, w2));
+        lds9_put<LT>(lds, e0 + 3 * dq, ln::mul<LnField<FT255>>(b2, w2));
       } else {
-        const Fe29 w1 = pk_load(blk, period, vb + 1, jl);
-        const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-        L9 c0 = l9::add(x0, x1);
-        l9::normalize(c0);
+        const LN<9> w1 = pk_load(blk, period, vb + 1, jl);
+        const LN<9> x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
+        LN<9> c0 = ln::add(x0, x1);
+        ln::normalize<LnField<FT255>>(c0);
         lds9_put<LT>(lds, e0, c0);
-        lds9_put<LT>(lds, e0 + dq, l9::mul(l9::sub(x0, x1), w2c));
-        const L9 b2 = l9::mul(x0, w0), b3 = l9::mul(x1, w1);
-        L9 c2 = l9::add(b2, b3);
-        l9::normalize(c2);
+        lds9_put<LT>(lds, e0 + dq, ln::mul<LnField<FT255>>(ln::sub(x0, x1), w2c));
+        const LN<9> b2 = ln::mul<LnField<FT255>>(x0, w0), b3 = ln::mul<LnField<FT255>>(x1, w1);
+        LN<9> c2 = ln::add(b2, b3);
+        ln::normalize<LnField<FT255>>(c2);
         lds9_put<LT>(lds, e0 + 2 * dq, c2);
-        lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(l9::sub(b2, b3), w2));
+        lds9_put<LT>(lds, e0 + 3 * dq, ln::mul<LnField<FT255>>(ln::sub(b2, b3), w2));
       }
       __syncthreads();
       continue;
     }
-    const L9 x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
-    const L9 x2 = lds9_get<LT>(lds, e0 + 2 * dq), x3 = lds9_get<LT>(lds, e0 + 3 * dq);
-    const L9 b0 = l9::add(x0, x2), b1 = l9::add(x1, x3);
-    L9 c0 = l9::add(b0, b1);                                 // limbs [0, 2^31), |value| < 16p
+    const LN<9> x0 = lds9_get<LT>(lds, e0), x1 = lds9_get<LT>(lds, e0 + dq);
+    const LN<9> x2 = lds9_get<LT>(lds, e0 + 2 * dq), x3 = lds9_get<LT>(lds, e0 + 3 * dq);
+    const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);
+    LN<9> c0 = ln::add(b0, b1);                                 // limbs [0, 2^31), |value| < 16p
     if (last_two) {
-      l9::normalize(c0);
-      const Fe29 wq = tw29(a.roots29, 1u << (k - 2));
-      L9 c1 = l9::sub(b0, b1);
-      const L9 b2 = l9::sub(x0, x2);
-      const L9 b3 = l9::mul(l9::sub(x1, x3), wq);
-      L9 c2 = l9::add(b2, b3);
-      L9 c3 = l9::sub(b2, b3);
-      l9::normalize(c1); l9::normalize(c2); l9::normalize(c3);
+      ln::normalize<LnField<FT255>>(c0);
+      const LN<9> wq = tw29(a.roots29, 1u << (k - 2));
+      LN<9> c1 = ln::sub(b0, b1);
+      const LN<9> b2 = ln::sub(x0, x2);
+      const LN<9> b3 = ln::mul<LnField<FT255>>(ln::sub(x1, x3), wq);
+      LN<9> c2 = ln::add(b2, b3);
+      LN<9> c3 = ln::sub(b2, b3);
+      ln::normalize<LnField<FT255>>(c1); ln::normalize<LnField<FT255>>(c2); ln::normalize<LnField<FT255>>(c3);
       lds9_put<LT>(lds, e0, c0);
       lds9_put<LT>(lds, e0 + dq, c1);
       lds9_put<LT>(lds, e0 + 2 * dq, c2);
@@ -443,19 +443,19 @@ __global__ void __launch_bounds__(256, 4) v2_kernel(NttPassArgs a, const u32* __
       }
       const bool blk0c = canon && blk0_tile && q < period;
       const u32 vb = blk0c ? 3u : 0u;
-      const Fe29 w0 = pk_load(blk, period, vb + 0, jl), w1 = pk_load(blk, period, vb + 1, jl);
-      const Fe29 w2 = pk_load(blk, period, 2, jl);
-      const L9 d1 = l9::sub(b0, b1);
-      L9 c1;
-      if (blk0c) c1 = l9::mul(d1, pk_load(blk, period, 5, jl));
-      else c1 = l9::mul(d1, w2);
+      const LN<9> w0 = pk_load(blk, period, vb + 0, jl), w1 = pk_load(blk, period, vb + 1, jl);
+      const LN<9> w2 = pk_load(blk, period, 2, jl);
+      const LN<9> d1 = ln::sub(b0, b1);
+      LN<9> c1;
+      if (blk0c) c1 = ln::mul<LnField<FT255>>(d1, pk_load(blk, period, 5, jl));
+      else c1 = ln::mul<LnField<FT255>>(d1, w2);
       lds9_put<LT>(lds, e0 + dq, c1);
-      const L9 b2 = l9::mul(l9::sub(x0, x2), w0);
-      const L9 b3 = l9::mul(l9::sub(x1, x3), w1);
-      L9 c2 = l9::add(b2, b3);
-      l9::normalize(c2);
+      const LN<9> b2 = ln::mul<LnField<FT255>>(ln::sub(x0, x2), w0);
+      const LN<9> b3 = ln::mul<LnField<FT255>>(ln::sub(x1, x3), w1);
+      LN<9> c2 = ln::add(b2, b3);
+      ln::normalize<LnField<FT255>>(c2);
       lds9_put<LT>(lds, e0 + 2 * dq, c2);
-      lds9_put<LT>(lds, e0 + 3 * dq, l9::mul(l9::sub(b2, b3), w2));
+      lds9_put<LT>(lds, e0 + 3 * dq, ln::mul<LnField<FT255>>(ln::sub(b2, b3), w2));
       if constexpr (!(X & 1)) {
         l9x::clamp_apply(c0, nt);
         lds9_put<LT>(lds, e0, c0);
@@ -467,16 +467,16 @@ __global__ void __launch_bounds__(256, 4) v2_kernel(NttPassArgs a, const u32* __
 #pragma unroll
   for (u32 e = tid; e < T; e += 256) {
     const u32 g = gindex(e);
-    L9 x = lds9_get<LT>(lds, e);
+    LN<9> x = lds9_get<LT>(lds, e);
     // exact clamp (normalised input): [0, p + 2^239)
     l9x::clamp_apply(x, l9x::row_load(nqp, l9x::clamp_q(x.v[8])));
     u32 w[8];
-    fe_from29(w, x.v);
+    ln::to_packed<LnField<FT255>>(w, x.v);
     Fe<NL> v;
     if constexpr (LAST) {
       // [0, p + 2^239) -> [0, p): the clamp leaves value >= p only when the top limb reaches floor(p / 2^232), about one
       // element in 2^17 -- the conditional subtract runs for the (rare) waves that hold such an element
-      if (__any((int)(x.v[8] >= (u32)P29::limb(8)))) v = fe_reduce_once8(w);
+      if (__any((int)(x.v[8] >= LnField<FT255>::limb(8)))) v = fe_reduce_once<8>(w);
       else {
 #pragma unroll
         for (int i = 0; i < 8; i++) v.v[i] = w[i];
@@ -649,10 +649,10 @@ int main(int argc, char** argv) {
   check("v2 X=1");
   {
     // the library's specialised kernel (ntt_l9s.hip) through its own packs
-    const NttPackInfo qa = ntt_l9s_pack_info(8, true), qb = ntt_l9s_pack_info(10, false);
+    const NttPackInfo qa = ntt_lns_pack_info(8, 8, true), qb = ntt_lns_pack_info(8, 10, false);
     u32 *pa, *pb;
     CHECK(hipMalloc(&pa, (size_t)n_cls_A * qa.class_words * 4)); CHECK(hipMalloc(&pb, (size_t)qb.class_words * 4));
-    CHECK(launch_ntt_l9s_pack(B.pa, true, qa, n_cls_A, pa, nullptr)); CHECK(launch_ntt_l9s_pack(B.pb, false, qb, 1, pb, nullptr));
+    CHECK(launch_ntt_lns_pack(8, B.pa, true, qa, n_cls_A, pa, nullptr)); CHECK(launch_ntt_lns_pack(8, B.pb, false, qb, 1, pb, nullptr));
     CHECK(hipDeviceSynchronize());
     // (since round 6 the library's passes convert block 0 before their uniform rounds: no Montgomery prefix reaches the last store, the first
     // pass of 8 stages has left none -- blk0_gone -- and both take the shifted multiples of w^(n/4), which this lab does not build:

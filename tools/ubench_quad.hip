@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "field_dev.h"
+#include "field_ln.h"
 using namespace lcpc;
 #define CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e__), __LINE__); exit(1); } } while (0)
 #define ITERS 256
@@ -16,30 +16,30 @@ __global__ void __launch_bounds__(256, 4) quad_kernel(const u32* in, const u32* 
   for (u32 i = threadIdx.x; i < 64 * 12; i += 256) qp[i] = qp_g[i];
   __syncthreads();
   const u32 tid = blockIdx.x * 256 + threadIdx.x;
-  L9 x0, x1, x2, x3;
-  Fe29 w0, w1, w2;
+  LN<9> x0, x1, x2, x3;
+  LN<9> w0, w1, w2;
 #pragma unroll
   for (int k = 0; k < 9; k++) {
-    x0.v[k] = in[tid * 9 + k] & l9::M; x1.v[k] = in[(tid + 1) * 9 + k] & l9::M; x2.v[k] = in[(tid + 2) * 9 + k] & l9::M; x3.v[k] = in[(tid + 3) * 9 + k] & l9::M;
-    w0.v[k] = in[(tid + 4) * 9 + k] & l9::M; w1.v[k] = in[(tid + 5) * 9 + k] & l9::M; w2.v[k] = in[(tid + 6) * 9 + k] & l9::M;
+    x0.v[k] = in[tid * 9 + k] & ((1u << 29) - 1); x1.v[k] = in[(tid + 1) * 9 + k] & ((1u << 29) - 1); x2.v[k] = in[(tid + 2) * 9 + k] & ((1u << 29) - 1); x3.v[k] = in[(tid + 3) * 9 + k] & ((1u << 29) - 1);
+    w0.v[k] = in[(tid + 4) * 9 + k] & ((1u << 29) - 1); w1.v[k] = in[(tid + 5) * 9 + k] & ((1u << 29) - 1); w2.v[k] = in[(tid + 6) * 9 + k] & ((1u << 29) - 1);
   }
   x0.v[8] &= 0xfffff; x1.v[8] &= 0xfffff; x2.v[8] &= 0xfffff; x3.v[8] &= 0xfffff; w0.v[8] &= 0x3fffff; w1.v[8] &= 0x3fffff; w2.v[8] &= 0x3fffff;
   for (int it = 0; it < ITERS; it++) {
-    L9 b0, b1, c0, d1, e0, e1;
+    LN<9> b0, b1, c0, d1, e0, e1;
     if constexpr (MODE & M_ADDSUB) {
-      b0 = l9::add(x0, x2); b1 = l9::add(x1, x3); c0 = l9::add(b0, b1); d1 = l9::sub(b0, b1); e0 = l9::sub(x0, x2); e1 = l9::sub(x1, x3);
+      b0 = ln::add(x0, x2); b1 = ln::add(x1, x3); c0 = ln::add(b0, b1); d1 = ln::sub(b0, b1); e0 = ln::sub(x0, x2); e1 = ln::sub(x1, x3);
     } else { c0 = x0; d1 = x1; e0 = x2; e1 = x3; }
-    if constexpr (MODE & M_NORM) l9::normalize(c0);
-    if constexpr (MODE & M_CLAMP) l9::clamp(c0, qp);
-    L9 c1, b2, b3, c2, c3;
-    if constexpr (MODE & M_MUL) { c1 = l9::mul(d1, w2); b2 = l9::mul(e0, w0); b3 = l9::mul(e1, w1); }
+    if constexpr (MODE & M_NORM) ln::normalize<LnField<FT255>>(c0);
+    if constexpr (MODE & M_CLAMP) ln::clamp(c0, qp);
+    LN<9> c1, b2, b3, c2, c3;
+    if constexpr (MODE & M_MUL) { c1 = ln::mul<LnField<FT255>>(d1, w2); b2 = ln::mul<LnField<FT255>>(e0, w0); b3 = ln::mul<LnField<FT255>>(e1, w1); }
     else { c1 = d1; b2 = e0; b3 = e1; }
-    if constexpr (MODE & M_ADDSUB) { c2 = l9::add(b2, b3); c3 = l9::sub(b2, b3); } else { c2 = b2; c3 = b3; }
-    if constexpr (MODE & M_NORM) l9::normalize(c2);
-    if constexpr (MODE & M_MUL) c3 = l9::mul(c3, w2);
+    if constexpr (MODE & M_ADDSUB) { c2 = ln::add(b2, b3); c3 = ln::sub(b2, b3); } else { c2 = b2; c3 = b3; }
+    if constexpr (MODE & M_NORM) ln::normalize<LnField<FT255>>(c2);
+    if constexpr (MODE & M_MUL) c3 = ln::mul<LnField<FT255>>(c3, w2);
     if constexpr (!(MODE & M_NORM)) {      // keep limbs bounded without the carry pass (1 op per limb instead of 3)
 #pragma unroll
-      for (int k = 0; k < 9; k++) { c0.v[k] &= l9::M; c2.v[k] &= l9::M; }
+      for (int k = 0; k < 9; k++) { c0.v[k] &= ((1u << 29) - 1); c2.v[k] &= ((1u << 29) - 1); }
     }
     x0 = c0; x1 = c1; x2 = c2; x3 = c3;
   }
