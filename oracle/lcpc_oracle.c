@@ -275,6 +275,72 @@ int lo_fft_io(int fid, u64 *x, unsigned log_n) {
   free(roots);
   return 0;
 }
+/* a / 2 mod p of a fully reduced a (either form: halving is linear) */
+AINL void fhalf(u64 *a, const fld_t *f, const int L) {
+  u64 c = 0;
+  if (a[0] & 1) {
+    for (int i = 0; i < L; i++) {
+      u128 s = (u128)a[i] + f->p[i] + c;
+      a[i] = (u64)s;
+      c = (u64)(s >> 64);
+    }
+  }
+  for (int i = 0; i < L; i++) a[i] = (a[i] >> 1) | (i + 1 < L ? a[i + 1] << 63 : c << 63);
+}
+static void fpow_u64(u64 *o, const u64 *b, u64 e, const fld_t *f, const int L) {
+  u64 acc[MAXL], sq[MAXL];
+  fcopy(acc, f->r, L);
+  fcopy(sq, b, L);
+  for (; e; e >>= 1) {
+    if (e & 1) fmul(acc, acc, sq, f, L);
+    fmul(sq, sq, sq, f, L);
+  }
+  fcopy(o, acc, L);
+}
+AINL void dif_stage_L(u64 *x, u64 len, u64 gap, const u64 *b, int inverse, int nthreads, const fld_t *f, const int L) {
+  u64 *tw = malloc(gap * L * 8);
+  const u64 CH = 1024;
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+  for (u64 c = 0; c < (gap + CH - 1) / CH; c++) {
+    const u64 i0 = c * CH, i1 = i0 + CH < gap ? i0 + CH : gap;
+    fpow_u64(tw + i0 * L, b, i0, f, L);
+    for (u64 i = i0 + 1; i < i1; i++) fmul(tw + i * L, tw + (i - 1) * L, b, f, L);
+  }
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+  for (u64 j = 0; j < len / 2; j++) {
+    const u64 i = j % gap;
+    u64 *lo = x + ((j / gap) * 2 * gap + i) * L, *hi = lo + gap * L;
+    u64 t[MAXL];
+    if (inverse) {
+      fmul(t, hi, tw + i * L, f, L);
+      fsub(hi, lo, t, f, L);
+      fadd(lo, lo, t, f, L);
+      fhalf(lo, f, L);
+      fhalf(hi, f, L);
+    } else {
+      fsub(t, lo, hi, f, L);
+      fadd(lo, lo, hi, f, L);
+      fmul(hi, t, tw + i * L, f, L);
+    }
+  }
+  free(tw);
+}
+/* stage k of fft_io_L for a length-2^log_n transform (gap = 2^log_n >> (k + 1), lo' = lo + hi, hi' = (lo - hi) w^(2^k idx)), or
+ * its inverse, in place over len elements: consecutive blocks of 2 gap (a whole row, a prefix of one made of whole blocks, or
+ * many rows back to back).  Test infrastructure: the stage-input builder of tests/common.py. */
+int lo_dif_stage(int fid, u64 *x, u64 len, unsigned log_n, unsigned k, int inverse, int nthreads) {
+  const fld_t *f = getf(fid);
+  if (!f || log_n > f->S || k >= log_n) return LO_ERR_ARG;
+  const u64 gap = ((u64)1 << log_n) >> (k + 1);
+  if (len % (2 * gap)) return LO_ERR_ARG;
+  const int L = f->L;
+  u64 b[MAXL];                                   /* w^(2^k), of order 2 gap; its inverse is its (2 gap - 1)-th power */
+  fcopy(b, f->rou, L);
+  for (unsigned i = 0; i < f->S - log_n + k; i++) fmul(b, b, b, f, L);
+  if (inverse) fpow_u64(b, b, 2 * gap - 1, f, L);
+  DISPATCH_L(f, dif_stage_L(x, len, gap, b, inverse, nthreads > 0 ? nthreads : 1, f, L));
+  return 0;
+}
 
 /* ======================================================================
  * BLAKE3 (plain hash mode) [3P] -- the D: Digest of every reference test

@@ -46,6 +46,8 @@ void lo_f_from_u64(int fid, const uint64_t *v, uint64_t *out, size_t n);
 /* ---- NTT (fffft fft_io_pc) ---- */
 int  lo_roots_table(int fid, unsigned log_n, uint64_t *out /* max(1,n/2) * L */);
 int  lo_fft_io(int fid, uint64_t *x, unsigned log_n);
+/* one DIF stage k of lo_fft_io's transform, or its inverse, over len elements (whole blocks of 2^(log_n - k)) */
+int  lo_dif_stage(int fid, uint64_t *x, uint64_t len, unsigned log_n, unsigned k, int inverse, int nthreads);
 
 /* ---- hashes / rng ---- */
 void lo_blake3(const uint8_t *in, size_t len, uint8_t out[32]);

@@ -182,3 +182,177 @@ def row_with_stage_input(fid, log_n, s, pattern):
     for k in range(s - 1, 0, -1):
         _butterflies(x, n, n >> (k + 1), w, p, True)
     return x
+
+
+def stage_input_rows(fid, log_n, stages, pattern, log_rate=1, n_threads=16):
+    """row_with_stage_input, vectorised and at any rate 2^-log_rate: (len(stages), n >> log_rate, L) limbs, row j the free prefix
+    x of a row (x, 0, ..., 0) whose values entering DIF stage stages[j] equal `pattern` (repeated) on the first n >> log_rate
+    entries.  Stages 0 .. log_rate - 1 work in blocks of more than n >> log_rate and leave that prefix as it was (its partners
+    are zero); from stage log_rate on the prefix is a union of whole blocks that never meets the rest of the row again.  So for
+    s <= log_rate the prefix is the pattern, and for s > log_rate it is the pattern taken back through the inverse of stages
+    s - 1 .. log_rate (oracle lo_dif_stage: one call per stage over every row that still needs it, rows by falling s)."""
+    import oracle_lib as O
+    L, m = FIELD_L[fid], (1 << log_n) >> log_rate
+    stages = list(stages)
+    assert all(0 <= s < log_n for s in stages) and m % len(pattern) == 0
+    order = sorted(range(len(stages)), key=lambda j: -stages[j])
+    rows = np.empty((len(stages), m, L), np.uint64)
+    rows[:] = np.tile(to_limbs(pattern, L), (m // len(pattern), 1))
+    for k in range(max(stages) - 1, log_rate - 1, -1):
+        cnt = sum(1 for s in stages if s > k)
+        assert O.lib().lo_dif_stage(fid, O.ptr(rows), cnt * m, log_n, k, 1, n_threads) == 0
+    out = np.empty_like(rows)
+    out[order] = rows
+    return out
+
+
+# ---- the row-NTT plan, restated (lcpc_amd/csrc/ctx.cpp plan_passes, build_limb_plan, ntt_mid_rows; kernels.h *_supported) -------------
+NTT_NL = {0: 2, 1: 4, 2: 6, 3: 8}
+FIELD_BITS = {0: 63, 1: 127, 2: 191, 3: 255}
+
+
+def general_passes(fid, log_n, general=False):
+    """plan_passes: the general kernel's passes as (t0, stages, log_tj, log_tile)"""
+    k, NL = log_n, NTT_NL[fid]
+    lt_small = 10 if NL >= 6 else (11 if NL == 4 else 12)
+    lt_big = 11 if NL >= 6 else 12
+    ltj_min = 0
+    while (NL * 4 << ltj_min) < 128:
+        ltj_min += 1
+    if k <= lt_small:
+        return [(0, k, 0, lt_small)]
+
+    def n_pass(lt):
+        return 1 + -(-(k - lt) // (lt - ltj_min))
+
+    if fid == 3 and k in (19, 20) and not general:
+        return [(0, k - 10, 20 - k, 10), (k - 10, 10, 0, 10)]
+    LT = lt_big if n_pass(lt_small) > 2 and n_pass(lt_big) < n_pass(lt_small) else lt_small
+    P, rem, t0, out = n_pass(LT), k - LT, 0, []
+    for i in range(P - 1):
+        s = -(-rem // (P - 1 - i))
+        out.append((t0, s, LT - s, LT))
+        t0, rem = t0 + s, rem - s
+    return out + [(t0, LT, 0, LT)]
+
+
+def ntt_mid_rows(fid, log_n, n_passes, n_rows, mid_mb=None):
+    """rows per batch of K1s's 36-byte limb intermediate (0: packed intermediate); mid_mb is LCPC_NTT_MID_MAX_MB (None: unset)"""
+    if n_passes != 2 or fid != 3 or n_rows == 0 or (mid_mb is None and log_n > 15):
+        return 0
+    max_mb = 6144 if mid_mb is None else mid_mb
+    fit = (max_mb << 20) // ((1 << log_n) * 36)
+    if max_mb == 0 or fit == 0:
+        return 0
+    if fit >= n_rows:
+        return n_rows
+    batches = -(-n_rows // fit)
+    return -(-n_rows // batches)
+
+
+def ntt_plan(fid, log_n, general=False, mid_mb=None, n_rows=1):
+    """the passes a Ligero encoder of 2^log_n columns launches: dicts with kernel ("K1s", "K1n" or "general"), t0 / s (the stages
+    [t0, t0 + s) of the whole row), first (the first-pass template), mid (rows per limb-intermediate batch, 0 = packed) and
+    blk0_gone (canonical output: block 0 converted by the pass before)"""
+    gp = general_passes(fid, log_n, general)
+    n_pass = 0
+    if not general:
+        if fid == 3:
+            n_pass = 2 if len(gp) == 2 and gp[0][3] == 10 and 11 <= log_n <= 20 else 3 if 21 <= log_n <= 26 else 0
+        elif len(gp) >= 2:
+            n_pass = 2 if 11 <= log_n <= 20 else 3 if 21 <= log_n <= 26 else 0
+    if not n_pass:
+        return [dict(kernel="general", t0=t0, s=s, first=i + 1 < len(gp), mid=0, blk0_gone=False, n_pass=len(gp))
+                for i, (t0, s, _, _) in enumerate(gp)]
+    s0 = log_n - 10 * (n_pass - 1)
+    mid = ntt_mid_rows(fid, log_n, n_pass, n_rows, mid_mb)
+    out = []
+    for i in range(n_pass):
+        last = i + 1 == n_pass
+        s = s0 if i == 0 else 10
+        out.append(dict(kernel="K1s" if fid == 3 else "K1n", t0=0 if i == 0 else s0 + 10 * (i - 1), s=s, first=not last, mid=mid,
+                        blk0_gone=last and NTT_NL[fid] != 2 and out[i - 1]["s"] >= 8, n_pass=n_pass))
+    return out
+
+
+def ntt_instantiations(fid, plan, log_n):
+    """the kernel instantiations a plan reaches, by name"""
+    ft, names = "ft%d" % FIELD_BITS[fid], set()
+    for i, p in enumerate(plan):
+        if p["kernel"] == "general":
+            names.add("general-%dpass-%s-2^%d" % (p["n_pass"], ft, log_n) if p["n_pass"] == 1 else "general-%s" % ft)
+            continue
+        k = "K1s" if fid == 3 else "K1n-" + ft
+        mid = "-mid%d" % bool(p["mid"]) if fid == 3 else ""
+        if p["first"]:
+            names.add("%s-first-S%d%s" % (k, p["s"], mid))
+            if i == 0 and p["n_pass"] == 3:
+                names.add("3pass-%s-first-S%d" % (ft, p["s"]))
+        else:
+            names.add("%s-last%s-blk0%s" % (k, mid, "gone" if p["blk0_gone"] else "kept"))
+    return names
+
+
+def ntt_required_instantiations():
+    """what the row-NTT worst-case matrix must reach (tests/test_gpu_lazy_worst.py NTT_CASES)"""
+    req = {"K1s-first-S%d-mid%d" % (s, m) for s in range(1, 11) for m in (0, 1)}
+    req |= {"K1s-last-mid%d-blk0%s" % (m, g) for m in (0, 1) for g in ("gone", "kept")}
+    for fid in (0, 1, 2):
+        req |= {"K1n-ft%d-first-S%d" % (FIELD_BITS[fid], s) for s in range(1, 11)}
+    for fid in (1, 2):
+        req |= {"K1n-ft%d-last-blk0%s" % (FIELD_BITS[fid], g) for g in ("gone", "kept")}
+    req |= {"3pass-ft%d-first-S%d" % (FIELD_BITS[fid], s) for fid in range(4) for s in (1, 2)}
+    for fid in range(4):
+        k = max(k for k in range(1, 27) if len(general_passes(fid, k)) == 1)
+        req.add("general-1pass-ft%d-2^%d" % (FIELD_BITS[fid], k))
+    return req
+
+
+# ---- the shape matrix of tests/test_gpu_lazy_worst.py::test_ntt_extremes_at_every_stage ----------------------------------------------
+FIRST_TWO_PASS = {0: 13, 1: 12, 2: 11, 3: 11}      # smallest log2 n_cols with a two-pass plan, per field
+# the 13 shapes the test started with (fid, log_n, LCPC_NTT_GENERAL), kept with their ids
+NTT_LEGACY = [(3, 12, False), (3, 13, False), (3, 14, False), (3, 13, True), (0, 13, False), (0, 14, False), (0, 13, True),
+              (1, 12, False), (1, 14, False), (1, 12, True), (2, 11, False), (2, 14, False), (2, 11, True)]
+
+
+def ntt_worst_cases():
+    """(fid, log_n, log_rate, LCPC_NTT_GENERAL, LCPC_NTT_MID_MAX_MB or None): the legacy shapes; every two-pass size to 2^20 (Ft255
+    with the limb intermediate off and forced on, 64 MiB: row batches from 2^17 on); the three-pass plans at 2^21 / 2^22; each
+    field's largest one-pass plan; the general kernel forced at 2^18 / 2^21 (Ft255, Ft127); rate 1/4 at 2^18 (Ft255) / 2^16 (Ft127)"""
+    cases = [(f, k, 1, g, None) for f, k, g in NTT_LEGACY]
+    for fid in (3, 0, 1, 2):
+        for k in range(FIRST_TWO_PASS[fid], 21):
+            if fid == 3:
+                cases += [(3, k, 1, False, 0), (3, k, 1, False, 64)]
+            elif (fid, k, False) not in NTT_LEGACY:
+                cases.append((fid, k, 1, False, None))
+    cases += [(fid, k, 1, False, None) for fid in (3, 0, 1, 2) for k in (21, 22)]
+    cases += [(fid, max(k for k in range(1, 27) if len(general_passes(fid, k)) == 1), 1, False, None) for fid in (3, 0, 1, 2)]
+    cases += [(fid, k, 1, True, None) for fid in (3, 1) for k in (18, 21)]
+    cases += [(3, 18, 2, False, None), (1, 16, 2, False, None)]
+    return cases
+
+
+def ntt_case_stages(fid, log_n, general=False):
+    """every stage up to 2^20 columns; above, stage 0, the last two, and each pass boundary t0 with its neighbours t0 +- 1
+    (three-pass limb plans: s0 and s0 + 10): what differs between the stages inside one pass is the round they fall in, and the
+    two-pass sizes already give every round of every pass template its crafted inputs"""
+    if log_n <= 20:
+        return list(range(log_n))
+    st = {0, log_n - 2, log_n - 1}
+    for p in ntt_plan(fid, log_n, general)[1:]:
+        st |= {p["t0"] - 1, p["t0"], p["t0"] + 1}
+    return sorted(st)
+
+
+def ntt_case_id(fid, log_n, log_rate, general, mid_mb):
+    if log_rate == 1 and mid_mb is None and (fid, log_n, general) in NTT_LEGACY:
+        return "ft%d-2^%d%s" % (fid, log_n, "-general" if general else "")
+    plan = ntt_plan(fid, log_n, general, mid_mb)
+    out = "ft%d-2^%d%s" % (FIELD_BITS[fid], log_n, "-r%d" % (1 << log_rate) if log_rate != 1 else "")
+    if plan[0]["kernel"] == "general":
+        return out + "-general-%dpass%s" % (len(plan), "-forced" if general else "")
+    out += "-S%d" % plan[0]["s"] + ("-3pass" if len(plan) == 3 else "")
+    if fid == 3:
+        out += "-mid%d" % bool(plan[0]["mid"]) + ("-mb%d" % mid_mb if mid_mb is not None else "")
+    return out + ("-blk0gone" if plan[-1]["blk0_gone"] else "")

@@ -41,6 +41,7 @@ def lib():
             "lo_f_from_u64": (None, [C.c_int, vp, vp, C.c_size_t]),
             "lo_roots_table": (C.c_int, [C.c_int, C.c_uint, vp]),
             "lo_fft_io": (C.c_int, [C.c_int, vp, C.c_uint]),
+            "lo_dif_stage": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_uint, C.c_uint, C.c_int, C.c_int]),
             "lo_blake3": (None, [vp, C.c_size_t, vp]),
             "lo_keccak_f1600": (None, [vp]),
             "lo_rng_from_seed": (vp, [vp]),

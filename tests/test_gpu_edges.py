@@ -181,13 +181,15 @@ def test_lazy_limb_ntt_range_stress(oracle):
     the range analysis of its multiplier and of a quotient-estimate clamp (field_ln.h, LnField<FT255>).  Inputs chosen to push every bound: rows of
     all p-1, all (p-1)/2, alternating 0 / p-1, and limbs with all 29-bit fields saturated -- at n_cols = 2^12 (one
     pass), 2^13 (two passes) and 2^18 (the headline row: 4+5 radix-4 rounds), rates 1/2 and 38/39 (n_per_row not a
-    power of two).  Bit-exact against the oracle."""
+    power of two); nearly full rows (38/39) at 2^19 / 2^20 (first passes of 9 / 10 stages, blk0_gone) and 2^21 (three passes),
+    where no zero half shapes the stage inputs.  Bit-exact against the oracle."""
     import pyref as P
     O = oracle
     F = P.FT255
     sat = sum(((1 << 29) - 1) << (29 * k) for k in range(9)) % F.p
     pats = [[F.p - 1], [(F.p - 1) // 2], [0, F.p - 1], [sat, F.p - 2, 1], [F.p - 1, F.p - 1, F.p - 1, 0]]
-    for log_n, n_per_row in ((12, 2048), (13, 4096), (13, 7983), (18, 131072)):
+    for log_n, n_per_row in ((12, 2048), (13, 4096), (13, 7983), (18, 131072), (19, (1 << 19) * 38 // 39), (20, (1 << 20) * 38 // 39),
+                             (21, (1 << 21) * 38 // 39)):
         n = 1 << log_n
         enc = LigeroEncoding.new_from_dims(3, n_per_row, n)
         oenc = O.Encoding.ligero_from_dims(3, n_per_row, n)

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import lcpc_amd
-from common import field_p, maxc, maxt, mk_transcript, ntt_maxlimb, ntt_root, row_with_stage_input, to_int, to_limbs
+from common import (field_p, maxc, maxt, mk_transcript, ntt_case_id, ntt_case_stages, ntt_maxlimb, ntt_root, ntt_worst_cases,
+                    stage_input_rows, to_int, to_limbs)
 from lcpc_amd import LcCommit, LigeroEncoding, SdigEncoding, Transcript
 
 pytestmark = pytest.mark.gpu
@@ -269,56 +270,94 @@ def _ntt_patterns(fid):
     return {"p-1": [p - 1], "0/p-1": [0, p - 1], "maxlimb": [ntt_maxlimb(fid)]}
 
 
-NTT_SHAPES = [(3, 12, False), (3, 13, False), (3, 14, False), (3, 13, True),
-              (0, 13, False), (0, 14, False), (0, 13, True), (1, 12, False), (1, 14, False), (1, 12, True),
-              (2, 11, False), (2, 14, False), (2, 11, True)]
+def _ntt_stage_batches(fid, log_n, log_rate, stages, max_bytes=512 << 20):
+    """(tags, rows) batches of the stage-input rows, pattern by pattern, stage by stage; no batch's codewords exceed max_bytes"""
+    L, n = _L(fid), 1 << log_n
+    per = max(1, max_bytes // (n * L * 8))
+    tags, buf = [], []
+    for name, pat in _ntt_patterns(fid).items():
+        rows = stage_input_rows(fid, log_n, stages, pat, log_rate)
+        for s, row in zip(stages, rows):
+            tags.append((name, s))
+            buf.append(row)
+            if len(buf) == per:
+                yield tags, np.stack(buf)
+                tags, buf = [], []
+        del rows
+    if buf:
+        yield tags, np.stack(buf)
 
 
-@pytest.mark.parametrize("fid,log_n,general", NTT_SHAPES,
-                         ids=["ft%d-2^%d%s" % (f, l, "-general" if g else "") for f, l, g in NTT_SHAPES])
-def test_ntt_extremes_at_every_stage(oracle, fid, log_n, general):
-    """Rate-1/2 rows built so that the values entering DIF stage s (oracle/lcpc_oracle.c fft_io_L: natural in, bit-reversed out,
+def _ints(row):
+    b, L = row.tobytes(), row.shape[-1]
+    return [int.from_bytes(b[8 * L * i:8 * L * (i + 1)], "little") for i in range(row.shape[0])]
+
+
+NTT_CASES = ntt_worst_cases()
+
+
+@pytest.mark.parametrize("fid,log_n,log_rate,general,mid_mb", NTT_CASES, ids=[ntt_case_id(*c) for c in NTT_CASES])
+def test_ntt_extremes_at_every_stage(oracle, fid, log_n, log_rate, general, mid_mb):
+    """Rows built so that the values entering DIF stage s (oracle/lcpc_oracle.c fft_io_L: natural in, bit-reversed out,
     w = ROOT^(2^(S - log n)); restated in tests/common.py dif_stage) are a pattern P -- all p - 1, alternating 0 / p - 1, or the element
-    with every low limb of the NTT's limb form at 2^W - 1 -- for every s in [0, log n).  The zero half of a rate-1/2 row fixes the second
-    half of every stage's input (x w^i after stage 0), so P holds on the first half: 1/2 of the stage-s inputs carry it, every stage,
-    including the pass boundary and the register-fed last round.  Kernels: ntt_l9s.hip (Ft255, signed 29-bit lazy limbs, |v| < 4p
-    between rounds) / ntt_lns.hip (Ft63 / Ft127 / Ft191), or the general kernel of kernels.hip with LCPC_NTT_GENERAL=1; all shapes
-    here are two-pass plans.  Every row through encode (Montgomery output) and commit (canonical-output path + hashes) against the
-    oracle, and 16 sampled columns of two rows against the definition sum_i c_i w^(i bitrev(j)) mod p in Python ints."""
+    with every low limb of the NTT's limb form at 2^W - 1.  A rate-2^-r row (x, 0, ..., 0) keeps its free prefix x through stages
+    0 .. r - 1, and from stage r on that prefix never meets the rest of the row (tests/common.py stage_input_rows), so P holds on
+    the first n / 2^r inputs of stage s: every stage up to 2^20 columns, including the pass boundaries and the register-fed last
+    round; above (three-pass plans, the forced general kernel at 2^21) stage 0, the last two and each pass boundary with its
+    neighbours (tests/common.py ntt_case_stages).  The shapes (tests/common.py ntt_worst_cases; the id names the instantiation:
+    first-pass stages S, three-pass plan, K1s's limb intermediate and LCPC_NTT_MID_MAX_MB, blk0_gone of the canonical-output last
+    pass) take every first-pass template of ntt_l9s.hip (K1s, Ft255) and ntt_lns.hip (K1n, Ft63 / Ft127 / Ft191), both last-pass
+    variants, the three-pass plans, the one-pass general plan, and the general kernel of kernels.hip (LCPC_NTT_GENERAL=1);
+    tests/test_lazy_bounds.py::test_ntt_worst_cases_reach_every_instantiation checks that.  Rows go in batches of at most 512 MiB
+    of codewords (a ragged row count: one row per stage).  Every row through encode (Montgomery output) against the oracle's
+    encoding of it, and commit (canonical-output path: comm, hashes, root) against the oracle's commit; sampled columns of two rows
+    against the definition sum_i c_i w^(i bitrev(j)) mod p in Python ints."""
     import os
     O = oracle
     p, L, n = _p(fid), _L(fid), 1 << log_n
-    npr = n // 2
-    rows, tags = [], []
-    for name, pat in _ntt_patterns(fid).items():
-        for s in range(log_n):
-            rows.append(row_with_stage_input(fid, log_n, s, pat))
-            tags.append((name, s))
-    msg = to_limbs([v for r in rows for v in r], L)
-    if general:
-        os.environ["LCPC_NTT_GENERAL"] = "1"
+    npr = n >> log_rate
+    rho = (1, 1 << log_rate)
+    what = ntt_case_id(fid, log_n, log_rate, general, mid_mb)
+    stages = ntt_case_stages(fid, log_n, general)
+    env = {"LCPC_NTT_GENERAL": "1"} if general else {}
+    if mid_mb is not None:
+        env["LCPC_NTT_MID_MAX_MB"] = str(mid_mb)
+    os.environ.update(env)
     try:
-        enc = LigeroEncoding.new_from_dims(fid, npr, n)
+        enc = LigeroEncoding.new_from_dims(fid, npr, n, rho=rho)
     finally:
-        os.environ.pop("LCPC_NTT_GENERAL", None)
-    oenc = O.Encoding.ligero_from_dims(fid, npr, n)
-    padded = np.zeros((len(rows), n, L), np.uint64)
-    padded[:, :npr] = msg.reshape(len(rows), npr, L)
-    got = enc.encode(padded).reshape(len(rows), n, L)
-    for i in range(len(rows)):
-        assert (got[i] == oenc.encode(padded[i].copy())).all(), tags[i]
-    c = LcCommit.commit(msg, enc)
-    oc = O.Commit.commit(msg, oenc, n_threads=8)
-    assert (c.comm().reshape(len(rows), n, L) == got).all()
-    assert (c.hashes() == oc.hashes()).all() and c.get_root() == oc.get_root()
+        for k in env:
+            os.environ.pop(k, None)
+    oenc = O.Encoding.ligero_from_dims(fid, npr, n, rho=rho)
+    probe = {("maxlimb", stages[-1]), ("p-1", stages[len(stages) // 2])}
+    kept = {}
+    for tags, rows in _ntt_stage_batches(fid, log_n, log_rate, stages):
+        nb = len(tags)
+        msg = rows.reshape(-1, L)
+        oc = O.Commit.commit(msg, oenc, n_threads=16)
+        want = oc.comm().reshape(nb, n, L)
+        padded = np.zeros((nb, n, L), np.uint64)
+        padded[:, :npr] = rows
+        got = enc.encode(padded).reshape(nb, n, L)
+        del padded
+        for i in range(nb):
+            assert (got[i] == want[i]).all(), (what, "encode", tags[i])
+        for i, t in enumerate(tags):
+            if t in probe:
+                kept[t] = (_ints(rows[i]), got[i].copy())
+        del got
+        c = LcCommit.commit(msg, enc)
+        assert (c.comm().reshape(nb, n, L) == want).all(), (what, "commit", tags)
+        assert (c.hashes() == oc.hashes()).all() and c.get_root() == oc.get_root(), (what, "hashes", tags)
+        del c, oc, want
     # the definition, independent of the oracle and of pyref
     w = ntt_root(fid, log_n)
     rnd = random.Random(log_n * 10 + fid)
-    cols = [0, 1, n - 1] + [rnd.randrange(n) for _ in range(13)]
-    for i in (tags.index(("maxlimb", log_n - 1)), tags.index(("p-1", log_n // 2))):
+    cols = [0, 1, n - 1] + [rnd.randrange(n) for _ in range(13 if log_n <= 16 else 1)]
+    for t, (x, out) in sorted(kept.items()):
         for j in cols:
             wj = pow(w, int(format(j, "0%db" % log_n)[::-1], 2), p)
             acc = 0
-            for v in reversed(rows[i]):
+            for v in reversed(x):
                 acc = (acc * wj + v) % p
-            assert to_int(got[i, j]) == acc, (tags[i], j)
+            assert to_int(out[j]) == acc, (what, t, j)

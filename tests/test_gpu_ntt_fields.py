@@ -92,7 +92,9 @@ def test_lazy_limb_range_stress_small_fields(oracle, fid):
     sat = sum(((1 << W) - 1) << (W * k) for k in range(N)) % F.p
     pats = [[F.p - 1], [(F.p - 1) // 2], [0, F.p - 1], [sat, F.p - 2, 1], [F.p - 1, F.p - 1, F.p - 1, 0]]
     k0 = FIRST_TWO_PASS[fid]
-    for log_n, n_per_row in ((k0, 1 << (k0 - 1)), (k0 + 1, (1 << (k0 + 1)) * 38 // 39), (16, 1 << 15), (17, 1 << 16)):
+    # nearly full rows (38/39) up to the three-pass plan at 2^21, where no zero half shapes the stage inputs
+    for log_n, n_per_row in ((k0, 1 << (k0 - 1)), (k0 + 1, (1 << (k0 + 1)) * 38 // 39), (16, 1 << 15), (17, 1 << 16),
+                             (18, (1 << 18) * 38 // 39), (19, (1 << 19) * 38 // 39), (20, (1 << 20) * 38 // 39), (21, (1 << 21) * 38 // 39)):
         n = 1 << log_n
         enc = LigeroEncoding.new_from_dims(fid, n_per_row, n, rho=(38, 39) if n_per_row > n // 2 else (1, 2))
         oenc = O.Encoding.ligero_from_dims(fid, n_per_row, n, rho=(38, 39) if n_per_row > n // 2 else (1, 2))

@@ -387,3 +387,87 @@ def test_dif_stage_restatement_and_stage_inputs(fid):
             for k in range(s):
                 CM.dif_stage(row, k, w, p)
             assert all(row[i] == pat[i % len(pat)] for i in range(n // 2)), s
+
+
+@pytest.mark.parametrize("fid", [0, 1, 2, 3])
+@pytest.mark.parametrize("log_n", [10, 11, 12])
+def test_stage_input_builder(fid, log_n):
+    """tests/common.py stage_input_rows (one oracle lo_dif_stage call per stage over all rows) equals row_with_stage_input at rate
+    1/2 for every stage and pattern; at rates 1/2 and 1/4 the forward stages 0 .. s-1 of its row (free prefix, zeros after) put
+    the pattern on the free prefix"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import common as CM
+    p, n, L = CM.field_p(fid), 1 << log_n, CM.FIELD_L[fid]
+    w = CM.ntt_root(fid, log_n)
+    for pat in ([p - 1], [0, p - 1], [CM.ntt_maxlimb(fid)]):
+        for log_rate in (1, 2):
+            m = n >> log_rate
+            rows = CM.stage_input_rows(fid, log_n, range(log_n), pat, log_rate)
+            assert rows.shape == (log_n, m, L)
+            for s in range(log_n):
+                x = [CM.to_int(v) for v in rows[s]]
+                if log_rate == 1:
+                    assert x == CM.row_with_stage_input(fid, log_n, s, pat), (pat, s)
+                row = x + [0] * (n - m)
+                for k in range(s):
+                    CM.dif_stage(row, k, w, p)
+                assert all(row[i] == pat[i % len(pat)] for i in range(m)), (pat, log_rate, s)
+
+
+@pytest.mark.parametrize("fid", [0, 1, 2, 3])
+def test_dif_stages_compose_to_the_oracle_ntt(fid):
+    """lo_dif_stage over stages 0 .. log n - 1 is lo_fft_io at 2^16 (a random row and two rows at once), and the inverse stages
+    in reverse order give the row back"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import oracle_lib as O
+    import numpy as np
+    log_n, n = 16, 1 << 16
+    x = O.random_elems(fid, 2 * n, 77 + fid)
+    want = x.copy()
+    for r in range(2):
+        O.lib().lo_fft_io(fid, O.ptr(want[r * n:]), log_n)
+    y = x.copy()
+    for k in range(log_n):
+        assert O.lib().lo_dif_stage(fid, O.ptr(y), 2 * n, log_n, k, 0, 4) == 0
+    assert (y == want).all()
+    for k in range(log_n - 1, -1, -1):
+        assert O.lib().lo_dif_stage(fid, O.ptr(y), 2 * n, log_n, k, 1, 4) == 0
+    assert (y == x).all()
+    assert O.lib().lo_dif_stage(fid, O.ptr(y), n // 2 + 1, log_n, 1, 0, 1) != 0     # not whole blocks
+
+
+def test_ntt_worst_cases_reach_every_instantiation():
+    """the shape matrix of test_gpu_lazy_worst.test_ntt_extremes_at_every_stage, through the restated plan choice (tests/common.py
+    ntt_plan: ctx.cpp plan_passes, build_limb_plan, ntt_mid_rows, kernels.h *_supported), launches every first-pass template
+    S = 1 .. 10 of K1s (limb intermediate on and off) and of K1n (Ft63, Ft127, Ft191), both last-pass variants (blk0_gone, and the
+    limb intermediate for K1s), the three-pass first passes S = 1, 2 of every field and each field's one-pass general plan"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import common as CM
+    cases = CM.ntt_worst_cases()
+    ids = [CM.ntt_case_id(*c) for c in cases]
+    assert len(set(ids)) == len(ids)
+    assert [c for c in cases if c[2] == 1 and c[4] is None and (c[0], c[1], c[3]) in CM.NTT_LEGACY] == \
+        [(f, k, 1, g, None) for f, k, g in CM.NTT_LEGACY]
+    reached = set()
+    for fid, log_n, log_rate, general, mid_mb in cases:
+        reached |= CM.ntt_instantiations(fid, CM.ntt_plan(fid, log_n, general, mid_mb), log_n)
+    missing = sorted(CM.ntt_required_instantiations() - reached)
+    assert not missing, "not reached: %s" % missing
+
+
+def test_ntt_plan_restatement():
+    """spot values of the restated plan choice: FIRST_TWO_PASS matches plan_passes, K1s at 2^19 / 2^20 keeps two passes on
+    1024-element tiles (the general kernel takes 2048), the limb intermediate is on by default only up to 2^15 and LCPC_NTT_MID_MAX_MB=64 batches
+    rows from 2^17 on, blk0_gone from a first pass of 8 stages (not for Ft63), three passes of s0, 10, 10 stages from 2^21"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import common as CM
+    for fid, k0 in CM.FIRST_TWO_PASS.items():
+        assert len(CM.general_passes(fid, k0 - 1)) == 1 and len(CM.general_passes(fid, k0)) == 2
+    assert CM.general_passes(3, 20) == [(0, 10, 0, 10), (10, 10, 0, 10)] and CM.general_passes(3, 20, True) == [(0, 9, 2, 11), (9, 11, 0, 11)]
+    assert [CM.ntt_plan(3, k)[0]["mid"] > 0 for k in (15, 16)] == [True, False]
+    assert CM.ntt_mid_rows(3, 16, 2, 16, 64) == 16 and CM.ntt_mid_rows(3, 17, 2, 17, 64) == 9 and CM.ntt_mid_rows(3, 18, 2, 18, 64) == 6 and CM.ntt_mid_rows(3, 20, 2, 3, 64) == 1
+    assert CM.ntt_mid_rows(3, 13, 2, 5, 0) == 0
+    for fid in range(4):
+        assert [p["blk0_gone"] for p in CM.ntt_plan(fid, 17)] == [False, False]
+        assert [p["blk0_gone"] for p in CM.ntt_plan(fid, 18)] == [False, fid != 0]
+        assert [(p["t0"], p["s"], p["first"]) for p in CM.ntt_plan(fid, 22)] == [(0, 2, True), (2, 10, True), (12, 10, False)]
