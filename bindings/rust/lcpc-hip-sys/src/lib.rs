@@ -21,9 +21,12 @@ pub const LCPC_FT255: u32 = 3;
 // encodings: lcpc-ligero-pc/src/lib.rs:31-37 (LigeroEncodingRho), lcpc-brakedown-pc/src/lib.rs:41-47 (SdigEncodingS)
 pub const LCPC_ENC_LIGERO: u32 = 0;
 pub const LCPC_ENC_SDIG: u32 = 1;
-// D: Digest -- every reference test uses blake3::Hasher; sha3::Sha3_256 is the other 32-byte digest the reference benchmarks
+// D: Digest -- every reference test uses blake3::Hasher; the reference also benchmarks sha3::Sha3_256 (32 bytes) and blake2::Blake2b (64 bytes)
 pub const LCPC_HASH_BLAKE3: u32 = 0;
 pub const LCPC_HASH_SHA3_256: u32 = 1;
+pub const LCPC_HASH_BLAKE2B: u32 = 2;
+// the longest Output<D> (BLAKE2b, 64 bytes): every root / path / hashes buffer holds the encoder's digest length
+pub const LCPC_DIGEST_LEN_MAX: u32 = 64;
 
 // lcpc_status
 pub const LCPC_OK: c_int = 0;

@@ -55,19 +55,28 @@ enum { LCPC_FT63 = 0, LCPC_FT127 = 1, LCPC_FT191 = 2, LCPC_FT255 = 3 };
 /* encodings: lcpc-ligero-pc/src/lib.rs:31-37 (LigeroEncodingRho), lcpc-brakedown-pc/src/lib.rs:41-47 (SdigEncodingS) */
 enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
 /* D: Digest of LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184).  Every reference test uses blake3::Hasher; the reference also
- * benchmarks sha3::Sha3_256.  Both have 32-byte outputs, so roots, paths and `hashes` keep their layout.
- * LCPC_HASH_SHA3_256 (FIPS 202 SHA3-256 of the same leaf and node messages), at each entry point:
- *  - lcpc_commit, lcpc_commit_device, lcpc_commit_from_parts, lcpc_commit_from_bincode: one Keccak sponge per column over the
- *    whole leaf message (sha3.hip; one permutation per 17 limbs), then one permutation per tree node.  The host-memory
- *    lcpc_commit hashes after the last row batch instead of behind each batch.  Measured on one MI355X at 2^26 Ft255
- *    coefficients (512 x 262144): column hash 3.97 ms and tree 0.22 ms, against 1.52 / 0.03 ms for BLAKE3;
- *  - lcpc_commit_from_bincode refuses (LCPC_ERR_COMMIT) a stream whose `hashes` were made with the other digest;
- *  - lcpc_prove, lcpc_open_columns, lcpc_collapse: unchanged (the transcript never sees D);
- *  - lcpc_verify: leaves and path folds with the encoder's digest; a proof made under the other digest fails with
- *    LCPC_VERR_COLUMN_PATH;
- *  - row sharding: lcpc_ctx_create returns LCPC_ERR_ARG for shard_count > 1 (a sponge cannot be split by rows), and the
- *    sharded commit entry points return LCPC_ERR_ARG on a SHA3 encoder. */
-enum { LCPC_HASH_BLAKE3 = 0, LCPC_HASH_SHA3_256 = 1 };
+ * benchmarks sha3::Sha3_256 and blake2::Blake2b.  Every root, path entry and `hashes` slot holds the encoder's digest length:
+ * 32 bytes for LCPC_HASH_BLAKE3 and LCPC_HASH_SHA3_256, 64 bytes (LCPC_DIGEST_LEN_MAX) for LCPC_HASH_BLAKE2B.
+ *  - LCPC_HASH_BLAKE3 (default): chunked leaf hash (1 KiB chunks), one compression per tree node.
+ *  - LCPC_HASH_SHA3_256 (FIPS 202): one Keccak sponge per column over the whole leaf message (sha3.hip; one permutation per
+ *    17 limbs), then one permutation per tree node.  Measured on one MI355X at 2^26 Ft255 coefficients (512 x 262144): column
+ *    hash 3.97 ms and tree 0.22 ms, against 1.52 / 0.03 ms for BLAKE3.
+ *  - LCPC_HASH_BLAKE2B (RFC 7693 BLAKE2b-512, unkeyed): leaf = BLAKE2b(0^64 || to_repr(col[0]) || ...), node =
+ *    BLAKE2b(left64 || right64); one compression chain per column over the whole leaf message (blake2b.hip; one compression
+ *    per 16 limbs), one compression per tree node.  Measured at the same shape in DESIGN.md section 6.
+ * For SHA3-256 and BLAKE2b, at each entry point:
+ *  - lcpc_commit, lcpc_commit_device, lcpc_commit_from_parts, lcpc_commit_from_bincode: as above.  The host-memory lcpc_commit
+ *    hashes after the last row batch instead of behind each batch;
+ *  - lcpc_commit_from_bincode refuses (LCPC_ERR_COMMIT) a stream whose `hashes` were made with another digest (or whose
+ *    digest entries are not the encoder's length);
+ *  - lcpc_prove, lcpc_open_columns, lcpc_collapse: the transcript never sees D; path entries are the encoder's digest length;
+ *  - lcpc_verify: leaves and path folds with the encoder's digest; a proof made under another digest of the same length fails
+ *    with LCPC_VERR_COLUMN_PATH, one whose path entries have another length with LCPC_VERR_MALFORMED;
+ *  - row sharding: lcpc_ctx_create returns LCPC_ERR_ARG for shard_count > 1 (the chain cannot be split by rows), and the
+ *    sharded commit entry points return LCPC_ERR_ARG on such an encoder. */
+enum { LCPC_HASH_BLAKE3 = 0, LCPC_HASH_SHA3_256 = 1, LCPC_HASH_BLAKE2B = 2 };
+/* the longest Output<D> (BLAKE2b): a caller that serves every digest sizes root / path buffers with it */
+enum { LCPC_DIGEST_LEN_MAX = 64 };
 
 typedef enum {
   LCPC_OK = 0,
@@ -106,7 +115,7 @@ typedef struct lcpc_transcript lcpc_transcript;
 typedef struct {
   uint32_t field;        /* LCPC_FT* */
   uint32_t encoding;     /* LCPC_ENC_* */
-  uint32_t hash;         /* LCPC_HASH_BLAKE3 or LCPC_HASH_SHA3_256 */
+  uint32_t hash;         /* LCPC_HASH_BLAKE3, LCPC_HASH_SHA3_256 or LCPC_HASH_BLAKE2B */
   uint32_t rho_num, rho_den;  /* Ligero rate Rn/Rd (default alias 1/2: ligero lib.rs:189) */
   uint32_t sdig_code;    /* 1..6 = SdigCode1..6 (codespec.rs:169-232); default 3 (brakedown lib.rs:19) */
   uint64_t seed;         /* Brakedown matgen seed (brakedown lib.rs:103) */
@@ -167,7 +176,8 @@ int  lcpc_commit_create(lcpc_ctx *enc, lcpc_commit_t **out);
 void lcpc_commit_destroy(lcpc_commit_t *cm);
 const char *lcpc_commit_last_error(const lcpc_commit_t *cm);
 /* commit(coeffs, enc) (lib.rs:299-301 -> 622-671): pad, encode every row, hash columns, Merkleize.
- * comm / coeffs / hashes stay on the device.  `root` (32 bytes) may be NULL.  Returns after the work is complete. */
+ * comm / coeffs / hashes stay on the device.  `root` (the encoder's digest length: 32 bytes, 64 for LCPC_HASH_BLAKE2B) may be
+ * NULL.  Returns after the work is complete. */
 int  lcpc_commit(lcpc_commit_t *cm, const uint64_t *coeffs_host, uint64_t n_coeffs, uint8_t *root);
 /* same with the coefficients already resident in HBM (device pointer), work enqueued on `stream`;
  * if `root` is non-NULL the call synchronises the stream and copies the root out.
@@ -194,7 +204,7 @@ int  lcpc_commit_from_parts(lcpc_commit_t *cm, const uint64_t *comm_host, const 
  * hand a COMMITMENT to or from the reference (its fields are private; GPU commit -> reference prove, or a reference
  * commitment -> GPU prove):
  *   u64 len(comm) | comm: len x L u64 limbs (Montgomery form, row-major) | u64 len(coeffs) | coeffs | u64 n_rows | u64 n_cols |
- *   u64 n_per_row | u64 len(hashes) | len x (u64 32 | 32 digest bytes)
+ *   u64 n_per_row | u64 len(hashes) | len x (u64 D | D digest bytes), D = the encoder's digest length (32; BLAKE2b 64)
  * Streaming: 6 GiB at the headline never sits in one host buffer.  `write` receives consecutive pieces (<= 64 MiB each),
  * `read` must fill exactly `len` bytes; either returns 0 to go on, anything else aborts the call (LCPC_ERR_ARG).
  * lcpc_commit_from_bincode checks what check_comm (lib.rs:673-688) checks -- lengths against the dims and the encoder's
@@ -206,10 +216,11 @@ typedef int (*lcpc_read_fn)(void *user, uint8_t *data, uint64_t len);
 uint64_t lcpc_commit_bincode_size(const lcpc_commit_t *cm);             /* 0: nothing committed */
 int  lcpc_commit_bincode_write(lcpc_commit_t *cm, lcpc_write_fn write, void *user);
 int  lcpc_commit_from_bincode(lcpc_commit_t *cm, lcpc_read_fn read, void *user, uint8_t *root);
-int  lcpc_get_root(lcpc_commit_t *cm, uint8_t root[32]);                /* get_root lib.rs:276-281 */
+/* get_root lib.rs:276-281: the encoder's digest length into root (32 bytes; 64 for LCPC_HASH_BLAKE2B) */
+int  lcpc_get_root(lcpc_commit_t *cm, uint8_t root[32]);
 int  lcpc_commit_dims(const lcpc_commit_t *cm, uint64_t *n_rows, uint64_t *n_per_row, uint64_t *n_cols,
                       uint64_t *n_hashes);                               /* get_n_rows/.. lib.rs:283-296 */
-int  lcpc_get_hashes(lcpc_commit_t *cm, uint8_t *hashes);               /* LcCommit.hashes: (2*np2-1)*32 bytes */
+int  lcpc_get_hashes(lcpc_commit_t *cm, uint8_t *hashes);               /* LcCommit.hashes: (2*np2-1)*D bytes (D = 32; BLAKE2b 64) */
 int  lcpc_get_comm(lcpc_commit_t *cm, uint64_t row0, uint64_t n_rows, uint64_t *out);    /* LcCommit.comm rows (Montgomery form,
                                                                                              whatever the device keeps) */
 int  lcpc_get_coeffs(lcpc_commit_t *cm, uint64_t row0, uint64_t n_rows, uint64_t *out);  /* LcCommit.coeffs rows */
@@ -217,7 +228,7 @@ int  lcpc_get_coeffs(lcpc_commit_t *cm, uint64_t row0, uint64_t n_rows, uint64_t
 /* collapse_columns (lib.rs:1095-1123; test alias eval_outer lib.rs:1176-1202) for n_tensors tensors
  * of n_rows elements each, fused into one pass over coeffs: polys[t][j] = sum_r coeffs[r][j]*tensors[t][r]. */
 int  lcpc_collapse(lcpc_commit_t *cm, const uint64_t *tensors_host, uint32_t n_tensors, uint64_t *polys_host);
-/* open_column (lib.rs:788-825) for n columns: col_vals[n][n_rows][L], paths[n][path_len][32],
+/* open_column (lib.rs:788-825) for n columns: col_vals[n][n_rows][L], paths[n][path_len][D] (D = the encoder's digest length),
  * path_len = ceil(log2 n_cols).  LCPC_ERR_COLUMN_NUMBER if any column >= n_cols. */
 int  lcpc_open_columns(lcpc_commit_t *cm, const uint64_t *cols, uint32_t n, uint64_t *col_vals, uint8_t *paths);
 
@@ -239,12 +250,13 @@ void lcpc_transcript_free(lcpc_transcript *);
 int  lcpc_prove(lcpc_commit_t *cm, const uint64_t *outer_tensor, uint64_t n_outer, lcpc_transcript *tr,
                 uint8_t **proof, uint64_t *proof_len, uint64_t *cols_opened);
 /* LcEvalProof::verify (lib.rs:518-527 -> 832-952) on a bincode proof; `ctx` plays the role of `enc`
- * (it need not hold a commitment).  eval_out: L limbs.  Bytes after the last column are ignored, as by
+ * (it need not hold a commitment).  root: the encoder's digest length (32 bytes; 64 for LCPC_HASH_BLAKE2B).  eval_out: L limbs.  Bytes after the last column are ignored, as by
  * bincode::deserialize (bincode 1.3's top-level functions allow trailing bytes). */
 int  lcpc_verify(lcpc_ctx *ctx, const uint8_t root[32], const uint64_t *outer_tensor, uint64_t n_outer,
                  const uint64_t *inner_tensor, uint64_t n_inner, const uint8_t *proof, uint64_t proof_len,
                  lcpc_transcript *tr, uint64_t *eval_out);
-/* bincode of LcRoot (lib.rs:373-384): 8-byte length + 32 bytes -> out[40] */
+/* bincode of LcRoot (lib.rs:373-384): 8-byte length + 32 bytes -> out[40].  32-byte digests only: for a 64-byte BLAKE2b root
+ * the caller writes u64 64 | root (72 bytes). */
 void lcpc_root_bincode(const uint8_t root[32], uint8_t out[40]);
 void lcpc_free(void *p);
 

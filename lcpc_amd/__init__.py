@@ -17,6 +17,10 @@ FIELD_LIMBS = {FT63: 1, FT127: 2, FT191: 3, FT255: 4}
 ENC_LIGERO, ENC_SDIG = 0, 1
 # D of LcCommit<D, E>: LCPC_HASH_BLAKE3 / LCPC_HASH_SHA3_256 (include/lcpc_hip.h)
 DIGESTS = {"blake3": 0, "sha3_256": 1}
+# every digest `digest=` accepts: DIGESTS plus LCPC_HASH_BLAKE2B (BLAKE2b-512), and the bytes of one Output<D> of each -- a root,
+# a `hashes` slot, a path entry
+ALL_DIGESTS = dict(DIGESTS, blake2b=2)
+DIGEST_LEN = {"blake3": 32, "sha3_256": 32, "blake2b": 64}
 
 
 class LcpcError(RuntimeError):
@@ -84,7 +88,8 @@ class _Encoding:
             raise LcpcError(rc)
         self._h = h
         self.field = params.field
-        self.digest = {v: k for k, v in DIGESTS.items()}[params.hash]
+        self.digest = {v: k for k, v in ALL_DIGESTS.items()}[params.hash]
+        self.digest_len = DIGEST_LEN[self.digest]
         self.L = FIELD_LIMBS[params.field]
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _lib.lib().lcpc_get_dims(self._h, 1, C.byref(a), C.byref(b), C.byref(c))
@@ -140,9 +145,9 @@ class _Encoding:
 
 
 def _digest_id(digest):
-    if digest not in DIGESTS:
-        raise ValueError("digest must be one of %s, not %r" % (sorted(DIGESTS), digest))
-    return DIGESTS[digest]
+    if digest not in ALL_DIGESTS:
+        raise ValueError("digest must be one of %s, not %r" % (sorted(ALL_DIGESTS), digest))
+    return ALL_DIGESTS[digest]
 
 
 def _params(field, encoding, device, **kw):
@@ -233,7 +238,7 @@ ASYNC_TAIL = 2         # LCPC_COMMIT_ASYNC_TAIL (lcpc_commit_sharded_device)
 
 
 class LcCommit:
-    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = the encoder's digest (BLAKE3 or SHA3-256): one lcpc_commit_t -- comm / coeffs / hashes
+    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = the encoder's digest (BLAKE3, SHA3-256 or BLAKE2b): one lcpc_commit_t -- comm / coeffs / hashes
     of ONE commitment, resident in HBM.  Any number of them may be live under one encoding object (lib.rs:299-311)."""
 
     def __init__(self, enc):
@@ -269,7 +274,7 @@ class LcCommit:
         """same, coefficients already in HBM (`coeffs_ptr` = device address, e.g. torch tensor .data_ptr()).
         borrow: LCPC_COMMIT_BORROW_COEFFS -- the commitment keeps reading the caller's buffer instead of copying it."""
         cm = into if into is not None else cls(enc)
-        root = (C.c_uint8 * 32)() if sync else None
+        root = (C.c_uint8 * enc.digest_len)() if sync else None
         cm._check(_lib.lib().lcpc_commit_device(cm._h, C.c_void_p(coeffs_ptr), n_coeffs, C.c_void_p(stream),
                                                 BORROW_COEFFS if borrow else 0, root))
         return cm._refresh()
@@ -328,7 +333,7 @@ class LcCommit:
         return cm._refresh()
 
     def get_root(self):
-        out = (C.c_uint8 * 32)()
+        out = (C.c_uint8 * self.enc.digest_len)()
         self._check(_lib.lib().lcpc_get_root(self._h, out))
         return bytes(out)
 
@@ -342,7 +347,7 @@ class LcCommit:
         return self.n_per_row
 
     def hashes(self):
-        out = np.zeros((self.n_hashes, 32), np.uint8)
+        out = np.zeros((self.n_hashes, self.enc.digest_len), np.uint8)
         self._check(_lib.lib().lcpc_get_hashes(self._h, _ptr(out)))
         return out
 
@@ -373,7 +378,7 @@ class LcCommit:
         n = cols.size
         path_len = max(0, (self.n_cols - 1).bit_length())
         vals = np.zeros((n, self.n_rows, self.enc.L), np.uint64)
-        paths = np.zeros((n, max(path_len, 1), 32), np.uint8)
+        paths = np.zeros((n, max(path_len, 1), self.enc.digest_len), np.uint8)
         self._check(_lib.lib().lcpc_open_columns(self._h, _ptr(cols), n, _ptr(vals), _ptr(paths)))
         return vals, paths[:, :path_len]
 
@@ -457,7 +462,10 @@ class LcEvalProof:
         o, i = _elems(outer_tensor, enc.L), _elems(inner_tensor, enc.L)
         out = np.zeros(enc.L, np.uint64)
         buf = np.frombuffer(self._own.view if self._own else self._bytes, np.uint8)
-        rootb = np.frombuffer(bytes(root), np.uint8)
+        # the library reads the encoder's digest length: a shorter root is zero-filled (it cannot match), a longer one cut
+        rootb = np.zeros(enc.digest_len, np.uint8)
+        rb = bytes(root)[:enc.digest_len]
+        rootb[:len(rb)] = np.frombuffer(rb, np.uint8)
         rc = _lib.lib().lcpc_verify(enc._h, _ptr(rootb), _ptr(o), o.size // enc.L, _ptr(i), i.size // enc.L,
                                     _ptr(buf), buf.size, tr._h, _ptr(out))
         if rc:
@@ -466,6 +474,9 @@ class LcEvalProof:
 
 
 def root_bincode(root):
+    """bincode of LcRoot (lib.rs:373-384): u64 len | the digest (40 bytes; 72 for a 64-byte BLAKE2b root)"""
+    if len(root) == 64:
+        return np.uint64(64).tobytes() + bytes(root)
     out = (C.c_uint8 * 40)()
     _lib.lib().lcpc_root_bincode(bytes(root), out)
     return bytes(out)

@@ -65,7 +65,7 @@ int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coef
     if ((rc = dev_alloc(&m->err, &m->d_comm, (size_t)rows * c->n_cols * eb))) return rc;
     m->cap_comm_rows = rows;
   }
-  if (!m->d_hashes && (rc = dev_alloc(&m->err, &m->d_hashes, (size_t)(2 * c->np2 - 1) * 32))) return rc;
+  if (!m->d_hashes && (rc = dev_alloc(&m->err, &m->d_hashes, (size_t)(2 * c->np2 - 1) * digest_len(c)))) return rc;
   return 0;
 }
 
@@ -92,7 +92,7 @@ int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStre
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
   const lcpc_ctx* c = m->enc;
   if (c->np2 > c->n_cols)   // hashes[n_cols..np2) stay zero (lib.rs:656-666)
-    HIPCHK(m, hipMemsetAsync(m->d_hashes + c->n_cols * 8, 0, (size_t)(c->np2 - c->n_cols) * 32, st));
+    HIPCHK(m, hipMemsetAsync(m->d_hashes + c->n_cols * digest_words(c), 0, (size_t)(c->np2 - c->n_cols) * digest_len(c), st));
   if (c->np2 > 1) {
     if (!m->h_root) {             // once per object; without the mapping the root is copied out as before
       void* hp = nullptr;
@@ -104,6 +104,7 @@ int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
       if (!m->h_root) (void)hipGetLastError();   // the failed call's error must not surface at the next launch check
     }
     if (is_sha3(c)) HIPCHK(m, launch_sha3_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
+    else if (is_blake2b(c)) HIPCHK(m, launch_blake2b_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
     else HIPCHK(m, launch_merkle_tree_from(m->d_hashes, c->np2, levels_done, st, m->d_root_alias));
     m->launches[2]++;
   }
@@ -114,10 +115,10 @@ static int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   const lcpc_ctx* c = m->enc;
   if (m->d_root_alias && c->np2 > 1) {
     HIPCHK(m, hipStreamSynchronize(st));
-    memcpy(root, m->h_root, 32);
+    memcpy(root, m->h_root, digest_len(c));
     return 0;
   }
-  HIPCHK(m, hipMemcpyAsync(root, m->d_hashes + (2 * c->np2 - 2) * 8, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(m, hipMemcpyAsync(root, m->d_hashes + (2 * c->np2 - 2) * digest_words(c), digest_len(c), hipMemcpyDeviceToHost, st));
   HIPCHK(m, hipStreamSynchronize(st));
   return 0;
 }
@@ -137,10 +138,11 @@ static int finish_leaves(lcpc_commit_t* m, hipStream_t st) {
 static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
   LeafArgs la = leaf_args(m);
-  if (is_sha3(c)) {
-    // SHA3-256: one sponge per column over the whole leaf message (sha3.hip), then the tree
+  if (!is_blake3(c)) {
+    // SHA3-256 / BLAKE2b: one serial chain per column over the whole leaf message (sha3.hip, blake2b.hip), then the tree
     la.out = m->d_hashes;
-    HIPCHK(m, launch_sha3_leaves(c->NL, la, st));
+    if (is_sha3(c)) HIPCHK(m, launch_sha3_leaves(c->NL, la, st));
+    else HIPCHK(m, launch_blake2b_leaves(c->NL, la, st));
     m->launches[1]++;
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
     return merkle_top(m, st);
@@ -406,7 +408,10 @@ int open_columns_device(lcpc_commit_t* m, const uint64_t* d_cols, uint32_t n, ui
     else
       HIPCHK(m, launch_gather_columns(c->NL, m->d_comm, m->n_rows_local, c->n_cols, 1, d_cols, n, d_vals, c->comm_canon ? c->d_r2 : nullptr, st));
   }
-  if (d_paths && c->path_len) HIPCHK(m, launch_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, st));
+  if (d_paths && c->path_len) {
+    if (is_blake2b(c)) HIPCHK(m, launch_blake2b_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, st));
+    else HIPCHK(m, launch_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, st));
+  }
   return 0;
 }
 
@@ -422,7 +427,7 @@ int open_columns_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* cols, uint3
   HIPCHK(m, hipSetDevice(c->prm.device));
   const size_t eb = elem_bytes(c);
   const size_t col_b = (size_t)m->n_rows_local * eb;
-  const size_t vb = (((size_t)n * col_b) + 255) & ~(size_t)255, pb = (((size_t)n * c->path_len * 32) + 255) & ~(size_t)255;
+  const size_t vb = (((size_t)n * col_b) + 255) & ~(size_t)255, pb = (((size_t)n * c->path_len * digest_len(c)) + 255) & ~(size_t)255;
   const size_t cb = (((size_t)n * 8) + 255) & ~(size_t)255;
   int rc = ensure_scratch(m, &ws->sc, vb + pb + cb);
   if (rc) return rc;
@@ -439,7 +444,7 @@ int open_columns_host(lcpc_commit_t* m, CallSet* ws, const uint64_t* cols, uint3
     else
       HIPCHK(m, hipMemcpy2DAsync(col_vals, vals_pitch, d_vals, col_b, col_b, n, hipMemcpyDeviceToHost, st));
   }
-  if (paths && c->path_len) HIPCHK(m, hipMemcpyAsync(paths, d_paths, (size_t)n * c->path_len * 32, hipMemcpyDeviceToHost, st));
+  if (paths && c->path_len) HIPCHK(m, hipMemcpyAsync(paths, d_paths, (size_t)n * c->path_len * digest_len(c), hipMemcpyDeviceToHost, st));
   HIPCHK(m, hipStreamSynchronize(st));
   return 0;
 }
@@ -647,9 +652,9 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   if ((rc = order_after_commit(m, m->s_copy)) || (rc = order_after_commit(m, m->s_comp))) return rc;
   if ((rc = zero_coeffs_tail(m, n_coeffs, m->s_copy))) return rc;
   const uint64_t rows_per = (n_rows + NB - 1) / NB;
-  // SHA3-256: a column's sponge is one serial chain over all rows, so nothing is hashed behind the batches -- the whole column
-  // hash runs after the last one (merkleize_device)
-  const bool per_batch = !is_sha3(c) && m->n_chunks > 1;
+  // SHA3-256 / BLAKE2b: a column's hash is one serial chain over all rows, so nothing is hashed behind the batches -- the whole
+  // column hash runs after the last one (merkleize_device)
+  const bool per_batch = is_blake3(c) && m->n_chunks > 1;
   uint64_t chunks_hashed = 0;
   if (per_batch && (rc = ensure_cvs(m, m->n_chunks))) return rc;
   for (int b = 0; b < NB; b++) {
@@ -718,7 +723,7 @@ uint64_t lcpc_commit_bincode_size(const lcpc_commit_t* m) {
   if (!m->committed || m->enc->prm.shard_count > 1) return 0;
   const lcpc_ctx* c = m->enc;
   const uint64_t eb = elem_bytes(c);
-  return 8 + m->n_rows * c->n_cols * eb + 8 + m->n_rows * c->n_per_row * eb + 24 + 8 + (2 * c->np2 - 1) * 40;
+  return 8 + m->n_rows * c->n_cols * eb + 8 + m->n_rows * c->n_per_row * eb + 24 + 8 + (2 * c->np2 - 1) * (8 + digest_len(c));
 }
 
 int lcpc_commit_bincode_write(lcpc_commit_t* m, lcpc_write_fn fn, void* user) {
@@ -748,13 +753,13 @@ int lcpc_commit_bincode_write(lcpc_commit_t* m, lcpc_write_fn fn, void* user) {
   }
   if (put64(m->n_rows) || put64(c->n_cols) || put64(c->n_per_row)) return LCPC_ERR_ARG;
   const uint64_t nh = 2 * c->np2 - 1;
-  std::vector<uint8_t> h((size_t)nh * 32), w((size_t)nh * 40);
+  const uint64_t dl = digest_len(c), we = 8 + dl;            // one WrappedOutput: u64 len | len bytes (lib.rs:354-372)
+  std::vector<uint8_t> h((size_t)(nh * dl)), w((size_t)(nh * we));
   int rc = get_hashes(m, h.data());
   if (rc) return rc;
   for (uint64_t i = 0; i < nh; i++) {
-    const uint64_t l = 32;
-    memcpy(&w[i * 40], &l, 8);
-    memcpy(&w[i * 40 + 8], &h[i * 32], 32);
+    memcpy(&w[i * we], &dl, 8);
+    memcpy(&w[i * we + 8], &h[i * dl], dl);
   }
   if (put64(nh)) return LCPC_ERR_ARG;
   for (uint64_t off = 0; off < w.size(); off += (uint64_t)64 << 20)
@@ -817,8 +822,15 @@ int lcpc_commit_from_bincode(lcpc_commit_t* m, lcpc_read_fn fn, void* user, uint
   if (bad_read) return LCPC_ERR_ARG;
   if (s_rows != n_rows || s_cols != c->n_cols || s_per_row != c->n_per_row || !lcpc_dims_ok(c, s_per_row, s_cols) || nh != 2 * c->np2 - 1)
     return LCPC_ERR_COMMIT;
-  std::vector<uint8_t> w((size_t)nh * 40), have((size_t)nh * 32);
-  for (uint64_t off = 0; off < w.size(); off += (uint64_t)64 << 20)
+  const uint64_t dl = digest_len(c), we = 8 + dl;            // every entry must be the encoder's digest length
+  std::vector<uint8_t> w((size_t)(nh * we)), have((size_t)(nh * dl));
+  // the first entry's length first: a stream of another digest length (a 32-byte digest handed to a BLAKE2b commitment, or the
+  // reverse) is refused as such, not read past its end
+  uint64_t l0 = get64();
+  if (bad_read) return LCPC_ERR_ARG;
+  if (l0 != dl) return LCPC_ERR_COMMIT;
+  memcpy(w.data(), &l0, 8);
+  for (uint64_t off = 8; off < w.size(); off += (uint64_t)64 << 20)
     if (fn(user, w.data() + off, std::min<uint64_t>((uint64_t)64 << 20, w.size() - off))) return LCPC_ERR_ARG;
   if (m->timing) { HIPCHK(m, hipEventRecord(m->ev[0], nullptr)); }
   if ((rc = commit_tail(m, nullptr, nullptr))) return rc;              // hash_columns + merkle_tree from comm, on the device
@@ -826,11 +838,11 @@ int lcpc_commit_from_bincode(lcpc_commit_t* m, lcpc_read_fn fn, void* user, uint
   HIPCHK(m, hipMemcpy(have.data(), m->d_hashes, have.size(), hipMemcpyDeviceToHost));
   for (uint64_t i = 0; i < nh; i++) {
     uint64_t l;
-    memcpy(&l, &w[i * 40], 8);
-    if (l != 32 || memcmp(&w[i * 40 + 8], &have[i * 32], 32) != 0) return LCPC_ERR_COMMIT;
+    memcpy(&l, &w[i * we], 8);
+    if (l != dl || memcmp(&w[i * we + 8], &have[i * dl], dl) != 0) return LCPC_ERR_COMMIT;
   }
   m->committed = true;
-  if (root) memcpy(root, &have[(size_t)(nh - 1) * 32], 32);
+  if (root) memcpy(root, &have[(size_t)((nh - 1) * dl)], dl);
   return 0;
   LCPC_CATCH(m)
 }
@@ -841,7 +853,7 @@ int lcpc_get_root(lcpc_commit_t* m, uint8_t root[32]) {
   if (!m->committed) return LCPC_ERR_STATE;
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
   { int orc = order_after_commit(m, nullptr); if (orc) return orc; }
-  HIPCHK(m, hipMemcpy(root, m->d_hashes + (2 * m->enc->np2 - 2) * 8, 32, hipMemcpyDeviceToHost));
+  HIPCHK(m, hipMemcpy(root, m->d_hashes + (2 * m->enc->np2 - 2) * digest_words(m->enc), digest_len(m->enc), hipMemcpyDeviceToHost));
   return 0;
 }
 int lcpc_commit_dims(const lcpc_commit_t* m, uint64_t* nr, uint64_t* np, uint64_t* nc, uint64_t* nh) {
@@ -860,7 +872,7 @@ static int get_hashes(lcpc_commit_t* m, uint8_t* hashes) {
   if (!m->committed) return LCPC_ERR_STATE;
   HIPCHK(m, hipSetDevice(m->enc->prm.device));
   { int orc = order_after_commit(m, nullptr); if (orc) return orc; }
-  HIPCHK(m, hipMemcpy(hashes, m->d_hashes, (size_t)(2 * m->enc->np2 - 1) * 32, hipMemcpyDeviceToHost));
+  HIPCHK(m, hipMemcpy(hashes, m->d_hashes, (size_t)(2 * m->enc->np2 - 1) * digest_len(m->enc), hipMemcpyDeviceToHost));
   return 0;
 }
 static int get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) {

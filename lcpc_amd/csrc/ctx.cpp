@@ -624,9 +624,9 @@ int lcpc_ctx_create(const lcpc_params* p, lcpc_ctx** out) {
   lcpc_ctx* c = nullptr;
   LCPC_TRY
   const FieldDesc* f = field_desc((int)p->field);
-  if (!f || (p->hash != LCPC_HASH_BLAKE3 && p->hash != LCPC_HASH_SHA3_256)) return LCPC_ERR_ARG;
-  // row shards exchange BLAKE3 chunk chaining values; a SHA3 sponge cannot be split by rows
-  if (p->hash == LCPC_HASH_SHA3_256 && p->shard_count > 1) return LCPC_ERR_ARG;
+  if (!f || (p->hash != LCPC_HASH_BLAKE3 && p->hash != LCPC_HASH_SHA3_256 && p->hash != LCPC_HASH_BLAKE2B)) return LCPC_ERR_ARG;
+  // row shards exchange BLAKE3 chunk chaining values; a SHA3 sponge or a BLAKE2b chain cannot be split by rows
+  if (p->hash != LCPC_HASH_BLAKE3 && p->shard_count > 1) return LCPC_ERR_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev) return LCPC_ERR_NO_DEVICE;
   if (hipSetDevice(p->device) != hipSuccess) return LCPC_ERR_NO_DEVICE;

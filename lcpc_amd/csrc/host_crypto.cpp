@@ -451,4 +451,58 @@ void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
   memcpy(out, a, 32);
 }
 
+namespace {
+constexpr uint64_t B2_IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                               0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+constexpr uint8_t B2_SIGMA[10][16] = {
+    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+    {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+    {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+    {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+    {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}};
+inline uint64_t b2_rotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
+// F(h, m, t, f) of RFC 7693 section 3.2 (t < 2^64 here)
+void b2_compress(uint64_t h[8], const uint8_t blk[128], uint64_t t, bool last) {
+  uint64_t m[16], v[16];
+  memcpy(m, blk, 128);                             // little-endian words
+  for (int i = 0; i < 8; i++) { v[i] = h[i]; v[8 + i] = B2_IV[i]; }
+  v[12] ^= t;
+  if (last) v[14] = ~v[14];
+  auto g = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+    v[a] = v[a] + v[b] + x; v[d] = b2_rotr(v[d] ^ v[a], 32);
+    v[c] = v[c] + v[d];     v[b] = b2_rotr(v[b] ^ v[c], 24);
+    v[a] = v[a] + v[b] + y; v[d] = b2_rotr(v[d] ^ v[a], 16);
+    v[c] = v[c] + v[d];     v[b] = b2_rotr(v[b] ^ v[c], 63);
+  };
+  for (int r = 0; r < 12; r++) {
+    const uint8_t* s = B2_SIGMA[r % 10];
+    g(0, 4, 8, 12, m[s[0]], m[s[1]]);   g(1, 5, 9, 13, m[s[2]], m[s[3]]);
+    g(2, 6, 10, 14, m[s[4]], m[s[5]]);  g(3, 7, 11, 15, m[s[6]], m[s[7]]);
+    g(0, 5, 10, 15, m[s[8]], m[s[9]]);  g(1, 6, 11, 12, m[s[10]], m[s[11]]);
+    g(2, 7, 8, 13, m[s[12]], m[s[13]]); g(3, 4, 9, 14, m[s[14]], m[s[15]]);
+  }
+  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+}
+}  // namespace
+
+void blake2b_host(const uint8_t* in, size_t len, uint8_t out[64]) {
+  uint64_t h[8];
+  memcpy(h, B2_IV, sizeof h);
+  h[0] ^= 0x01010040ull;                           // digest length 64, no key, fanout 1, depth 1
+  uint8_t blk[128];
+  uint64_t t = 0;
+  // every block but the last is compressed as it comes; the last (a full one if len is a multiple of 128, an empty one if
+  // len == 0) is zero-padded and carries the final flag
+  while (len > 128) {
+    t += 128;
+    b2_compress(h, in, t, false);
+    in += 128; len -= 128;
+  }
+  memset(blk, 0, sizeof blk);
+  memcpy(blk, in, len);
+  t += len;
+  b2_compress(h, blk, t, true);
+  memcpy(out, h, 64);
+}
+
 }  // namespace lcpc

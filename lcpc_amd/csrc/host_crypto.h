@@ -66,5 +66,7 @@ class ChaCha20Rng {
 void blake3_host(const uint8_t* in, size_t len, uint8_t out[32]);
 // SHA3-256 (FIPS 202) of a contiguous message, on keccak_f1600 (so LCPC_KECCAK selects its form as for the transcript)
 void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]);
+// BLAKE2b-512 (RFC 7693, unkeyed, 64-byte output) of a contiguous message: portable C++
+void blake2b_host(const uint8_t* in, size_t len, uint8_t out[64]);
 
 }  // namespace lcpc

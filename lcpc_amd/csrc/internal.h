@@ -408,6 +408,12 @@ template <typename T> int ensure_dev(ErrText* err, T** p, uint64_t* cap, uint64_
 
 inline size_t elem_bytes(const lcpc_ctx* c) { return (size_t)8 * c->L; }
 inline bool is_sha3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA3_256; }
+inline bool is_blake2b(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE2B; }
+// BLAKE3 is the only digest whose leaf hash splits into chunks (row batches, row shards); SHA3-256 and BLAKE2b are one serial chain
+inline bool is_blake3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE3; }
+// bytes of one Output<D>: a hashes slot, a root, a path entry (32; BLAKE2b 64)
+inline uint32_t digest_len(const lcpc_ctx* c) { return is_blake2b(c) ? 64u : 32u; }
+inline uint32_t digest_words(const lcpc_ctx* c) { return digest_len(c) / 4; }
 // leaf message = 32 + F * n_rows bytes -> BLAKE3 chunks of 1 KiB
 inline uint64_t leaf_chunks(const lcpc_ctx* c, uint64_t n_rows) { return (32 + elem_bytes(c) * n_rows + 1023) / 1024; }
 

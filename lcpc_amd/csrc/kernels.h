@@ -109,6 +109,15 @@ hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);
 // the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
 hipError_t launch_sha3_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
 
+// ---- BLAKE2b-512 digest (blake2b.hip): the same leaves and tree with 64-byte digests (16 words per hashes slot) ----
+// leaf digests [n_cols][16] of the whole column (a.n_chunks_* unused: the chain is not split); a.out = LcCommit.hashes
+hipError_t launch_blake2b_leaves(int nl, const LeafArgs& a, hipStream_t st);
+// the whole tree above the np2 leaf digests; root_out (may be null): 16 more words the root is written to
+hipError_t launch_blake2b_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
+// launch_gather_paths for 64-byte digests: paths [n][path_len][16]
+hipError_t launch_blake2b_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
+                                       uint32_t* paths, hipStream_t st);
+
 struct CollapseArgs {
   const uint32_t* coeffs;      // local rows x n_per_row
   const uint32_t* tensors;     // [n_tensors][n_rows_local]

@@ -102,7 +102,8 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   // front, so the proof is written once, straight into the buffer the caller receives: the polynomials by a helper
   // thread while this one runs the (serial) transcript, the opened columns by the device-to-host copy itself.
   const size_t pbytes = np * L * 8;
-  const size_t col_bytes = 8 + nr * L * 8 + 8 + (size_t)c->path_len * 40;
+  const size_t dl = digest_len(c);                                            // each path entry: u64 dl | dl bytes (lib.rs:354-372)
+  const size_t col_bytes = 8 + nr * L * 8 + 8 + (size_t)c->path_len * (8 + dl);
   const size_t off_eval = 8 + 8, off_rand0 = off_eval + pbytes + 8 + 8;      // first element of p_eval / of p_random_vec[0]
   const size_t head = 8 + (8 + pbytes) + 8 + n_deg * (8 + pbytes) + 8;
   const size_t total = head + n_open * col_bytes;
@@ -190,7 +191,7 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   std::vector<uint64_t> cols(n_open);
   for (auto& x : cols) x = rng.uniform(c->n_cols);
   if (cols_opened) memcpy(cols_opened, cols.data(), n_open * 8);
-  std::unique_ptr<uint8_t[]> paths(new uint8_t[(size_t)n_open * c->path_len * 32 + 32]);
+  std::unique_ptr<uint8_t[]> paths(new uint8_t[(size_t)n_open * c->path_len * dl + dl]);
   if (filler.joinable()) filler.join();
   tp[3] = now_ms();
   int rc;
@@ -214,7 +215,7 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
       q64(nr);
       q += nr * L * 8;                                                        // the values are already there
       q64(c->path_len);
-      for (uint32_t l = 0; l < c->path_len; l++) { q64(32); memcpy(q, &paths[((size_t)k * c->path_len + l) * 32], 32); q += 32; }
+      for (uint32_t l = 0; l < c->path_len; l++) { q64(dl); memcpy(q, &paths[((size_t)k * c->path_len + l) * dl], dl); q += dl; }
     }
   });
   *proof = out.p; *proof_len = total;
@@ -231,16 +232,22 @@ struct Rd {
   uint64_t u64_() { uint64_t v = 0; if (pos + 8 > len) { bad = true; return 0; } memcpy(&v, p + pos, 8); pos += 8; return v; }
   const uint8_t* take(uint64_t n) { if (n > len - pos) { bad = true; return nullptr; } const uint8_t* q = p + pos; pos += n; return q; }
 };
-// D(0^32 || to_repr(col[0]) || ...) with the encoder's digest (lib.rs:719-735)
-void hash_column_host(const FieldDesc& f, bool sha3, const uint64_t* col, uint64_t n_rows, uint8_t out[32]) {
-  std::vector<uint8_t> msg(32 + n_rows * 8 * f.L, 0);
+// D(in) with the encoder's digest: 32 bytes into out, 64 for BLAKE2b
+void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out) {
+  if (hash == LCPC_HASH_SHA3_256) sha3_256_host(in, len, out);
+  else if (hash == LCPC_HASH_BLAKE2B) blake2b_host(in, len, out);
+  else blake3_host(in, len, out);
+}
+// D(Output<D>::default() || to_repr(col[0]) || ...) with the encoder's digest (lib.rs:719-735): a prefix of dl zero bytes
+void hash_column_host(const FieldDesc& f, uint32_t hash, const uint64_t* col, uint64_t n_rows, uint8_t* out) {
+  const size_t dl = hash == LCPC_HASH_BLAKE2B ? 64 : 32;
+  std::vector<uint8_t> msg(dl + n_rows * 8 * f.L, 0);
   for (uint64_t r = 0; r < n_rows; r++) {
     uint64_t t[MAXL];
     h_canon(f, t, col + r * f.L);
-    memcpy(&msg[32 + r * 8 * f.L], t, 8 * f.L);
+    memcpy(&msg[dl + r * 8 * f.L], t, 8 * f.L);
   }
-  if (sha3) sha3_256_host(msg.data(), msg.size(), out);
-  else blake3_host(msg.data(), msg.size(), out);
+  digest_host(hash, msg.data(), msg.size(), out);
 }
 // every element of an untrusted vector must be a reduced Montgomery representative (< p): the device arithmetic
 // (lazy-limb NTT, lazy dot products) is only proven for reduced inputs.  The reference's derived Deserialize
@@ -290,7 +297,8 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   if (!c || !root || !outer || !inner || !proof || !trw || !eval_out) return LCPC_ERR_ARG;
   LCPC_TRY
   const FieldDesc& f = *c->f;
-  const bool sha3 = is_sha3(c);               // the leaf and node digest (verify_column_path lib.rs:955-982)
+  const uint32_t hash = c->prm.hash;          // the leaf and node digest (verify_column_path lib.rs:955-982)
+  const uint64_t dl = digest_len(c);          // Output<D>: 32 bytes, BLAKE2b 64
   const int L = f.L;
   const uint64_t F = 8 * L;
   Transcript& tr = trw->t;
@@ -324,7 +332,7 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   const uint64_t n_columns = r.u64_();
   if (r.bad || n_columns > proof_len / 8) return LCPC_VERR_MALFORMED;
   std::vector<View> cols(n_columns);
-  struct PathView { const uint8_t* p = nullptr; uint64_t n = 0; };      // n entries of (u64 32, 32 bytes): digest k at p + 40 k + 8
+  struct PathView { const uint8_t* p = nullptr; uint64_t n = 0; };      // n entries of (u64 dl, dl bytes): digest k at p + (8 + dl) k + 8
   std::vector<PathView> paths(n_columns);
   for (uint64_t i = 0; i < n_columns; i++) {
     const uint64_t l = r.u64_();
@@ -333,13 +341,12 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
     if (!q) return LCPC_VERR_MALFORMED;
     cols[i] = View{reinterpret_cast<const uint64_t*>(q), l * L};
     const uint64_t pl = r.u64_();
-    if (r.bad || pl > proof_len / 40) return LCPC_VERR_MALFORMED;
+    if (r.bad || pl > proof_len / (8 + dl)) return LCPC_VERR_MALFORMED;
     paths[i].p = proof + r.pos;
     paths[i].n = pl;
     for (uint64_t k = 0; k < pl; k++) {
-      const uint64_t dl = r.u64_();
-      const uint8_t* d = r.take(32);
-      if (r.bad || dl != 32 || !d) return LCPC_VERR_MALFORMED;     // Output<D> is 32 bytes
+      const uint64_t el = r.u64_();
+      if (r.bad || el != dl || !r.take(dl)) return LCPC_VERR_MALFORMED;     // every entry is one Output<D> of the encoder's digest
     }
   }
   // (bytes after the last column are ignored, as by bincode::deserialize, whose legacy options allow trailing bytes)
@@ -380,7 +387,7 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   std::vector<std::vector<uint64_t>> rand_tensors(n_deg, std::vector<uint64_t>(n_rows * L));
   std::vector<uint64_t> cols_to_open(n_columns);
   std::vector<uint64_t> dots((n_deg + 1) * n_columns * MAXL);                 // dots[d][i] = <tensor_d, column i>
-  std::vector<uint8_t> leaf(n_columns * 32);
+  std::vector<uint8_t> leaf(n_columns * dl);
   uint64_t eval_acc[MAXL] = {0, 0, 0, 0};
   // to_repr of the polynomials is published in chunks: the transcript starts absorbing a polynomial as soon as its first
   // chunk is there instead of waiting for all of it.  1024 elements per chunk (50 us of conversion on one pool thread): with 8192 a
@@ -439,7 +446,7 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
             for (uint64_t k = 0; k < n_rows; k++) { h_mul(f, t, tensor + k * L, cols[i].data() + k * L); h_add(f, acc, acc, t); }
             memcpy(&dots[(d * n_columns + i) * MAXL], acc, F);
           }
-          hash_column_host(f, sha3, cols[i].data(), n_rows, &leaf[i * 32]);
+          hash_column_host(f, hash, cols[i].data(), n_rows, &leaf[i * dl]);
         }
       }, n_columns * n_rows > ((uint64_t)1 << 19) ? 64u : 15u);       // Brakedown opens 6593 columns: ~0.1 s of work single-threaded
       t_side = now_ms() - t0;
@@ -491,17 +498,16 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
         const bool ok = h_eq(f, &dots[(d * n_columns + i) * MAXL], &enc[(d * n_cols + cn) * L]);   // verify_column_value lib.rs:985-1000
         if (d < n_deg) rnd = rnd && ok; else evl = ok;
       }
-      uint8_t h[32], blk[64];                                                    // verify_column_path lib.rs:955-982
-      memcpy(h, &leaf[i * 32], 32);
+      uint8_t h[64], blk[128];                                                   // verify_column_path lib.rs:955-982
+      memcpy(h, &leaf[i * dl], dl);
       uint64_t cc = cn;
       for (uint64_t k = 0; k < paths[i].n; k++) {
-        const uint8_t* pk = paths[i].p + 40 * k + 8;
-        if (cc % 2 == 0) { memcpy(blk, h, 32); memcpy(blk + 32, pk, 32); } else { memcpy(blk, pk, 32); memcpy(blk + 32, h, 32); }
-        if (sha3) sha3_256_host(blk, 64, h);
-        else blake3_host(blk, 64, h);
+        const uint8_t* pk = paths[i].p + (8 + dl) * k + 8;
+        if (cc % 2 == 0) { memcpy(blk, h, dl); memcpy(blk + dl, pk, dl); } else { memcpy(blk, pk, dl); memcpy(blk + dl, h, dl); }
+        digest_host(hash, blk, 2 * dl, h);
         cc >>= 1;
       }
-      const bool pth = memcmp(h, root, 32) == 0;
+      const bool pth = memcmp(h, root, dl) == 0;
       const int stt = !rnd ? LCPC_VERR_COLUMN_DEGREE : (!evl ? LCPC_VERR_COLUMN_EVAL : (!pth ? LCPC_VERR_COLUMN_PATH : 0));
       col_status[i] = (uint8_t)(-stt);
       if (stt) {

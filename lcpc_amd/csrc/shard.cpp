@@ -412,7 +412,7 @@ int lcpc_shard_nodes(uint64_t n_chunks, uint32_t G, uint32_t g, uint32_t* n_node
 // hash step failed must not build a tree over stale digests.
 int lcpc_commit_shard_device(lcpc_commit_t* m, const uint64_t* coeffs_local, uint64_t n_rows_total, void* stream, uint32_t flags,
                              uint8_t* nodes_dev) {
-  if (!m || n_rows_total == 0 || !nodes_dev || is_sha3(m->enc)) return LCPC_ERR_ARG;
+  if (!m || n_rows_total == 0 || !nodes_dev || !is_blake3(m->enc)) return LCPC_ERR_ARG;
   LCPC_TRY
   std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
@@ -427,7 +427,7 @@ int lcpc_commit_shard_device(lcpc_commit_t* m, const uint64_t* coeffs_local, uin
 }
 
 int lcpc_commit_finish_device(lcpc_commit_t* m, uint8_t* gathered, uint64_t n_rows_total, uint32_t slots_per_rank, void* stream, uint8_t* root) {
-  if (!m || !gathered || is_sha3(m->enc)) return LCPC_ERR_ARG;
+  if (!m || !gathered || !is_blake3(m->enc)) return LCPC_ERR_ARG;
   LCPC_TRY
   std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
@@ -542,7 +542,7 @@ static int xchg_enqueue(lcpc_commit_t* m, const XchgPlan& p, hipStream_t sx) {
 //     free again after the column hash, so the next commit (another lcpc_commit_t of the same encoder) encodes while this one's
 //     node values are on the wire.  The commitment is complete behind its event, which every reader and a refill wait for.
 int lcpc_commit_sharded_device(lcpc_commit_t* m, const uint64_t* coeffs_local, uint64_t n_rows_total, void* stream, uint32_t flags, uint8_t* root) {
-  if (!m || n_rows_total == 0 || is_sha3(m->enc)) return LCPC_ERR_ARG;
+  if (!m || n_rows_total == 0 || !is_blake3(m->enc)) return LCPC_ERR_ARG;
   lcpc_ctx* c = m->enc;
   if (!c->comm) return LCPC_ERR_STATE;             // lcpc_comm_init first
   LCPC_TRY

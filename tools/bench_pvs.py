@@ -27,10 +27,11 @@ N_ITERS = 10
 RHO = {"ligero": (1, 2), "ligero_hlf": (1, 2), "ligero_dfl": (1, 4), "ligero_isz": (38, 39)}
 
 
-def run(kind, lgl, fid=3):
+def run(kind, lgl, fid=3, digest="blake3"):
+    """one JSON line for (kind, 2^lgl, field) under `digest` (blake3 / sha3_256 / blake2b; a non-default digest is named in the line)"""
     n = 1 << lgl
     L = fid + 1
-    enc = LigeroEncoding.new(fid, n, rho=RHO[kind]) if kind in RHO else SdigEncoding.new(fid, n, 0)
+    enc = LigeroEncoding.new(fid, n, rho=RHO[kind], digest=digest) if kind in RHO else SdigEncoding.new(fid, n, 0, digest=digest)
     coeffs = B.rand_coeffs(n, L, lgl)
     st = torch.cuda.current_stream().cuda_stream
     c = LcCommit(enc)
@@ -56,10 +57,12 @@ def run(kind, lgl, fid=3):
     t_prove, t_prove_min = timed(lambda: c.prove(outer, enc, mk_transcript(Transcript, root, nco)))
     pf.verify(root, outer, inner, enc, mk_transcript(Transcript, root, nco))
     t_verify, t_verify_min = timed(lambda: pf.verify(root, outer, inner, enc, mk_transcript(Transcript, root, nco)))
-    print(json.dumps({"enc": kind, "field": ("ft63", "ft127", "ft191", "ft255")[fid], "lgl": lgl, "dims": [c.n_rows, c.n_per_row, c.n_cols], "commit_ms": round(t_commit * 1e3, 3),
-                      "prove_ms": round(t_prove * 1e3, 3), "verify_ms": round(t_verify * 1e3, 3),
-                      "min_ms": [round(t_commit_min * 1e3, 3), round(t_prove_min * 1e3, 3), round(t_verify_min * 1e3, 3)], "proof_bytes": len(pf.to_bytes())}),
-          flush=True)
+    rec = {"enc": kind, "field": ("ft63", "ft127", "ft191", "ft255")[fid], "lgl": lgl, "dims": [c.n_rows, c.n_per_row, c.n_cols], "commit_ms": round(t_commit * 1e3, 3),
+           "prove_ms": round(t_prove * 1e3, 3), "verify_ms": round(t_verify * 1e3, 3),
+           "min_ms": [round(t_commit_min * 1e3, 3), round(t_prove_min * 1e3, 3), round(t_verify_min * 1e3, 3)], "proof_bytes": len(pf.to_bytes())}
+    if digest != "blake3":
+        rec["digest"] = digest
+    print(json.dumps(rec), flush=True)
     del coeffs, c, enc
     torch.cuda.empty_cache()
 
