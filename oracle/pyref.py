@@ -26,6 +26,7 @@ marked [3P] below.
 
 All citations `file:line` are into /root/reference.
 """
+import hashlib
 import math
 import struct
 
@@ -261,6 +262,32 @@ def _b3_subtree(data, chunk0, is_root):
 
 def blake3(data):
     return struct.pack("<8I", *_b3_subtree(bytes(data), 0, True))
+
+
+# --------------------------------------------------------------------------
+# D: Digest of LcCommit<D, E> / LcEvalProof<D, E>  (lcpc-2d/src/lib.rs:172-184, 490-500).
+# The reference is generic over digest::Digest; Output<D>::default() is `size` zero bytes.
+# --------------------------------------------------------------------------
+
+
+class Digest:
+    """one D: a name, the output size in bytes and bytes -> digest"""
+
+    def __init__(self, name, size, fn):
+        self.name, self.size, self.fn = name, size, fn
+        self.zero = b"\0" * size              # Output<D>::default(): leaf prefix and filler of the slots beyond n_cols
+
+    def __call__(self, data):
+        return self.fn(bytes(data))
+
+    def __repr__(self):
+        return "Digest(%s)" % self.name
+
+
+BLAKE3 = Digest("blake3", 32, blake3)
+SHA3_256 = Digest("sha3_256", 32, lambda b: hashlib.sha3_256(b).digest())     # FIPS 202
+BLAKE2B = Digest("blake2b", 64, lambda b: hashlib.blake2b(b).digest())        # RFC 7693: BLAKE2b-512, no key
+DIGESTS = {d.name: d for d in (BLAKE3, SHA3_256, BLAKE2B)}
 
 
 # --------------------------------------------------------------------------
@@ -814,26 +841,26 @@ class LcCommit:
         return self.hashes[-1]
 
 
-def hash_column(F, col_vals):
-    """leaf digest: D(0^32 || to_repr(col[0]) || ...)  (lib.rs:719-735)."""
-    return blake3(b"\0" * 32 + b"".join(F.to_repr(v) for v in col_vals))
+def hash_column(F, col_vals, digest=BLAKE3):
+    """leaf digest: D(Output<D>::default() || to_repr(col[0]) || ...)  (lib.rs:719-735)."""
+    return digest(digest.zero + b"".join(F.to_repr(v) for v in col_vals))
 
 
-def merkleize(F, c):
+def merkleize(F, c, digest=BLAKE3):
     """lib.rs:690-704 via the serial twin merkleize_ser lib.rs:1127-1158."""
     np2 = next_pow2(c.n_cols)
-    hashes = [b"\0" * 32] * (2 * np2 - 1)
+    hashes = [digest.zero] * (2 * np2 - 1)
     for col in range(c.n_cols):
-        hashes[col] = hash_column(F, [c.comm[r * c.n_cols + col] for r in range(c.n_rows)])
+        hashes[col] = hash_column(F, [c.comm[r * c.n_cols + col] for r in range(c.n_rows)], digest)
     ins, outs, width = 0, np2, np2
     while width > 1:
         for i in range(width // 2):
-            hashes[outs + i] = blake3(hashes[ins + 2 * i] + hashes[ins + 2 * i + 1])
+            hashes[outs + i] = digest(hashes[ins + 2 * i] + hashes[ins + 2 * i + 1])
         ins, outs, width = outs, outs + width // 2, width // 2
     c.hashes = hashes
 
 
-def commit(F, coeffs_in, enc):
+def commit(F, coeffs_in, enc, digest=BLAKE3):
     """lib.rs:622-671."""
     n_rows, n_per_row, n_cols = enc.get_dims(len(coeffs_in))
     assert n_rows * n_per_row >= len(coeffs_in) > (n_rows - 1) * n_per_row
@@ -844,7 +871,7 @@ def commit(F, coeffs_in, enc):
         row = coeffs[r * n_per_row:(r + 1) * n_per_row] + [0] * (n_cols - n_per_row)
         comm += enc.encode(row)
     c = LcCommit(comm, coeffs, n_rows, n_cols, n_per_row, None)
-    merkleize(F, c)
+    merkleize(F, c, digest)
     return c
 
 
@@ -904,7 +931,11 @@ class VerifierError(Exception):
     pass
 
 
-def verify(F, root, outer_tensor, inner_tensor, proof, enc, tr):
+class MalformedProof(Exception):
+    """bincode::deserialize::<LcEvalProof<D, E>> would fail on these bytes (or the reference would panic on them)"""
+
+
+def verify(F, root, outer_tensor, inner_tensor, proof, enc, tr, digest=BLAKE3):
     """lib.rs:832-952."""
     n_col_opens = enc.get_n_col_opens()
     if n_col_opens != len(proof.columns) or n_col_opens == 0:
@@ -918,6 +949,8 @@ def verify(F, root, outer_tensor, inner_tensor, proof, enc, tr):
         raise VerifierError("OuterTensor")
     if not enc.dims_ok(n_per_row, n_cols):
         raise VerifierError("EncodingDims")
+    if len(proof.p_random_vec) < enc.get_n_degree_tests():
+        raise MalformedProof("fewer p_random than degree tests")     # the reference panics indexing p_random_vec[i] below
     rand_tensors, p_random_fft = [], []
     for i in range(enc.get_n_degree_tests()):
         key = tr.challenge_bytes(enc.LABEL_DT, 32)
@@ -938,10 +971,10 @@ def verify(F, root, outer_tensor, inner_tensor, proof, enc, tr):
                 raise VerifierError("ColumnDegree")
         if sum(t * e for t, e in zip(outer_tensor, col)) % F.p != p_eval_fft[col_num]:
             raise VerifierError("ColumnEval")
-        h = hash_column(F, col)
+        h = hash_column(F, col, digest)
         cn = col_num
         for pth in path:
-            h = blake3(h + pth) if cn % 2 == 0 else blake3(pth + h)
+            h = digest(h + pth) if cn % 2 == 0 else digest(pth + h)
             cn >>= 1
         if h != root:
             raise VerifierError("ColumnPath")
@@ -977,7 +1010,110 @@ def ser_proof(F, pf):
     return out
 
 
-def proof_size(F, n_rows, n_per_row, n_cols, n_opens, n_deg):
+def proof_size(F, n_rows, n_per_row, n_cols, n_opens, n_deg, dl=32):
+    """bytes of a serialised proof with dl-byte digests: a path entry is u64 dl | digest"""
     Fb = F.nbytes
     return (8 + (8 + Fb * n_per_row) + 8 + n_deg * (8 + Fb * n_per_row) + 8 +
-            n_opens * (8 + Fb * n_rows + 8 + log2_ceil(n_cols) * 40))
+            n_opens * (8 + Fb * n_rows + 8 + log2_ceil(n_cols) * (8 + dl)))
+
+
+class _Reader:
+    def __init__(self, blob):
+        self.b, self.pos = bytes(blob), 0
+
+    def u64(self):
+        if self.pos + 8 > len(self.b):
+            raise MalformedProof("short read")
+        v = struct.unpack_from("<Q", self.b, self.pos)[0]
+        self.pos += 8
+        return v
+
+    def take(self, n):
+        if n > len(self.b) - self.pos:
+            raise MalformedProof("short read")
+        out = self.b[self.pos:self.pos + n]
+        self.pos += n
+        return out
+
+
+def deser_proof(F, blob, dl=32, expect_columns=None):
+    """bincode::deserialize of WrappedLcEvalProof (lib.rs:550-609) with dl-byte digests: the inverse of ser_proof.  Raises
+    MalformedProof where the bytes do not hold the reference's types: a read past the end (every Vec's length prefix is an
+    untrusted u64, so an absurd count ends there too), or a path entry whose serde_bytes length is not dl (Output<D> is a
+    fixed-size array: lib.rs:360-371 refuses another length).  Bytes after the proof are allowed (bincode 1.3's top-level
+    deserialize does not look at them).
+
+    Three checks the reference makes by panicking on an index or inside the encoder, not in serde, are reported the same way,
+    as oracle/lcpc_oracle.c lo_verify and the library do: a p_random entry whose length is not p_eval's, a column whose length
+    is not column 0's, more than 64 path entries.
+
+    expect_columns: lo_verify and the library compare the column count with the encoder's n_col_opens *before* they read the
+    columns, so a wrong count is VerifierError NumColOpens even where the rest of the bytes is short; pass the encoder's count
+    to get that order.
+
+    Elements are stored Montgomery limbs (derive(Deserialize) on [u64; L] takes any limbs); the result holds their values
+    mod p, and .n_unreduced counts the limb vectors >= p."""
+    r = _Reader(blob)
+    Fb = F.nbytes
+    cap = len(r.b) // Fb
+    unred = [0]
+
+    def elems(n):
+        raw = r.take(n * Fb)
+        out = []
+        for i in range(n):
+            am = int.from_bytes(raw[Fb * i:Fb * (i + 1)], "little")
+            if am >= F.p:
+                unred[0] += 1
+            out.append(F.from_mont(am))
+        return out
+
+    n_cols = r.u64()
+    n_per_row = r.u64()
+    if n_per_row > cap:
+        raise MalformedProof("p_eval longer than the buffer")
+    p_eval = elems(n_per_row)
+    n_deg = r.u64()
+    if n_deg > 1024:
+        raise MalformedProof("absurd p_random count")
+    p_random_vec = []
+    for _ in range(n_deg):
+        n = r.u64()
+        if n != n_per_row:
+            raise MalformedProof("p_random length")
+        p_random_vec.append(elems(n))
+    n_columns = r.u64()
+    if expect_columns is not None and (n_columns != expect_columns or expect_columns == 0):
+        raise VerifierError("NumColOpens")
+    columns, n_rows = [], 0
+    for i in range(n_columns):
+        n = r.u64()
+        if i == 0:
+            n_rows = n
+        if n != n_rows or n > cap:
+            raise MalformedProof("column length")
+        col = elems(n)
+        path_len = r.u64()
+        if path_len > 64:
+            raise MalformedProof("absurd path length")
+        path = []
+        for _ in range(path_len):
+            if r.u64() != dl:
+                raise MalformedProof("path entry is not %d bytes" % dl)
+            path.append(r.take(dl))
+        columns.append((col, path))
+    pf = LcEvalProof(n_cols, p_eval, p_random_vec, columns)
+    pf.n_unreduced = unred[0]
+    return pf
+
+
+def verify_bytes(F, digest, root, outer_tensor, inner_tensor, blob, enc, tr):
+    """deserialise + LcEvalProof::verify (lib.rs:518-527) as a caller of the reference sees it: the evaluation, or the name of
+    the error -- "Malformed" for bytes bincode refuses, else the VerifierError (lib.rs:139-166)."""
+    try:
+        pf = deser_proof(F, blob, digest.size, enc.get_n_col_opens())
+        return verify(F, root, outer_tensor, inner_tensor, pf, enc, tr, digest)
+    except MalformedProof:
+        return "Malformed"
+    except VerifierError as e:
+        return e.args[0]

@@ -37,12 +37,12 @@ def mk_tr(root, n_col_opens):
 
 def commit_bincode(F, c):
     """bincode 1.3 of WrappedLcCommit (lcpc-2d/src/lib.rs:186-197): Vec<F> = u64 len + raw Montgomery limbs, usize = u64,
-    Vec<WrappedOutput> = u64 len + (u64 32 + digest) each"""
+    Vec<WrappedOutput> = u64 len + (u64 digest length + digest) each"""
     padded = list(c.coeffs) + [0] * (c.n_rows * c.n_per_row - len(c.coeffs))
     out = [len(c.comm).to_bytes(8, "little"), mont_bytes(F, c.comm), len(padded).to_bytes(8, "little"), mont_bytes(F, padded)]
     out += [v.to_bytes(8, "little") for v in (c.n_rows, c.n_cols, c.n_per_row)]
     out.append(len(c.hashes).to_bytes(8, "little"))
-    out += [(32).to_bytes(8, "little") + h for h in c.hashes]
+    out += [len(h).to_bytes(8, "little") + h for h in c.hashes]
     return b"".join(out)
 
 
@@ -76,7 +76,53 @@ def commit_case(name, F, enc, enc_desc, n, kind, seed, with_proof=True):
     return out
 
 
+# (name, field, encoder, its description, n_coeffs, coefficient kind, seed) of tests/golden/digest_cases.json: both encodings, all
+# four fields, ragged last rows, Brakedown's n_cols not a power of two (leaf slots beyond it hold Output<D>::default())
+def digest_shapes():
+    return [
+        ("ligero_ft63_1000", P.FT63, P.LigeroEncoding.new(P.FT63, 1000), dict(kind="ligero", rho=[1, 2], length=1000), 1000, "rand", 1),
+        ("ligero_ft191_dims_100_256", P.FT191, P.LigeroEncoding(P.FT191, 100, 256), dict(kind="ligero", rho=[1, 2], n_per_row=100, n_cols=256),
+         950, "rand", 3),
+        ("ligero_ft255_1500", P.FT255, P.LigeroEncoding.new(P.FT255, 1500), dict(kind="ligero", rho=[1, 2], length=1500), 1500, "rand", 4),
+        ("sdig_ft127_300_code6", P.FT127, P.SdigEncoding.new(P.FT127, 300, 9, 6), dict(kind="sdig", code=6, seed=9, length=300), 300, "rand", 5),
+    ]
+
+
+def digest_cases():
+    """every shape of digest_shapes under every digest of pyref.DIGESTS: root, sha256 of the serde bytes of the commitment and of
+    the proof, the first opened columns, the evaluation.  The code word is the same under every digest, so each shape is encoded
+    once and merkleized again per digest."""
+    out = []
+    for name, F, enc, desc, n, kind, seed in digest_shapes():
+        coeffs = coeffs_for(F, n, kind, seed)
+        c = P.commit(F, coeffs, enc)
+        x = 0x1234567 % F.p
+        inner = [pow(x, i, F.p) for i in range(c.n_per_row)]
+        xr = pow(x, c.n_per_row, F.p)
+        outer = [pow(xr, i, F.p) for i in range(c.n_rows)]
+        want_ev = sum(cf * pow(x, i, F.p) for i, cf in enumerate(coeffs)) % F.p
+        for D in P.DIGESTS.values():
+            P.merkleize(F, c, D)
+            ser_c = commit_bincode(F, c)
+            root, nco = c.get_root(), enc.get_n_col_opens()
+            pf, cols = P.prove(F, c, outer, enc, mk_tr(root, nco))
+            ser = P.ser_proof(F, pf)
+            assert len(ser) == P.proof_size(F, c.n_rows, c.n_per_row, c.n_cols, nco, enc.get_n_degree_tests(), D.size)
+            ev = P.verify_bytes(F, D, root, outer, inner, ser, enc, mk_tr(root, nco))
+            assert ev == want_ev, ev
+            out.append(dict(name="%s_%s" % (D.name, name), digest=D.name, digest_len=D.size, field=F.fid, enc=desc, n_coeffs=n,
+                            coeffs=kind, seed=seed, n_rows=c.n_rows, n_per_row=c.n_per_row, n_cols=c.n_cols, n_col_opens=nco,
+                            root=root.hex(), leaf0=c.hashes[0].hex(),
+                            hashes_sha256=hashlib.sha256(b"".join(c.hashes)).hexdigest(),
+                            commit_bincode_len=len(ser_c), commit_bincode_sha256=hashlib.sha256(ser_c).hexdigest(),
+                            eval_point=hex(x), proof_len=len(ser), proof_sha256=hashlib.sha256(ser).hexdigest(),
+                            cols_opened_head=cols[:8], eval=hex(ev)))
+    return out
+
+
 def main():
+    with open(os.path.join(HERE, "digest_cases.json"), "w") as f:
+        json.dump(digest_cases(), f, indent=1)
     cases = []
     cases.append(commit_case("ligero_ft63_2e10_iota", P.FT63, P.LigeroEncoding.new(P.FT63, 1024),
                              dict(kind="ligero", rho=[1, 2], length=1024), 1024, "iota", 0))

@@ -63,9 +63,9 @@ def _setup(O, kind):
         fid, n = 1, 1 << 16
         enc, oenc = SdigEncoding.new(fid, n, 7), O.Encoding.sdig(fid, n, 7)
         coeffs = O.random_elems(fid, n, 92)
-    else:                            # SHA3-256 digest: the library's serial prove / verify is the reference (test_gpu_sha3.py checks it)
-        fid, n = 3, 1 << 16
-        enc, oenc = LigeroEncoding.new(fid, n, digest="sha3_256"), None
+    else:                            # SHA3-256 / BLAKE2b digest: the library's serial prove / verify is the reference
+        fid, n = 3, 1 << 16           # (test_gpu_sha3.py, test_gpu_blake2b.py and test_gpu_digests_*.py check it)
+        enc, oenc = LigeroEncoding.new(fid, n, digest="blake2b" if kind.startswith("blake2b") else "sha3_256"), None
         coeffs = O.random_elems(fid, n, 93)
     c = LcCommit.commit(coeffs, enc)
     oc = O.Commit.commit(coeffs, oenc, n_threads=8) if oenc else None
@@ -74,7 +74,7 @@ def _setup(O, kind):
     return enc, c, oenc, oc, fid
 
 
-@pytest.mark.parametrize("kind", ["ligero_ft255", "sdig_ft127", "sha3_ligero_ft255"])
+@pytest.mark.parametrize("kind", ["ligero_ft255", "sdig_ft127", "sha3_ligero_ft255", "blake2b_ligero_ft255"])
 def test_concurrent_prove_verify_bytes(oracle, kind):
     O = oracle
     enc, c, oenc, oc, fid = _setup(O, kind)

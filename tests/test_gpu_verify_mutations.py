@@ -3,14 +3,11 @@ values, path digests and length fields, truncations).  lcpc_verify (LcEvalProof:
 must neither crash nor accept, and must report the VerifierError the oracle's restatement of the reference reports for the
 same bytes -- except where it is deliberately stricter: a limb vector >= p is refused as malformed,
 where the reference computes on it mod p and fails later (or, for a column entry, not at all if the residue matches)."""
-import random
-import struct
-
-import numpy as np
 import pytest
 
 import lcpc_amd
 from common import mk_transcript, powers
+from digest_ref import mutation_cases
 from lcpc_amd import LcCommit, LcEvalProof, LigeroEncoding, SdigEncoding, Transcript
 
 pytestmark = pytest.mark.gpu
@@ -48,39 +45,9 @@ def test_mutated_proofs_same_verdict_as_oracle(oracle, kind, fid, n):
     O = oracle
     enc, oenc, root, nco, inner, outer, pf, c = _setup(O, kind, fid, n, 5 + fid)
     assert _both(O, enc, oenc, root, nco, inner, outer, pf) == (0, 0)
-    F = 8 * enc.L
-    npr, n_rows = c.n_per_row, c.n_rows
-    # wire layout (lib.rs:550-609): n_cols, len, p_eval, n_deg, (len, p_random)*, n_columns, (len, col, path_len, (32, digest)*)*
-    off_eval = 16
-    off_nd = off_eval + npr * F
-    n_deg = struct.unpack_from("<Q", pf, off_nd)[0]
-    off_rand = off_nd + 8 + 8
-    off_ncol = off_nd + 8 + n_deg * (8 + npr * F)
-    off_col0 = off_ncol + 8
-    rnd = random.Random(1000 + fid)
-    spots = {
-        "n_cols": 0, "p_eval len": 8, "p_eval": off_eval + rnd.randrange(npr * F), "n_deg": off_nd,
-        "p_random len": off_nd + 8, "p_random": off_rand + rnd.randrange(npr * F), "n_columns": off_ncol,
-        "col0 len": off_col0, "col0 value": off_col0 + 8 + rnd.randrange(n_rows * F),
-        "col0 path len": off_col0 + 8 + n_rows * F, "col0 digest len": off_col0 + 8 + n_rows * F + 8,
-        "col0 digest": off_col0 + 8 + n_rows * F + 16 + rnd.randrange(32), "last byte": len(pf) - 1,
-    }
-    cases = []
-    for name, pos in spots.items():
-        for bit in (0, rnd.randrange(8)):
-            b = bytearray(pf)
-            b[pos] ^= 1 << bit
-            cases.append((name + " bit %d" % bit, bytes(b)))
-    for _ in range(24):                                   # anywhere
-        b = bytearray(pf)
-        pos = rnd.randrange(len(pf))
-        b[pos] ^= 1 << rnd.randrange(8)
-        cases.append(("byte %d" % pos, bytes(b)))
-    cases += [("truncated", pf[:-1]), ("truncated 8", pf[:-8]), ("half", pf[:len(pf) // 2]), ("header only", pf[:16]), ("empty", b"")]
-    # a limb vector >= p in p_eval: all ones in the top limb of element 0
-    b = bytearray(pf)
-    b[off_eval + F - 8:off_eval + F] = b"\xff" * 8
-    cases.append(("p_eval[0] >= p", bytes(b)))
+    # the case list is shared with the sweeps under the other digests (tests/digest_ref.py: same generator, same draws)
+    cases = mutation_cases(pf, enc.L, c.n_per_row, c.n_rows, 1000 + fid, 32, c.n_cols)
+    assert len(cases) == 56
     n_strict = 0
     for name, blob in cases:
         rc, orc = _both(O, enc, oenc, root, nco, inner, outer, blob)
