@@ -25,6 +25,9 @@ pub const LCPC_ENC_SDIG: u32 = 1;
 pub const LCPC_HASH_BLAKE3: u32 = 0;
 pub const LCPC_HASH_SHA3_256: u32 = 1;
 pub const LCPC_HASH_BLAKE2B: u32 = 2;
+// the two digests an EVM verifier recomputes: Keccak[512](M || 01, 256) (sha3::Keccak256, 32 bytes) and sha2::Sha256 (32 bytes)
+pub const LCPC_HASH_KECCAK256: u32 = 3;
+pub const LCPC_HASH_SHA256: u32 = 4;
 // the longest Output<D> (BLAKE2b, 64 bytes): every root / path / hashes buffer holds the encoder's digest length
 pub const LCPC_DIGEST_LEN_MAX: u32 = 64;
 

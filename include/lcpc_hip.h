@@ -55,8 +55,10 @@ enum { LCPC_FT63 = 0, LCPC_FT127 = 1, LCPC_FT191 = 2, LCPC_FT255 = 3 };
 /* encodings: lcpc-ligero-pc/src/lib.rs:31-37 (LigeroEncodingRho), lcpc-brakedown-pc/src/lib.rs:41-47 (SdigEncodingS) */
 enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
 /* D: Digest of LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184).  Every reference test uses blake3::Hasher; the reference also
- * benchmarks sha3::Sha3_256 and blake2::Blake2b.  Every root, path entry and `hashes` slot holds the encoder's digest length:
- * 32 bytes for LCPC_HASH_BLAKE3 and LCPC_HASH_SHA3_256, 64 bytes (LCPC_DIGEST_LEN_MAX) for LCPC_HASH_BLAKE2B.
+ * benchmarks sha3::Sha3_256 and blake2::Blake2b; Keccak-256 and SHA-256 are the two digests a verifier on the EVM (the KECCAK256
+ * opcode, the SHA-256 precompile) can recompute.  Every root, path entry and `hashes` slot holds the encoder's digest length:
+ * 32 bytes for LCPC_HASH_BLAKE3, LCPC_HASH_SHA3_256, LCPC_HASH_KECCAK256 and LCPC_HASH_SHA256, 64 bytes (LCPC_DIGEST_LEN_MAX) for
+ * LCPC_HASH_BLAKE2B.
  *  - LCPC_HASH_BLAKE3 (default): chunked leaf hash (1 KiB chunks), one compression per tree node.
  *  - LCPC_HASH_SHA3_256 (FIPS 202): one Keccak sponge per column over the whole leaf message (sha3.hip; one permutation per
  *    17 limbs), then one permutation per tree node.  Measured on one MI355X at 2^26 Ft255 coefficients (512 x 262144): column
@@ -64,7 +66,12 @@ enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
  *  - LCPC_HASH_BLAKE2B (RFC 7693 BLAKE2b-512, unkeyed): leaf = BLAKE2b(0^64 || to_repr(col[0]) || ...), node =
  *    BLAKE2b(left64 || right64); one compression chain per column over the whole leaf message (blake2b.hip; one compression
  *    per 16 limbs), one compression per tree node.  Measured at the same shape in DESIGN.md section 6.
- * For SHA3-256 and BLAKE2b, at each entry point:
+ *  - LCPC_HASH_KECCAK256: Keccak[512](M || 01, 256), the pre-FIPS padding (Ethereum's keccak256).  The sponge, rate and kernels of
+ *    LCPC_HASH_SHA3_256 with the padding's first byte 0x01 instead of 0x06; every digest differs from SHA3-256's.
+ *  - LCPC_HASH_SHA256 (FIPS 180-4): leaf = SHA-256(0^32 || to_repr(col[0]) || ...), node = SHA-256(left || right); one
+ *    Merkle-Damgard chain per column over the whole leaf message (sha256.hip; one compression per 8 limbs, big-endian words),
+ *    two compressions per tree node (the second on a constant padding block).  Measured in DESIGN.md section 6.
+ * For SHA3-256, BLAKE2b, Keccak-256 and SHA-256, at each entry point:
  *  - lcpc_commit, lcpc_commit_device, lcpc_commit_from_parts, lcpc_commit_from_bincode: as above.  The host-memory lcpc_commit
  *    hashes after the last row batch instead of behind each batch;
  *  - lcpc_commit_from_bincode refuses (LCPC_ERR_COMMIT) a stream whose `hashes` were made with another digest (or whose
@@ -74,7 +81,9 @@ enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
  *    with LCPC_VERR_COLUMN_PATH, one whose path entries have another length with LCPC_VERR_MALFORMED;
  *  - row sharding: lcpc_ctx_create returns LCPC_ERR_ARG for shard_count > 1 (the chain cannot be split by rows), and the
  *    sharded commit entry points return LCPC_ERR_ARG on such an encoder. */
-enum { LCPC_HASH_BLAKE3 = 0, LCPC_HASH_SHA3_256 = 1, LCPC_HASH_BLAKE2B = 2 };
+enum { LCPC_HASH_BLAKE3 = 0, LCPC_HASH_SHA3_256 = 1, LCPC_HASH_BLAKE2B = 2,
+       LCPC_HASH_KECCAK256 = 3,   /* Keccak[512](M || 01, 256): the pre-FIPS padding, Ethereum's keccak256 */
+       LCPC_HASH_SHA256 = 4 };    /* FIPS 180-4 */
 /* the longest Output<D> (BLAKE2b): a caller that serves every digest sizes root / path buffers with it */
 enum { LCPC_DIGEST_LEN_MAX = 64 };
 
@@ -115,7 +124,7 @@ typedef struct lcpc_transcript lcpc_transcript;
 typedef struct {
   uint32_t field;        /* LCPC_FT* */
   uint32_t encoding;     /* LCPC_ENC_* */
-  uint32_t hash;         /* LCPC_HASH_BLAKE3, LCPC_HASH_SHA3_256 or LCPC_HASH_BLAKE2B */
+  uint32_t hash;         /* LCPC_HASH_BLAKE3, _SHA3_256, _BLAKE2B, _KECCAK256 or _SHA256 */
   uint32_t rho_num, rho_den;  /* Ligero rate Rn/Rd (default alias 1/2: ligero lib.rs:189) */
   uint32_t sdig_code;    /* 1..6 = SdigCode1..6 (codespec.rs:169-232); default 3 (brakedown lib.rs:19) */
   uint64_t seed;         /* Brakedown matgen seed (brakedown lib.rs:103) */

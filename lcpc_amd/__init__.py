@@ -21,6 +21,9 @@ DIGESTS = {"blake3": 0, "sha3_256": 1}
 # a `hashes` slot, a path entry
 ALL_DIGESTS = dict(DIGESTS, blake2b=2)
 DIGEST_LEN = {"blake3": 32, "sha3_256": 32, "blake2b": 64}
+# the table `digest=` is looked up in: the three above plus LCPC_HASH_KECCAK256 (Keccak-256, the pre-FIPS padding of the EVM's
+# KECCAK256) and LCPC_HASH_SHA256 -- name -> (lcpc_params.hash, bytes of one Output<D>)
+DIGEST_TABLE = {"blake3": (0, 32), "sha3_256": (1, 32), "blake2b": (2, 64), "keccak256": (3, 32), "sha256": (4, 32)}
 
 
 class LcpcError(RuntimeError):
@@ -88,8 +91,8 @@ class _Encoding:
             raise LcpcError(rc)
         self._h = h
         self.field = params.field
-        self.digest = {v: k for k, v in ALL_DIGESTS.items()}[params.hash]
-        self.digest_len = DIGEST_LEN[self.digest]
+        self.digest = {v[0]: k for k, v in DIGEST_TABLE.items()}[params.hash]
+        self.digest_len = DIGEST_TABLE[self.digest][1]
         self.L = FIELD_LIMBS[params.field]
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _lib.lib().lcpc_get_dims(self._h, 1, C.byref(a), C.byref(b), C.byref(c))
@@ -145,9 +148,9 @@ class _Encoding:
 
 
 def _digest_id(digest):
-    if digest not in ALL_DIGESTS:
-        raise ValueError("digest must be one of %s, not %r" % (sorted(ALL_DIGESTS), digest))
-    return ALL_DIGESTS[digest]
+    if digest not in DIGEST_TABLE:
+        raise ValueError("digest must be one of %s, not %r" % (sorted(DIGEST_TABLE), digest))
+    return DIGEST_TABLE[digest][0]
 
 
 def _params(field, encoding, device, **kw):
@@ -238,7 +241,7 @@ ASYNC_TAIL = 2         # LCPC_COMMIT_ASYNC_TAIL (lcpc_commit_sharded_device)
 
 
 class LcCommit:
-    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = the encoder's digest (BLAKE3, SHA3-256 or BLAKE2b): one lcpc_commit_t -- comm / coeffs / hashes
+    """LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184, 270-312) with D = the encoder's digest (BLAKE3, SHA3-256, BLAKE2b, Keccak-256 or SHA-256): one lcpc_commit_t -- comm / coeffs / hashes
     of ONE commitment, resident in HBM.  Any number of them may be live under one encoding object (lib.rs:299-311)."""
 
     def __init__(self, enc):

@@ -105,6 +105,8 @@ int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
     }
     if (is_sha3(c)) HIPCHK(m, launch_sha3_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
     else if (is_blake2b(c)) HIPCHK(m, launch_blake2b_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
+    else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));
+    else if (is_sha256(c)) HIPCHK(m, launch_sha256_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));
     else HIPCHK(m, launch_merkle_tree_from(m->d_hashes, c->np2, levels_done, st, m->d_root_alias));
     m->launches[2]++;
   }
@@ -139,9 +141,12 @@ static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
   LeafArgs la = leaf_args(m);
   if (!is_blake3(c)) {
-    // SHA3-256 / BLAKE2b: one serial chain per column over the whole leaf message (sha3.hip, blake2b.hip), then the tree
+    // SHA3-256 / BLAKE2b / Keccak-256 / SHA-256: one serial chain per column over the whole leaf message (sha3.hip, blake2b.hip,
+    // sha256.hip), then the tree
     la.out = m->d_hashes;
     if (is_sha3(c)) HIPCHK(m, launch_sha3_leaves(c->NL, la, st));
+    else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_leaves(c->NL, la, st));
+    else if (is_sha256(c)) HIPCHK(m, launch_sha256_leaves(c->NL, la, st));
     else HIPCHK(m, launch_blake2b_leaves(c->NL, la, st));
     m->launches[1]++;
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
@@ -652,7 +657,7 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   if ((rc = order_after_commit(m, m->s_copy)) || (rc = order_after_commit(m, m->s_comp))) return rc;
   if ((rc = zero_coeffs_tail(m, n_coeffs, m->s_copy))) return rc;
   const uint64_t rows_per = (n_rows + NB - 1) / NB;
-  // SHA3-256 / BLAKE2b: a column's hash is one serial chain over all rows, so nothing is hashed behind the batches -- the whole
+  // every digest but BLAKE3: a column's hash is one serial chain over all rows, so nothing is hashed behind the batches -- the whole
   // column hash runs after the last one (merkleize_device)
   const bool per_batch = is_blake3(c) && m->n_chunks > 1;
   uint64_t chunks_hashed = 0;

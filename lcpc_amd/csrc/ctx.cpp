@@ -624,8 +624,8 @@ int lcpc_ctx_create(const lcpc_params* p, lcpc_ctx** out) {
   lcpc_ctx* c = nullptr;
   LCPC_TRY
   const FieldDesc* f = field_desc((int)p->field);
-  if (!f || (p->hash != LCPC_HASH_BLAKE3 && p->hash != LCPC_HASH_SHA3_256 && p->hash != LCPC_HASH_BLAKE2B)) return LCPC_ERR_ARG;
-  // row shards exchange BLAKE3 chunk chaining values; a SHA3 sponge or a BLAKE2b chain cannot be split by rows
+  if (!f || p->hash > LCPC_HASH_SHA256) return LCPC_ERR_ARG;      // BLAKE3, SHA3-256, BLAKE2b, Keccak-256, SHA-256
+  // row shards exchange BLAKE3 chunk chaining values; a sponge (SHA3-256, Keccak-256) or a chain (BLAKE2b, SHA-256) cannot be split by rows
   if (p->hash != LCPC_HASH_BLAKE3 && p->shard_count > 1) return LCPC_ERR_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev) return LCPC_ERR_NO_DEVICE;

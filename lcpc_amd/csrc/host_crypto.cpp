@@ -430,7 +430,8 @@ void blake3_host(const uint8_t* in, size_t len, uint8_t out[32]) {
   memcpy(out, cv, 32);
 }
 
-void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
+// Keccak[512](M || domain bits, 256): rate 136; dom = the domain bits and the first bit of pad10*1 (SHA3-256: 0x06, Keccak-256: 0x01)
+static void keccak_sponge_256(const uint8_t* in, size_t len, uint8_t dom, uint8_t out[32]) {
   constexpr size_t RATE = 136;
   uint64_t a[25] = {0};
   uint8_t blk[RATE];
@@ -438,9 +439,9 @@ void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
     const size_t n = len < RATE ? len : RATE;
     memcpy(blk, in, n);
     const bool last = n < RATE;
-    if (last) {                                    // pad10*1 with the SHA3 domain bits
+    if (last) {                                    // pad10*1 behind the domain bits
       memset(blk + n, 0, RATE - n);
-      blk[n] ^= 0x06;
+      blk[n] ^= dom;
       blk[RATE - 1] ^= 0x80;
     }
     for (int i = 0; i < 17; i++) { uint64_t w; memcpy(&w, blk + 8 * i, 8); a[i] ^= w; }
@@ -450,6 +451,8 @@ void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
   }
   memcpy(out, a, 32);
 }
+void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]) { keccak_sponge_256(in, len, 0x06, out); }
+void keccak256_host(const uint8_t* in, size_t len, uint8_t out[32]) { keccak_sponge_256(in, len, 0x01, out); }
 
 namespace {
 constexpr uint64_t B2_IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
@@ -503,6 +506,56 @@ void blake2b_host(const uint8_t* in, size_t len, uint8_t out[64]) {
   t += len;
   b2_compress(h, blk, t, true);
   memcpy(out, h, 64);
+}
+
+namespace {
+constexpr uint32_t S2_K[64] = {
+    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u,
+    0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu,
+    0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u,
+    0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u,
+    0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
+    0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+// the compression function of FIPS 180-4 section 6.2.2 on one 64-byte block
+void s2_compress(uint32_t h[8], const uint8_t blk[64]) {
+  uint32_t w[64];
+  for (int i = 0; i < 16; i++)
+    w[i] = (uint32_t)blk[4 * i] << 24 | (uint32_t)blk[4 * i + 1] << 16 | (uint32_t)blk[4 * i + 2] << 8 | (uint32_t)blk[4 * i + 3];
+  for (int i = 16; i < 64; i++) {
+    const uint32_t s0 = ror32(w[i - 15], 7) ^ ror32(w[i - 15], 18) ^ (w[i - 15] >> 3);
+    const uint32_t s1 = ror32(w[i - 2], 17) ^ ror32(w[i - 2], 19) ^ (w[i - 2] >> 10);
+    w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+  }
+  uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+  for (int i = 0; i < 64; i++) {
+    const uint32_t t1 = hh + (ror32(e, 6) ^ ror32(e, 11) ^ ror32(e, 25)) + ((e & f) ^ (~e & g)) + S2_K[i] + w[i];
+    const uint32_t t2 = (ror32(a, 2) ^ ror32(a, 13) ^ ror32(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+    hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+}
+}  // namespace
+
+void sha256_host(const uint8_t* in, size_t len, uint8_t out[32]) {
+  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  const uint64_t bits = (uint64_t)len * 8;
+  while (len >= 64) {
+    s2_compress(h, in);
+    in += 64; len -= 64;
+  }
+  // the tail, 0x80, zeros and the big-endian bit length: one block if the tail leaves 9 bytes free, else two
+  uint8_t blk[128];
+  memset(blk, 0, sizeof blk);
+  memcpy(blk, in, len);
+  blk[len] = 0x80;
+  const size_t n = len < 56 ? 64 : 128;
+  for (int i = 0; i < 8; i++) blk[n - 1 - i] = (uint8_t)(bits >> (8 * i));
+  s2_compress(h, blk);
+  if (n == 128) s2_compress(h, blk + 64);
+  for (int i = 0; i < 8; i++) {
+    out[4 * i] = (uint8_t)(h[i] >> 24); out[4 * i + 1] = (uint8_t)(h[i] >> 16); out[4 * i + 2] = (uint8_t)(h[i] >> 8); out[4 * i + 3] = (uint8_t)h[i];
+  }
 }
 
 }  // namespace lcpc

@@ -68,5 +68,9 @@ void blake3_host(const uint8_t* in, size_t len, uint8_t out[32]);
 void sha3_256_host(const uint8_t* in, size_t len, uint8_t out[32]);
 // BLAKE2b-512 (RFC 7693, unkeyed, 64-byte output) of a contiguous message: portable C++
 void blake2b_host(const uint8_t* in, size_t len, uint8_t out[64]);
+// Keccak-256 = Keccak[512](M || 01, 256): the sponge of sha3_256_host with the pre-FIPS padding (first padding byte 0x01, not 0x06)
+void keccak256_host(const uint8_t* in, size_t len, uint8_t out[32]);
+// SHA-256 (FIPS 180-4) of a contiguous message: portable C++
+void sha256_host(const uint8_t* in, size_t len, uint8_t out[32]);
 
 }  // namespace lcpc

@@ -409,7 +409,10 @@ template <typename T> int ensure_dev(ErrText* err, T** p, uint64_t* cap, uint64_
 inline size_t elem_bytes(const lcpc_ctx* c) { return (size_t)8 * c->L; }
 inline bool is_sha3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA3_256; }
 inline bool is_blake2b(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE2B; }
-// BLAKE3 is the only digest whose leaf hash splits into chunks (row batches, row shards); SHA3-256 and BLAKE2b are one serial chain
+inline bool is_keccak256(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_KECCAK256; }
+inline bool is_sha256(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA256; }
+// BLAKE3 is the only digest whose leaf hash splits into chunks (row batches, row shards); SHA3-256, BLAKE2b, Keccak-256 and SHA-256
+// are one serial chain
 inline bool is_blake3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE3; }
 // bytes of one Output<D>: a hashes slot, a root, a path entry (32; BLAKE2b 64)
 inline uint32_t digest_len(const lcpc_ctx* c) { return is_blake2b(c) ? 64u : 32u; }

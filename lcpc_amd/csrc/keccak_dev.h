@@ -1,4 +1,4 @@
-// lcpc_amd/csrc/keccak_dev.h -- Keccak-f[1600] for gfx950, one sponge per lane (SHA3-256, FIPS 202).
+// lcpc_amd/csrc/keccak_dev.h -- Keccak-f[1600] for gfx950, one sponge per lane (SHA3-256, FIPS 202; Keccak-256).
 //
 // The digest D of LcCommit<D, E> (lcpc-2d/src/lib.rs:172-184) when the encoder is built with LCPC_HASH_SHA3_256:
 // leaf = SHA3-256(0^32 || to_repr(col[0]) || ...) (lib.rs:719-735), parent = SHA3-256(left || right) (lib.rs:770-775).
@@ -17,6 +17,10 @@ namespace lcpc {
 namespace kc {
 
 struct Lane { uint32_t lo, hi; };
+
+// the byte that opens pad10*1 (the domain bits and the first padding bit): SHA3-256 (FIPS 202), and Keccak-256, the pre-FIPS
+// padding of LCPC_HASH_KECCAK256 -- the same sponge otherwise (rate 136, 32-byte output)
+constexpr uint32_t KC_DOM_SHA3 = 0x06u, KC_DOM_KECCAK = 0x01u;
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t r;

@@ -108,6 +108,15 @@ hipError_t launch_leaf_tree(int nl, const LeafArgs& a, uint32_t* hashes, uint64_
 hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);
 // the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
 hipError_t launch_sha3_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
+// Keccak-256 (LCPC_HASH_KECCAK256): the same kernels with the padding's first byte 0x01 instead of 0x06
+hipError_t launch_keccak256_leaves(int nl, const LeafArgs& a, hipStream_t st);
+hipError_t launch_keccak256_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
+
+// ---- SHA-256 digest (sha256.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA256 ----
+// leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a Merkle-Damgard chain is not split); a.out = LcCommit.hashes
+hipError_t launch_sha256_leaves(int nl, const LeafArgs& a, hipStream_t st);
+// the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
+hipError_t launch_sha256_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
 
 // ---- BLAKE2b-512 digest (blake2b.hip): the same leaves and tree with 64-byte digests (16 words per hashes slot) ----
 // leaf digests [n_cols][16] of the whole column (a.n_chunks_* unused: the chain is not split); a.out = LcCommit.hashes

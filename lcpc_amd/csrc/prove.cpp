@@ -236,6 +236,8 @@ struct Rd {
 void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out) {
   if (hash == LCPC_HASH_SHA3_256) sha3_256_host(in, len, out);
   else if (hash == LCPC_HASH_BLAKE2B) blake2b_host(in, len, out);
+  else if (hash == LCPC_HASH_KECCAK256) keccak256_host(in, len, out);
+  else if (hash == LCPC_HASH_SHA256) sha256_host(in, len, out);
   else blake3_host(in, len, out);
 }
 // D(Output<D>::default() || to_repr(col[0]) || ...) with the encoder's digest (lib.rs:719-735): a prefix of dl zero bytes

@@ -1,4 +1,7 @@
-// lcpc_amd/csrc/sha3.hip -- SHA3-256 column hash and Merkle tree (LcCommit<Sha3_256, E>) for gfx950.
+// lcpc_amd/csrc/sha3.hip -- SHA3-256 and Keccak-256 column hash and Merkle tree (LcCommit<Sha3_256, E>, LcCommit<Keccak256, E>)
+// for gfx950.  The two differ in one constant, the byte DOM that opens the padding: 0x06 for SHA3-256 (FIPS 202), 0x01 for
+// Keccak-256 (the pre-FIPS padding, the EVM's KECCAK256).  It is a template parameter of every kernel here; what follows is
+// written for SHA3-256.
 //
 //   leaf[c] = SHA3-256(0^32 || to_repr(comm[0][c]) || ... || to_repr(comm[R-1][c]))   (lcpc-2d lib.rs:719-735)
 //   node    = SHA3-256(left || right)                                               (lib.rs:770-775)
@@ -46,25 +49,34 @@ __device__ __forceinline__ void sha3_absorb_block(Lane s[25], const LeafArgs& a,
   }
 }
 
-template <int NL, bool CANON, int B>
+template <int NL, bool CANON, u32 DOM, int B>
 __device__ __forceinline__ void sha3_group_step(Lane s[25], const LeafArgs& a, u64 col, u64 j, u64 n_words, u64 n_blocks) {
   constexpr int L = NL / 2;
   const u64 blk = j * L + B;
   if (blk >= n_blocks) return;
   sha3_absorb_block<NL, CANON, B>(s, a, col, (int64_t)(17 * j));
   if (17 * blk + 17 > n_words) {
-    // the block that holds the end of the message: pad10*1 with the SHA3 domain bits (0x06 ... 0x80); the message is whole
-    // words, so the 0x06 byte starts lane n_words - 17 blk
+    // the block that holds the end of the message: pad10*1 behind the domain bits (DOM ... 0x80; SHA3: 0x06); the message is whole
+    // words, so the DOM byte starts lane n_words - 17 blk
     const u32 q = (u32)(n_words - 17 * blk);
+    if constexpr (DOM == kc::KC_DOM_SHA3) {
 #pragma unroll
-    for (u32 p = 0; p < 17; p++) s[p].lo ^= (p == q) ? 6u : 0u;
+      for (u32 p = 0; p < 17; p++) s[p].lo ^= (p == q) ? DOM : 0u;
+    } else {
+      // the same selects as the SHA3-256 instantiation: the byte comes from a scalar register the compiler cannot see through,
+      // so that it does not turn `? 1 : 0` into a per-lane boolean and allocate the whole kernel differently
+      u32 dom = DOM;
+      asm volatile("" : "+s"(dom));
+#pragma unroll
+      for (u32 p = 0; p < 17; p++) s[p].lo ^= (p == q) ? dom : 0u;
+    }
     s[16].hi ^= 0x80000000u;
   }
   kc::keccak_f(s);
-  if constexpr (B + 1 < L) sha3_group_step<NL, CANON, B + 1>(s, a, col, j, n_words, n_blocks);
+  if constexpr (B + 1 < L) sha3_group_step<NL, CANON, DOM, B + 1>(s, a, col, j, n_words, n_blocks);
 }
 
-template <int NL, bool CANON>
+template <int NL, bool CANON, u32 DOM>
 __global__ void __launch_bounds__(256) sha3_leaf_kernel(LeafArgs a) {
   const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
   if (col >= a.n_cols) return;
@@ -74,19 +86,20 @@ __global__ void __launch_bounds__(256) sha3_leaf_kernel(LeafArgs a) {
   Lane s[25];
 #pragma unroll
   for (int i = 0; i < 25; i++) s[i] = {0u, 0u};
-  for (u64 j = 0; j * L < n_blocks; j++) sha3_group_step<NL, CANON, 0>(s, a, col, j, n_words, n_blocks);
+  for (u64 j = 0; j * L < n_blocks; j++) sha3_group_step<NL, CANON, DOM, 0>(s, a, col, j, n_words, n_blocks);
   u32* o = a.out + col * 8;
   *reinterpret_cast<uint4*>(o) = make_uint4(s[0].lo, s[0].hi, s[1].lo, s[1].hi);
   *reinterpret_cast<uint4*>(o + 4) = make_uint4(s[2].lo, s[2].hi, s[3].lo, s[3].hi);
 }
 
-hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st) {
+template <u32 DOM>
+static hipError_t launch_keccak_leaves(int nl, const LeafArgs& a, hipStream_t st) {
   if (a.n_cols == 0) return hipSuccess;
   const dim3 grid((unsigned)((a.n_cols + 255) / 256));
 #define SHA3_CASE(NLV)                                                                                          \
   case NLV:                                                                                                     \
-    if (a.canon_in) hipLaunchKernelGGL((sha3_leaf_kernel<NLV, true>), grid, dim3(256), 0, st, a);            \
-    else hipLaunchKernelGGL((sha3_leaf_kernel<NLV, false>), grid, dim3(256), 0, st, a);                      \
+    if (a.canon_in) hipLaunchKernelGGL((sha3_leaf_kernel<NLV, true, DOM>), grid, dim3(256), 0, st, a);       \
+    else hipLaunchKernelGGL((sha3_leaf_kernel<NLV, false, DOM>), grid, dim3(256), 0, st, a);                 \
     break;
   switch (nl) {
     SHA3_CASE(2) SHA3_CASE(4) SHA3_CASE(6) SHA3_CASE(8)
@@ -95,15 +108,18 @@ hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st) {
 #undef SHA3_CASE
   return hipGetLastError();
 }
+hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st) { return launch_keccak_leaves<kc::KC_DOM_SHA3>(nl, a, st); }
+hipError_t launch_keccak256_leaves(int nl, const LeafArgs& a, hipStream_t st) { return launch_keccak_leaves<kc::KC_DOM_KECCAK>(nl, a, st); }
 
-// parent = SHA3-256(left || right): 8 words, one permutation
+// parent = SHA3-256(left || right) (DOM = 0x01: Keccak-256): 8 words, one permutation
+template <u32 DOM>
 __device__ __forceinline__ void sha3_node(u32 o[8], const u32* l, const u32* r) {
   Lane s[25];
 #pragma unroll
   for (int i = 0; i < 25; i++) s[i] = {0u, 0u};
 #pragma unroll
   for (int i = 0; i < 4; i++) { s[i] = {l[2 * i], l[2 * i + 1]}; s[4 + i] = {r[2 * i], r[2 * i + 1]}; }
-  s[8].lo = 6u;
+  s[8].lo = DOM;
   s[16].hi = 0x80000000u;
   kc::keccak_f(s);
 #pragma unroll
@@ -112,6 +128,7 @@ __device__ __forceinline__ void sha3_node(u32 o[8], const u32* l, const u32* r) 
 
 // the counterpart of merkle_subtree_kernel (kernels.hip): each workgroup folds 2^lsub consecutive nodes of a level `lsub` levels
 // up through LDS, one node per lane, writing every level to its slot of the flat `hashes` array (lib.rs:656-666, 747-760)
+template <u32 DOM>
 __global__ void __launch_bounds__(256) sha3_merkle_subtree_kernel(u32* hashes, u64 in_off, u64 width, u32 lsub, u32* root_out) {
   __shared__ u32 buf[256 * 8];
   const u32 tid = threadIdx.x;
@@ -123,7 +140,7 @@ __global__ void __launch_bounds__(256) sha3_merkle_subtree_kernel(u32* hashes, u
     const u32* g = hashes + (layer_in + base + 2 * tid) * 8;
 #pragma unroll
     for (int i = 0; i < 8; i++) { l[i] = g[i]; r[i] = g[8 + i]; }
-    sha3_node(o, l, r);
+    sha3_node<DOM>(o, l, r);
     u32* d = hashes + (layer_out + (base >> 1) + tid) * 8;
 #pragma unroll
     for (int i = 0; i < 8; i++) { d[i] = o[i]; buf[tid * 8 + i] = o[i]; }
@@ -135,7 +152,7 @@ __global__ void __launch_bounds__(256) sha3_merkle_subtree_kernel(u32* hashes, u
     layer_out = layer_in + w;
     n_out >>= 1;
     const bool act = tid < n_out;
-    if (act) sha3_node(o, buf + 2 * tid * 8, buf + (2 * tid + 1) * 8);
+    if (act) sha3_node<DOM>(o, buf + 2 * tid * 8, buf + (2 * tid + 1) * 8);
     __syncthreads();
     if (act) {
       u32* d = hashes + (layer_out + (base >> j) + tid) * 8;
@@ -149,20 +166,27 @@ __global__ void __launch_bounds__(256) sha3_merkle_subtree_kernel(u32* hashes, u
   }
 }
 
-hipError_t launch_sha3_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) {
+template <u32 DOM>
+static hipError_t launch_keccak_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) {
   u64 in_off = 0, width = np2;
   while (width > 1) {
     u32 lw = 0;
     while (((u64)1 << lw) < width) lw++;
     const u32 lsub = lw < 9 ? lw : 9;
     const u64 nwg = width >> lsub;
-    hipLaunchKernelGGL(sha3_merkle_subtree_kernel, dim3((unsigned)nwg), dim3(256), 0, st, hashes, in_off, width, lsub,
+    hipLaunchKernelGGL(sha3_merkle_subtree_kernel<DOM>, dim3((unsigned)nwg), dim3(256), 0, st, hashes, in_off, width, lsub,
                        lsub == lw ? root_out : (u32*)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     for (u32 j = 0; j < lsub; j++) { in_off += width; width >>= 1; }
   }
   return hipSuccess;
+}
+hipError_t launch_sha3_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) {
+  return launch_keccak_merkle_tree<kc::KC_DOM_SHA3>(hashes, np2, st, root_out);
+}
+hipError_t launch_keccak256_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) {
+  return launch_keccak_merkle_tree<kc::KC_DOM_KECCAK>(hashes, np2, st, root_out);
 }
 
 }  // namespace lcpc

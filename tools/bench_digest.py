@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""BLAKE3 vs SHA3-256 vs BLAKE2b commitment digest on one GPU: the kernel-group times of lcpc_get_timings for device-resident commits
+"""BLAKE3 vs SHA3-256 vs BLAKE2b vs Keccak-256 vs SHA-256 commitment digest on one GPU: the kernel-group times of lcpc_get_timings for device-resident commits
 (Ligero Ft255 2^20 / 2^24 / 2^26, Ligero Ft127 2^24, Brakedown Ft255 2^24), and prove / verify wall times at 2^24.
 
 One JSON line per (config, digest) on stdout, then a Markdown table.  The same input vector (drawn on the device, seed 0) is
-committed under every digest; the roots must differ.
+committed under every digest; the roots must differ.  Keccak-256 runs SHA3-256's instruction stream with another constant, so its times belong inside the spread that repeated
+SHA3-256 measurements show: after the five digests the two are measured again, alternating ("sha3_256#2", "keccak256#2", ...
+up to #4; each a fresh encoder and commitment, median of --steps commits), and the last lines report min / median / max of both.
 
   python tools/bench_digest.py [--steps K] [--warmup W] [--only NAME ...]
 """
@@ -31,6 +33,10 @@ CONFIGS = [  # name, kind, field, log2 len, prove / verify timed
     ("lig_ft127_24", "ligero", 1, 24, True),
     ("sdig_ft255_24", "sdig", 3, 24, True),
 ]
+
+
+DIGESTS = ("blake3", "sha3_256", "blake2b", "keccak256", "sha256")
+REPEATS = tuple("%s#%d" % (d, k) for k in (2, 3, 4) for d in ("sha3_256", "keccak256"))
 
 
 def make_enc(kind, fid, n, digest):
@@ -92,12 +98,14 @@ def main():
         if a.only and name not in a.only:
             continue
         pair = {}
-        for digest in ("blake3", "sha3_256", "blake2b"):
-            r = run(name, kind, fid, log_n, pv, digest, a.steps, a.warmup)
+        for digest in DIGESTS + REPEATS:
+            r = run(name, kind, fid, log_n, pv and "#" not in digest, digest.split("#")[0], a.steps, a.warmup)
+            r["digest"] = digest
             print(json.dumps(r), flush=True)
             pair[digest] = r
             rows.append(r)
-        assert len({r["root"] for r in pair.values()}) == len(pair)
+        assert all(pair[d]["root"] == pair[d.split("#")[0]]["root"] for d in REPEATS)
+        assert len({r["root"] for d, r in pair.items() if "#" not in d}) == len(DIGESTS)
     print()
     print("| config | digest | rows x cols | encode ms | hash ms | merkle ms | total ms | prove ms | verify ms |")
     print("|---|---|---|---|---|---|---|---|---|")
@@ -105,6 +113,17 @@ def main():
         pv = ("%.1f" % r["prove_ms"], "%.1f" % r["verify_ms"]) if "prove_ms" in r else ("", "")
         print("| %s | %s | %d x %d | %.3f | %.3f | %.3f | %.3f | %s | %s |" % (r["config"], r["digest"], r["n_rows"], r["n_cols"],
               r["encode_ms"], r["hash_ms"], r["merkle_ms"], r["total_ms"], pv[0], pv[1]))
+    print()
+    by = {(r["config"], r["digest"]): r for r in rows}
+    for name in sorted({r["config"] for r in rows}, key=[c[0] for c in CONFIGS].index):
+        def spread(d, key):
+            v = sorted(by[(name, x)][key] for x in (d,) + tuple(r for r in REPEATS if r.startswith(d + "#")))
+            return "%.3f / %.3f / %.3f" % (v[0], statistics.median(v), v[-1])
+        print("%s: hash ms min / median / max of 4: SHA3-256 %s, Keccak-256 %s; merkle: SHA3-256 %s, Keccak-256 %s; "
+              "SHA-256 hash / SHA3-256 median hash = %.3f" % (name, spread("sha3_256", "hash_ms"), spread("keccak256", "hash_ms"),
+                                                               spread("sha3_256", "merkle_ms"), spread("keccak256", "merkle_ms"),
+                                                               by[(name, "sha256")]["hash_ms"] / statistics.median(
+                                                                   by[(name, x)]["hash_ms"] for x in ("sha3_256",) + tuple(r for r in REPEATS if r.startswith("sha3_256#")))))
 
 
 if __name__ == "__main__":
