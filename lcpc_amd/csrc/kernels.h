@@ -187,7 +187,8 @@ struct SpmmTArgs {
   const uint32_t* rowptr;       // [m+1]
   const uint32_t* colidx;       // [nnz]
   const uint32_t* vals;         // [nnz][NL]  Montgomery (R = 2^(32 NL))
-  const uint32_t* vals29;       // Ft255: [nnz][12]  value * 2^261 mod p as 9 x 29-bit limbs
+  const uint32_t* vals29;       // Ft255: [nnz][12]  value * 2^261 mod p as 9 x 29-bit limbs (required: null is refused); Ft127 / Ft191:
+                                // [nnz][8] value * R' mod p as 5 / 7 limbs, or null for the Wide<NL> path
   uint64_t m;
 };
 hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st);
@@ -197,7 +198,7 @@ hipError_t launch_sdig_rs_t(int nl, const uint32_t* in_t, uint32_t n_in, uint32_
 // Reed-Solomon base case (encode.rs:97-110): out[row][out_off + k] = sum_j in[row][j] (k+1)^j
 hipError_t launch_sdig_rs(int nl, const uint32_t* in, uint64_t in_stride, uint32_t n_in, uint32_t* mat, uint64_t stride,
                           uint64_t out_off, uint32_t n_out, uint64_t n_rows, const uint32_t* r2, hipStream_t st);
-// copy rows with zero padding: dst[row][0..n_valid) = src[row][..], rest zero (Brakedown row setup)
+// copy rows: dst[row][0..n_valid) = src[row][..]; the rest of a dst row is not written (Brakedown row setup: the encode fills it)
 hipError_t launch_pad_rows(int nl, const uint32_t* src, uint64_t src_stride, uint32_t* dst, uint64_t dst_stride,
                            uint64_t n_valid, uint64_t n_rows, hipStream_t st);
 

@@ -1508,6 +1508,7 @@ __global__ void __launch_bounds__(128 * SL) spmm_t_sliced_kernel(SpmmTArgs a) {
 }
 hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st) {
   if (a.m == 0 || a.n_rows == 0) return hipSuccess;
+  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // Ft255 has the limb path only here (spmm_t_terms reads vals29 unasked)
   if (a.m >= 8192) {
     // a last group of <= 48 rows goes to the packed-tail kernel (Ft255 limb path), the whole 64-row groups stay lane = row
     u32 n_main = (u32)a.n_rows;

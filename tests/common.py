@@ -131,6 +131,37 @@ def ntt_maxlimb(fid):
     return maximal_limbs(fid, W, N - 1)
 
 
+def _ln_fields():
+    """{fid: (N, W, NL, STRIDE)} of lcpc_amd/csrc/field_ln.h's LnField specialisations"""
+    import re
+    t = open(os.path.join(os.path.dirname(GOLDEN), os.pardir, "lcpc_amd", "csrc", "field_ln.h")).read()
+    out = {}
+    for fid, name in enumerate(("FT63", "FT127", "FT191", "FT255")):
+        m = re.search(r"struct LnField<%s> \{\s*static constexpr int FID = %s, N = (\d+), W = (\d+), NL = (\d+), WAVES = \d+, STRIDE = (\d+);"
+                      % (name, name), t)
+        out[fid] = tuple(int(v) for v in m.groups())
+    return out
+
+
+LN_SHAPE = {fid: v[:2] for fid, v in _ln_fields().items()}        # (N limbs, W bits): R' = 2^(N W)
+LN_STRIDE = {fid: v[3] for fid, v in _ln_fields().items()}        # words per limb-form table entry
+
+
+def ln_maxx(fid):
+    """the gathered operand of the Brakedown limb dot products (Ft127 / Ft191 / Ft255: ln::from_packed<FT> of the stored element) whose
+    limbs below the top one are all 2^W - 1; for Ft255 this is maxc"""
+    N, W = LN_SHAPE[fid]
+    return maximal_limbs(fid, W, N - 1)
+
+
+def ln_maxv(fid):
+    """the stored matrix value whose multiplied form has those limbs: the kernels multiply v R' / R mod p (R = 2^(64 L) the stored
+    Montgomery form, R' = 2^(N W): launch_ntt_lns_roots; Ft255: five doublings, R' / R = 2^5, so this is maxt)"""
+    p = field_p(fid)
+    N, W = LN_SHAPE[fid]
+    return ln_maxx(fid) * pow(2, 64 * FIELD_L[fid], p) * pow(2, -N * W, p) % p
+
+
 def to_limbs(vals, L):
     """python ints -> (n, L) uint64 limbs"""
     return np.array([[(v >> (64 * k)) & ((1 << 64) - 1) for k in range(L)] for v in vals], np.uint64).reshape(-1, L)

@@ -265,3 +265,26 @@ def test_product_library_has_no_test_hooks():
     assert b"LCPC_TEST_FAIL" in open(hooks, "rb").read()
     syms = lambda p: sorted(l.split()[-1] for l in subprocess.check_output(["nm", "-D", "--defined-only", p], text=True).splitlines() if " T lcpc_" in l)
     assert syms(hooks) == syms(_lib.LIB_PATH)
+
+
+def test_k2_harness_is_a_separate_library():
+    """lib/liblcpc_k2_harness.so (tests/native/k2_harness.cpp, the third artefact of the Makefile) exports the k2h_* entry points of
+    tests/k2_harness.py and nothing of the product, which it links against instead of carrying a copy: the product's own export list
+    is the header's, with or without the harness beside it."""
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import k2_harness
+    assert os.path.dirname(k2_harness.LIB_PATH) == os.path.dirname(_lib.LIB_PATH) and os.path.exists(k2_harness.LIB_PATH)
+    defined = [l.split() for l in subprocess.check_output(["nm", "-D", "--defined-only", k2_harness.LIB_PATH], text=True).splitlines()]
+    funcs = sorted(l[-1] for l in defined if l[-2] in "TtWw")
+    assert funcs == sorted(k2_harness.SYMBOLS) and all(f.startswith("k2h_") for f in funcs)
+    assert not any("lcpc" in l[-1] for l in defined)
+    needed = re.findall(r"NEEDED.*\[(.*?)\]", subprocess.run(["readelf", "-d", k2_harness.LIB_PATH], capture_output=True, text=True).stdout)
+    assert "liblcpc_hip.so" in needed
+    product = sorted(l.split()[-1] for l in subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True).splitlines()
+                     if " T lcpc_" in l)
+    assert product == header_symbols() and len(product) == 58
+    assert b"k2h_" not in open(_lib.LIB_PATH, "rb").read()
+    mk = open(os.path.join(ROOT, "lcpc_amd", "csrc", "Makefile")).read()
+    assert "tests/native/k2_harness.cpp" in mk and "$(K2H_OUT)" in mk.split("\nall:")[1].split("\n")[0]

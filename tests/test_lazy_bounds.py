@@ -79,6 +79,29 @@ def wide_batches():
     return out
 
 
+def k2_thresholds():
+    """what decides which Brakedown (K2) kernel runs and where its lazy path ends, read from kernels.hip / internal.h: launch_spmm_t's
+    selection by the number of outputs m (spmm_t_kernel<NL, OPW> from `opw_min_m`; below it spmm_t_sliced_kernel<NL, SL> with SL by
+    falling m: m > above[i] takes sliced_sl[i], the rest the last one), the longest last row group the packed-tail kernel takes, the
+    lanes per output of spmv_kernel and the terms per lane up to which it stays lazy, and the row count from which the host takes
+    the position-major path.  tests/test_k2_cases.py restates the selection on these, so a changed threshold fails there instead of
+    silently moving a case to another kernel."""
+    k = _src("kernels.hip")
+    b = _body(k, "hipError_t launch_spmm_t(int nl")
+    one = lambda pat, text: (lambda v: v[0] if len(v) == 1 else pytest.fail("%s: %s" % (pat, v)))(_ints(pat, text))
+    out = dict(opw_min_m=one(r"a\.m >= (\d+)\)", b), sliced_above=_ints(r"a\.m > (\d+)\)", b),
+               sliced_sl=_ints(r"spmm_t_sliced_kernel<NLV, (\d+)>", b), opw=one(r"spmm_t_kernel<NLV, (\d+)>", b),
+               tail_max=one(r"tail <= (\d+)\)", b), rows_per_group=one(r"a\.n_rows & (\d+)\)", b) + 1)
+    assert "nl == 8 && a.vals29 != nullptr && tail != 0 && tail <= " in b            # the tail kernel: Ft255 limb path only
+    b = _body(k, "hipError_t launch_spmv(int nl")
+    out["spmv_sl"] = one(r"constexpr int SL = (\d+);", b)
+    b = _body(k, "__global__ void __launch_bounds__(256) spmv_kernel(")
+    out["spmv_lazy_terms"] = one(r"k1 - k0 <= (\d+) \* SL", b)
+    assert "lazy = a.vals29 != nullptr && k1 - k0 <= " in b and "if constexpr (NL == 8) {" in b
+    out["t_min_rows"] = one(r"constexpr uint64_t SDIG_T_MIN_ROWS = (\d+);", _src("internal.h"))
+    return out
+
+
 def ln_params():
     """{fid: (N, W, NL)} from field_ln.h's LnField specialisations"""
     t = _src("field_ln.h")
@@ -253,6 +276,8 @@ def test_cadences_are_read_from_the_sources():
     assert all(len(set(v)) == 1 for v in wb.values()) and {n: v[0] for n, v in wb.items()} == {
         "collapse_kernel": 8, "spmv_kernel (Wide)": 8, "spmm_t_terms (Wide)": 8}
     assert ln_params() == {0: (3, 26, 2), 1: (5, 29, 4), 2: (7, 29, 6), 3: (9, 29, 8)}
+    assert k2_thresholds() == dict(opw_min_m=8192, sliced_above=[2048, 256], sliced_sl=[2, 4, 8], opw=4, tail_max=48, rows_per_group=64,
+                                   spmv_sl=8, spmv_lazy_terms=60, t_min_rows=24)
 
 
 @pytest.mark.parametrize("name", list(LIMB_ACCS))
