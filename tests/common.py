@@ -387,3 +387,68 @@ def ntt_case_id(fid, log_n, log_rate, general, mid_mb):
     if fid == 3:
         out += "-mid%d" % bool(plan[0]["mid"]) + ("-mb%d" % mid_mb if mid_mb is not None else "")
     return out + ("-blk0gone" if plan[-1]["blk0_gone"] else "")
+
+
+# ---- the BLAKE3 column hash and tree, restated (lcpc_amd/csrc/kernels.hip K3 / K4 launchers, commit.cpp merkleize_device) ---------------
+K3_QUAD_MAX = 65536        # launch_leaf_chunks_nl: n_cols * n_chunks_local <= this runs four lanes per column; leaf_tree_supported's bound too
+K3_SLICE = 32768           # launch_leaf_chunks: chunks per launch (grid.y)
+
+
+def leaf_len(fid, n_rows):
+    """bytes of a column's leaf message: the 32-byte zero prefix and 8 L bytes per row"""
+    return 32 + 8 * FIELD_L[fid] * n_rows
+
+
+def leaf_n_chunks(fid, n_rows):
+    return max(1, -(-leaf_len(fid, n_rows) // 1024))
+
+
+def leaf_last(fid, n_rows):
+    """(bytes in the last chunk, its 64-byte blocks, bytes in its last block)"""
+    b = leaf_len(fid, n_rows) - 1024 * (leaf_n_chunks(fid, n_rows) - 1)
+    nb = max(1, -(-b // 64))
+    return b, nb, b - 64 * (nb - 1)
+
+
+def leaf_quad(n_cols, n_chunks_local):
+    """launch_leaf_chunks_nl: QUAD (four lanes per column) or one lane per column"""
+    return n_cols * n_chunks_local <= K3_QUAD_MAX
+
+
+def leaf_block_phases(fid, chunks):
+    """leaf_chunk_cv block_row0: the word phases (first word of a block inside its first element) over the blocks of `chunks`"""
+    nl = NTT_NL[fid]
+    return {(16 * (16 * c + b) - 8) % nl for c in chunks for b in range(16)}
+
+
+def leaf_tree_supported(n_cols, np2, chunk_begin, n_chunks_local, n_chunks_total):
+    """kernels.hip leaf_tree_supported"""
+    return (n_chunks_total <= 2 and n_chunks_local == n_chunks_total and chunk_begin == 0 and np2 == n_cols and n_cols >= 128
+            and n_cols % 64 == 0 and n_cols * n_chunks_total <= K3_QUAD_MAX)
+
+
+def merkle_launches(np2, levels_done=0):
+    """launch_merkle_tree_from: [(BS, n_workgroups, lsub, branches)] -- branches: the sides of merkle_subtree_kernel's n_out > BS / 4 test
+    its levels take ("lane": one compression per lane, "quad": one per four lanes)"""
+    width, out = np2 >> levels_done, []
+    while width > 1:
+        lw = (width - 1).bit_length()
+        bs, lsub, nwg = (1024, lw, 1) if lw <= 9 else (256, 9, width >> 9)
+        out.append((bs, nwg, lsub, {"lane" if (1 << lsub >> j) > bs // 4 else "quad" for j in range(1, lsub + 1)}))
+        if lw <= 9:
+            break
+        width >>= 9
+    return out
+
+
+def k3_plan(fid, n_rows, n_cols, np2=None):
+    """what an unsharded BLAKE3 commit of n_rows x n_cols launches for its leaves (commit.cpp merkleize_device): path ("fused": leaf_tree_kernel;
+    "one_chunk": leaf_chunk_kernel straight into hashes; "chunks+finish"), quad (None for fused, which is always four lanes per column),
+    hash_launches, levels_done and the tree launches"""
+    np2 = np2 or 1 << (n_cols - 1).bit_length()
+    nc = leaf_n_chunks(fid, n_rows)
+    if leaf_tree_supported(n_cols, np2, 0, nc, nc):
+        return dict(path="fused", quad=None, n_chunks=nc, hash_launches=1, levels_done=6, tree=merkle_launches(np2, 6))
+    path = "one_chunk" if nc == 1 else "chunks+finish"
+    return dict(path=path, quad=leaf_quad(n_cols, nc), n_chunks=nc, hash_launches=1 + (nc > 1), levels_done=0,
+                tree=merkle_launches(np2, 0))

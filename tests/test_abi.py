@@ -267,24 +267,35 @@ def test_product_library_has_no_test_hooks():
     assert syms(hooks) == syms(_lib.LIB_PATH)
 
 
-def test_k2_harness_is_a_separate_library():
-    """lib/liblcpc_k2_harness.so (tests/native/k2_harness.cpp, the third artefact of the Makefile) exports the k2h_* entry points of
-    tests/k2_harness.py and nothing of the product, which it links against instead of carrying a copy: the product's own export list
-    is the header's, with or without the harness beside it."""
+def _harness_is_a_separate_library(module, prefix, source, make_var):
+    import importlib
     import subprocess
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import k2_harness
-    assert os.path.dirname(k2_harness.LIB_PATH) == os.path.dirname(_lib.LIB_PATH) and os.path.exists(k2_harness.LIB_PATH)
-    defined = [l.split() for l in subprocess.check_output(["nm", "-D", "--defined-only", k2_harness.LIB_PATH], text=True).splitlines()]
+    H = importlib.import_module(module)
+    assert os.path.dirname(H.LIB_PATH) == os.path.dirname(_lib.LIB_PATH) and os.path.exists(H.LIB_PATH)
+    defined = [l.split() for l in subprocess.check_output(["nm", "-D", "--defined-only", H.LIB_PATH], text=True).splitlines()]
     funcs = sorted(l[-1] for l in defined if l[-2] in "TtWw")
-    assert funcs == sorted(k2_harness.SYMBOLS) and all(f.startswith("k2h_") for f in funcs)
+    assert funcs == sorted(H.SYMBOLS) and all(f.startswith(prefix) for f in funcs)
     assert not any("lcpc" in l[-1] for l in defined)
-    needed = re.findall(r"NEEDED.*\[(.*?)\]", subprocess.run(["readelf", "-d", k2_harness.LIB_PATH], capture_output=True, text=True).stdout)
+    needed = re.findall(r"NEEDED.*\[(.*?)\]", subprocess.run(["readelf", "-d", H.LIB_PATH], capture_output=True, text=True).stdout)
     assert "liblcpc_hip.so" in needed
     product = sorted(l.split()[-1] for l in subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True).splitlines()
                      if " T lcpc_" in l)
     assert product == header_symbols() and len(product) == 58
-    assert b"k2h_" not in open(_lib.LIB_PATH, "rb").read()
+    assert prefix.encode() not in open(_lib.LIB_PATH, "rb").read()
     mk = open(os.path.join(ROOT, "lcpc_amd", "csrc", "Makefile")).read()
-    assert "tests/native/k2_harness.cpp" in mk and "$(K2H_OUT)" in mk.split("\nall:")[1].split("\n")[0]
+    assert source in mk and "$(%s)" % make_var in mk.split("\nall:")[1].split("\n")[0]
+
+
+def test_k2_harness_is_a_separate_library():
+    """lib/liblcpc_k2_harness.so (tests/native/k2_harness.cpp, the third artefact of the Makefile) exports the k2h_* entry points of
+    tests/k2_harness.py and nothing of the product, which it links against instead of carrying a copy: the product's own export list
+    is the header's, with or without the harness beside it."""
+    _harness_is_a_separate_library("k2_harness", "k2h_", "tests/native/k2_harness.cpp", "K2H_OUT")
+
+
+def test_k3_harness_is_a_separate_library():
+    """the same separation for lib/liblcpc_k3_harness.so (tests/native/k3_harness.cpp, the fourth artefact): k3h_* only, linked against
+    the product, of which the product carries no trace"""
+    _harness_is_a_separate_library("k3_harness", "k3h_", "tests/native/k3_harness.cpp", "K3H_OUT")
