@@ -73,7 +73,10 @@ enum { LCPC_ENC_LIGERO = 0, LCPC_ENC_SDIG = 1 };
  *    two compressions per tree node (the second on a constant padding block).  Measured in DESIGN.md section 6.
  * For SHA3-256, BLAKE2b, Keccak-256 and SHA-256, at each entry point:
  *  - lcpc_commit, lcpc_commit_device, lcpc_commit_from_parts, lcpc_commit_from_bincode: as above.  The host-memory lcpc_commit
- *    hashes after the last row batch instead of behind each batch;
+ *    of a large Ligero input resumes every column's chain behind each of its 16 row batches, for the blocks whose rows that batch
+ *    completed (the chaining values wait in a buffer the commitment object keeps); only the last batch's blocks and the tree run
+ *    after the upload.  Same digests as lcpc_commit_device.  What this gains over hashing after the last batch has not been
+ *    measured yet (DESIGN.md section 6 says how it is to be);
  *  - lcpc_commit_from_bincode refuses (LCPC_ERR_COMMIT) a stream whose `hashes` were made with another digest (or whose
  *    digest entries are not the encoder's length);
  *  - lcpc_prove, lcpc_open_columns, lcpc_collapse: the transcript never sees D; path entries are the encoder's digest length;

@@ -92,6 +92,61 @@ hipError_t launch_blake2b_leaves(int nl, const LeafArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- the same chain a block range at a time (kernels.h: launch_blake2b_leaves_range) ----
+// b2_group_step for the blocks of group j that lie in [b0, b1): a block outside the range is neither loaded nor compressed.  The byte
+// counter of a block that is not the last is 128 (blk + 1), so the chaining value is all a later launch needs
+template <int NL, bool CANON, int B>
+__device__ __forceinline__ void b2_range_step(uint64_t h[8], const LeafArgs& a, u64 col, u64 j, u64 n_words, u64 n_blocks, u64 b0, u64 b1) {
+  constexpr int L = NL / 2;
+  const u64 blk = j * L + B;
+  if (blk >= b0 && blk < b1) {
+    uint64_t m[16];
+    b2_load_block<NL, CANON, B>(m, a, col, (int64_t)(16 * j));
+    const bool last = blk + 1 == n_blocks;
+    b2b::compress(h, m, last ? 8 * n_words : 128 * (blk + 1), last);
+  }
+  if constexpr (B + 1 < L) b2_range_step<NL, CANON, B + 1>(h, a, col, j, n_words, n_blocks, b0, b1);
+}
+
+// state: word i of column c at state[i * n_cols + c]
+template <int NL, bool CANON>
+__global__ void __launch_bounds__(256) blake2b_leaf_range_kernel(LeafArgs a, u64 b0, u64 b1, uint64_t* state) {
+  const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (col >= a.n_cols) return;
+  constexpr int L = NL / 2;
+  const u64 n_words = 8 + (u64)L * a.n_rows_total;
+  const u64 n_blocks = (n_words + 15) / 16;
+  uint64_t h[8];
+  if (b0 == 0) {
+    b2b::init(h);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = state[(u64)i * a.n_cols + col];
+  }
+  for (u64 j = b0 / L; j * L < b1; j++) b2_range_step<NL, CANON, 0>(h, a, col, j, n_words, n_blocks, b0, b1);
+  if (b1 == n_blocks) {
+    b2_store(a.out + col * 16, h);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; i++) state[(u64)i * a.n_cols + col] = h[i];
+  }
+}
+
+hipError_t launch_blake2b_leaves_range(int nl, const LeafArgs& a, uint64_t b0, uint64_t b1, uint64_t* state, hipStream_t st) {
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
+  if (b0 > b1 || b1 > blake2b_leaf_blocks(nl, a.n_rows_total)) return hipErrorInvalidValue;
+  if (a.n_cols == 0 || b0 == b1) return hipSuccess;
+  const dim3 grid((unsigned)((a.n_cols + 255) / 256));
+#define B2_CASE(NLV)                                                                                                        \
+  case NLV:                                                                                                                 \
+    if (a.canon_in) hipLaunchKernelGGL((blake2b_leaf_range_kernel<NLV, true>), grid, dim3(256), 0, st, a, b0, b1, state);   \
+    else hipLaunchKernelGGL((blake2b_leaf_range_kernel<NLV, false>), grid, dim3(256), 0, st, a, b0, b1, state);             \
+    break;
+  switch (nl) { B2_CASE(2) B2_CASE(4) B2_CASE(6) B2_CASE(8) }
+#undef B2_CASE
+  return hipGetLastError();
+}
+
 // parent = BLAKE2b(left || right): 16 words, one compression with t = 128 and the last-block flag
 __device__ __forceinline__ void blake2b_node(u32 o[16], const u32* l, const u32* r) {
   uint64_t m[16], h[8];

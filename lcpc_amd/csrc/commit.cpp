@@ -125,6 +125,28 @@ static int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
   return 0;
 }
 
+// SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b on the host-memory path: a column's chain is resumed behind every row batch
+// (kernels.h launch_*_leaves_range), its chaining value kept in d_chain between the launches
+struct ChainShape { uint32_t prefix_words, block_words, state_words; uint64_t n_blocks; };   // 64-bit words; state in 32-bit words
+static ChainShape chain_shape(const lcpc_ctx* c, uint64_t n_rows) {
+  if (is_blake2b(c)) return {8, 16, BLAKE2B_STATE_WORDS, blake2b_leaf_blocks(c->NL, n_rows)};
+  if (is_sha256(c)) return {4, 8, SHA256_STATE_WORDS, sha256_leaf_blocks(c->NL, n_rows)};
+  return {4, 17, SHA3_STATE_WORDS, sha3_leaf_blocks(c->NL, n_rows)};
+}
+// blocks [b0, b1) of every column's leaf message, all of whose rows are in d_comm
+static int hash_block_range(lcpc_commit_t* m, uint64_t b0, uint64_t b1, hipStream_t st) {
+  const lcpc_ctx* c = m->enc;
+  if (b0 == b1) return 0;
+  LeafArgs la = leaf_args(m);
+  la.out = m->d_hashes;
+  if (is_sha3(c)) HIPCHK(m, launch_sha3_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
+  else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
+  else if (is_sha256(c)) HIPCHK(m, launch_sha256_leaves_range(c->NL, la, b0, b1, m->d_chain, st));
+  else HIPCHK(m, launch_blake2b_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
+  m->launches[1]++;
+  return 0;
+}
+
 // the chunk chaining values of every column in d_cvs (n_chunks > 1) -> leaf digests; then the tree
 static int finish_leaves(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
@@ -480,7 +502,7 @@ void lcpc_commit_destroy(lcpc_commit_t* m) {
   (void)hipSetDevice(m->enc->prm.device);
   m->sets.clear();
   m->sc.release();
-  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs);
+  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs); dev_free(m->d_chain);
   for (auto& t : m->node_tabs) dev_free(t.d);
   dev_free(m->ws.d_tmp); dev_free(m->ws.d_t); dev_free(m->ws.d_mid); dev_free(m->d_gather); dev_free(m->d_xsend); dev_free(m->d_xrecv);
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
@@ -657,11 +679,15 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   if ((rc = order_after_commit(m, m->s_copy)) || (rc = order_after_commit(m, m->s_comp))) return rc;
   if ((rc = zero_coeffs_tail(m, n_coeffs, m->s_copy))) return rc;
   const uint64_t rows_per = (n_rows + NB - 1) / NB;
-  // every digest but BLAKE3: a column's hash is one serial chain over all rows, so nothing is hashed behind the batches -- the whole
-  // column hash runs after the last one (merkleize_device)
   const bool per_batch = is_blake3(c) && m->n_chunks > 1;
   uint64_t chunks_hashed = 0;
   if (per_batch && (rc = ensure_cvs(m, m->n_chunks))) return rc;
+  // every digest but BLAKE3: a column's hash is one serial chain over all rows.  It is resumed behind every batch for the blocks
+  // that batch completed, the chaining values waiting in d_chain; the last batch's launch ends the chain and writes the digests
+  const bool chained = !is_blake3(c);
+  const ChainShape cs = chained ? chain_shape(c, n_rows) : ChainShape{};
+  uint64_t blocks_hashed = 0;
+  if (chained && (rc = ensure_dev(&m->err, &m->d_chain, &m->cap_chain, (uint64_t)cs.state_words * 4 * c->n_cols))) return rc;
   for (int b = 0; b < NB; b++) {
     const uint64_t r0 = (uint64_t)b * rows_per;
     if (r0 >= n_rows) break;
@@ -686,9 +712,16 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
         chunks_hashed = done;
       }
     }
+    // the same for a serial chain: a block is hashed once all its rows are encoded (one that straddles the batch boundary waits for
+    // the next batch and reads its earlier rows from comm again)
+    if (chained) {
+      const uint64_t done = r1 == n_rows ? cs.n_blocks : std::min<uint64_t>(cs.n_blocks, (cs.prefix_words + (uint64_t)(c->NL / 2) * r1) / cs.block_words);
+      if ((rc = hash_block_range(m, blocks_hashed, done, m->s_comp))) return rc;
+      blocks_hashed = done;
+    }
   }
   m->coeffs_view = m->d_coeffs;
-  if ((rc = per_batch ? finish_leaves(m, m->s_comp) : merkleize_device(m, m->s_comp))) return rc;
+  if ((rc = chained ? merkle_top(m, m->s_comp) : per_batch ? finish_leaves(m, m->s_comp) : merkleize_device(m, m->s_comp))) return rc;
   if ((rc = seal_commit(m, m->s_comp, root))) return rc;
   HIPCHK(m, hipStreamSynchronize(m->s_comp));              // later calls use the null stream / caller streams
   HIPCHK(m, hipStreamSynchronize(m->s_copy));              // (the tail memset when no batch followed it)

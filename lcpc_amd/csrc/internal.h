@@ -311,6 +311,8 @@ struct lcpc_commit_s {
   const uint32_t* coeffs_view = nullptr;   // LcCommit.coeffs as prove/collapse read it: d_coeffs, or the caller's buffer
                                            // when the commit was made with LCPC_COMMIT_BORROW_COEFFS
   uint64_t cap_coeff_rows = 0, cap_comm_rows = 0, cap_cvs = 0;
+  uint32_t* d_chain = nullptr;     // host-memory commit under SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: every column's chaining value between
+  uint64_t cap_chain = 0;          // the row batches (kernels.h launch_*_leaves_range), word-major; capacity in bytes; kept across refills
   lcpc::EncodeWs ws;
   bool comm_t = false;             // Brakedown commit with >= sdig_t_min_rows() local rows: the commitment matrix lives in ws.d_t (position-major,
                                    // element (row, col) at (col * n_rows_local + row)); hash / open read it there, d_comm is only

@@ -127,6 +127,27 @@ hipError_t launch_blake2b_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_
 hipError_t launch_blake2b_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
                                        uint32_t* paths, hipStream_t st);
 
+// ---- resumable column hash of the three serial-chain families (sha3.hip, sha256.hip, blake2b.hip) ----
+// The same leaf message hashed a block range at a time: a launch runs blocks [blk_begin, blk_end) of every column's chain.  It
+// starts from the IV / the zero sponge when blk_begin == 0 and from `state` otherwise; it leaves the chaining value in `state`
+// when blk_end is not the message's last block and the digest in a.out (the one-shot layout) when it is.  An empty range launches
+// nothing; a range past the last block is hipErrorInvalidValue.  A launch loads only the rows its blocks hold bytes of, so comm
+// needs nothing behind them yet (the host-memory commit hashes behind each row batch: commit.cpp).
+// state: the chaining value alone, word-major so that consecutive columns are consecutive addresses -- word i of column c at
+// state[i * n_cols + c]: 25 x u64 lanes (sponges), 8 x u32 (SHA-256), 8 x u64 (BLAKE2b; its byte counter is 128 (blk + 1)).
+// blocks of the whole leaf message of n_rows_total rows (padding blocks included); nl = 2 / 4 / 6 / 8
+inline uint64_t sha3_leaf_blocks(int nl, uint64_t n_rows_total) { return (4 + (uint64_t)(nl / 2) * n_rows_total) / 17 + 1; }
+inline uint64_t sha256_leaf_blocks(int nl, uint64_t n_rows_total) {
+  const uint64_t w = 4 + (uint64_t)(nl / 2) * n_rows_total;
+  return w / 8 + 1 + ((w & 7) == 7 ? 1 : 0);
+}
+inline uint64_t blake2b_leaf_blocks(int nl, uint64_t n_rows_total) { return (8 + (uint64_t)(nl / 2) * n_rows_total + 15) / 16; }
+constexpr uint32_t SHA3_STATE_WORDS = 50, SHA256_STATE_WORDS = 8, BLAKE2B_STATE_WORDS = 16;     // u32 words per column
+hipError_t launch_sha3_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
+hipError_t launch_keccak256_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
+hipError_t launch_sha256_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint32_t* state, hipStream_t st);
+hipError_t launch_blake2b_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
+
 struct CollapseArgs {
   const uint32_t* coeffs;      // local rows x n_per_row
   const uint32_t* tensors;     // [n_tensors][n_rows_local]

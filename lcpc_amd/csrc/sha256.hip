@@ -101,6 +101,71 @@ hipError_t launch_sha256_leaves(int nl, const LeafArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- the same chain a block range at a time (kernels.h: launch_sha256_leaves_range) ----
+// s2_group_step for the blocks of group j that lie in [b0, b1): a block outside the range is neither loaded nor compressed
+template <int NL, bool CANON, int B>
+__device__ __forceinline__ void s2_range_step(u32 h[8], const LeafArgs& a, u64 col, u64 j, u64 n_words, u64 n_blocks, u64 b0, u64 b1) {
+  constexpr int L = NL / 2;
+  const u64 blk = j * L + B;
+  if (blk >= b0 && blk < b1) {
+    u32 m[16];
+    s2_load_block<NL, CANON, B>(m, a, col, (int64_t)(8 * j));
+    if (blk == n_words / 8) {               // 0x80 behind the last message word, as in s2_group_step
+      const u32 q = (u32)(n_words - 8 * blk);
+#pragma unroll
+      for (u32 p = 0; p < 8; p++) m[2 * p] |= (p == q) ? 0x80000000u : 0u;
+    }
+    if (blk + 1 == n_blocks) {
+      const u64 bits = 64 * n_words;
+      m[14] = (u32)(bits >> 32);
+      m[15] = (u32)bits;
+    }
+    s256::compress(h, m);
+  }
+  if constexpr (B + 1 < L) s2_range_step<NL, CANON, B + 1>(h, a, col, j, n_words, n_blocks, b0, b1);
+}
+
+// state: word i of column c at state[i * n_cols + c] (the working h[], not byte-swapped)
+template <int NL, bool CANON>
+__global__ void __launch_bounds__(256) sha256_leaf_range_kernel(LeafArgs a, u64 b0, u64 b1, u32* state) {
+  const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (col >= a.n_cols) return;
+  constexpr int L = NL / 2;
+  const u64 n_words = 4 + (u64)L * a.n_rows_total;
+  const u64 n_blocks = n_words / 8 + 1 + ((n_words & 7) == 7 ? 1 : 0);
+  u32 h[8];
+  if (b0 == 0) {
+    s256::init(h);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = state[(u64)i * a.n_cols + col];
+  }
+  for (u64 j = b0 / L; j * L < b1; j++) s2_range_step<NL, CANON, 0>(h, a, col, j, n_words, n_blocks, b0, b1);
+  if (b1 == n_blocks) {
+    u32* o = a.out + col * 8;
+    *reinterpret_cast<uint4*>(o) = make_uint4(s256::bswap(h[0]), s256::bswap(h[1]), s256::bswap(h[2]), s256::bswap(h[3]));
+    *reinterpret_cast<uint4*>(o + 4) = make_uint4(s256::bswap(h[4]), s256::bswap(h[5]), s256::bswap(h[6]), s256::bswap(h[7]));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; i++) state[(u64)i * a.n_cols + col] = h[i];
+  }
+}
+
+hipError_t launch_sha256_leaves_range(int nl, const LeafArgs& a, uint64_t b0, uint64_t b1, uint32_t* state, hipStream_t st) {
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
+  if (b0 > b1 || b1 > sha256_leaf_blocks(nl, a.n_rows_total)) return hipErrorInvalidValue;
+  if (a.n_cols == 0 || b0 == b1) return hipSuccess;
+  const dim3 grid((unsigned)((a.n_cols + 255) / 256));
+#define S2_CASE(NLV)                                                                                                        \
+  case NLV:                                                                                                                 \
+    if (a.canon_in) hipLaunchKernelGGL((sha256_leaf_range_kernel<NLV, true>), grid, dim3(256), 0, st, a, b0, b1, state);    \
+    else hipLaunchKernelGGL((sha256_leaf_range_kernel<NLV, false>), grid, dim3(256), 0, st, a, b0, b1, state);              \
+    break;
+  switch (nl) { S2_CASE(2) S2_CASE(4) S2_CASE(6) S2_CASE(8) }
+#undef S2_CASE
+  return hipGetLastError();
+}
+
 // parent = SHA-256(left || right): 64 message bytes are one block, the padding a second one that is the same for every node
 __device__ __forceinline__ void sha256_node(u32 o[8], const u32* l, const u32* r) {
   u32 m[16], h[8];

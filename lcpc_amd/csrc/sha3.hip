@@ -111,6 +111,77 @@ static hipError_t launch_keccak_leaves(int nl, const LeafArgs& a, hipStream_t st
 hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st) { return launch_keccak_leaves<kc::KC_DOM_SHA3>(nl, a, st); }
 hipError_t launch_keccak256_leaves(int nl, const LeafArgs& a, hipStream_t st) { return launch_keccak_leaves<kc::KC_DOM_KECCAK>(nl, a, st); }
 
+// ---- the same chain a block range at a time (kernels.h: launch_sha3_leaves_range) ----
+// sha3_group_step for the blocks of group j that lie in [b0, b1): a block outside the range is neither loaded nor permuted
+template <int NL, bool CANON, u32 DOM, int B>
+__device__ __forceinline__ void sha3_range_step(Lane s[25], const LeafArgs& a, u64 col, u64 j, u64 n_words, u64 b0, u64 b1) {
+  constexpr int L = NL / 2;
+  const u64 blk = j * L + B;
+  if (blk >= b0 && blk < b1) {
+    sha3_absorb_block<NL, CANON, B>(s, a, col, (int64_t)(17 * j));
+    if (17 * blk + 17 > n_words) {          // the block that holds the end of the message: padded as in sha3_group_step
+      const u32 q = (u32)(n_words - 17 * blk);
+      u32 dom = DOM;
+      asm volatile("" : "+s"(dom));
+#pragma unroll
+      for (u32 p = 0; p < 17; p++) s[p].lo ^= (p == q) ? dom : 0u;
+      s[16].hi ^= 0x80000000u;
+    }
+    kc::keccak_f(s);
+  }
+  if constexpr (B + 1 < L) sha3_range_step<NL, CANON, DOM, B + 1>(s, a, col, j, n_words, b0, b1);
+}
+
+// state: lane i of column c at state[i * n_cols + c] -- a wave reads and writes 64 consecutive 8-byte words per lane index
+template <int NL, bool CANON, u32 DOM>
+__global__ void __launch_bounds__(256) sha3_leaf_range_kernel(LeafArgs a, u64 b0, u64 b1, uint2* state) {
+  const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (col >= a.n_cols) return;
+  constexpr int L = NL / 2;
+  const u64 n_words = 4 + (u64)L * a.n_rows_total;
+  const u64 n_blocks = n_words / 17 + 1;
+  Lane s[25];
+  if (b0 == 0) {
+#pragma unroll
+    for (int i = 0; i < 25; i++) s[i] = {0u, 0u};
+  } else {
+#pragma unroll
+    for (int i = 0; i < 25; i++) { const uint2 v = state[(u64)i * a.n_cols + col]; s[i] = {v.x, v.y}; }
+  }
+  for (u64 j = b0 / L; j * L < b1; j++) sha3_range_step<NL, CANON, DOM, 0>(s, a, col, j, n_words, b0, b1);
+  if (b1 == n_blocks) {
+    u32* o = a.out + col * 8;
+    *reinterpret_cast<uint4*>(o) = make_uint4(s[0].lo, s[0].hi, s[1].lo, s[1].hi);
+    *reinterpret_cast<uint4*>(o + 4) = make_uint4(s[2].lo, s[2].hi, s[3].lo, s[3].hi);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 25; i++) state[(u64)i * a.n_cols + col] = make_uint2(s[i].lo, s[i].hi);
+  }
+}
+
+template <u32 DOM>
+static hipError_t launch_keccak_leaves_range(int nl, const LeafArgs& a, u64 b0, u64 b1, uint64_t* state, hipStream_t st) {
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
+  if (b0 > b1 || b1 > sha3_leaf_blocks(nl, a.n_rows_total)) return hipErrorInvalidValue;
+  if (a.n_cols == 0 || b0 == b1) return hipSuccess;
+  const dim3 grid((unsigned)((a.n_cols + 255) / 256));
+  uint2* s2 = reinterpret_cast<uint2*>(state);
+#define SHA3_CASE(NLV)                                                                                                      \
+  case NLV:                                                                                                                 \
+    if (a.canon_in) hipLaunchKernelGGL((sha3_leaf_range_kernel<NLV, true, DOM>), grid, dim3(256), 0, st, a, b0, b1, s2);    \
+    else hipLaunchKernelGGL((sha3_leaf_range_kernel<NLV, false, DOM>), grid, dim3(256), 0, st, a, b0, b1, s2);              \
+    break;
+  switch (nl) { SHA3_CASE(2) SHA3_CASE(4) SHA3_CASE(6) SHA3_CASE(8) }
+#undef SHA3_CASE
+  return hipGetLastError();
+}
+hipError_t launch_sha3_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st) {
+  return launch_keccak_leaves_range<kc::KC_DOM_SHA3>(nl, a, blk_begin, blk_end, state, st);
+}
+hipError_t launch_keccak256_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st) {
+  return launch_keccak_leaves_range<kc::KC_DOM_KECCAK>(nl, a, blk_begin, blk_end, state, st);
+}
+
 // parent = SHA3-256(left || right) (DOM = 0x01: Keccak-256): 8 words, one permutation
 template <u32 DOM>
 __device__ __forceinline__ void sha3_node(u32 o[8], const u32* l, const u32* r) {

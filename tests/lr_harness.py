@@ -1,0 +1,73 @@
+"""ctypes side of tests/native/lr_harness.cpp (lcpc_amd/lib/liblcpc_lr_harness.so, built by lcpc_amd/csrc/Makefile): the resumable column
+hash of SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b (launch_*_leaves_range of lcpc_amd/csrc/kernels.h) on buffers a test builds.  Elements
+cross as (.., L) uint64 arrays of limbs, the chaining state and the digests as flat uint32 arrays that are modified in place.  Every call
+returns after the device has finished and raises on any hipError_t; BadArgs means the harness refused the call before touching the
+device."""
+import ctypes as C
+import os
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_lr_harness.so")
+NL = {0: 2, 1: 4, 2: 6, 3: 8}
+FAMILY = {"sha3_256": 0, "keccak256": 1, "sha256": 2, "blake2b": 3}
+# per digest: 64-bit words of zero prefix, 64-bit words per block, 32-bit words of chaining state per column, 32-bit words per digest
+SHAPE = {"sha3_256": (4, 17, 50, 8), "keccak256": (4, 17, 50, 8), "sha256": (4, 8, 8, 8), "blake2b": (8, 16, 16, 16)}
+
+
+class BadArgs(ValueError):
+    pass
+
+
+class HipError(RuntimeError):
+    def __init__(self, what, code):
+        RuntimeError.__init__(self, "%s: hipError_t %d" % (what, code))
+        self.code = code
+
+
+_vp, _u64, _i32 = C.c_void_p, C.c_uint64, C.c_int
+SYMBOLS = {
+    "lrh_device_count": (_i32, []),
+    "lrh_leaf_blocks": (_u64, [_i32, _i32, _u64]),
+    "lrh_leaf_range": (_i32, [_i32, _i32, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _u64, _i32, _vp, _u64, _u64, _vp, _u64, _u64]),
+}
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
+        try:
+            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
+        except ImportError:
+            pass
+        L = C.CDLL(LIB_PATH)
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = L
+    return _lib
+
+
+def leaf_blocks(digest, fid, n_rows):
+    """blocks of the whole leaf message, padding blocks included (0: refused)"""
+    return int(lib().lrh_leaf_blocks(FAMILY[digest], NL[fid], n_rows))
+
+
+def leaf_range(digest, fid, comm, row_stride, col_stride, n_cols, n_rows_total, blk_begin, blk_end, canon_in, state, state_off, out, out_off):
+    """one launch of blocks [blk_begin, blk_end).  comm: flat (comm_elems, L) uint64, element (r, c) at r row_stride + c col_stride -- it
+    has to hold the rows the range reads, no more.  state / out: flat uint32 arrays, in / out; the kernel's regions start at word
+    state_off / out_off"""
+    assert comm.dtype == np.uint64 and comm.flags.c_contiguous and comm.ndim == 2 and comm.shape[1] * 2 == NL[fid], (comm.dtype, comm.shape)
+    for a in (state, out):
+        assert a.dtype == np.uint32 and a.flags.c_contiguous and a.ndim == 1
+    rc = lib().lrh_leaf_range(FAMILY[digest], NL[fid], comm.ctypes.data_as(_vp), comm.shape[0], row_stride, col_stride, n_cols, n_rows_total,
+                              blk_begin, blk_end, int(canon_in), state.ctypes.data_as(_vp), state.size, state_off, out.ctypes.data_as(_vp),
+                              out.size, out_off)
+    if rc == -1:
+        raise BadArgs("lrh_leaf_range")
+    if rc:
+        raise HipError("lrh_leaf_range", rc)
