@@ -414,6 +414,41 @@ class LcCommit:
             pass
 
 
+def commit_batch(enc, coeffs, n_coeffs=None, stream=0, sync=True, borrow=False, into=None, return_roots=False):
+    """lcpcx_commit_batch_device (include/lcpc_hip_batch.h): every row of `coeffs` committed under `enc` in one pipeline.
+    coeffs: a device tensor [n_batch, W] of 64-bit limbs (W = n_coeffs * L), or a list of equal-length device tensors, which is
+    stacked.  n_coeffs: elements per polynomial when a row holds more than the polynomial (poly_stride = W / L; the rest of a row is
+    never read).  borrow: LCPC_COMMIT_BORROW_COEFFS -- the members keep reading the tensor, which they keep alive.  into: the
+    LcCommit objects to refill.  sync=False only enqueues on `stream`.  Returns the list of commitment objects (return_roots: and
+    the list of roots the call itself reported; needs sync)."""
+    import torch
+    if isinstance(coeffs, (list, tuple)):
+        coeffs = torch.stack([t.reshape(-1) for t in coeffs])
+    if coeffs.dim() != 2 or coeffs.element_size() != 8 or not coeffs.is_contiguous() or coeffs.shape[1] % enc.L:
+        raise ValueError("coeffs must be a contiguous [n_batch, n * L] tensor of 64-bit limbs")
+    n_batch, stride = coeffs.shape[0], coeffs.shape[1] // enc.L
+    n_coeffs = stride if n_coeffs is None else n_coeffs
+    cms = list(into) if into is not None else [LcCommit(enc) for _ in range(n_batch)]
+    if len(cms) != n_batch:
+        raise ValueError("`into` must hold one LcCommit per polynomial")
+    handles = (C.c_void_p * max(n_batch, 1))(*[cm._h for cm in cms])
+    roots = (C.c_uint8 * (enc.digest_len * max(n_batch, 1)))() if sync else None
+    rc = _lib.lib().lcpcx_commit_batch_device(handles, n_batch, C.c_void_p(coeffs.data_ptr()), n_coeffs, stride, C.c_void_p(stream),
+                                              BORROW_COEFFS if borrow else 0, roots)
+    if rc:
+        raise LcpcError(rc, _lib.lib().lcpc_commit_last_error(cms[0]._h).decode() if cms else "")
+    for cm in cms:
+        # borrow: the members read the tensor for as long as they live.  sync=False: the encode that reads it is only enqueued, and
+        # a stacked temporary has no other owner -- the members keep it until their next fill
+        cm._coeffs_ref = coeffs if (borrow or not sync) else None
+        cm._refresh()
+    if return_roots:
+        if not sync:
+            raise ValueError("return_roots needs sync=True")
+        return cms, [bytes(roots[i * enc.digest_len:(i + 1) * enc.digest_len]) for i in range(n_batch)]
+    return cms
+
+
 class _OwnedBuffer:
     """a malloc'ed buffer handed out by the library (lcpc_prove): viewed in place, released with lcpc_free"""
 

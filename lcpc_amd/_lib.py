@@ -91,6 +91,13 @@ SYMBOLS = {
     "lcpc_get_timings": (_i32, [_vp, C.POINTER(LcpcTimings)]),
 }
 
+# the batch extension (include/lcpc_hip_batch.h): its own prefix, table and version -- SYMBOLS and ABI_VERSION above are the core header's
+BATCH_VERSION = 1
+BATCH_SYMBOLS = {
+    "lcpcx_batch_version": (_i32, []),
+    "lcpcx_commit_batch_device": (_i32, [C.POINTER(_vp), _u32, _vp, _u64, _u64, _vp, _u32, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -122,5 +129,11 @@ def lib():
             fn.argtypes = args
         if L.lcpc_abi_version() != ABI_VERSION:
             raise RuntimeError("lcpc_amd: ABI version mismatch")
+        for name, (res, args) in BATCH_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcx_batch_version() != BATCH_VERSION:
+            raise RuntimeError("lcpc_amd: batch extension version mismatch")
         _lib = L
     return _lib

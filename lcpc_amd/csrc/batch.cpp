@@ -1,0 +1,266 @@
+// lcpc_amd/csrc/batch.cpp -- lcpcx_commit_batch_device (include/lcpc_hip_batch.h): n_batch equal-shape polynomials committed under
+// one encoder in one pipeline.
+//
+// Ligero x BLAKE3: the members' comm / coeffs / hashes live member-major in one slab (internal.h BatchSlab), the row NTT runs once
+// over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as the batched
+// kernels of batch_kernels.hip (K3b / K4b) -- as many launches as ONE commit of the shape.  Every other encoder: the single-commit
+// pipeline (commit.cpp commit_device_locked) for each member in turn.
+#include "internal.h"
+#include "../../include/lcpc_hip_batch.h"
+#include <functional>
+
+using namespace lcpc;
+
+namespace {
+
+constexpr uint64_t align256(uint64_t b) { return (b + 255) & ~(uint64_t)255; }
+
+struct BatchShape {
+  uint64_t n_rows, n_chunks, stride;   // stride: elements between polynomials
+  bool contiguous;                     // whole rows, back to back: the encode reads the caller's buffer in place
+  bool borrow;
+  bool tree;                           // leaf_tree_supported
+  bool need_coeffs() const { return !(borrow && contiguous); }   // (a strided borrow still stages the rows for the encode)
+  bool need_cvs() const { return !tree && n_chunks > 1; }
+};
+
+LeafArgs batch_leaf_args(const lcpc_ctx* c, const BatchShape& s, const uint32_t* comm) {
+  LeafArgs la{};
+  la.comm = comm; la.canon_in = c->comm_canon ? 1u : 0u; la.row_stride = c->n_cols; la.col_stride = 1; la.n_cols = c->n_cols;
+  la.row_base = 0; la.n_rows_total = s.n_rows;
+  la.chunk_begin = 0; la.n_chunks_local = la.n_chunks_total = (uint32_t)s.n_chunks;
+  return la;
+}
+
+int make_slab(const lcpc_ctx* c, ErrText* err, const BatchShape& s, uint32_t n_batch, std::shared_ptr<BatchSlab>* out) {
+  std::shared_ptr<BatchSlab> sl(new BatchSlab());
+  const uint64_t eb = elem_bytes(c);
+  sl->n_batch = n_batch; sl->n_rows = s.n_rows;
+  sl->comm_stride = s.n_rows * c->n_cols * c->NL;
+  sl->coeffs_stride = s.need_coeffs() ? s.n_rows * c->n_per_row * c->NL : 0;
+  sl->hashes_stride = (2 * c->np2 - 1) * 8;
+  sl->cvs_stride = s.need_cvs() ? s.n_chunks * c->n_cols * 8 : 0;
+  uint64_t off = 0;
+  sl->off_comm = off; off = align256(off + (uint64_t)n_batch * s.n_rows * c->n_cols * eb);
+  sl->off_coeffs = off; off = align256(off + (uint64_t)n_batch * sl->coeffs_stride * 4);
+  sl->off_hashes = off; off = align256(off + (uint64_t)n_batch * sl->hashes_stride * 4);
+  sl->off_cvs = off; off = align256(off + (uint64_t)n_batch * sl->cvs_stride * 4);
+  if (int rc = dev_alloc(err, &sl->d, (size_t)off)) return rc;
+  void* hp = nullptr;              // without the mapping the roots are copied out (fetch_roots)
+  if (hipHostMalloc(&hp, (size_t)n_batch * 32, hipHostMallocMapped) == hipSuccess) {
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) { sl->h_roots = static_cast<uint32_t*>(hp); sl->d_roots_alias = static_cast<uint32_t*>(dp); }
+    else (void)hipHostFree(hp);
+  }
+  if (!sl->h_roots) (void)hipGetLastError();
+  *out = std::move(sl);
+  return 0;
+}
+
+// the slab these members were last filled into together, if this batch fits it as it is
+std::shared_ptr<BatchSlab> reusable_slab(lcpc_commit_t* const* cms, uint32_t n_batch, const BatchShape& s) {
+  const std::shared_ptr<BatchSlab>& sl = cms[0]->slab;
+  if (!sl || sl->n_batch != n_batch || sl->n_rows != s.n_rows) return nullptr;
+  if ((s.need_coeffs() && !sl->coeffs_stride) || (s.need_cvs() && !sl->cvs_stride)) return nullptr;
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (cms[i]->slab != sl || cms[i]->slab_index != i) return nullptr;
+  return sl;
+}
+
+// every member's root on the host behind ONE synchronisation of st
+int fetch_roots(lcpc_commit_t* const* cms, uint32_t n_batch, const BatchSlab* sl, hipStream_t st, uint8_t* roots) {
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  const uint32_t dl = digest_len(c);
+  if (sl && sl->d_roots_alias && c->np2 > 1) {
+    HIPCHK(m0, hipStreamSynchronize(st));
+    memcpy(roots, sl->h_roots, (size_t)n_batch * dl);
+    return 0;
+  }
+  for (uint32_t i = 0; i < n_batch; i++)
+    HIPCHK(m0, hipMemcpyAsync(roots + (size_t)i * dl, cms[i]->d_hashes + (2 * c->np2 - 2) * digest_words(c), dl, hipMemcpyDeviceToHost, st));
+  HIPCHK(m0, hipStreamSynchronize(st));
+  return 0;
+}
+
+// Ligero x BLAKE3 (every member's fill_mu and mu held, the device current)
+int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
+                      hipStream_t st, uint32_t flags, uint8_t* roots) {
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  BatchShape s{};
+  s.n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
+  s.n_chunks = leaf_chunks(c, s.n_rows);
+  s.stride = poly_stride ? poly_stride : n_coeffs;
+  const bool whole = s.n_rows * c->n_per_row == n_coeffs;
+  s.contiguous = whole && s.stride == n_coeffs;
+  s.borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && whole;
+  s.tree = leaf_tree_supported(batch_leaf_args(c, s, nullptr), c->np2);
+  int rc;
+  // st behind every member's last fill; the members are un-committed from here until the batch is sealed
+  for (uint32_t i = 0; i < n_batch; i++)
+    if ((rc = begin_commit(cms[i], st, s.n_rows, 0, s.n_rows, 0, s.n_chunks))) { m0->err = cms[i]->err.c_str(); return rc; }
+  std::shared_ptr<BatchSlab> sl = reusable_slab(cms, n_batch, s);
+  if (!sl) {
+    if ((rc = make_slab(c, &m0->err, s, n_batch, &sl))) return rc;
+    for (uint32_t i = 0; i < n_batch; i++) {
+      lcpc_commit_t* m = cms[i];
+      if (m->slab) leave_slab(m);
+      else {
+        dev_free(m->d_comm); dev_free(m->d_coeffs); dev_free(m->d_hashes);
+        m->d_comm = m->d_coeffs = m->d_hashes = nullptr;
+        m->cap_comm_rows = m->cap_coeff_rows = 0;
+      }
+      m->slab = sl; m->slab_index = i;
+    }
+  }
+  for (uint32_t i = 0; i < n_batch; i++) {       // the views (a reused slab may have grown a use for its coeffs segment)
+    lcpc_commit_t* m = cms[i];
+    m->d_comm = sl->seg(sl->off_comm, sl->comm_stride, i);
+    m->d_coeffs = sl->coeffs_stride ? sl->seg(sl->off_coeffs, sl->coeffs_stride, i) : nullptr;
+    m->d_hashes = sl->seg(sl->off_hashes, sl->hashes_stride, i);
+  }
+  const bool timing = m0->timing;
+  uint32_t launches[3] = {0, 0, 0};
+  if (timing) HIPCHK(m0, hipEventRecord(m0->ev[0], st));
+
+  // ---- encode: one matrix of n_batch * n_rows rows
+  uint32_t* comm0 = sl->seg(sl->off_comm, sl->comm_stride, 0);
+  uint32_t* coeffs0 = sl->coeffs_stride ? sl->seg(sl->off_coeffs, sl->coeffs_stride, 0) : nullptr;
+  EncodeJob j;
+  j.src_stride = c->n_per_row; j.n_valid = c->n_per_row; j.dst = comm0; j.n_rows = (uint64_t)n_batch * s.n_rows;
+  j.canon_out = c->comm_canon;
+  if (s.contiguous) {
+    // read in place; the first pass writes the members' coeffs copies as it streams the source (unless they are borrowed)
+    j.src = reinterpret_cast<const uint32_t*>(coeffs_dev);
+    j.copy_dst = s.borrow ? nullptr : coeffs0;
+  } else {
+    // ragged rows or a stride: the polynomials into the slab's padded coeffs rows first (one launch: copy + zero tails)
+    HIPCHK(m0, launch_batch_place(coeffs_dev, s.stride * c->L, n_coeffs * c->L, reinterpret_cast<uint64_t*>(coeffs0),
+                                  s.n_rows * c->n_per_row * c->L, n_batch, st));
+    launches[0]++;
+    j.src = coeffs0;
+  }
+  if ((rc = encode_rows_device(c, &sl->ws, j, st, &m0->err, &launches[0]))) return rc;
+  if (timing) HIPCHK(m0, hipEventRecord(m0->ev[1], st));
+
+  // ---- column hash + tree: the launches of one commit, each over the whole batch (commit.cpp merkleize_device)
+  LeafArgs la = batch_leaf_args(c, s, comm0);
+  uint32_t* hashes0 = sl->seg(sl->off_hashes, sl->hashes_stride, 0);
+  uint32_t levels_done = 0;
+  if (s.tree) {
+    HIPCHK(m0, launch_leaf_tree_batch(c->NL, la, hashes0, c->np2, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    launches[1]++;
+    levels_done = 6;
+  } else {
+    uint32_t* cvs0 = s.need_cvs() ? sl->seg(sl->off_cvs, sl->cvs_stride, 0) : nullptr;
+    la.out = cvs0 ? cvs0 : hashes0;              // (one chunk: the digests themselves)
+    HIPCHK(m0, launch_leaf_chunks_batch(c->NL, la, n_batch, sl->comm_stride, cvs0 ? sl->cvs_stride : sl->hashes_stride, st));
+    launches[1]++;
+    if (cvs0) {
+      HIPCHK(m0, launch_leaf_finish_batch(cvs0, (uint32_t)s.n_chunks, c->n_cols, hashes0, n_batch, sl->cvs_stride, sl->hashes_stride, st));
+      launches[1]++;
+    }
+  }
+  if (timing) HIPCHK(m0, hipEventRecord(m0->ev[2], st));
+  if (c->np2 > c->n_cols)          // hashes[n_cols..np2) of every member stay zero (lib.rs:656-666)
+    HIPCHK(m0, hipMemset2DAsync(hashes0 + c->n_cols * 8, (size_t)sl->hashes_stride * 4, 0, (size_t)(c->np2 - c->n_cols) * 32, n_batch, st));
+  if (c->np2 > 1) {
+    HIPCHK(m0, launch_merkle_tree_from_batch(hashes0, c->np2, levels_done, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    launches[2]++;
+  }
+
+  // ---- seal (commit.cpp seal_commit, for every member)
+  if (timing) {
+    HIPCHK(m0, hipEventRecord(m0->ev[3], st));
+    HIPCHK(m0, hipEventSynchronize(m0->ev[3]));
+    lcpc_timings t{};
+    (void)hipEventElapsedTime(&t.encode_ms, m0->ev[0], m0->ev[1]);
+    (void)hipEventElapsedTime(&t.hash_ms, m0->ev[1], m0->ev[2]);
+    (void)hipEventElapsedTime(&t.merkle_ms, m0->ev[2], m0->ev[3]);
+    (void)hipEventElapsedTime(&t.total_ms, m0->ev[0], m0->ev[3]);
+    for (uint32_t i = 0; i < n_batch; i++) {     // phase times and launch counts only: the other fields are the member's own (begin_commit reset them)
+      lcpc_timings& l = cms[i]->last;
+      l.encode_ms = t.encode_ms; l.hash_ms = t.hash_ms; l.merkle_ms = t.merkle_ms; l.total_ms = t.total_ms;
+      l.encode_launches = launches[0]; l.hash_launches = launches[1]; l.merkle_launches = launches[2];
+    }
+  }
+  for (uint32_t i = 0; i < n_batch; i++) {
+    lcpc_commit_t* m = cms[i];
+    m->launches[0] = launches[0]; m->launches[1] = launches[1]; m->launches[2] = launches[2];
+    m->coeffs_view = s.borrow ? reinterpret_cast<const uint32_t*>(coeffs_dev) + (size_t)i * s.stride * c->NL : m->d_coeffs;
+    if (!m->ev_done) HIPCHK(m0, hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming));
+    HIPCHK(m0, hipEventRecord(m->ev_done, st));
+  }
+  for (uint32_t i = 0; i < n_batch; i++) cms[i]->committed = true;
+  return roots ? fetch_roots(cms, n_batch, sl.get(), st, roots) : 0;
+}
+
+// every other encoder: the single-commit pipeline member by member on st; the batch's timings are the sums
+int commit_batch_each(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
+                      hipStream_t st, uint32_t flags, uint8_t* roots) {
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  const uint64_t stride = poly_stride ? poly_stride : n_coeffs;
+  const bool timing = m0->timing;
+  lcpc_timings sum{};
+  for (uint32_t i = 0; i < n_batch; i++) {
+    lcpc_commit_t* m = cms[i];
+    const bool own_timing = m->timing;
+    m->timing = timing;
+    int rc = commit_device_locked(m, coeffs_dev + (size_t)i * stride * c->L, n_coeffs, st, flags, nullptr);
+    m->timing = own_timing;
+    if (rc) {
+      if (m != m0) m0->err = m->err.c_str();
+      return rc;
+    }
+    if (timing) {
+      sum.encode_ms += m->last.encode_ms; sum.hash_ms += m->last.hash_ms; sum.merkle_ms += m->last.merkle_ms; sum.total_ms += m->last.total_ms;
+      sum.encode_launches += m->last.encode_launches; sum.hash_launches += m->last.hash_launches; sum.merkle_launches += m->last.merkle_launches;
+    }
+  }
+  if (timing)
+    for (uint32_t i = 0; i < n_batch; i++) {
+      lcpc_timings& t = cms[i]->last;
+      t.encode_ms = sum.encode_ms; t.hash_ms = sum.hash_ms; t.merkle_ms = sum.merkle_ms; t.total_ms = sum.total_ms;
+      t.encode_launches = sum.encode_launches; t.hash_launches = sum.hash_launches; t.merkle_launches = sum.merkle_launches;
+    }
+  return roots ? fetch_roots(cms, n_batch, nullptr, st, roots) : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lcpcx_batch_version(void) { return LCPCX_BATCH_VERSION; }
+
+int lcpcx_commit_batch_device(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs,
+                              uint64_t poly_stride, void* stream, uint32_t flags, uint8_t* roots) {
+  if (!cms || !coeffs_dev || n_batch == 0 || n_batch > 65535 || n_coeffs == 0 || (poly_stride != 0 && poly_stride < n_coeffs)) return LCPC_ERR_ARG;
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (!cms[i] || cms[i]->enc != cms[0]->enc) return LCPC_ERR_ARG;
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  LCPC_TRY
+  // one global lock order -- by address -- whatever order the caller lists the members in: overlapping batches cannot deadlock
+  std::vector<lcpc_commit_t*> order(cms, cms + n_batch);
+  std::sort(order.begin(), order.end(), std::less<lcpc_commit_t*>());
+  if (std::adjacent_find(order.begin(), order.end()) != order.end()) return LCPC_ERR_ARG;       // a member listed twice
+  if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
+  std::vector<std::unique_lock<FillLock>> fills;
+  std::vector<std::unique_lock<std::mutex>> mus;
+  fills.reserve(n_batch); mus.reserve(n_batch);
+  for (lcpc_commit_t* m : order) fills.emplace_back(m->fill_mu);     // fills: each waits for the readers in flight (internal.h)
+  for (lcpc_commit_t* m : order) mus.emplace_back(m->mu);
+  HIPCHK(m0, hipSetDevice(c->prm.device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool fast = c->prm.encoding == LCPC_ENC_LIGERO && is_blake3(c);
+  int rc = fast ? commit_batch_fast(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots)
+                : commit_batch_each(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots);
+  if (rc)                          // a failed batch leaves no member committed
+    for (uint32_t i = 0; i < n_batch; i++) cms[i]->committed = false;
+  return rc;
+  LCPC_CATCH(m0)
+}
+
+}  // extern "C"

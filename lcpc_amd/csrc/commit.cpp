@@ -49,8 +49,16 @@ int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks) {
 
 // comm (unless the commitment will live position-major in ws.d_t and nothing asks for the row-major one: comm_rows), coeffs
 // (unless borrowed), hashes
+void leave_slab(lcpc_commit_t* m) {
+  if (!m->slab) return;
+  m->d_comm = m->d_coeffs = m->d_hashes = nullptr;
+  m->cap_comm_rows = m->cap_coeff_rows = 0;
+  m->slab.reset();                 // (the last member frees the slab: hipFree waits for whatever still reads it)
+}
+
 int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows) {
   const lcpc_ctx* c = m->enc;
+  leave_slab(m);                   // a fill of this object alone: buffers of its own again (readers never come here with a slab: Ligero only)
   const size_t eb = elem_bytes(c);
   const uint64_t rows = n_rows_local ? n_rows_local : 1;
   int rc;
@@ -502,6 +510,7 @@ void lcpc_commit_destroy(lcpc_commit_t* m) {
   (void)hipSetDevice(m->enc->prm.device);
   m->sets.clear();
   m->sc.release();
+  leave_slab(m);
   dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs); dev_free(m->d_chain);
   for (auto& t : m->node_tabs) dev_free(t.d);
   dev_free(m->ws.d_tmp); dev_free(m->ws.d_t); dev_free(m->ws.d_mid); dev_free(m->d_gather); dev_free(m->d_xsend); dev_free(m->d_xrecv);
@@ -527,7 +536,14 @@ int lcpc_commit_device(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_
   std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
-  hipStream_t st = (hipStream_t)stream;
+  return commit_device_locked(m, coeffs_dev, n_coeffs, (hipStream_t)stream, flags, root);
+  LCPC_CATCH(m)
+}
+
+}  // extern "C"
+
+int lcpc::commit_device_locked(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_coeffs, hipStream_t st, uint32_t flags, uint8_t* root) {
+  const lcpc_ctx* c = m->enc;
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;    // get_dims (ligero lib.rs:166-169)
   int rc = begin_commit(m, st, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
@@ -535,8 +551,9 @@ int lcpc_commit_device(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_
   if ((rc = ensure_commit_buffers(m, n_rows, !borrow, false))) return rc;
   if ((rc = encode_coeffs(m, reinterpret_cast<const uint32_t*>(coeffs_dev), n_coeffs, borrow, st))) return rc;
   return commit_tail(m, st, root);
-  LCPC_CATCH(m)
 }
+
+extern "C" {
 
 // ---- host memory -> HBM ---------------------------------------------------------------------------------------------
 // LcCommit::commit(&coeffs, &enc) (lcpc-2d/src/lib.rs:299-301, 636-645) takes a slice of ordinary -- pageable -- memory.

@@ -226,6 +226,27 @@ template <typename S> struct SetLease {
   ~SetLease() { if (s) { s->quiesce(); pool.give(s); } }
 };
 
+// The storage of one batched commit (batch.cpp, include/lcpc_hip_batch.h): comm, coeffs, hashes and the chunk chaining values of
+// every member in ONE device allocation, member-major, so that the row encode sees one matrix of n_batch * n_rows rows and the batched
+// hash / tree kernels reach member i at a fixed stride.  The members share it (lcpc_commit_s::slab); the last one to leave frees it.
+// A member's d_comm / d_coeffs / d_hashes are then views into it: leave_slab before anything frees or regrows them.
+struct BatchSlab {
+  uint8_t* d = nullptr;
+  uint64_t off_comm = 0, off_coeffs = 0, off_hashes = 0, off_cvs = 0;   // bytes; a segment is member-major
+  uint64_t comm_stride = 0, coeffs_stride = 0, hashes_stride = 0, cvs_stride = 0;   // 32-bit words per member (0: no such segment)
+  uint32_t n_batch = 0;
+  uint64_t n_rows = 0;
+  uint32_t* h_roots = nullptr;     // pinned, device-mapped [n_batch][8]: written by the launch that produces the roots
+  uint32_t* d_roots_alias = nullptr;
+  EncodeWs ws;                     // the batch's row encode (a batch call holds every member's lock)
+  uint32_t* seg(uint64_t off, uint64_t stride, uint32_t i) const { return reinterpret_cast<uint32_t*>(d + off) + (size_t)i * stride; }
+  ~BatchSlab() {
+    if (d) (void)hipFree(d);
+    if (ws.d_mid) (void)hipFree(ws.d_mid);
+    if (h_roots) (void)hipHostFree(h_roots);
+  }
+};
+
 }  // namespace lcpc
 
 struct lcpc_transcript {
@@ -311,6 +332,8 @@ struct lcpc_commit_s {
   const uint32_t* coeffs_view = nullptr;   // LcCommit.coeffs as prove/collapse read it: d_coeffs, or the caller's buffer
                                            // when the commit was made with LCPC_COMMIT_BORROW_COEFFS
   uint64_t cap_coeff_rows = 0, cap_comm_rows = 0, cap_cvs = 0;
+  std::shared_ptr<lcpc::BatchSlab> slab;   // member of a batched commit: d_comm / d_coeffs / d_hashes are views into it, not allocations
+  uint32_t slab_index = 0;                 // (leave_slab, commit.cpp)
   uint32_t* d_chain = nullptr;     // host-memory commit under SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: every column's chaining value between
   uint64_t cap_chain = 0;          // the row batches (kernels.h launch_*_leaves_range), word-major; capacity in bytes; kept across refills
   lcpc::EncodeWs ws;
@@ -460,6 +483,10 @@ int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks);
 int begin_commit(lcpc_commit_t* m, hipStream_t st, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end, uint64_t chunk_begin,
                  uint64_t chunk_end);
 int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows);
+// a member of a batched commit gives up its views of the shared slab (and its share of it): it owns no comm / coeffs / hashes then
+void leave_slab(lcpc_commit_t* m);
+// lcpc_commit_device behind its argument checks and locks (the caller holds m->fill_mu exclusively and m->mu; the device is current)
+int commit_device_locked(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_coeffs, hipStream_t st, uint32_t flags, uint8_t* root);
 int encode_coeffs(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src, bool borrow, hipStream_t st);
 int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st);
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);

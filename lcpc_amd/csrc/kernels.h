@@ -103,6 +103,22 @@ hipError_t launch_merkle_tree_from(uint32_t* hashes, uint64_t np2, uint32_t leve
 bool leaf_tree_supported(const LeafArgs& a, uint64_t np2);
 hipError_t launch_leaf_tree(int nl, const LeafArgs& a, uint32_t* hashes, uint64_t np2, hipStream_t st);
 
+// ---- batched BLAKE3 column hash and tree (batch_kernels.hip K3b / K4b): n_batch <= 65535 equal-shape commitments of one encoder in one
+// launch each, the member index a grid dimension.  `a`, `hashes`, `cvs`, `digests` describe member 0; member i's comm, a.out, hashes,
+// cvs and digests start i * (the given stride, in 32-bit words) behind it.  Same digests as the single launchers, bit for bit.
+hipError_t launch_leaf_chunks_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
+hipError_t launch_leaf_finish_batch(uint32_t* cvs, uint32_t n_chunks, uint64_t n_cols, uint32_t* digests, uint32_t n_batch, uint64_t cvs_stride,
+                                    uint64_t digests_stride, hipStream_t st);
+hipError_t launch_leaf_tree_batch(int nl, const LeafArgs& a, uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t comm_stride,
+                                  uint64_t hashes_stride, hipStream_t st);
+// root_out (may be null): [n_batch][8] words, member i's root written by the launch that produces it (host-mapped memory)
+hipError_t launch_merkle_tree_from_batch(uint32_t* hashes, uint64_t np2, uint32_t levels_done, uint32_t n_batch, uint64_t hashes_stride,
+                                         hipStream_t st, uint32_t* root_out);
+// member i: n_valid 64-bit words from src + i * src_stride -> dst + i * dst_stride, the rest of its dst_stride words zero (strides in
+// 64-bit words; n_valid <= both)
+hipError_t launch_batch_place(const uint64_t* src, uint64_t src_stride, uint64_t n_valid, uint64_t* dst, uint64_t dst_stride, uint32_t n_batch,
+                              hipStream_t st);
+
 // ---- SHA3-256 digest (sha3.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA3_256 ----
 // leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a sponge is not split); a.out = LcCommit.hashes
 hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);
