@@ -106,6 +106,9 @@ hipError_t launch_leaf_tree(int nl, const LeafArgs& a, uint32_t* hashes, uint64_
 // ---- batched BLAKE3 column hash and tree (batch_kernels.hip K3b / K4b): n_batch <= 65535 equal-shape commitments of one encoder in one
 // launch each, the member index a grid dimension.  `a`, `hashes`, `cvs`, `digests` describe member 0; member i's comm, a.out, hashes,
 // cvs and digests start i * (the given stride, in 32-bit words) behind it.  Same digests as the single launchers, bit for bit.
+// Alignment: every stride must be a multiple of 4 words (16 bytes), and member 0's pointers 16-byte aligned as for the single launchers --
+// the kernels move chaining values and digests as uint4 and load elements 8 or 16 bytes at a time (fe_load), at the member's offset.
+// A stride must be at least one member's extent: nothing here checks that members do not overlap.
 hipError_t launch_leaf_chunks_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
 hipError_t launch_leaf_finish_batch(uint32_t* cvs, uint32_t n_chunks, uint64_t n_cols, uint32_t* digests, uint32_t n_batch, uint64_t cvs_stride,
                                     uint64_t digests_stride, hipStream_t st);

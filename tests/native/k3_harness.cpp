@@ -1,7 +1,7 @@
 // tests/native/k3_harness.cpp -- test-only C entry points over the BLAKE3 column-hash (K3), Merkle-tree (K4) and path-gather launchers of
-// lcpc_amd/csrc/kernels.h, so that a test can hand a kernel a commitment matrix, a chunk range, a node table or a leaf layer of its own
-// making (tests/k3_harness.py, tests/test_gpu_k3_kernels.py).  Built by lcpc_amd/csrc/Makefile into lcpc_amd/lib/liblcpc_k3_harness.so
-// and linked against the product library, which gains nothing by it.
+// lcpc_amd/csrc/kernels.h and their batch forms (batch_kernels.hip), so that a test can hand a kernel a commitment matrix, a chunk range,
+// a node table or a leaf layer of its own making (tests/k3_harness.py, tests/test_gpu_k3_kernels.py, tests/test_gpu_k3_batch.py).  Built by
+// lcpc_amd/csrc/Makefile into lcpc_amd/lib/liblcpc_k3_harness.so and linked against the product library, which gains nothing by it.
 //
 // Every wrapper takes HOST pointers, checks that every index the kernel will form stays inside the buffers it was given (a refused call
 // returns K3H_BAD_ARGS and launches nothing), allocates device buffers, copies in, launches on the null stream, synchronises, copies
@@ -203,4 +203,111 @@ K3H_EXPORT int k3h_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t p
   K3H_TRY(lcpc::launch_gather_paths(d_hashes.p, np2, path_len, reinterpret_cast<const uint64_t*>(d_cols.p), n, d_paths.p, nullptr));
   K3H_TRY(hipDeviceSynchronize());
   return (int)d_paths.get(paths, p_bytes);
+}
+
+// ---- the batch forms (lcpc_amd/csrc/batch_kernels.hip): member i of a buffer starts i * stride 32-bit words behind member 0 and the
+// buffer is n_batch * stride words, so every member -- the last one too -- is followed by its gap.  Refused before anything is launched:
+// n_batch outside 1 .. 65535 (a grid dimension), a stride smaller than one member (a member's region would reach into the next), and a
+// stride that is no multiple of 4 words (kernels.h: the kernels load and store 16 bytes at a time at member offsets).
+namespace {
+
+bool batch_ok(uint32_t n_batch) { return n_batch >= 1 && n_batch <= 65535; }
+bool stride_ok(uint64_t stride, uint64_t member_words) { return stride >= member_words && stride % 4 == 0 && stride <= MAX_DIM; }
+
+}  // namespace
+
+// launch_leaf_chunks_batch: every member as for k3h_leaf_chunks -- a comm of comm_elems elements and an out of out_slots x n_cols x 8
+// words, of which slots [out_slot0, out_slot0 + n_chunks_local) are written -- comm_stride / out_stride words apart
+K3H_EXPORT int k3h_leaf_chunks_batch(int nl, const uint32_t* comm, uint64_t comm_elems, uint64_t row_stride, uint64_t col_stride,
+                                     uint64_t n_cols, int64_t row_base, uint64_t n_rows_local, uint64_t n_rows_total, uint32_t chunk_begin,
+                                     uint32_t n_chunks_local, uint32_t n_chunks_total, int canon_in, uint32_t* out, uint64_t out_slots,
+                                     uint64_t out_slot0, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride) {
+  if (!leaf_ok(nl, comm_elems, row_stride, col_stride, n_cols, row_base, n_rows_local, n_rows_total, chunk_begin, n_chunks_local,
+               n_chunks_total)) return K3H_BAD_ARGS;       // (the same indices in every member: one check holds for all)
+  if (out_slots > MAX_DIM || out_slot0 + n_chunks_local > out_slots || comm_elems > MAX_DIM) return K3H_BAD_ARGS;
+  if (!batch_ok(n_batch) || !stride_ok(comm_stride, comm_elems * nl) || !stride_ok(out_stride, out_slots * n_cols * 8)) return K3H_BAD_ARGS;
+  DevBuf d_comm, d_out;
+  const size_t out_bytes = (size_t)n_batch * out_stride * 4;
+  K3H_TRY(d_comm.put(comm, (size_t)n_batch * comm_stride * 4));
+  K3H_TRY(d_out.put(out, out_bytes));
+  const lcpc::LeafArgs a = leaf_args(d_comm.p, row_stride, col_stride, n_cols, row_base, n_rows_total, chunk_begin, n_chunks_local,
+                                     n_chunks_total, canon_in, d_out.p + out_slot0 * n_cols * 8);
+  K3H_TRY(lcpc::launch_leaf_chunks_batch(nl, a, n_batch, comm_stride, out_stride, nullptr));
+  K3H_TRY(hipDeviceSynchronize());
+  return (int)d_out.get(out, out_bytes);
+}
+
+// launch_leaf_tree_batch: every member as for k3h_leaf_tree, hashes (2 np2 - 1 slots per member) hashes_stride words apart.  The buffers
+// hold n_batch members; the launcher is told n_batch_told members, which is n_batch or a count the launcher must refuse without a launch
+// (0, or above 65535: no grid takes it either) -- so that its own answer to those is seen on buffers it must leave alone
+K3H_EXPORT int k3h_leaf_tree_batch(int nl, const uint32_t* comm, uint64_t comm_elems, uint64_t row_stride, uint64_t col_stride,
+                                   uint64_t n_cols, int64_t row_base, uint64_t n_rows_local, uint64_t n_rows_total, uint32_t chunk_begin,
+                                   uint32_t n_chunks_local, uint32_t n_chunks_total, int canon_in, uint32_t* hashes, uint64_t np2,
+                                   uint32_t n_batch, uint64_t comm_stride, uint64_t hashes_stride, uint32_t n_batch_told) {
+  if (!leaf_ok(nl, comm_elems, row_stride, col_stride, n_cols, row_base, n_rows_local, n_rows_total, chunk_begin, n_chunks_local,
+               n_chunks_total)) return K3H_BAD_ARGS;
+  if (!pow2(np2) || np2 < 2 || np2 > MAX_DIM || comm_elems > MAX_DIM) return K3H_BAD_ARGS;
+  if (!batch_ok(n_batch) || !stride_ok(comm_stride, comm_elems * nl) || !stride_ok(hashes_stride, (2 * np2 - 1) * 8)) return K3H_BAD_ARGS;
+  if (n_batch_told != n_batch && n_batch_told != 0 && n_batch_told <= 65535) return K3H_BAD_ARGS;
+  const lcpc::LeafArgs probe = leaf_args(nullptr, row_stride, col_stride, n_cols, row_base, n_rows_total, chunk_begin, n_chunks_local,
+                                         n_chunks_total, canon_in, nullptr);
+  if (lcpc::leaf_tree_supported(probe, np2) && (np2 != n_cols || n_cols < 128 || n_cols % 64 || n_chunks_total > 2)) return K3H_BAD_ARGS;
+  DevBuf d_comm, d_hashes;
+  const size_t h_bytes = (size_t)n_batch * hashes_stride * 4;
+  K3H_TRY(d_comm.put(comm, (size_t)n_batch * comm_stride * 4));
+  K3H_TRY(d_hashes.put(hashes, h_bytes));
+  const lcpc::LeafArgs a = leaf_args(d_comm.p, row_stride, col_stride, n_cols, row_base, n_rows_total, chunk_begin, n_chunks_local,
+                                     n_chunks_total, canon_in, d_hashes.p);
+  const hipError_t e = lcpc::launch_leaf_tree_batch(nl, a, d_hashes.p, np2, n_batch_told, comm_stride, hashes_stride, nullptr);
+  K3H_TRY(hipDeviceSynchronize());
+  K3H_TRY(d_hashes.get(hashes, h_bytes));                    // (copied back after a refusal too: the caller sees that nothing was written)
+  return (int)e;
+}
+
+// launch_leaf_finish_batch: every member as for k3h_leaf_finish -- cvs of n_chunks x n_cols x 8 words (in / out), digests of
+// dig_cols >= n_cols columns (in / out) -- cvs_stride / digests_stride words apart
+K3H_EXPORT int k3h_leaf_finish_batch(uint32_t* cvs, uint32_t n_chunks, uint64_t n_cols, uint64_t cvs_stride, uint32_t* digests,
+                                     uint64_t dig_cols, uint64_t digests_stride, uint32_t n_batch) {
+  if (!n_chunks || !n_cols || n_cols > MAX_DIM || n_chunks > MAX_DIM || dig_cols < n_cols || dig_cols > MAX_DIM) return K3H_BAD_ARGS;
+  if (!batch_ok(n_batch) || !stride_ok(cvs_stride, (uint64_t)n_chunks * n_cols * 8) || !stride_ok(digests_stride, dig_cols * 8)) return K3H_BAD_ARGS;
+  DevBuf d_cvs, d_dig;
+  const size_t cv_bytes = (size_t)n_batch * cvs_stride * 4, dig_bytes = (size_t)n_batch * digests_stride * 4;
+  K3H_TRY(d_cvs.put(cvs, cv_bytes));
+  K3H_TRY(d_dig.put(digests, dig_bytes));
+  K3H_TRY(lcpc::launch_leaf_finish_batch(d_cvs.p, n_chunks, n_cols, d_dig.p, n_batch, cvs_stride, digests_stride, nullptr));
+  K3H_TRY(hipDeviceSynchronize());
+  K3H_TRY(d_cvs.get(cvs, cv_bytes));
+  return (int)d_dig.get(digests, dig_bytes);
+}
+
+// launch_merkle_tree_from_batch: every member as for k3h_merkle_tree_from, hashes_stride words apart; root_out (n_batch x 8 words and 8
+// more that no member owns, in / out) or null
+K3H_EXPORT int k3h_merkle_tree_from_batch(uint32_t* hashes, uint64_t np2, uint32_t levels_done, uint32_t n_batch, uint64_t hashes_stride,
+                                          uint32_t* root_out) {
+  if (!pow2(np2) || np2 < 2 || np2 > ((uint64_t)1 << 24) || levels_done >= log2u(np2)) return K3H_BAD_ARGS;
+  if (!batch_ok(n_batch) || !stride_ok(hashes_stride, (2 * np2 - 1) * 8)) return K3H_BAD_ARGS;
+  DevBuf d_hashes, d_root;
+  const size_t h_bytes = (size_t)n_batch * hashes_stride * 4, r_bytes = ((size_t)n_batch + 1) * 32;
+  K3H_TRY(d_hashes.put(hashes, h_bytes));
+  if (root_out) K3H_TRY(d_root.put(root_out, r_bytes));
+  K3H_TRY(lcpc::launch_merkle_tree_from_batch(d_hashes.p, np2, levels_done, n_batch, hashes_stride, nullptr, root_out ? d_root.p : nullptr));
+  K3H_TRY(hipDeviceSynchronize());
+  K3H_TRY(d_hashes.get(hashes, h_bytes));
+  return (int)(root_out ? d_root.get(root_out, r_bytes) : hipSuccess);
+}
+
+// launch_batch_place: src (n_batch x src_stride 64-bit words), dst (dst_words >= n_batch x dst_stride 64-bit words, in / out: the
+// words behind the last member belong to nobody); member i's first n_valid words are copied, the rest of its dst_stride words zeroed.
+// Strides are in 64-bit words here (any count: the kernel moves one such word at a time); a stride below n_valid is one smaller than a member
+K3H_EXPORT int k3h_batch_place(const uint64_t* src, uint64_t src_stride, uint64_t n_valid, uint64_t* dst, uint64_t dst_stride,
+                               uint64_t dst_words, uint32_t n_batch) {
+  if (!batch_ok(n_batch) || !dst_stride || src_stride > MAX_DIM || dst_stride > MAX_DIM) return K3H_BAD_ARGS;
+  if (n_valid > src_stride || n_valid > dst_stride || dst_words < (uint64_t)n_batch * dst_stride || dst_words > ((uint64_t)1 << 32)) return K3H_BAD_ARGS;
+  DevBuf d_src, d_dst;
+  K3H_TRY(d_src.put(src, (size_t)n_batch * src_stride * 8));
+  K3H_TRY(d_dst.put(dst, (size_t)dst_words * 8));
+  K3H_TRY(lcpc::launch_batch_place(reinterpret_cast<const uint64_t*>(d_src.p), src_stride, n_valid, reinterpret_cast<uint64_t*>(d_dst.p),
+                                   dst_stride, n_batch, nullptr));
+  K3H_TRY(hipDeviceSynchronize());
+  return (int)d_dst.get(dst, (size_t)dst_words * 8);
 }

@@ -366,6 +366,152 @@ def leaf_tree_cases():
     return out
 
 
+# ---- batch cases (lcpc_amd/csrc/batch_kernels.hip, tests/test_gpu_k3_batch.py) ---------------------------------------------------------
+# A batched buffer holds member i in the first words of row i of an (n_batch, stride) word array.  A gap is what a stride adds to one
+# member rounded up to 4 words (kernels.h: strides are multiples of 4 words); None: more than a member
+BATCH_SIZES = (1, 2, 3, 7)
+BATCH_COLS = (1, 63, 64, 65, 255, 257, 300)                 # the last workgroup partly filled: 64 columns (QUAD), 256 (one lane each)
+BATCH_CHUNKS = (1, 2, 3, 5)
+BATCH_GAPS = ((0, 0), (4, 4), (None, None), (0, 12), (8, 0))          # (comm, out): tight, 4 words, above a member, unequal
+BatchLeafCase = namedtuple("BatchLeafCase", "fid n_rows n_cols canon layout split n_batch comm_gap out_gap")
+
+
+def batch_stride(member_words, gap):
+    m = -(-member_words // 4) * 4
+    return m + (m + 8 if gap is None else gap)
+
+
+def batch_index(fid, n_rows, n_cols, n_batch, seed):
+    """(n_batch, n_rows, n_cols) pool indices, every member its own table: a quarter extremes, the rest anything, and (up to POOL columns
+    and members) row 0 of member m is column number + 3 m mod POOL -- the columns of a member differ, and so does column c of any two;
+    a batch of more members carries the member number in base POOL in its first two columns, so that whole members differ"""
+    g = np.random.default_rng([fid, n_rows, n_cols, n_batch, seed])
+    shape = (n_batch, n_rows, n_cols)
+    idx = np.where(g.random(shape) < 0.25, g.integers(0, N_SPECIAL, shape), g.integers(0, POOL, shape))
+    if n_cols <= POOL and n_batch <= POOL:
+        idx[:, 0] = (np.arange(n_cols)[None, :] + 3 * np.arange(n_batch)[:, None]) % POOL
+    elif n_batch > POOL:
+        assert n_cols >= 2 and n_batch <= POOL * POOL
+        idx[:, 0, 0], idx[:, 0, 1] = np.arange(n_batch) % POOL, np.arange(n_batch) // POOL
+    return idx
+
+
+def batch_message_words(fid, idx):
+    """(n_batch * n_cols, 8 + NL n_rows): message_words of every member, member-major"""
+    n_batch, n_rows, n_cols = idx.shape
+    return message_words(fid, idx.transpose(1, 0, 2).reshape(n_rows, n_batch * n_cols))
+
+
+def batch_comm_buffer(fid, idx, row_base, n_local, layout, canon):
+    """comm_buffer for every member: -> ((n_batch, elems, L) uint64, row_stride, col_stride)"""
+    vals = pool(fid)[2 if canon else 1][idx[:, row_base:row_base + n_local]]              # (n_batch, n_local, n_cols, L)
+    n_batch, L = idx.shape[0], CM.FIELD_L[fid]
+    if layout == "row":
+        return np.ascontiguousarray(vals).reshape(n_batch, -1, L), idx.shape[2], 1
+    return np.ascontiguousarray(vals.transpose(0, 2, 1, 3)).reshape(n_batch, -1, L), 1, n_local
+
+
+@functools.lru_cache(maxsize=None)
+def batch_leaf_cases():
+    """the four-lanes-per-column form: every column count with every field, the other axes cycling at periods that do not divide"""
+    out = []
+    for fid in FIDS:
+        first = first_rows_of_chunk_count(fid)
+        for i, n_cols in enumerate(BATCH_COLS):
+            k = len(BATCH_COLS) * fid + i
+            nc = BATCH_CHUNKS[(i + fid) % 4]
+            gap = BATCH_GAPS[k % 5]
+            out.append(BatchLeafCase(fid, first[nc] + i % 3, n_cols, bool((i + fid) & 1), "pos" if (k // 2) & 1 else "row", _splits(nc, k // 3),
+                                     BATCH_SIZES[(k + k // 4) % 4], gap[0], gap[1]))
+    return out
+
+
+BORDER_COLS = 257                                            # 255 members: 65535 pairs; 256 members: 65792
+
+
+@functools.lru_cache(maxsize=None)
+def batch_lane_cases():
+    """either side of launch_leaf_chunks_batch_nl's 65536 (column, chunk) pairs: exactly that many and one member more; every
+    leaf_chunk_batch_kernel<NL, CANON, false> just above it on a column count that fills no workgroup; three chunks on one shape in both
+    forms; a batch whose range launch (1, 2) is one lane per column as well"""
+    one = ((0, 1),)
+    out = [BatchLeafCase(0, 1, 256, False, "row", one, 256, 0, 0), BatchLeafCase(0, 1, 256, False, "row", one, 257, 0, 0)]
+    for fid in FIDS:
+        for canon in (False, True):
+            out.append(BatchLeafCase(fid, 1 + fid, BORDER_COLS, canon, "pos" if canon else "row", one, 256, 4 if canon else 0, 0))
+    out.append(BatchLeafCase(1, 1, BORDER_COLS, True, "row", one, 255, 0, 0))
+    three = first_rows_of_chunk_count(2)[3]
+    out += [BatchLeafCase(2, three, 300, False, "row", ((0, 1), (1, 2)), n, 0, 0) for n in (72, 73)]
+    out.append(BatchLeafCase(3, first_rows_of_chunk_count(3)[3], BORDER_COLS, True, "pos", ((0, 1), (1, 2)), 128, 0, 4))
+    return out
+
+
+GRID_LIMIT_LEAF = BatchLeafCase(0, 1, 4, False, "row", ((0, 1),), CM.K3B_MAX_BATCH, 0, 0)
+
+
+def batch_case_id(c):
+    gap = lambda g: "m" if g is None else str(g)
+    return "%s-b%d-g%s.%s" % (leaf_case_id(c), c.n_batch, gap(c.comm_gap), gap(c.out_gap))
+
+
+TREE_BATCH = (1, 2, 5)
+
+
+@functools.lru_cache(maxsize=None)
+def tree_batch_cases():
+    """(np2, levels_done, n_batch, gap): every width from either starting level; all of TREE_BATCH where the width handed to the launcher is
+    256 .. 2048 (either side of lw <= 9: one 1024-thread launch, or 256-thread launches first), one of them elsewhere, two members above
+    2^16 leaves (2^19: three launches over two members) and one at 2^20, where the reference of a second would take the test's time"""
+    out = []
+    for ld, widths in ((0, TREE_NP2), (6, FUSED_NP2)):
+        for k, np2 in enumerate(widths):
+            if np2 > 1 << 16:
+                nbs = (2,) if np2 < 1 << 20 else (1,)
+            elif 256 <= np2 >> ld <= 2048:
+                nbs = TREE_BATCH
+            else:
+                nbs = (TREE_BATCH[k % 3],)
+            for j, nb in enumerate(nbs):
+                out.append((np2, ld, nb, (0, 4, None)[(k + j) % 3] if np2 <= 1 << 16 else (0, 4)[k % 2]))
+    return out
+
+
+LEAF_TREE_BATCH = (1, 3, 5)
+
+
+def leaf_tree_batch_cases():
+    """leaf_tree_cases() with (n_batch, comm gap, hashes gap) cycling"""
+    return [c + (LEAF_TREE_BATCH[i % 3],) + BATCH_GAPS[i % 5] for i, c in enumerate(leaf_tree_cases())]
+
+
+def finish_stack_slots(n_chunks):
+    """the slots of cvs that leaf_finish_kernel's stack stores to (the rule of ref_fold_nodes on single chunks); the others are only read"""
+    depth, written = 0, set()
+    for j in range(n_chunks - 1):
+        t = j + 1
+        while t & 1 == 0:
+            depth -= 1
+            t >>= 1
+        written.add(depth)
+        depth += 1
+    return written
+
+
+PLACE_BIG = 4096 * 256 + 257                                 # batch_place_kernel's grid is capped at 4096 workgroups: a second trip of its loop
+
+
+def place_cases():
+    """(n_batch, src_stride, n_valid, dst_stride)"""
+    out = []
+    for i, ds in enumerate((1, 255, 256, 257)):
+        for j, nv in enumerate(sorted({0, 1, ds - 1, ds})):
+            for loose in (False, True):
+                out.append(((1, 3)[(i + j + loose) % 2], nv + 3 if loose else nv, nv, ds))
+    out.append((2, PLACE_BIG + 2, PLACE_BIG - 1, PLACE_BIG))
+    out.append((CM.K3B_MAX_BATCH, 5, 3, 4))
+    return out
+
+
 # =========================================================================================================================================
 # checks
 # =========================================================================================================================================
@@ -647,3 +793,151 @@ def test_harness_refuses_bad_indices_before_the_device():
     # the pure rule needs no device either, and is the restated one on every probe
     for p in LEAF_TREE_PROBES:
         assert H.leaf_tree_supported(*p) == CM.leaf_tree_supported(*p), p
+
+
+# ---- the batch tables ------------------------------------------------------------------------------------------------------------------
+def _batch_launches(c):
+    """(quad, begin, count, row_base) of the whole-message launch and the range launches of a batch case"""
+    nc = CM.leaf_n_chunks(c.fid, c.n_rows)
+    return [(CM.leaf_quad_batch(c.n_cols, k, c.n_batch), b, k, launch_rows(c, b, k, whole)[0])
+            for whole, (b, k) in [(True, (0, nc))] + [(False, s) for s in c.split]]
+
+
+def test_batch_selection_rule_matches_the_source():
+    src = open(os.path.join(ROOT, "lcpc_amd", "csrc", "batch_kernels.hip")).read()
+    assert int(re.search(r"const bool quad = \(u64\)a\.n_cols \* a\.n_chunks_local \* n_batch <= (\d+);", src).group(1)) == CM.K3B_QUAD_MAX
+    assert src.count("n_batch > 65535") == 5 and CM.K3B_MAX_BATCH == 65535          # each of the five launchers
+    assert "if (lw <= 9) {" in src and "blocks < 4096 ? blocks : 4096" in src
+    assert CM.leaf_quad_batch(256, 1, 256) and not CM.leaf_quad_batch(256, 1, 257) and CM.leaf_quad_batch(2048, 3, 1) == CM.leaf_quad(2048, 3)
+
+
+def test_batch_leaf_cases_reach_every_axis():
+    cases = batch_leaf_cases()
+    nc = lambda c: CM.leaf_n_chunks(c.fid, c.n_rows)
+    assert all(all(l[0] for l in _batch_launches(c)) for c in cases)                   # the quad form throughout
+    assert {(c.fid, c.n_cols) for c in cases} == {(f, n) for f in FIDS for n in BATCH_COLS}
+    assert {(c.fid, c.canon) for c in cases} == {(f, b) for f in FIDS for b in (False, True)}
+    assert {c.n_batch for c in cases} == set(BATCH_SIZES) and {nc(c) for c in cases} == set(BATCH_CHUNKS)
+    assert {(c.comm_gap, c.out_gap) for c in cases} == set(BATCH_GAPS) and {c.layout for c in cases} == {"row", "pos"}
+    for fid in (1, 2):                                                                  # many chunks for the fields named for it
+        assert any(c.fid == fid and nc(c) >= 3 for c in cases)
+    assert (32 + 24 * 41) < 1024 < (32 + 24 * 42) and any(c.fid == 2 and c.n_rows >= 43 for c in cases)      # Ft191's straddling element
+    many = [c for c in cases if c.n_batch > 1]
+    # a partly filled last workgroup in a batch of several, at tight strides (its idle lanes would land in the next member)
+    assert any(c.n_cols % 64 and (c.comm_gap, c.out_gap) == (0, 0) for c in many)
+    # the two strides differ from each other wherever there is a second member (comm and out members differ), and the gaps differ in some
+    for c in many:
+        L, slots = CM.FIELD_L[c.fid], nc(c) + 2
+        assert batch_stride(2 * L * c.n_rows * c.n_cols, c.comm_gap) != batch_stride(slots * c.n_cols * 8, c.out_gap)
+    assert any(c.comm_gap != c.out_gap for c in many)
+    ranges = [(c, l) for c in cases for l in _batch_launches(c)[1:]]
+    assert any(l[1] > 0 and l[1] + l[2] < nc(c) and c.n_batch > 1 for c, l in ranges)   # starts and ends mid-message
+    assert any(l[3] > 0 and c.n_batch > 1 and c.layout == lay for c, l in ranges for lay in ("row", "pos"))     # row_base > 0
+    for c in cases:
+        assert sum(k for _, k in c.split) == nc(c) and c.split[0][0] == 0
+        assert all(c.split[i][0] + c.split[i][1] == c.split[i + 1][0] for i in range(len(c.split) - 1))
+
+
+def test_batch_lane_cases_sit_on_the_border():
+    cases = batch_lane_cases()
+    pairs = lambda c: c.n_cols * CM.leaf_n_chunks(c.fid, c.n_rows) * c.n_batch
+    assert pairs(cases[0]) == CM.K3B_QUAD_MAX and pairs(cases[1]) == CM.K3B_QUAD_MAX + 256 and cases[1].n_batch == cases[0].n_batch + 1
+    assert (cases[0].n_cols, cases[0].n_rows, cases[0].n_batch) == (256, 1, 256)
+    whole = {c: _batch_launches(c)[0][0] for c in cases}
+    assert whole[cases[0]] and not whole[cases[1]]
+    lane = [c for c in cases if not whole[c]]
+    assert {(c.fid, c.canon) for c in lane if c.n_cols % 256} == {(f, b) for f in FIDS for b in (False, True)}
+    assert any(whole[c] and c.n_cols % 256 and pairs(c) == CM.K3B_QUAD_MAX - 1 for c in cases)
+    three = [c for c in cases if CM.leaf_n_chunks(c.fid, c.n_rows) == 3]
+    assert any(a._replace(n_batch=0) == b._replace(n_batch=0) and whole[a] and not whole[b] for a in three for b in three)
+    assert any(not l[0] and l[1] > 0 for c in cases for l in _batch_launches(c)[1:])    # a lane-per-column launch of a range that starts mid-message
+    g = GRID_LIMIT_LEAF
+    assert (g.fid, g.n_rows, g.n_cols, g.n_batch) == (0, 1, 4, 65535) and not _batch_launches(g)[0][0]
+
+
+def test_batch_members_differ():
+    """no test that tiles one member can pass: column c of any two members differs (whole members, where the batch outnumbers the pool)"""
+    for c in batch_leaf_cases() + batch_lane_cases() + [GRID_LIMIT_LEAF]:
+        idx = batch_index(c.fid, c.n_rows, c.n_cols, c.n_batch, 1)
+        if c.n_batch <= POOL:
+            per_col = idx.transpose(2, 0, 1)                                            # (n_cols, n_batch, n_rows)
+            assert all(len(np.unique(m, axis=0)) == c.n_batch for m in per_col[:: max(1, c.n_cols // 7)]), c
+            assert all(len(np.unique(m.T, axis=0)) == c.n_cols for m in idx[:: max(1, c.n_batch // 5)]), c
+        else:
+            assert len(np.unique(idx.reshape(c.n_batch, -1), axis=0)) == c.n_batch, c
+    for fid, n_rows, n_cols, canon, layout, n_batch, _, _ in leaf_tree_batch_cases():
+        idx = batch_index(fid, n_rows, n_cols, n_batch, 2)
+        assert len(np.unique(idx[:, :, 5], axis=0)) == n_batch
+    # the member-major references are the single ones on each member
+    idx = batch_index(2, 45, 5, 3, 1)
+    words = batch_message_words(2, idx)
+    for m in range(3):
+        assert np.array_equal(words[5 * m:5 * m + 5], message_words(2, idx[m]))
+        for layout in ("row", "pos"):
+            got, rs, cs = batch_comm_buffer(2, idx, 3, 40, layout, False)
+            one, rs1, cs1 = comm_buffer(2, idx[m], 3, 40, layout, False)
+            assert np.array_equal(got[m], one) and (rs, cs) == (rs1, cs1)
+
+
+def test_tree_finish_and_place_batch_tables():
+    tc = tree_batch_cases()
+    assert {(n, ld) for n, ld, _, _ in tc} == {(n, 0) for n in TREE_NP2} | {(n, 6) for n in FUSED_NP2}
+    for ld in (0, 6):
+        for first_bs in (1024, 256):                            # every batch size on either side of lw <= 9, from either starting level
+            assert {nb for n, l, nb, _ in tc if l == ld and CM.merkle_launches(n, l)[0][0] == first_bs and n <= 1 << 16} >= set(TREE_BATCH)
+        assert {g for _, l, nb, g in tc if l == ld and nb > 1} == {0, 4, None}
+    assert any(nb > 1 and len(CM.merkle_launches(n, l)) == 3 for n, l, nb, _ in tc)
+    lt = leaf_tree_batch_cases()
+    assert {c[5] for c in lt} == set(LEAF_TREE_BATCH) and {c[6:] for c in lt if c[5] > 1} == set(BATCH_GAPS)
+    assert {(CM.leaf_n_chunks(c[0], c[1]), c[5] > 1) for c in lt} == {(1, False), (1, True), (2, False), (2, True)}
+    assert finish_stack_slots(1) == set() and finish_stack_slots(2) == {0} and finish_stack_slots(5) == {0, 1} and finish_stack_slots(8) == {0, 1, 2}
+    assert all(max(finish_stack_slots(n), default=-1) < n - 1 for n in CHUNK_COUNTS if n > 1)    # the last chunk's slot is only read
+    pc = place_cases()
+    assert {ds for _, _, _, ds in pc} == {1, 255, 256, 257, PLACE_BIG, 4} and {nb for nb, _, _, _ in pc} == {1, 2, 3, 65535}
+    for ds in (1, 255, 256, 257):
+        mine = [c for c in pc if c[3] == ds]
+        assert {c[2] for c in mine} == {0, 1, ds - 1, ds} and {c[1] == c[2] for c in mine} == {True, False}
+        assert {c[0] for c in mine} == {1, 3} or ds == 1
+    assert {c[0] for c in pc if c[3] == 1} == {1, 3}
+    assert all(nv <= ss and nv <= ds for _, ss, nv, ds in pc)
+    assert -(-PLACE_BIG // 256) > 4096 and (65535, 5, 3, 4) in pc and (2, PLACE_BIG + 2, PLACE_BIG - 1, PLACE_BIG) in pc
+
+
+def test_harness_refuses_bad_batches_before_the_device():
+    """the batch entry points of tests/native/k3_harness.cpp: what test_harness_refuses_bad_indices_before_the_device checks per member, and
+    a member count outside 1 .. 65535, a stride below one member and a stride that is no multiple of 4 words"""
+    import k3_harness as H
+    bad = lambda fn, *a: pytest.raises(H.BadArgs, fn, *a) and None
+    w = lambda n_batch, stride: np.zeros((n_batch, stride), np.uint32)
+
+    def lb(n_batch=2, comm_stride=None, **kw):
+        leaf = _leaf(H, **kw)
+        return H.LeafBatch(leaf, w(n_batch, 2 * leaf.comm.size if comm_stride is None else comm_stride))
+
+    # Ft63, 300 rows x 8 columns: a comm member is 4800 words, an out member of 3 slots 192, a hashes member of 128 leaves 2040
+    for b, out in ((lb(0), w(0, 192)), (lb(65536, 4800), w(65536, 192)), (lb(comm_stride=4796), w(2, 192)), (lb(comm_stride=4802), w(2, 192)),
+                   (lb(), w(2, 188)), (lb(), w(2, 194)), (lb(total=2), w(2, 192)), (lb(begin=2, count=2), w(2, 192)),
+                   (lb(begin=1, count=1, row_base=125, n_local=175), w(2, 192)), (lb(comm_elems=300 * 8 - 1, comm_stride=4800), w(2, 192)),
+                   (lb(n_cols=0, comm_stride=8), w(2, 192))):
+        bad(H.leaf_chunks_batch, b, out, 3)
+    bad(H.leaf_chunks_batch, lb(begin=1, count=1, row_base=124, n_local=128), w(2, 192), 3, 3)      # output slot past the member
+    t = dict(n_cols=128)
+    for b, hashes in ((lb(0, **t), w(0, 2040)), (lb(65536, 8, n_rows=1, **t), w(65536, 2040)), (lb(comm_stride=76796, **t), w(2, 2040)),
+                      (lb(comm_stride=76802, **t), w(2, 2040)), (lb(**t), w(2, 2036)), (lb(**t), w(2, 2042)), (lb(total=2, **t), w(2, 2040)),
+                      (lb(comm_elems=128 * 300 - 1, comm_stride=76800, **t), w(2, 2040))):
+        bad(H.leaf_tree_batch, b, hashes, 128)
+    bad(H.leaf_tree_batch, lb(n_cols=96), w(2, 191 * 8), 96)                 # np2 is no power of two
+    bad(H.leaf_tree_batch, lb(**t), w(2, 2040), 128, 1)                     # the launcher may be told n_batch, 0 or more than 65535 only
+    bad(H.leaf_tree_batch, lb(**t), w(2, 2040), 128, 65535)
+    fin = lambda n_batch=2, cs=3 * 5 * 8, ds=5 * 8, dig_cols=5: (w(n_batch, cs), 3, 5, w(n_batch, ds), dig_cols)
+    for a in (fin(0), fin(65536), fin(cs=116), fin(cs=122), fin(ds=36), fin(ds=42), fin(dig_cols=4), fin(ds=40, dig_cols=6)):
+        bad(H.leaf_finish_batch, *a)
+    root = lambda n: np.zeros((n + 1, 8), np.uint32)
+    for hashes, np2, ld, r in ((w(0, 2040), 128, 0, None), (w(65536, 24), 2, 0, None), (w(2, 2036), 128, 0, None), (w(2, 2042), 128, 0, None),
+                               (w(2, 2040), 128, 7, root(2)), (w(2, 40), 3, 0, None), (w(2, 8), 1, 0, None), (w(2, 24), 2, 1, root(2))):
+        bad(H.merkle_tree_from_batch, hashes, np2, ld, r)
+    u = lambda n_batch, stride: np.zeros((n_batch, stride), np.uint64)
+    d = lambda n: np.zeros(n, np.uint64)
+    for src, nv, dst, ds in ((u(0, 4), 4, d(8), 4), (u(65536, 1), 1, d(65536), 1), (u(2, 4), 5, d(16), 8),      # n_valid > src_stride
+                             (u(2, 8), 5, d(16), 4), (u(2, 4), 4, d(7), 4), (u(2, 4), 0, d(8), 0)):               # .. > dst_stride; dst too short
+        bad(H.batch_place, src, nv, dst, ds)
