@@ -259,15 +259,24 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
       // ntt_lns.hip), or already in the pass before if that has >= 8 stages: then the last pass sees canonical values only
       p.mont_prefix = last && c->NL == 2 ? 4u : 0u;
       p.blk0_gone = last && c->NL != 2 && plan[i - 1].a.s >= 8 ? 1u : 0u;
-      p.pack_info = ntt_lns_pack_info(c->NL, p.a.s, p.first);
-      const uint32_t n_classes = p.first ? 1u << (p.a.log_n - 10) : 1u;  // first pass: one class per tile position
+      // K1s two-pass plans in the pure / coset form (LCPC_NTT_FORM, ntt_l9s.hip): the first pass's twiddles do not depend on the tile
+      // (one class) and convert all of block 0, the last pass's depend on it (one class per tile position) and are all plain.
+      // By default from 2^16 columns on, where the pure pass has a uniform round (s0 >= 6): measured -1.3 .. -1.7 % per commit at
+      // 2^16 .. 2^20 columns; below, the last pass gets heavier (+12 %) than the short first pass gets lighter -- 2^11 +4.4 %, 2^12 +6.9 %,
+      // 2^13 .. 2^15 inside the noise (LABNOTES.md, profiles/r07_ntt_form_ab.json) -- and the DIF form stays
+      const bool nf = c->L == 4 && n_pass == 2 && (c->sw_ntt_form == 1 || (c->sw_ntt_form < 0 && s0 >= 6));
+      p.a.form = nf ? 1u : 0u;
+      if (nf && last) p.blk0_gone = 1u;
+      p.pack_info = nf ? ntt_l9s_form_pack_info(p.a.s, p.first) : ntt_lns_pack_info(c->NL, p.a.s, p.first);
+      const uint32_t n_classes = p.first != nf ? 1u << (p.a.log_n - 10) : 1u;  // DIF first pass, coset last pass: one class per tile position
 #ifdef LCPC_TEST_HOOKS
       if (n_pass == 3 && i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;   // (the fallback below)
 #endif
       if ((r = alloc(&p.pack, (size_t)n_classes * p.pack_info.class_words * 4))) return r;
       NttPassArgs pa{};
       pa.roots29 = p.a.roots29; pa.roots29c = p.roots29c; pa.log_n = p.a.log_n; pa.t0 = p.a.t0; pa.s = p.a.s; pa.log_tj = p.a.log_tj;
-      HIPCHK(c, launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
+      if (nf) HIPCHK(c, launch_ntt_l9s_form_pack(pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
+      else HIPCHK(c, launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
     }
     HIPCHK(c, hipDeviceSynchronize());
     return 0;
@@ -636,6 +645,7 @@ int lcpc_ctx_create(const lcpc_params* p, lcpc_ctx** out) {
   if (c->prm.sdig_code == 0) c->prm.sdig_code = 3;
   // the switches: read here, once per context, never on a launch path
   c->sw_ntt_general = getenv("LCPC_NTT_GENERAL") != nullptr;
+  if (const char* ev = getenv("LCPC_NTT_FORM")) c->sw_ntt_form = !strcmp(ev, "dif") ? 0 : (!strcmp(ev, "coset") ? 1 : -1);
   if (const char* ev = getenv("LCPC_NTT_MID_MAX_MB")) c->sw_ntt_mid_max_mb = (int64_t)strtoull(ev, nullptr, 10);
   if (const char* ev = getenv("LCPC_HOST_STAGE")) c->sw_host_stage = (int32_t)strtol(ev, nullptr, 10);
   c->sw_debug_timing = getenv("LCPC_DEBUG_TIMING") != nullptr;

@@ -259,6 +259,8 @@ struct lcpc_ctx {
   // A/B switches, read from the environment ONCE, when the context is created (never on a launch path: getenv next to a
   // setenv of another thread is undefined behaviour, and a context must not change plans under a running commit)
   bool sw_ntt_general = false;     // LCPC_NTT_GENERAL: every Ligero row on the general kernel (K1) instead of the shape-specialised plans
+  int sw_ntt_form = -1;            // LCPC_NTT_FORM=dif|coset: the K1s two-pass plans' factorisation (ntt_l9s.hip): 0 = DIF, 1 = pure first pass + coset
+                                   // last pass at every size, -1 (unset) = coset from 2^16 columns on (build_limb_plan)
   int64_t sw_ntt_mid_max_mb = -1;  // LCPC_NTT_MID_MAX_MB: -1 = the default rule of ntt_mid_rows
   bool sw_debug_timing = false;    // LCPC_DEBUG_TIMING: phase times of construction / prove / verify on stderr
   // forced allocation failures: set and read only in lib/liblcpc_hip_testhooks.so (the tests' second build of ctx.cpp, with

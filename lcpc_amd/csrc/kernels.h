@@ -35,6 +35,8 @@ struct NttPassArgs {
   uint32_t tile_group = 0; // shape-specialised first pass (ntt_l9s.hip, ntt_lns.hip): 2^tile_group neighbouring tiles of a row are
                            // consecutive workgroups of one XCD (short strided runs then meet in that L2); needs
                            // tiles_per_row >= 8 << tile_group
+  uint32_t form = 0;       // K1s two-pass plans (ntt_l9s.hip): 0 = DIF with the twist on the first pass, 1 = pure first pass and coset-form
+                           // last pass; the packs differ (launch_ntt_l9s_form_pack), the results do not
 };
 hipError_t launch_ntt_pass(int nl, int log_tile, const NttPassArgs& a, hipStream_t st);
 
@@ -52,6 +54,10 @@ bool ntt_l9s_supported(uint32_t log_n, uint32_t n_passes, int log_tile);
 // blocks are independent transforms with the root w^(2^s0)), from a sub-sampled twiddle table
 bool ntt_l9s3_supported(uint32_t log_n);
 hipError_t launch_ntt_pass_l9s(const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st);
+// the packs of the pure / coset form (NttPassArgs.form == 1; built in ntt_lns.hip beside the other packs).  First pass: one class;
+// last pass: one class per tile position, 2^(log_n - 10).  a: log_n, s, roots29, roots29c
+NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first);
+hipError_t launch_ntt_l9s_form_pack(const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st);
 
 // ---- shape-specialised lazy-limb NTT for Ft63 / Ft127 / Ft191, two-pass plans on 1024-element tiles (ntt_lns.hip) ----
 // nl = 2 / 4 / 6.  a.roots29 = the limb-form twiddle table (w^i R' mod p, ntt_lns_stride words per entry), a.qp29 = the

@@ -45,7 +45,27 @@ namespace {
 // The first pass then stores its tile as it stands (no clamp, no reduction, no 29 -> 32-bit packing: ~60 VALU per element)
 // and the last pass's tile load is a plain 36 KiB copy into LDS (no unpacking: ~17 per element), at 36 instead of 32 bytes
 // per element of intermediate traffic on a kernel that HBM does not bind.
-template <int S, int LTJ, bool FIRST, bool MID>
+//
+// NF, the pure / coset form of the two-pass plans (a.form).  With a column index n = b + 1024 i and a frequency
+// k = k1 + 2^S k2 (S = log n - 10 first-pass stages),
+//   X[k] = sum_b w^(b k1) w1024^(b k2) ( sum_i x[b + 1024 i] w_{2^S}^(i k1) ):
+// the inner sum is a plain 2^S-point DFT whose twiddles do not depend on b, and the "twist" w^(b k1) can ride on the stage twiddles of
+// either pass.  The DIF form above lets the first pass carry it; here the last pass does:
+//   * first pass, pure: a 2^S-point DIF per column, one pack class for every tile, row and lp.  Distinct twiddle triples per radix-4
+//     round: 4^(NR4 - 1), .., 16, 4, 1 (ntt_ln_dev.h PureShape) -- the round with 4 is wave-uniform (waves dealt by j mod 4), the round
+//     with 1 multiplies by I only;
+//   * last pass, coset: tile t (it holds k1 = rev_S(t) of every column) evaluates its 1024 coefficients on g_t <w1024>, g_t = w^k1, by
+//     multiply-then-butterfly rounds over z^m - gamma (natural order in, bit-reversed out): in round r = 0 .. 4 the quad x0 .. x3
+//     (a quarter of its sub-block apart) of sub-block m < 4^r takes the triple w, w^2, w^3 with w = W^E,
+//     E = 2^(8 - 2r) (k1 + 2^S rev_2r(m)) < n / 4:
+//       p_i = x_i w^i;  t = (p1 - p3) I;  y0 = (x0 + p2) + (p1 + p3), y1 = (x0 + p2) - (p1 + p3), y2 = (x0 - p2) + t, y3 = (x0 - p2) - t.
+//     Round 0's triple is one per tile and round 1's one per wave (wave = sub-block, no special deal of the lanes): ln::mul_u; rounds
+//     2, 3, 4 have 16, 64, 256 triples: ln::mul from the pack, which is per tile class and read in the XCD-aware order that keeps the
+//     rows of one tile position back to back.
+// Per quad chain of the headline (8 + 10): 6 + 9 lane-varying and 7 + 11 uniform multiplies against 9 + 9 and 7 + 8.
+// Canonical output: block 0 of the pure pass is the low sub-block of EVERY tile; it leaves through the converting twiddles as before,
+// and the pure sum that would carry it on is converted in round RC (PureShape), so the coset pass sees canonical values only.
+template <int S, int LTJ, bool FIRST, bool MID, bool NF>
 __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, const u32* __restrict__ pack, NttPackInfo pi) {
   using FT = LnField<FT255>;
   constexpr int NL = 8, LT = S + LTJ, LBT = LTJ;
@@ -53,11 +73,29 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   static_assert(LT == 10, "1024-element tiles: one radix-4 quad (two radix-2 pairs) per thread and round");
   static_assert(FIRST || (LTJ == 0 && S % 2 == 0), "the last pass works on contiguous tiles and ends with the trivial stages k-2, k-1");
   using SH = Shape<S, LBT>;
-  constexpr int RU = SH::RU;
+  using SP = PureShape<S>;
+  constexpr int RU = NF ? (FIRST ? SP::RU : -1) : SH::RU;   // (the coset pass's two uniform rounds need no deal of the lanes)
+  constexpr int RC = NF && FIRST ? SP::RC : -1;
   // a pass with a uniform round reads its tile with a lane stride of 16 elements there (64-way bank conflicts on the uint4
   // planes): the tile is kept XOR-swizzled -- element e at slot e ^ ((e >> 4) & 15), a permutation inside every aligned block
-  // of 16 -- which leaves the consecutive accesses of the other rounds conflict-free and spreads that round's over all banks
-  auto SWZ = [](u32 e) -> u32 { if constexpr (RU >= 0) return e ^ ((e >> 4) & 15u); else return e; };
+  // of 16 -- which leaves the consecutive accesses of the other rounds conflict-free and spreads that round's over all banks.
+  // The new form keeps a swizzle, chosen from the bank arithmetic of a 16-lane group (16 uint4 slots = one 256-byte bank row):
+  //   * coset pass: no uniform deal, but round 3 reads lanes (m, q & 3) at element 16 m + (q & 3) + 4 k and round 4 lane q at 4 q + k
+  //     (k = 0 .. 3 the quad's four reads): without a swizzle a group meets 4 of the 16 slots.  With b = bits 4-5 of the element
+  //     XORed into BOTH bit pairs of the slot (e ^ 5 b), round 3's group maps (q & 3, m & 3) -> ((q & 3) ^ m, k ^ m) and round 4's
+  //     (q & 3, (q >> 2) & 3) -> (k ^ b, (q & 3) ^ b): 16 distinct slots each; rounds 0 .. 2 read runs of >= 16 consecutive elements, which
+  //     any permutation inside the aligned blocks of 16 leaves conflict-free;
+  //   * pure pass at the headline's LBT = 2: the uniform round's lanes (m, lp) read element 64 m + 4 w + lp + 16 k and the I-only
+  //     round's lanes (j, lp) read 16 j + lp + 4 k: bits 4-5 XOR bits 6-7 of the element, XORed into slot bits 2-3, give the group
+  //     (lp, w ^ m ^ k) and (lp, k ^ j) -- 16 distinct slots each.  Other first passes with a uniform round keep the DIF form's swizzle
+  //     (LBT = 0: lanes 16 and 4 elements apart, which it was made for).
+  constexpr bool SWZD = NF ? (LAST || SP::RU >= 0) : RU >= 0;
+  auto SWZ = [](u32 e) -> u32 {
+    if constexpr (NF && LAST) return e ^ (((e >> 4) & 3u) * 5u);
+    else if constexpr (NF && FIRST && SWZD && LBT == 2) return e ^ ((((e >> 4) ^ (e >> 6)) & 3u) << 2);
+    else if constexpr (SWZD) return e ^ ((e >> 4) & 15u);
+    else return e;
+  };
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
   constexpr u32 T = 1u << LT;
   u32* nqp = lds + (size_t)T * 9;                            // NEGATED q*p rows (ln::clamp_apply)
@@ -102,7 +140,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     // the tile as the first pass left it: [limbs 0-3][limbs 4-7][limb 8] planes, the LDS layout itself
     const uint4* t4 = reinterpret_cast<const uint4*>(a.mid + (row << k) * 9 + (size_t)tile * (9 * T));
     uint4* l4 = reinterpret_cast<uint4*>(lds);
-    if constexpr (RU >= 0) {
+    if constexpr (SWZD) {
       // (the swizzled tile: planes 0 and 1 move whole uint4s, the limb-8 plane word by word -- (e + j) -> SWZ(e) ^ j for e = 0 mod 4)
 #pragma unroll
       for (u32 i = tid; i < 2 * T; i += 256) l4[(i & ~(T - 1)) | SWZ(i & (T - 1))] = t4[i];
@@ -134,10 +172,14 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   }
   __builtin_amdgcn_sched_barrier(0);                         // (the first round's twiddle loads stay behind the conversions: registers)
   }
-  const u32* cls_pack = pack + (size_t)(FIRST ? tile : 0u) * pi.class_words;
+  // (pack classes: DIF first pass and coset last pass one per tile position; DIF last pass and pure first pass one)
+  const u32* cls_pack = pack + (size_t)(FIRST != NF ? tile : 0u) * pi.class_words;
   // tiles that hold elements of "block 0" (never multiplied so far).  a.blk0_gone: an earlier pass had a uniform round and
   // converted what was left of block 0 before it (below): nothing is in Montgomery form any more
-  const bool blk0_tile = (FIRST || tile == 0) && a.blk0_gone == 0;
+  const bool blk0_tile = (FIRST || tile == 0) && a.blk0_gone == 0;   // (pure first pass: every tile holds its columns' block 0)
+  LN<9> k32;                                                 // 2^5 = 2^261 R^-1: ln::mul by it converts (Montgomery form -> canonical)
+#pragma unroll
+  for (int i = 0; i < 9; i++) k32.v[i] = i == 0 ? 32u : 0u;
   const bool zero_hi = FIRST && a.n_valid <= (1ull << (k - 1));
   // the limb intermediate's tile sits in LDS; otherwise only the q*p table does, which no first round reads (their pure sums are
   // sums of loads: normalised, not clamped): the barrier at the end of that round serves
@@ -151,17 +193,20 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
 #pragma unroll
     for (u32 pp = 0; pp < 2; pp++) {
       const u32 e1 = tid + 256u * pp;                        // slots with the top stage bit clear are [0, half)
-      const LN<9> w = pack_get<FT, 2>(blk, SH::period2, canon ? 1u : 0u, e1);
+      // pure form: w_{2^S}^i for the pair's i = e1 >> LBT, whatever the tile and lp
+      const LN<9> w = NF ? pack_get<FT, 2>(blk, 1u << (S - 1), canon ? 1u : 0u, e1 >> LBT) : pack_get<FT, 2>(blk, SH::period2, canon ? 1u : 0u, e1);
       const LN<9> x = DIRECT ? xin[pp] : planes_get<FT>(lds, T, SWZ(e1));
       if (pp == 0) mem_phase(false);
+      // pure form, S = 1 and 3: no later round reads the pack, so the sum half is converted here as well (RC < 0, ntt_ln_dev.h)
+      const bool cvs = NF && canon && SH::NR4 <= 1;
       if (zero_hi) {
-        if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e1), x);
+        if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e1), cvs ? ln::mul<FT>(x, k32) : x);
         planes_put<FT>(lds, T, SWZ(e1 + half), ln::mul<FT>(x, w));         // (x, 0) -> (x, x w)
       } else {
         const LN<9> y = DIRECT ? xin[pp + 2] : planes_get<FT>(lds, T, SWZ(e1 + half));
         LN<9> sum = ln::add(x, y);                              // [0, 2p)
         ln::normalize<FT>(sum);
-        planes_put<FT>(lds, T, SWZ(e1), sum);
+        planes_put<FT>(lds, T, SWZ(e1), cvs ? ln::mul<FT>(sum, k32) : sum);
         planes_put<FT>(lds, T, SWZ(e1 + half), ln::mul<FT>(ln::sub(x, y), w));
       }
     }
@@ -170,24 +215,140 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   }
 
   const u32 q = tid;                                         // one quad per thread per radix-4 round (T / 4 == 256)
+  if constexpr (NF && LAST) {
+    // ---- the coset form (head comment): five multiply-then-butterfly rounds, thread q on quad q of its round throughout.
+    //      What the tile holds between rounds is NOT invariant I: y1, y2, y3 are stored as they come out, un-normalised.  Per round:
+    //        x0            round 0: a load (< 2^256, or the limb intermediate: normalised, |value| < 10.8p -- the pure pass's I-only
+    //                      round) ; later: limbs in (-2^30, 2^30), |value| < 12.1p.  Clamped first (but for the packed loads): [0, p + 2^239).
+    //                      ln::clamp_apply's carry pass is signed, and its quotient estimate from the un-normalised top limb is off by
+    //                      the carries still below it, here in [-2, 2] instead of [0, 3]: V - q p >= (QBIAS - |q| - 2.01) B > 0 and
+    //                      < (PTOP + 1 + QBIAS + |q| + 3.01) B < p + 64 B for |q| <= 18, the margins field_ln.h states
+    //        x1, x2, x3    rounds 0, 1 (ln::mul_u): normalised -- round 0's inputs are loads, and round 0 normalises all four outputs
+    //                      for round 1 (mul_u wants sum |limb| < 9 * 2^29; top limb: |value| < 12.1p is < 2^27);
+    //                      rounds 2 .. 4 (ln::mul): limbs in (-2^30, 2^30), |value| < 9.1p < 16p
+    //        p1, p2, p3    normalised; mul_u: (-2p, 2.7p), mul: (-1.2p, 0.2p]
+    //        t             mul_u of p1 - p3 (a difference of two normalised values): normalised, (-2p, 2.7p)
+    //        y0            x0 + p2 + p1 + p3: limbs [0, 2^31 - 4] -- normalised before it is stored (the one output that needs headroom)
+    //        y1            (x0 + p2) - (p1 + p3): limbs (-2^30, 2^30);  y2, y3 = (x0 - p2) +- t: limbs (-2^30, 2^30)
+    //        |y|           round 0: < 4p + 3 * 2.7p = 12.1p (x0 un-clamped from the packed loads: < 2.5p + 8.1p); round 1: < 1.001p + 8.1p = 9.1p;
+    //                      rounds 2 .. 4: < 1.001p + 3.6p = 4.6p
+    //      The final round reduces and stores its four consecutive elements from the registers, as the DIF form's does.
+#pragma unroll
+    for (int r = 0; r < 5; r++) {
+      const int hb = 9 - 2 * r;                              // quarter distance D = 2^(hb - 1) = 256, 64, 16, 4, 1
+      const u32 D = 1u << (hb - 1);
+      const u32 m = q >> (hb - 1);                           // the quad's sub-block, < 4^r
+      const u32 e0 = (m << (hb + 1)) | (q & (D - 1));
+      const bool from_regs = DIRECT && r == 0;               // (e0 == tid, D == 256: the thread's own loads)
+      LN<9> x0 = from_regs ? xin[0] : planes_get<FT>(lds, T, SWZ(e0));
+      const LN<9> x1 = from_regs ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + D));
+      const LN<9> x2 = from_regs ? xin[2] : planes_get<FT>(lds, T, SWZ(e0 + 2 * D)), x3 = from_regs ? xin[3] : planes_get<FT>(lds, T, SWZ(e0 + 3 * D));
+      LN<9> p1, p2, p3;
+      if (r < 2) {
+        // round 0: one triple per tile; round 1: one per sub-block = per wave.  Scalar operands
+        const u32 sb = r == 0 ? 0u : (u32)__builtin_amdgcn_readfirstlane(tid >> 6);
+        const u32* wu = cls_pack + pi.u_off + ((u32)r * 4 + sb) * (3 * U_SLOT<FT>);
+        mem_phase(false);
+        if (!from_regs) ln::clamp_apply<FT>(x0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x0.v[8])));
+        p2 = ln::mul_u<FT>(x2, wu + U_SLOT<FT>);
+        p1 = ln::mul_u<FT>(x1, wu);
+        p3 = ln::mul_u<FT>(x3, wu + 2 * U_SLOT<FT>);
+      } else {
+        const u32* blk = cls_pack + pi.round_off[r];
+        const LN<9> w1 = pack_get<FT, 3>(blk, coset_sets(r), 0, m), w2 = pack_get<FT, 3>(blk, coset_sets(r), 1, m);
+        const LN<9> w3 = pack_get<FT, 3>(blk, coset_sets(r), 2, m);
+        mem_phase(false);
+        ln::clamp_apply<FT>(x0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x0.v[8])));
+        p2 = ln::mul<FT>(x2, w2);
+        p1 = ln::mul<FT>(x1, w1);
+        p3 = ln::mul<FT>(x3, w3);
+      }
+      const LN<9> s02 = ln::add(x0, p2), d02 = ln::sub(x0, p2), s13 = ln::add(p1, p3);
+      LN<9> y0 = ln::add(s02, s13), y1 = ln::sub(s02, s13);
+      ln::normalize<FT>(y0);
+      const LN<9> t = ln::mul_u<FT>(ln::sub(p1, p3), a.wq_w);
+      LN<9> y2 = ln::add(d02, t), y3 = ln::sub(d02, t);
+      if (r == 0 || r == 4) { ln::normalize<FT>(y1); ln::normalize<FT>(y2); ln::normalize<FT>(y3); }
+      mem_phase(true);
+      if (r < 4) {
+        planes_put<FT>(lds, T, SWZ(e0), y0);
+        planes_put<FT>(lds, T, SWZ(e0 + D), y1);
+        planes_put<FT>(lds, T, SWZ(e0 + 2 * D), y2);
+        planes_put<FT>(lds, T, SWZ(e0 + 3 * D), y3);
+        __syncthreads();
+      } else {
+        // D == 1: four consecutive elements of the row, normalised, |value| < 4.6p: clamp, pack, the rare conditional subtract, store
+        u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
+        LN<9> cc[4] = {y0, y1, y2, y3};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          LN<9> x = cc[c];
+          ln::clamp_apply<FT>(x, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x.v[8])));      // [0, p + 2^239) < 2^256
+          u32 w[8];
+          ln::to_packed<FT>(w, x.v);
+          Fe<NL> v;
+#pragma unroll
+          for (int i = 0; i < 8; i++) v.v[i] = w[i];
+          if (__any((int)(x.v[8] >= FT::limb(8)))) v = fe_reduce_once<8>(w);
+          fe_store<NL>(dstq + (size_t)c * NL, v);
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < SH::NR4; r++) {
     const int u = SH::U0 + 2 * r, hb = S - u - 1;            // stages (u, u + 1) of this pass; pair bit of stage u
     const bool last_two = LAST && (r == SH::NR4 - 1);        // stages k-2, k-1: twiddles 1, w^(n/4), 1
+    const bool triv = NF && FIRST && (r == SH::NR4 - 1);     // pure form: the round with one twiddle set -- 1, 1, I
     const u32 lp = q & ((1u << LBT) - 1), j = q >> LBT;
     const u32 i0 = ((j >> (hb - 1)) << (hb + 1)) | (j & ((1u << (hb - 1)) - 1));
     const u32 e0 = (i0 << LBT) | lp;
     constexpr u32 one = 1u;
     const u32 dq = one << (hb - 1 + LBT);
-    const u32 period = one << (hb - 1 + LBT);                // quads q and q + period share their twiddles
-    const u32 jl = q & (period - 1);
+    // quads q and q + period share their twiddles.  Pure form: the twiddles depend on the position in the sub-block alone, j mod 2^(hb - 1)
+    const u32 period = NF ? one << (hb - 1) : one << (hb - 1 + LBT);
+    const u32 jl = NF ? j & (period - 1) : q & (period - 1);
     const u32* blk = cls_pack + pi.round_off[SH::U0 + r];
+    if (triv) {
+      // ---- pure form, the last stage pair: c0 = b0 + b1, c1 = b0 - b1, c2, c3 = (x0 - x2) +- (x1 - x3) I.  Inputs: normalised,
+      //      |value| < 2.7p (the uniform round before it: clamped sums and mul_u outputs; a lane-varying round: < 2.4p; loads and the
+      //      radix-2 round's sums: < 2p), so |c0|, |c1| < 10.8p and |c2|, |c3| < 5.4p + 2.7p = 8.1p.  Stored normalised: the successor's
+      //      first round multiplies three of four by scalar operands (mul_u)
+      const bool fr = DIRECT && SH::U0 == 0 && r == 0;       // S == 2: the thread's own loads
+      const LN<9> x0 = fr ? xin[0] : planes_get<FT>(lds, T, SWZ(e0)), x1 = fr ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + dq));
+      const LN<9> x2 = fr ? xin[2] : planes_get<FT>(lds, T, SWZ(e0 + 2 * dq)), x3 = fr ? xin[3] : planes_get<FT>(lds, T, SWZ(e0 + 3 * dq));
+      mem_phase(false);
+      const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);
+      LN<9> c0 = ln::add(b0, b1), c1 = ln::sub(b0, b1);
+      const LN<9> b2 = ln::sub(x0, x2);
+      const LN<9> t = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);                                    // normalised, (-2p, 2.7p)
+      LN<9> c2 = ln::add(b2, t), c3 = ln::sub(b2, t);
+      ln::normalize<FT>(c1); ln::normalize<FT>(c2); ln::normalize<FT>(c3);
+      if (RC < 0 && SH::U0 == 0 && canon) {
+        // S == 2: no round before this one, every lane still holds Montgomery form: all four outputs are converted here
+        ln::normalize<FT>(c0);
+        c0 = ln::mul<FT>(c0, k32); c1 = ln::mul<FT>(c1, k32); c2 = ln::mul<FT>(c2, k32); c3 = ln::mul<FT>(c3, k32);
+      } else if (fr) {
+        ln::normalize<FT>(c0);                                                                  // (a sum of four loads: < 4.01p)
+      } else {
+        ln::clamp_apply<FT>(c0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(c0.v[8])));
+      }
+      planes_put<FT>(lds, T, SWZ(e0), c0);
+      planes_put<FT>(lds, T, SWZ(e0 + dq), c1);
+      planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), c2);
+      planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), c3);
+      mem_phase(true);
+      __syncthreads();
+      continue;
+    }
     if constexpr (RU >= 0) {
       if (r >= RU && !last_two) {
         // ---- a uniform round: wave w takes the quads q = w mod 4, whose twiddles are the three of pack slot (w): scalar operands.
         //      Block 0 is gone (converted in round RU - 1), so every lane multiplies by the same plain constants.
         const u32 wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const u32 qu = ((tid & 63u) << 2) | wv;
+        // pure form: the twiddles go by j mod 4, so wave w takes the quads j = 4 m + w, (m, lp) = the lane
+        const u32 qu = NF ? (((((tid & 63u) >> LBT) << 2) | wv) << LBT) | (tid & ((1u << LBT) - 1)) : ((tid & 63u) << 2) | wv;
         const u32 lpu = qu & ((1u << LBT) - 1), ju = qu >> LBT;
         const u32 iu = ((ju >> (hb - 1)) << (hb + 1)) | (ju & ((1u << (hb - 1)) - 1));
         const u32 eu = (iu << LBT) | lpu;
@@ -205,7 +366,9 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         const LN<9> b2 = ln::mul_u<FT>(ln::sub(x0, x2), wu);
         const LN<9> b3 = ln::mul_u<FT>(ln::sub(x1, x3), wu + U_SLOT<FT>);                            // (-2p, 2.7p)
         LN<9> c2 = ln::add(b2, b3);
-        ln::normalize<FT>(c2);
+        // (pure form: clamped, (-4p, 5.4p) -> [0, p + 2^239), so that the I-only round after it adds four values below 2.7p)
+        if constexpr (NF) ln::clamp_apply<FT>(c2, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(c2.v[8])));
+        else ln::normalize<FT>(c2);
         planes_put<FT>(lds, T, SWZ(eu + 2 * dq), c2);
         planes_put<FT>(lds, T, SWZ(eu + 3 * dq), ln::mul_u<FT>(ln::sub(b2, b3), wu + 2 * U_SLOT<FT>));
         mem_phase(true);
@@ -213,15 +376,16 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         continue;
       }
     }
-    if (u == 0 && zero_hi) {
+    if (u == 0 && zero_hi) {                                 // (pure form, S == 2: the I-only round above took it, zeros and all)
       // zero-padded first round (rate <= 1/2): x2 = x3 = 0, the stage-0 butterflies are (x, x w); inputs < p; everything
       // is block 0, so with canonical output the three multiplies leaving it (w0, w3, and w2 for c1) take the converting set
       const u32 vb = canon ? 3u : 0u;
       const LN<9> w0 = pack_get<FT, 6>(blk, period, vb + 0, jl), w3 = pack_get<FT, 6>(blk, period, vb + 1, jl), w2 = pack_get<FT, 6>(blk, period, vb + 2, jl);
       mem_phase(false);
+      const bool cv0 = NF && canon && r == RC;               // pure form: the round that converts the pure sum as well (below)
       if (a.n_valid <= (1ull << (k - 2))) {                  // rate <= 1/4: x1 is zero too
         const LN<9> x0 = DIRECT ? xin[0] : planes_get<FT>(lds, T, SWZ(e0));
-        if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e0), x0);
+        if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(x0, k32) : x0);
         planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(x0, w2));
         planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(x0, w0));
         planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), ln::mul<FT>(x0, w3));
@@ -229,7 +393,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         const LN<9> x0 = DIRECT ? xin[0] : planes_get<FT>(lds, T, SWZ(e0)), x1 = DIRECT ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + dq));
         LN<9> c0 = ln::add(x0, x1);                                                           // [0, 2p)
         ln::normalize<FT>(c0);
-        planes_put<FT>(lds, T, SWZ(e0), c0);
+        planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(c0, k32) : c0);
         planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(ln::sub(x0, x1), w2));
         const LN<9> t = ln::mul_u<FT>(x1, a.wq_w);                                                // x1 I (plain constant: t keeps x1's form); (-2p, 2.7p)
         planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(ln::add(x0, t), w0));                  // in: limbs (-2^29, 2^30), |value| < 3.7p
@@ -284,14 +448,15 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       // block 0 of stages (u, u + 1) = the quads whose elements all lie below n / 2^(t + 2): here exactly q < period in the
       // tiles that hold block 0.  Their three multiplies that leave block 0 (c1, c2, c3) take the converting set; c0 stays a
       // pure sum
-      const bool blk0c = canon && blk0_tile && q < period && (RU < 0 || r < RU);
-      if constexpr (RU >= 1) {
-        if (r == RU - 1 && blk0c) {
+      // Pure form: block 0 of a column is i < 2^(S - u - 2), the quads q < dq of EVERY tile, through round RC (every round that comes
+      // here), which converts c0 too: after it every slot is canonical -- c1, c2, c3 of the block-0 quads of rounds <= RC by their
+      // converting twiddles, c0 of round RC by 2^5, and everything else descends from those
+      const bool blk0c = NF ? canon && q < dq : canon && blk0_tile && q < period && (RU < 0 || r < RU);
+      if constexpr (NF ? RC >= 0 : RU >= 1) {
+        if (r == (NF ? RC : RU - 1) && blk0c) {
           // the last round before the uniform one: c0, the pure sum that would carry block 0 on, is converted as well (a multiply
-          // by 2^5 = 2^261 R^-1: 16 lanes of one wave per block-0 tile), so that the uniform round sees canonical values only
-          LN<9> k32;
-#pragma unroll
-          for (int i = 0; i < 9; i++) k32.v[i] = i == 0 ? 32u : 0u;
+          // by 2^5 = 2^261 R^-1: 16 lanes of one wave per block-0 tile; pure form: the lanes q < dq), so that the uniform round sees
+          // canonical values only
           planes_put<FT>(lds, T, SWZ(e0), ln::mul<FT>(c0, k32));
         }
       }
@@ -343,21 +508,22 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   }
 }
 
-template <int S, int LTJ, bool FIRST, bool MID>
+template <int S, int LTJ, bool FIRST, bool MID, bool NF>
 hipError_t launch_tm(const NttPassArgs& a, const u32* pack, const NttPackInfo& pi, hipStream_t st) {
   constexpr int LT = S + LTJ;
   const u64 tiles = ((u64)1 << (a.log_n - LT)) * a.n_rows;
   const size_t lds_bytes = (((size_t)1 << LT) * 9 + 64 * LnField<FT255>::STRIDE) * 4;   // tile + q*p table
   // hipFuncSetAttribute is idempotent and cheap; calling it on every launch keeps this free of unsynchronised caches
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_l9s_kernel<S, LTJ, FIRST, MID>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((ntt_pass_l9s_kernel<S, LTJ, FIRST, MID>), dim3((unsigned)tiles), dim3(256), lds_bytes, st, a, pack, pi);
+  hipLaunchKernelGGL((ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF>), dim3((unsigned)tiles), dim3(256), lds_bytes, st, a, pack, pi);
   return hipGetLastError();
 }
 template <int S, int LTJ, bool FIRST>
 hipError_t launch_t(const NttPassArgs& a, const u32* pack, const NttPackInfo& pi, hipStream_t st) {
-  return a.mid ? launch_tm<S, LTJ, FIRST, true>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false>(a, pack, pi, st);
+  if (a.form) return a.mid ? launch_tm<S, LTJ, FIRST, true, true>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, true>(a, pack, pi, st);
+  return a.mid ? launch_tm<S, LTJ, FIRST, true, false>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, false>(a, pack, pi, st);
 }
 
 }  // namespace
@@ -377,6 +543,7 @@ hipError_t launch_ntt_pass_l9s(const NttPassArgs& a, bool first, const uint32_t*
   }
   // two-pass plans: s + 10 stages in all; three-pass plans: s + 20 (the first pass works at element stride 2^20)
   if (a.t0 != 0 || a.s + a.log_tj != 10 || (a.s + 10 != a.log_n && a.s + 20 != a.log_n)) return hipErrorInvalidValue;
+  if (a.form && a.s + 10 != a.log_n) return hipErrorInvalidValue;      // (the pure / coset form: two-pass plans only)
   if (a.tile_group && ((1u << (a.log_n - 10)) >> a.tile_group) < 8) return hipErrorInvalidValue;
   switch (a.s) {
 #define X(SV) case SV: return launch_t<SV, 10 - SV, true>(a, pack, pi, st);

@@ -21,6 +21,24 @@ template <int S, int LBT> struct Shape {
   static constexpr int RU = NR4 >= 4 ? 3 : -1;
   static constexpr int NRU = RU < 0 ? 0 : NR4 - RU;
 };
+// ---- K1s, the Ft255 two-pass plans in the pure / coset form (ntt_l9s.hip, head comment).  The first pass is a plain 2^S-point DIF on
+//      every column of its tile: the twiddles of a round depend on the sub-block position only, sets(r) distinct triples in radix-4 round
+//      r -- 4^k down to 1.  The round with 4 sets is wave-uniform (RU; only where a lane-varying radix-4 round precedes it, which is where
+//      block 0 gets converted: RC), the round with 1 set multiplies by I alone.  RC: the last round that reads its twiddles from the
+//      pack; with canonical output it converts its pure sum c0 as well, so that nothing is left in Montgomery form after it.  RC < 0
+//      (S <= 3): the radix-2 round (S = 1, 3) or the I-only round (S = 2) converts every output instead.
+template <int S> struct PureShape {
+  static constexpr int U0 = S & 1;
+  static constexpr int NR4 = S / 2;
+  static constexpr u32 sets(int r) { return 1u << (S - U0 - 2 * r - 2); }
+  static constexpr int RU = NR4 >= 3 ? NR4 - 2 : -1;
+  static constexpr int RC = NR4 >= 3 ? NR4 - 3 : (NR4 == 2 ? 0 : -1);
+};
+// the last pass, coset form: five multiply-then-butterfly radix-4 rounds on a 1024-element tile; round r (stages 2r, 2r + 1) has
+// 4^r sub-blocks of 4^(5 - r) elements and one twiddle triple per sub-block.  Rounds 0 and 1 take theirs as shifted multiples (one per
+// tile, one per wave), rounds 2 .. 4 from the pack: [tile class][round][3 variants w, w^2, w^3][sub-block]
+constexpr u32 coset_sets(int r) { return 1u << (2 * r); }
+
 // words per shifted-multiples table in the packs: N^2 = 25 / 49 / 81 used of 32 / 64 / 96
 template <class FT> constexpr u32 U_SLOT = (FT::N * FT::N + 31) & ~31u;
 // word alignment of a pack's shifted-multiples tables (NttPackInfo.u_off): 64 bytes; Ft255's have always followed the last round's

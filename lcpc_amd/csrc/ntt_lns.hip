@@ -303,6 +303,21 @@ __global__ void __launch_bounds__(256, FT::WAVES) ntt_pass_lns_kernel(NttPassArg
 }
 
 // ---- the twiddle packs of both pass kernels (K1s: Ft255, ntt_l9s.hip; K1n: here), in the layout of ntt_ln_dev.h pack_put ----------
+// w^ix R' for ix < n.  The tables hold w^i for i < n / 2 and w^(n/2) = -1: past that, the negated entry, p - entry, limb-wise with
+// borrow (entry in (0, p))
+template <class FT> LCPC_DEV LN<FT::N> tab_entry_neg(const u32* tab, u32 ix, u32 half_n) {
+  LN<FT::N> m = tab_entry<FT>(tab, ix & (half_n - 1));
+  if (ix >= half_n) {
+    int32_t br = 0;
+#pragma unroll
+    for (int z = 0; z < FT::N; z++) {
+      const int32_t d = (int32_t)FT::limb(z) - (int32_t)m.v[z] - br;
+      br = d < 0 ? 1 : 0;
+      m.v[z] = z + 1 < FT::N ? (u32)d & ((1u << FT::W) - 1) : (u32)d;
+    }
+  }
+  return m;
+}
 // one thread per (class, round slot, position): copies the table entries a quad / pair will ask for into lane order
 template <class FT, int S, int LBT>
 __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
@@ -335,20 +350,7 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
     // w1 = w^(e + n/4) = I w0 is never read).  The tables hold w^i for i < n / 2 and w^(n/2) = -1: past that, the negated entry
     const u32 ex = (g0 & gm0) << t, half_n = 1u << (k - 1);
     const u32 idx[3] = {ex, 3 * ex, 2 * ex};
-    for (u32 v = 0; v < 6; v++) {
-      const u32 ix = idx[v % 3];
-      LN<FT::N> m = tab_entry<FT>(v < 3 ? a.roots29 : a.roots29c, ix & (half_n - 1));
-      if (ix >= half_n) {                                    // p - entry, limb-wise with borrow (entry in (0, p))
-        int32_t br = 0;
-#pragma unroll
-        for (int z = 0; z < FT::N; z++) {
-          const int32_t d = (int32_t)FT::limb(z) - (int32_t)m.v[z] - br;
-          br = d < 0 ? 1 : 0;
-          m.v[z] = z + 1 < FT::N ? (u32)d & ((1u << FT::W) - 1) : (u32)d;
-        }
-      }
-      pack_put<FT, 6>(blk, period, v, jl, m);
-    }
+    for (u32 v = 0; v < 6; v++) pack_put<FT, 6>(blk, period, v, jl, tab_entry_neg<FT>(v < 3 ? a.roots29 : a.roots29c, idx[v % 3], half_n));
   }
 }
 
@@ -357,30 +359,9 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
 // ln::mul_u / field_wmul_gen.h).  The table entry is w R' mod p: ln::mul(2^(W j), entry) = w 2^(W j), lazily reduced in
 // (-p - eps, eps] (Ft255: (-1.2p, 0.2p]); + p where that lies below -(p - 1) / 2.  Since the multiplier's range lies inside
 // (-1.5p, 0.5p), that one conditional + p lands every value on its unique representative in [-(p - 1) / 2, (p - 1) / 2].
-template <class FT, int S, int LBT>
-__global__ void __launch_bounds__(64) ntt_lns_upack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
-  using SH = Shape<S, LBT>;
+template <class FT> LCPC_DEV void upack_write(const LN<FT::N>& w, u32* out) {
   constexpr int N = FT::N, W = FT::W;
   constexpr u32 M = (1u << W) - 1;
-  const u32 k = a.log_n, t0 = a.t0;
-  const u32 lb = first ? k - S : 0u;
-  const u32 id = blockIdx.x * 64 + threadIdx.x;
-  if (id >= n_classes * SH::NRU * 12) return;
-  const u32 cls = id / (SH::NRU * 12), ru = (id / 12) % SH::NRU, jl0 = (id % 12) / 3, v = id % 3;
-  const u32 r = SH::RU + ru;
-  const u32 u = SH::U0 + 2 * r, hb = S - u - 1;
-  const u32 t = t0 + u;
-  if (t + 2 == k) return;                                    // (a last pass's final round: w^(n/4), not packed)
-  const u32 jl = jl0 & (SH::period4(r) - 1);                 // periods 2 and 1: the four slots repeat
-  const u32 lo = first ? (cls << LBT) : 0u;
-  const u32 gm0 = (1u << (k - t - 1)) - 1, gm1 = gm0 >> 1;
-  const u32 lp = jl & ((1u << LBT) - 1), j = jl >> LBT;
-  const u32 i0 = ((j >> (hb - 1)) << (hb + 1)) | (j & ((1u << (hb - 1)) - 1));
-  const u32 g0 = (i0 << lb) | lo | lp;
-  const u32 g1 = g0 + (1u << (hb - 1 + lb));
-  const u32 idx = v == 0 ? (g0 & gm0) << t : (v == 1 ? (g1 & gm0) << t : (g0 & gm1) << (t + 1));
-  const LN<N> w = tab_entry<FT>(a.roots29, idx);
-  u32* out = pack + (size_t)cls * pi.class_words + pi.u_off + ((ru * 4 + jl0) * 3 + v) * U_SLOT<FT>;
   for (u32 jj = 0; jj < (u32)N; jj++) {
     LN<N> sh;
 #pragma unroll
@@ -402,6 +383,78 @@ __global__ void __launch_bounds__(64) ntt_lns_upack_kernel(NttPassArgs a, NttPac
     for (int kk = 0; kk < N; kk++) out[N * kk + jj] = kk + 1 < N ? (x.v[kk] & M) : x.v[kk];
   }
   for (u32 z = N * N; z < U_SLOT<FT>; z++) out[z] = 0;
+}
+template <class FT, int S, int LBT>
+__global__ void __launch_bounds__(64) ntt_lns_upack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
+  using SH = Shape<S, LBT>;
+  const u32 k = a.log_n, t0 = a.t0;
+  const u32 lb = first ? k - S : 0u;
+  const u32 id = blockIdx.x * 64 + threadIdx.x;
+  if (id >= n_classes * SH::NRU * 12) return;
+  const u32 cls = id / (SH::NRU * 12), ru = (id / 12) % SH::NRU, jl0 = (id % 12) / 3, v = id % 3;
+  const u32 r = SH::RU + ru;
+  const u32 u = SH::U0 + 2 * r, hb = S - u - 1;
+  const u32 t = t0 + u;
+  if (t + 2 == k) return;                                    // (a last pass's final round: w^(n/4), not packed)
+  const u32 jl = jl0 & (SH::period4(r) - 1);                 // periods 2 and 1: the four slots repeat
+  const u32 lo = first ? (cls << LBT) : 0u;
+  const u32 gm0 = (1u << (k - t - 1)) - 1, gm1 = gm0 >> 1;
+  const u32 lp = jl & ((1u << LBT) - 1), j = jl >> LBT;
+  const u32 i0 = ((j >> (hb - 1)) << (hb + 1)) | (j & ((1u << (hb - 1)) - 1));
+  const u32 g0 = (i0 << lb) | lo | lp;
+  const u32 g1 = g0 + (1u << (hb - 1 + lb));
+  const u32 idx = v == 0 ? (g0 & gm0) << t : (v == 1 ? (g1 & gm0) << t : (g0 & gm1) << (t + 1));
+  const LN<FT::N> w = tab_entry<FT>(a.roots29, idx);
+  upack_write<FT>(w, pack + (size_t)cls * pi.class_words + pi.u_off + ((ru * 4 + jl0) * 3 + v) * U_SLOT<FT>);
+}
+
+// ---- K1s, the pure / coset form (ntt_l9s.hip head comment; NttPassArgs.form == 1), Ft255 ------------------------------------------------
+// The pure first pass's lane-order pack is ntt_lns_pack_kernel's for LBT = 0 and one class: the twiddles of a 2^S-point DIF at element
+// stride 2^10, by the position in the sub-block alone (radix-2 slot: i < 2^(S-1); radix-4 slot r: j < PureShape::sets(r)).  Its uniform
+// round (stage pair (u, u + 1), four positions): w0, w1 = I w0, w2 as in ntt_lns_upack_kernel, for the column-free index j << 10
+using F255 = LnField<FT255>;
+__global__ void __launch_bounds__(64) l9s_pure_upack_kernel(NttPassArgs a, NttPackInfo pi, u32 u, u32* pack) {
+  const u32 id = threadIdx.x;
+  if (id >= 12) return;
+  const u32 jl0 = id / 3, v = id % 3;
+  const u32 k = a.log_n, lb = k - a.s, hb = a.s - u - 1;      // (hb == 3)
+  const u32 gm0 = (1u << (k - u - 1)) - 1, gm1 = gm0 >> 1;
+  const u32 g0 = jl0 << lb, g1 = g0 + (1u << (hb - 1 + lb));
+  const u32 idx = v == 0 ? (g0 & gm0) << u : (v == 1 ? (g1 & gm0) << u : (g0 & gm1) << (u + 1));
+  upack_write<F255>(tab_entry<F255>(a.roots29, idx), pack + pi.u_off + (jl0 * 3 + v) * U_SLOT<F255>);
+}
+// The coset last pass: tile class c = the tile's position in the row holds the frequencies k1 = rev_S(c) of the pure pass (S = log n - 10)
+// and evaluates on g <w1024>, g = w^k1.  Round r (stages 2r, 2r + 1), sub-block m < 4^r: the triple w, w^2, w^3 with w = W^E,
+//   E = 2^(8 - 2r) (k1 + 2^S rev_2r(m))  < n / 4        (so 3 E < n: tab_entry_neg)
+// -- the square root of the sub-block's modulus constant gamma in z^(4^(5-r)) - gamma, taken so that the leaves come out in bit-reversed
+// order: the index rule tests/ntt_coset_rules.py restates and tests/test_ntt_coset_model.py holds to the direct DFT
+LCPC_DEV u32 coset_exp(u32 k, u32 cls, u32 r, u32 m) {
+  const u32 S = k - 10;
+  const u32 k1 = __brev(cls) >> (32 - S);
+  const u32 rm = r ? __brev(m) >> (32 - 2 * r) : 0u;
+  return (k1 + (rm << S)) << (8 - 2 * r);
+}
+// rounds 2, 3, 4 (16, 64, 256 triples): lane-order pack, plain table only -- the pure pass leaves nothing in Montgomery form
+__global__ void __launch_bounds__(256) l9s_coset_pack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, u32* pack) {
+  const u32 k = a.log_n, half_n = 1u << (k - 1);
+  const u64 total = (u64)n_classes * 336;
+  for (u64 id = (u64)blockIdx.x * 256 + threadIdx.x; id < total; id += (u64)gridDim.x * 256) {
+    const u32 cls = (u32)(id / 336), x = (u32)(id % 336);
+    const u32 r = x < 16 ? 2u : (x < 80 ? 3u : 4u), m = x < 16 ? x : (x < 80 ? x - 16 : x - 80);
+    const u32 E = coset_exp(k, cls, r, m);
+    u32* blk = pack + (size_t)cls * pi.class_words + pi.round_off[r];
+    for (u32 v = 0; v < 3; v++) pack_put<F255, 3>(blk, coset_sets(r), v, m, tab_entry_neg<F255>(a.roots29, (v + 1) * E, half_n));
+  }
+}
+// rounds 0 (one triple) and 1 (four): shifted multiples, table (r * 4 + m) * 3 + v
+__global__ void __launch_bounds__(64) l9s_coset_upack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, u32* pack) {
+  const u32 k = a.log_n, half_n = 1u << (k - 1);
+  const u32 id = blockIdx.x * 64 + threadIdx.x;
+  if (id >= n_classes * 15) return;
+  const u32 cls = id / 15, x = id % 15;
+  const u32 r = x < 3 ? 0u : 1u, m = x < 3 ? 0u : (x - 3) / 3, v = x % 3;
+  const u32 E = coset_exp(k, cls, r, m);
+  upack_write<F255>(tab_entry_neg<F255>(a.roots29, (v + 1) * E, half_n), pack + (size_t)cls * pi.class_words + pi.u_off + ((r * 4 + m) * 3 + v) * U_SLOT<F255>);
 }
 
 template <class FT, int S, int LBT> NttPackInfo pack_info_t() {
@@ -437,6 +490,25 @@ __global__ void __launch_bounds__(256) roots_ln_kernel(const u32* roots, u64 n, 
 }
 
 #define LNS_FIRST_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
+
+NttPackInfo form_pack_info(uint32_t s, bool first) {
+  NttPackInfo pi{};
+  u32 off = 0;
+  if (first) {
+    // as pack_info_t<F255, S, 0>: the radix-2 slot, then 6 variants x sets(r) per radix-4 round; then the uniform round's 4 x 3 tables
+    const u32 u0 = s & 1, nr4 = s / 2;
+    u32 slot = 0;
+    if (u0) { pi.round_off[slot++] = off; off += 2 * (1u << (s - 1)) * 9; off = (off + 3) & ~3u; }
+    for (u32 r = 0; r < nr4; r++) { pi.round_off[slot++] = off; off += 6 * (1u << (s - u0 - 2 * r - 2)) * 9; off = (off + 3) & ~3u; }
+    if (nr4 >= 3) { pi.u_off = off; off += 4 * 3 * U_SLOT<F255>; }
+  } else {
+    for (u32 r = 2; r < 5; r++) { pi.round_off[r] = off; off += 3 * coset_sets(r) * 9; }
+    pi.u_off = off;
+    off += 2 * 4 * 3 * U_SLOT<F255>;
+  }
+  pi.class_words = off;
+  return pi;
+}
 
 template <class FT> NttPackInfo pack_info_f(uint32_t s, bool first) {
   if (!first) return pack_info_t<FT, 10, 0>();
@@ -497,6 +569,24 @@ template <class FT> hipError_t launch_pass_f(const NttPassArgs& a, bool first, c
 // 0.73 / 1.43 / 2.30 ms against 0.76 / 1.63 / 2.90; 2^20 columns 1.97 / 2.26 ms against 2.02 / 3.26 for Ft127 / Ft191.  Ft63's
 // 8-byte first-pass runs lost at 2^20 columns until the first pass ran the tiles that share cache lines back to back on one
 // XCD (NttPassArgs.tile_group): 512 rows x 2^20 columns 12.9 ms on the general plan, 23.3 ungrouped, 11.2 grouped.
+NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first) { return form_pack_info(s, first); }
+hipError_t launch_ntt_l9s_form_pack(const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st) {
+  if (a.log_n < 11 || a.log_n > 20 || a.s != (first ? a.log_n - 10 : 10u)) return hipErrorInvalidValue;
+  if (!first) {
+    hipLaunchKernelGGL(l9s_coset_pack_kernel, dim3(n_classes >= 1024 ? 1344u : (n_classes * 336 + 255) / 256), dim3(256), 0, st, a, pi, n_classes, pack);
+    hipLaunchKernelGGL(l9s_coset_upack_kernel, dim3((n_classes * 15 + 63) / 64), dim3(64), 0, st, a, pi, n_classes, pack);
+    return hipGetLastError();
+  }
+  if (n_classes != 1) return hipErrorInvalidValue;
+  switch (a.s) {
+#define X(SV) case SV: hipLaunchKernelGGL((ntt_lns_pack_kernel<F255, SV, 0>), dim3(4), dim3(256), 0, st, a, pi, 1u, true, pack); break;
+    LNS_FIRST_CASES(X)
+#undef X
+  }
+  const u32 u0 = a.s & 1, nr4 = a.s / 2;
+  if (nr4 >= 3) hipLaunchKernelGGL(l9s_pure_upack_kernel, dim3(1), dim3(64), 0, st, a, pi, u0 + 2 * (nr4 - 2), pack);
+  return hipGetLastError();
+}
 bool ntt_lns_supported(int nl, uint32_t log_n) { return (nl == 2 || nl == 4 || nl == 6) && log_n >= 11 && log_n <= 20u; }
 bool ntt_lns3_supported(int nl, uint32_t log_n) { return (nl == 2 || nl == 4 || nl == 6) && log_n >= 21 && log_n <= 26; }
 __global__ void __launch_bounds__(256) lns_subtable_kernel(const u32* tab, u32 shift, u64 n, u32 words, u32* sub) {
