@@ -19,8 +19,8 @@
  *    header documents.
  *  - The members are independent afterwards: any of them may be destroyed, in any order; any of them may be refilled alone through
  *    any commit entry point of the core header, at other dims too; any of them may be refilled by another batch call, with the same
- *    or other partners.  (Members of a batched BLAKE3 Ligero commit share one device allocation; the last of them to be destroyed
- *    or refilled elsewhere frees it.  A batch call into the same members, in the same order, at the same shape reuses it.)
+ *    or other partners.  (Members of a batched Ligero commit, under any digest, share one device allocation; the last of them to be
+ *    destroyed or refilled elsewhere frees it.  A batch call into the same members, in the same order, at the same shape reuses it.)
  *  - flags: LCPC_COMMIT_BORROW_COEFFS means what it means in the core header -- honoured when n_coeffs fills whole rows; member i
  *    then keeps reading its slice of the caller's buffer, which must outlive it.  LCPC_COMMIT_ASYNC_TAIL is ignored, as by the
  *    single device commit.
@@ -34,13 +34,14 @@
  *    that overlap in members, issued from several threads, do not deadlock; readers in flight on any member are waited for.
  *
  * Which encoders are batched
- *  - Ligero encoders with the BLAKE3 digest, all four fields: ONE row encode over n_batch * n_rows rows (the row NTT is
- *    row-independent), then the batched column-hash and tree kernels (batch_kernels.hip K3b / K4b), the member index a grid dimension.
+ *  - Ligero encoders, all four fields, all five digests: ONE row encode over n_batch * n_rows rows (the row NTT is row-independent),
+ *    then batched column-hash and tree kernels, the member index a grid dimension.  BLAKE3: batch_kernels.hip (K3b / K4b).  SHA3-256,
+ *    Keccak-256, SHA-256 and BLAKE2b -- one serial chain per column -- run the batch forms of their leaf and subtree kernels (sha3.hip,
+ *    sha256.hip, blake2b.hip): one leaf launch and one tree call for the whole batch, roots and hashes slots of D bytes.
  *    The hash and tree of the whole batch cost as many launches as one member's; the encode costs one member's when n_coeffs fills
  *    whole rows and the polynomials are back to back, and one more (a strided placement that also zero-fills ragged tails) otherwise.
- *  - Everything else -- Brakedown encoders, and Ligero encoders with SHA3-256, BLAKE2b, Keccak-256 or SHA-256 -- gets the same
- *    results member by member: the single-commit pipeline runs for each member in turn on `stream`.  Batched kernels for the chained
- *    digests and for Brakedown's position-major path do not exist yet.
+ *  - Brakedown encoders, under any digest, get the same results member by member: the single-commit pipeline runs for each member
+ *    in turn on `stream`.  Batched kernels for Brakedown's position-major path do not exist yet.
  *
  * Timing: if lcpc_set_timing is on for cms[0], the call measures the BATCH -- phase times and launch counts of all members
  * together -- and stores those figures in every member's lcpc_timings.  They are the batch's, not one member's share.  (On the

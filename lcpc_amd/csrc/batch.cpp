@@ -1,10 +1,12 @@
 // lcpc_amd/csrc/batch.cpp -- lcpcx_commit_batch_device (include/lcpc_hip_batch.h): n_batch equal-shape polynomials committed under
 // one encoder in one pipeline.
 //
-// Ligero x BLAKE3: the members' comm / coeffs / hashes live member-major in one slab (internal.h BatchSlab), the row NTT runs once
-// over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as the batched
-// kernels of batch_kernels.hip (K3b / K4b) -- as many launches as ONE commit of the shape.  Every other encoder: the single-commit
-// pipeline (commit.cpp commit_device_locked) for each member in turn.
+// Ligero, under every digest: the members' comm / coeffs / hashes live member-major in one slab (internal.h BatchSlab), the row NTT runs
+// once over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as batched kernels
+// -- as many launches as ONE commit of the shape.  BLAKE3: batch_kernels.hip (K3b / K4b: chunk CVs, fold, or leaf digests with the
+// first six tree levels).  SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: one serial chain per column, so one leaf launch and one tree
+// call over the batch (the batch forms in sha3.hip, sha256.hip, blake2b.hip); hashes slots are digest_words(c) words.  Brakedown,
+// under any digest: the single-commit pipeline (commit.cpp commit_device_locked) for each member in turn.
 #include "internal.h"
 #include "../../include/lcpc_hip_batch.h"
 #include <functional>
@@ -19,9 +21,10 @@ struct BatchShape {
   uint64_t n_rows, n_chunks, stride;   // stride: elements between polynomials
   bool contiguous;                     // whole rows, back to back: the encode reads the caller's buffer in place
   bool borrow;
-  bool tree;                           // leaf_tree_supported
+  bool tree;                           // BLAKE3: leaf_tree_supported
+  bool chained;                        // SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: no chunk CVs, no leaf_tree form
   bool need_coeffs() const { return !(borrow && contiguous); }   // (a strided borrow still stages the rows for the encode)
-  bool need_cvs() const { return !tree && n_chunks > 1; }
+  bool need_cvs() const { return !chained && !tree && n_chunks > 1; }
 };
 
 LeafArgs batch_leaf_args(const lcpc_ctx* c, const BatchShape& s, const uint32_t* comm) {
@@ -38,7 +41,7 @@ int make_slab(const lcpc_ctx* c, ErrText* err, const BatchShape& s, uint32_t n_b
   sl->n_batch = n_batch; sl->n_rows = s.n_rows;
   sl->comm_stride = s.n_rows * c->n_cols * c->NL;
   sl->coeffs_stride = s.need_coeffs() ? s.n_rows * c->n_per_row * c->NL : 0;
-  sl->hashes_stride = (2 * c->np2 - 1) * 8;
+  sl->hashes_stride = (2 * c->np2 - 1) * digest_words(c);
   sl->cvs_stride = s.need_cvs() ? s.n_chunks * c->n_cols * 8 : 0;
   uint64_t off = 0;
   sl->off_comm = off; off = align256(off + (uint64_t)n_batch * s.n_rows * c->n_cols * eb);
@@ -47,7 +50,7 @@ int make_slab(const lcpc_ctx* c, ErrText* err, const BatchShape& s, uint32_t n_b
   sl->off_cvs = off; off = align256(off + (uint64_t)n_batch * sl->cvs_stride * 4);
   if (int rc = dev_alloc(err, &sl->d, (size_t)off)) return rc;
   void* hp = nullptr;              // without the mapping the roots are copied out (fetch_roots)
-  if (hipHostMalloc(&hp, (size_t)n_batch * 32, hipHostMallocMapped) == hipSuccess) {
+  if (hipHostMalloc(&hp, (size_t)n_batch * digest_len(c), hipHostMallocMapped) == hipSuccess) {
     void* dp = nullptr;
     if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) { sl->h_roots = static_cast<uint32_t*>(hp); sl->d_roots_alias = static_cast<uint32_t*>(dp); }
     else (void)hipHostFree(hp);
@@ -83,7 +86,7 @@ int fetch_roots(lcpc_commit_t* const* cms, uint32_t n_batch, const BatchSlab* sl
   return 0;
 }
 
-// Ligero x BLAKE3 (every member's fill_mu and mu held, the device current)
+// Ligero, every digest (every member's fill_mu and mu held, the device current)
 int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
                       hipStream_t st, uint32_t flags, uint8_t* roots) {
   lcpc_commit_t* m0 = cms[0];
@@ -95,7 +98,8 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   const bool whole = s.n_rows * c->n_per_row == n_coeffs;
   s.contiguous = whole && s.stride == n_coeffs;
   s.borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && whole;
-  s.tree = leaf_tree_supported(batch_leaf_args(c, s, nullptr), c->np2);
+  s.chained = !is_blake3(c);
+  s.tree = !s.chained && leaf_tree_supported(batch_leaf_args(c, s, nullptr), c->np2);
   int rc;
   // st behind every member's last fill; the members are un-committed from here until the batch is sealed
   for (uint32_t i = 0; i < n_batch; i++)
@@ -147,8 +151,17 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   // ---- column hash + tree: the launches of one commit, each over the whole batch (commit.cpp merkleize_device)
   LeafArgs la = batch_leaf_args(c, s, comm0);
   uint32_t* hashes0 = sl->seg(sl->off_hashes, sl->hashes_stride, 0);
+  const uint32_t dw = digest_words(c);
   uint32_t levels_done = 0;
-  if (s.tree) {
+  if (s.chained) {
+    // one serial chain per column over the whole leaf message: the digests themselves, in one launch
+    la.out = hashes0;
+    if (is_sha3(c)) HIPCHK(m0, launch_sha3_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    else HIPCHK(m0, launch_blake2b_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    launches[1]++;
+  } else if (s.tree) {
     HIPCHK(m0, launch_leaf_tree_batch(c->NL, la, hashes0, c->np2, n_batch, sl->comm_stride, sl->hashes_stride, st));
     launches[1]++;
     levels_done = 6;
@@ -164,9 +177,13 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   }
   if (timing) HIPCHK(m0, hipEventRecord(m0->ev[2], st));
   if (c->np2 > c->n_cols)          // hashes[n_cols..np2) of every member stay zero (lib.rs:656-666)
-    HIPCHK(m0, hipMemset2DAsync(hashes0 + c->n_cols * 8, (size_t)sl->hashes_stride * 4, 0, (size_t)(c->np2 - c->n_cols) * 32, n_batch, st));
+    HIPCHK(m0, hipMemset2DAsync(hashes0 + c->n_cols * dw, (size_t)sl->hashes_stride * 4, 0, (size_t)(c->np2 - c->n_cols) * digest_len(c), n_batch, st));
   if (c->np2 > 1) {
-    HIPCHK(m0, launch_merkle_tree_from_batch(hashes0, c->np2, levels_done, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    if (is_sha3(c)) HIPCHK(m0, launch_sha3_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    else if (is_blake2b(c)) HIPCHK(m0, launch_blake2b_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    else HIPCHK(m0, launch_merkle_tree_from_batch(hashes0, c->np2, levels_done, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
     launches[2]++;
   }
 
@@ -196,7 +213,7 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   return roots ? fetch_roots(cms, n_batch, sl.get(), st, roots) : 0;
 }
 
-// every other encoder: the single-commit pipeline member by member on st; the batch's timings are the sums
+// Brakedown: the single-commit pipeline member by member on st; the batch's timings are the sums
 int commit_batch_each(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
                       hipStream_t st, uint32_t flags, uint8_t* roots) {
   lcpc_commit_t* m0 = cms[0];
@@ -254,7 +271,7 @@ int lcpcx_commit_batch_device(lcpc_commit_t* const* cms, uint32_t n_batch, const
   for (lcpc_commit_t* m : order) mus.emplace_back(m->mu);
   HIPCHK(m0, hipSetDevice(c->prm.device));
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = c->prm.encoding == LCPC_ENC_LIGERO && is_blake3(c);
+  const bool fast = c->prm.encoding == LCPC_ENC_LIGERO;
   int rc = fast ? commit_batch_fast(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots)
                 : commit_batch_each(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots);
   if (rc)                          // a failed batch leaves no member committed

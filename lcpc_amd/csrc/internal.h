@@ -229,6 +229,7 @@ template <typename S> struct SetLease {
 // The storage of one batched commit (batch.cpp, include/lcpc_hip_batch.h): comm, coeffs, hashes and the chunk chaining values of
 // every member in ONE device allocation, member-major, so that the row encode sees one matrix of n_batch * n_rows rows and the batched
 // hash / tree kernels reach member i at a fixed stride.  The members share it (lcpc_commit_s::slab); the last one to leave frees it.
+// A hashes slot is digest_words(c) words (8; BLAKE2b 16); only BLAKE3 has chunk chaining values.
 // A member's d_comm / d_coeffs / d_hashes are then views into it: leave_slab before anything frees or regrows them.
 struct BatchSlab {
   uint8_t* d = nullptr;
@@ -236,7 +237,7 @@ struct BatchSlab {
   uint64_t comm_stride = 0, coeffs_stride = 0, hashes_stride = 0, cvs_stride = 0;   // 32-bit words per member (0: no such segment)
   uint32_t n_batch = 0;
   uint64_t n_rows = 0;
-  uint32_t* h_roots = nullptr;     // pinned, device-mapped [n_batch][8]: written by the launch that produces the roots
+  uint32_t* h_roots = nullptr;     // pinned, device-mapped [n_batch][digest_words]: written by the launch that produces the roots
   uint32_t* d_roots_alias = nullptr;
   EncodeWs ws;                     // the batch's row encode (a batch call holds every member's lock)
   uint32_t* seg(uint64_t off, uint64_t stride, uint32_t i) const { return reinterpret_cast<uint32_t*>(d + off) + (size_t)i * stride; }

@@ -128,6 +128,25 @@ hipError_t launch_merkle_tree_from_batch(uint32_t* hashes, uint64_t np2, uint32_
 hipError_t launch_batch_place(const uint64_t* src, uint64_t src_stride, uint64_t n_valid, uint64_t* dst, uint64_t dst_stride, uint32_t n_batch,
                               hipStream_t st);
 
+// ---- batched column hash and tree of the serial-chain digests (sha3.hip, sha256.hip, blake2b.hip): the batch forms of the
+// launch_*_leaves / launch_*_merkle_tree launchers below, n_batch <= 65535 members with the member index a grid dimension.  `a` and
+// `hashes` describe member 0; member i's comm, a.out and hashes start i * (the given stride, in 32-bit words) behind it.  Same digests
+// as the single launchers, bit for bit; alignment and stride rules as for the BLAKE3 batch launchers above.  Empty work (n_batch == 0,
+// no columns) is hipSuccess; nl == 8 with a.canon_in == 0 is hipErrorInvalidValue (a Ligero comm over Ft255 is always canonical, so
+// that kernel is not instantiated).
+hipError_t launch_sha3_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
+hipError_t launch_keccak256_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
+hipError_t launch_sha256_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
+hipError_t launch_blake2b_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
+// root_out (may be null): [n_batch][8] words ([n_batch][16] for BLAKE2b), member i's root written by the launch that produces it
+hipError_t launch_sha3_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st, uint32_t* root_out);
+hipError_t launch_keccak256_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
+                                              uint32_t* root_out);
+hipError_t launch_sha256_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
+                                           uint32_t* root_out);
+hipError_t launch_blake2b_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
+                                            uint32_t* root_out);
+
 // ---- SHA3-256 digest (sha3.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA3_256 ----
 // leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a sponge is not split); a.out = LcCommit.hashes
 hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);

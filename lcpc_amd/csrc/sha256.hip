@@ -101,6 +101,47 @@ hipError_t launch_sha256_leaves(int nl, const LeafArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- the batch form (kernels.h: launch_sha256_leaves_batch; batch.cpp) ----
+// sha256_leaf_kernel for n_batch equal-shape members of one encoder, the member index blockIdx.y: the same chain per column on
+// member i's comm and out, which start i * comm_stride / i * out_stride words behind member 0's
+// (The second launch bound is the one-shot twin's occupancy in waves per SIMD: without it the register allocator spreads the same
+// instruction stream over twice the VGPRs.)
+template <int NL, bool CANON>
+__global__ void __launch_bounds__(256, (NL == 6 && !CANON) ? 7 : 8) sha256_leaf_batch_kernel(LeafArgs a, u64 comm_stride, u64 out_stride) {
+  const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (col >= a.n_cols) return;
+  a.comm += (u64)blockIdx.y * comm_stride;
+  a.out += (u64)blockIdx.y * out_stride;
+  constexpr int L = NL / 2;
+  const u64 n_words = 4 + (u64)L * a.n_rows_total;
+  const u64 n_blocks = n_words / 8 + 1 + ((n_words & 7) == 7 ? 1 : 0);
+  u32 h[8];
+  s256::init(h);
+  for (u64 j = 0; j * L < n_blocks; j++) s2_group_step<NL, CANON, 0>(h, a, col, j, n_words, n_blocks);
+  u32* o = a.out + col * 8;
+  *reinterpret_cast<uint4*>(o) = make_uint4(s256::bswap(h[0]), s256::bswap(h[1]), s256::bswap(h[2]), s256::bswap(h[3]));
+  *reinterpret_cast<uint4*>(o + 4) = make_uint4(s256::bswap(h[4]), s256::bswap(h[5]), s256::bswap(h[6]), s256::bswap(h[7]));
+}
+
+hipError_t launch_sha256_leaves_batch(int nl, const LeafArgs& a, u32 n_batch, u64 comm_stride, u64 out_stride, hipStream_t st) {
+  if (n_batch > 65535) return hipErrorInvalidValue;          // grid.y
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
+  if (nl == 8 && !a.canon_in) return hipErrorInvalidValue;   // Ft255's Ligero comm is canonical: the other form has no batch user
+  if (a.n_cols == 0 || n_batch == 0) return hipSuccess;
+  const dim3 grid((unsigned)((a.n_cols + 255) / 256), n_batch);
+#define S2_CASE(NLV)                                                                                                                \
+  case NLV:                                                                                                                         \
+    if (a.canon_in) hipLaunchKernelGGL((sha256_leaf_batch_kernel<NLV, true>), grid, dim3(256), 0, st, a, comm_stride, out_stride);  \
+    else hipLaunchKernelGGL((sha256_leaf_batch_kernel<NLV, false>), grid, dim3(256), 0, st, a, comm_stride, out_stride);            \
+    break;
+  switch (nl) {
+    S2_CASE(2) S2_CASE(4) S2_CASE(6)
+    case 8: hipLaunchKernelGGL((sha256_leaf_batch_kernel<8, true>), grid, dim3(256), 0, st, a, comm_stride, out_stride); break;
+  }
+#undef S2_CASE
+  return hipGetLastError();
+}
+
 // ---- the same chain a block range at a time (kernels.h: launch_sha256_leaves_range) ----
 // s2_group_step for the blocks of group j that lie in [b0, b1): a block outside the range is neither loaded nor compressed
 template <int NL, bool CANON, int B>
@@ -226,6 +267,67 @@ hipError_t launch_sha256_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* 
     const u64 nwg = width >> lsub;
     hipLaunchKernelGGL(sha256_merkle_subtree_kernel, dim3((unsigned)nwg), dim3(256), 0, st, hashes, in_off, width, lsub,
                        lsub == lw ? root_out : (u32*)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    for (u32 j = 0; j < lsub; j++) { in_off += width; width >>= 1; }
+  }
+  return hipSuccess;
+}
+
+
+// sha256_merkle_subtree_kernel per member (blockIdx.y): member i's hashes start i * hashes_stride words behind member 0's; root_out
+// (may be null): [n_batch][8], member i's root at root_out + 8 i
+__global__ void __launch_bounds__(256) sha256_merkle_subtree_batch_kernel(u32* hashes, u64 in_off, u64 width, u32 lsub, u32* root_out,
+                                                                          u64 hashes_stride) {
+  __shared__ u32 buf[256 * 8];
+  hashes += (u64)blockIdx.y * hashes_stride;
+  const u32 tid = threadIdx.x;
+  const u64 base = (u64)blockIdx.x << lsub;
+  u64 layer_in = in_off, w = width, layer_out = in_off + width;
+  u32 n_out = 1u << (lsub - 1);
+  u32 l[8], r[8], o[8];
+  if (tid < n_out) {
+    const u32* g = hashes + (layer_in + base + 2 * tid) * 8;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { l[i] = g[i]; r[i] = g[8 + i]; }
+    sha256_node(o, l, r);
+    u32* d = hashes + (layer_out + (base >> 1) + tid) * 8;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { d[i] = o[i]; buf[tid * 8 + i] = o[i]; }
+  }
+  for (u32 j = 2; j <= lsub; j++) {
+    __syncthreads();
+    layer_in = layer_out;
+    w >>= 1;
+    layer_out = layer_in + w;
+    n_out >>= 1;
+    const bool act = tid < n_out;
+    if (act) sha256_node(o, buf + 2 * tid * 8, buf + (2 * tid + 1) * 8);
+    __syncthreads();
+    if (act) {
+      u32* d = hashes + (layer_out + (base >> j) + tid) * 8;
+#pragma unroll
+      for (int i = 0; i < 8; i++) { d[i] = o[i]; buf[tid * 8 + i] = o[i]; }
+    }
+  }
+  if (root_out != nullptr) {
+    __syncthreads();
+    if (tid < 8) root_out[(u64)blockIdx.y * 8 + tid] = buf[tid];
+  }
+}
+
+// launch_sha256_merkle_tree for every member: the same launches, each over the whole batch
+hipError_t launch_sha256_merkle_tree_batch(u32* hashes, u64 np2, u32 n_batch, u64 hashes_stride, hipStream_t st, u32* root_out) {
+  if (n_batch > 65535) return hipErrorInvalidValue;          // grid.y
+  if (n_batch == 0) return hipSuccess;
+  u64 in_off = 0, width = np2;
+  while (width > 1) {
+    u32 lw = 0;
+    while (((u64)1 << lw) < width) lw++;
+    const u32 lsub = lw < 9 ? lw : 9;
+    const u64 nwg = width >> lsub;
+    hipLaunchKernelGGL(sha256_merkle_subtree_batch_kernel, dim3((unsigned)nwg, n_batch), dim3(256), 0, st, hashes, in_off, width, lsub,
+                       lsub == lw ? root_out : (u32*)nullptr, hashes_stride);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     for (u32 j = 0; j < lsub; j++) { in_off += width; width >>= 1; }
