@@ -19,8 +19,8 @@
  *    header documents.
  *  - The members are independent afterwards: any of them may be destroyed, in any order; any of them may be refilled alone through
  *    any commit entry point of the core header, at other dims too; any of them may be refilled by another batch call, with the same
- *    or other partners.  (Members of a batched Ligero commit, under any digest, share one device allocation; the last of them to be
- *    destroyed or refilled elsewhere frees it.  A batch call into the same members, in the same order, at the same shape reuses it.)
+ *    or other partners.  (Members of a batched commit share one device allocation; the last of them to be destroyed or refilled
+ *    elsewhere frees it.  A batch call into the same members, in the same order, at the same shape reuses it.)
  *  - flags: LCPC_COMMIT_BORROW_COEFFS means what it means in the core header -- honoured when n_coeffs fills whole rows; member i
  *    then keeps reading its slice of the caller's buffer, which must outlive it.  LCPC_COMMIT_ASYNC_TAIL is ignored, as by the
  *    single device commit.
@@ -40,12 +40,27 @@
  *    sha256.hip, blake2b.hip): one leaf launch and one tree call for the whole batch, roots and hashes slots of D bytes.
  *    The hash and tree of the whole batch cost as many launches as one member's; the encode costs one member's when n_coeffs fills
  *    whole rows and the polynomials are back to back, and one more (a strided placement that also zero-fills ragged tails) otherwise.
- *  - Brakedown encoders, under any digest, get the same results member by member: the single-commit pipeline runs for each member
- *    in turn on `stream`.  Batched kernels for Brakedown's position-major path do not exist yet.
+ *  - Brakedown encoders: the expander matrices are the same for every row of every member, so the encode is ONE pass over the
+ *    n_batch * n_rows stacked rows, in the launches of one commit (one more when a placement is needed, as above).  By the member's
+ *    n_rows, at the threshold of the single commit (24), so that each member holds what it would hold alone:
+ *      n_rows < 24   the members keep row-major comm matrices in the shared allocation, as Ligero members do.  From 24 STACKED rows on
+ *                    the encode runs the position-major kernels on a working copy and transposes back; below, the row-major kernels.
+ *      n_rows >= 24  every member keeps its own position-major matrix, written by the batch forms of the position-major kernels
+ *                    (kernels.hip K2b: one lane per stacked row, full waves).  The row-major copy lcpc_get_comm makes on demand is
+ *                    the member's own allocation; reading it leaves the shared one and the other members alone.
+ *    BLAKE3: the batched column-hash and tree kernels, as for Ligero -- hash and tree cost one commit's launches.
+ *    LIMITATION -- SHA3-256, Keccak-256, SHA-256, BLAKE2b: the encode is batched as above, the hash and the tree run member by member
+ *    with the single-commit launchers, n_batch times one commit's launches (pinned by
+ *    tests/test_gpu_commit_batch_digests.py::test_brakedown_under_a_chained_digest); the roots are then copied out member by member
+ *    behind the one synchronisation.
+ *    LIMITATION -- a batch of more than 65535 * 32 stacked rows (the grid of the batch transposes) runs the single-commit pipeline for
+ *    each member in turn on `stream`: same results.
  *
  * Timing: if lcpc_set_timing is on for cms[0], the call measures the BATCH -- phase times and launch counts of all members
- * together -- and stores those figures in every member's lcpc_timings.  They are the batch's, not one member's share.  (On the
- * member-by-member path they are the sums over the members.)
+ * together -- and stores those figures in every member's lcpc_timings.  They are the batch's, not one member's share.  For Brakedown
+ * under BLAKE3 all of them are the batch's; under the four chained digests encode_ms and encode_launches are the batch's, hash_ms /
+ * merkle_ms and their launch counts are sums over the members (the members' hashes and trees alternate on the stream).  On the
+ * member-by-member path every figure is the sum over the members.
  */
 #ifndef LCPC_HIP_BATCH_H
 #define LCPC_HIP_BATCH_H

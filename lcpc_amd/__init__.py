@@ -420,8 +420,9 @@ def commit_batch(enc, coeffs, n_coeffs=None, stream=0, sync=True, borrow=False, 
     stacked.  n_coeffs: elements per polynomial when a row holds more than the polynomial (poly_stride = W / L; the rest of a row is
     never read).  borrow: LCPC_COMMIT_BORROW_COEFFS -- the members keep reading the tensor, which they keep alive.  into: the
     LcCommit objects to refill.  sync=False only enqueues on `stream`.  Ligero encoders run the batched pipeline under every digest
-    (BLAKE3, SHA3-256, Keccak-256, SHA-256, BLAKE2b: roots of enc.digest_len bytes); Brakedown encoders are committed member by
-    member behind the same call.  Returns the list of commitment objects (return_roots: and
+    (BLAKE3, SHA3-256, Keccak-256, SHA-256, BLAKE2b: roots of enc.digest_len bytes); Brakedown encoders run one expander encode over
+    the stacked rows of all members, the batched hash and tree under BLAKE3 and the hash and tree member by member under the other
+    four digests.  Returns the list of commitment objects (return_roots: and
     the list of roots the call itself reported; needs sync)."""
     import torch
     if isinstance(coeffs, (list, tuple)):

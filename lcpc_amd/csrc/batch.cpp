@@ -5,8 +5,17 @@
 // once over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as batched kernels
 // -- as many launches as ONE commit of the shape.  BLAKE3: batch_kernels.hip (K3b / K4b: chunk CVs, fold, or leaf digests with the
 // first six tree levels).  SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: one serial chain per column, so one leaf launch and one tree
-// call over the batch (the batch forms in sha3.hip, sha256.hip, blake2b.hip); hashes slots are digest_words(c) words.  Brakedown,
-// under any digest: the single-commit pipeline (commit.cpp commit_device_locked) for each member in turn.
+// call over the batch (the batch forms in sha3.hip, sha256.hip, blake2b.hip); hashes slots are digest_words(c) words.
+//
+// Brakedown: the expander matrices are the same for every row of every member, so the encode is one pass over the n_batch * n_rows
+// stacked rows, in one commit's launches.  Members of < SDIG_T_MIN_ROWS rows keep a row-major comm, as a single commit of theirs
+// does: the same pipeline as Ligero (from 24 STACKED rows on, encode_rows_device runs the position-major kernels on a working T
+// and transposes back).  Members of >= SDIG_T_MIN_ROWS rows keep their own position-major T_i[pos][row] (comm_t), member-major in
+// the slab's `t` segment, written by the batch forms of the K2 kernels (kernels.hip K2b: lane = batch row).  BLAKE3: the batched
+// hash and tree kernels read either layout through LeafArgs' strides.  Under the four chained digests the hash and tree of a
+// Brakedown batch run member by member through the one-shot launchers (merkleize_device):
+// tests/test_gpu_commit_batch_digests.py::test_brakedown_under_a_chained_digest pins that launch count.  A batch with more stacked
+// rows than the batch launchers' grids carry runs the single-commit pipeline (commit.cpp commit_device_locked) member by member.
 #include "internal.h"
 #include "../../include/lcpc_hip_batch.h"
 #include <functional>
@@ -23,6 +32,8 @@ struct BatchShape {
   bool borrow;
   bool tree;                           // BLAKE3: leaf_tree_supported
   bool chained;                        // SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: no chunk CVs, no leaf_tree form
+  bool pos_major;                      // Brakedown, n_rows >= SDIG_T_MIN_ROWS: the members hold T_i (slab segment `t`), not a row-major comm
+  bool member_hash;                    // Brakedown under a chained digest: hash and tree member by member, by the one-shot launchers
   bool need_coeffs() const { return !(borrow && contiguous); }   // (a strided borrow still stages the rows for the encode)
   bool need_cvs() const { return !chained && !tree && n_chunks > 1; }
 };
@@ -30,6 +41,7 @@ struct BatchShape {
 LeafArgs batch_leaf_args(const lcpc_ctx* c, const BatchShape& s, const uint32_t* comm) {
   LeafArgs la{};
   la.comm = comm; la.canon_in = c->comm_canon ? 1u : 0u; la.row_stride = c->n_cols; la.col_stride = 1; la.n_cols = c->n_cols;
+  if (s.pos_major) { la.canon_in = 1u; la.row_stride = 1; la.col_stride = s.n_rows; }   // (commit.cpp leaf_args, comm_t)
   la.row_base = 0; la.n_rows_total = s.n_rows;
   la.chunk_begin = 0; la.n_chunks_local = la.n_chunks_total = (uint32_t)s.n_chunks;
   return la;
@@ -39,12 +51,16 @@ int make_slab(const lcpc_ctx* c, ErrText* err, const BatchShape& s, uint32_t n_b
   std::shared_ptr<BatchSlab> sl(new BatchSlab());
   const uint64_t eb = elem_bytes(c);
   sl->n_batch = n_batch; sl->n_rows = s.n_rows;
-  sl->comm_stride = s.n_rows * c->n_cols * c->NL;
+  sl->comm_stride = s.pos_major ? 0 : s.n_rows * c->n_cols * c->NL;
+  // a member's T rounded up to 256 bytes: a multiple of 16 for every field (Ft63 with odd n_rows too), as the hash launchers ask
+  sl->t_stride = s.pos_major ? align256(s.n_rows * c->n_cols * eb) / 4 : 0;
+  sl->tmp_stride = s.pos_major ? align256(s.n_rows * c->d_pre.back().n_out * eb) / 4 : 0;
   sl->coeffs_stride = s.need_coeffs() ? s.n_rows * c->n_per_row * c->NL : 0;
   sl->hashes_stride = (2 * c->np2 - 1) * digest_words(c);
   sl->cvs_stride = s.need_cvs() ? s.n_chunks * c->n_cols * 8 : 0;
   uint64_t off = 0;
-  sl->off_comm = off; off = align256(off + (uint64_t)n_batch * s.n_rows * c->n_cols * eb);
+  sl->off_comm = off; off = align256(off + (uint64_t)n_batch * sl->comm_stride * 4);
+  sl->off_t = off; off = align256(off + (uint64_t)n_batch * sl->t_stride * 4);
   sl->off_coeffs = off; off = align256(off + (uint64_t)n_batch * sl->coeffs_stride * 4);
   sl->off_hashes = off; off = align256(off + (uint64_t)n_batch * sl->hashes_stride * 4);
   sl->off_cvs = off; off = align256(off + (uint64_t)n_batch * sl->cvs_stride * 4);
@@ -64,6 +80,7 @@ int make_slab(const lcpc_ctx* c, ErrText* err, const BatchShape& s, uint32_t n_b
 std::shared_ptr<BatchSlab> reusable_slab(lcpc_commit_t* const* cms, uint32_t n_batch, const BatchShape& s) {
   const std::shared_ptr<BatchSlab>& sl = cms[0]->slab;
   if (!sl || sl->n_batch != n_batch || sl->n_rows != s.n_rows) return nullptr;
+  if ((sl->t_stride != 0) != s.pos_major || (sl->comm_stride != 0) == s.pos_major) return nullptr;     // the other regime's segments
   if ((s.need_coeffs() && !sl->coeffs_stride) || (s.need_cvs() && !sl->cvs_stride)) return nullptr;
   for (uint32_t i = 0; i < n_batch; i++)
     if (cms[i]->slab != sl || cms[i]->slab_index != i) return nullptr;
@@ -86,7 +103,38 @@ int fetch_roots(lcpc_commit_t* const* cms, uint32_t n_batch, const BatchSlab* sl
   return 0;
 }
 
-// Ligero, every digest (every member's fill_mu and mu held, the device current)
+// the position-major encode of the whole batch into the members' T_i: sdig_walk once over the batch launchers (ctx.cpp
+// encode_rows_device's fast path with row -> batch row).  src: the members' rows stacked
+int encode_batch_t(const lcpc_ctx* c, ErrText* err, BatchSlab* sl, const uint32_t* src, uint32_t* copy_dst, hipStream_t st, uint32_t* launches) {
+  const DevCsr& pl = c->d_pre.back();
+  const uint32_t n_batch = sl->n_batch;
+  if (int rc = ensure_dev(err, &sl->ws.d_tmp, &sl->ws.tmp_cap, (uint64_t)n_batch * sl->tmp_stride * 4)) return rc;
+  uint32_t* t0 = sl->seg(sl->off_t, sl->t_stride, 0);
+  hipError_t e = launch_transpose_to_t_batch(c->NL, src, c->n_per_row, c->n_per_row, sl->n_rows, t0, n_batch, sl->t_stride, st, ~(uint64_t)0,
+                                             copy_dst, true);
+  if (e != hipSuccess) return fail_hip(err, e, "launch_transpose_to_t_batch");
+  ++*launches;
+  SpmmTArgs a{};
+  a.t = t0; a.n_rows = sl->n_rows;
+  auto mat = [&](const DevCsr& m, uint64_t in_off, uint64_t out_off, bool to_tmp) -> int {
+    a.out_alt = to_tmp ? sl->ws.d_tmp : nullptr; a.in_off = in_off; a.out_off = out_off;
+    a.rowptr = m.rowptr; a.colidx = m.colidx; a.vals = m.vals; a.vals29 = m.vals29; a.m = m.n_out;
+    hipError_t he = launch_spmm_t_batch(c->NL, a, n_batch, sl->t_stride, sl->tmp_stride, st);
+    if (he != hipSuccess) return fail_hip(err, he, "launch_spmm_t_batch");
+    ++*launches;
+    return 0;
+  };
+  auto rs = [&](uint64_t out_off, uint64_t n_out) -> int {
+    hipError_t he = launch_sdig_rs_t_batch(c->NL, sl->ws.d_tmp, (uint32_t)pl.n_out, t0, out_off, (uint32_t)n_out, sl->n_rows, c->d_r2, n_batch,
+                                           sl->tmp_stride, sl->t_stride, st);
+    if (he != hipSuccess) return fail_hip(err, he, "launch_sdig_rs_t_batch");
+    ++*launches;
+    return 0;
+  };
+  return sdig_walk(c, mat, rs);
+}
+
+// Ligero and Brakedown, every digest (every member's fill_mu and mu held, the device current)
 int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
                       hipStream_t st, uint32_t flags, uint8_t* roots) {
   lcpc_commit_t* m0 = cms[0];
@@ -99,6 +147,9 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   s.contiguous = whole && s.stride == n_coeffs;
   s.borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && whole;
   s.chained = !is_blake3(c);
+  const bool sdig = c->prm.encoding == LCPC_ENC_SDIG;
+  s.pos_major = sdig && s.n_rows >= SDIG_T_MIN_ROWS;
+  s.member_hash = sdig && s.chained;
   s.tree = !s.chained && leaf_tree_supported(batch_leaf_args(c, s, nullptr), c->np2);
   int rc;
   // st behind every member's last fill; the members are un-committed from here until the batch is sealed
@@ -109,18 +160,18 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
     if ((rc = make_slab(c, &m0->err, s, n_batch, &sl))) return rc;
     for (uint32_t i = 0; i < n_batch; i++) {
       lcpc_commit_t* m = cms[i];
-      if (m->slab) leave_slab(m);
-      else {
-        dev_free(m->d_comm); dev_free(m->d_coeffs); dev_free(m->d_hashes);
-        m->d_comm = m->d_coeffs = m->d_hashes = nullptr;
-        m->cap_comm_rows = m->cap_coeff_rows = 0;
-      }
+      leave_slab(m);               // (the views of another slab are dropped; what is left is the member's own)
+      dev_free(m->d_comm); dev_free(m->d_coeffs); dev_free(m->d_hashes);
+      m->d_comm = m->d_coeffs = m->d_hashes = nullptr;
+      m->cap_comm_rows = m->cap_coeff_rows = 0;
+      if (s.pos_major) { dev_free(m->ws.d_t); m->ws.d_t = nullptr; m->ws.t_cap = 0; }       // ws.d_t becomes a view
       m->slab = sl; m->slab_index = i;
     }
   }
   for (uint32_t i = 0; i < n_batch; i++) {       // the views (a reused slab may have grown a use for its coeffs segment)
     lcpc_commit_t* m = cms[i];
-    m->d_comm = sl->seg(sl->off_comm, sl->comm_stride, i);
+    if (sl->comm_stride) m->d_comm = sl->seg(sl->off_comm, sl->comm_stride, i);           // (else null, or the member's own row-major copy)
+    else { m->ws.d_t = sl->seg(sl->off_t, sl->t_stride, i); m->ws.t_cap = sl->t_stride * 4; m->comm_t = true; }
     m->d_coeffs = sl->coeffs_stride ? sl->seg(sl->off_coeffs, sl->coeffs_stride, i) : nullptr;
     m->d_hashes = sl->seg(sl->off_hashes, sl->hashes_stride, i);
   }
@@ -129,12 +180,15 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   if (timing) HIPCHK(m0, hipEventRecord(m0->ev[0], st));
 
   // ---- encode: one matrix of n_batch * n_rows rows
-  uint32_t* comm0 = sl->seg(sl->off_comm, sl->comm_stride, 0);
+  uint32_t* comm0 = s.pos_major ? sl->seg(sl->off_t, sl->t_stride, 0) : sl->seg(sl->off_comm, sl->comm_stride, 0);
+  const uint64_t comm_stride = s.pos_major ? sl->t_stride : sl->comm_stride;
   uint32_t* coeffs0 = sl->coeffs_stride ? sl->seg(sl->off_coeffs, sl->coeffs_stride, 0) : nullptr;
   EncodeJob j;
   j.src_stride = c->n_per_row; j.n_valid = c->n_per_row; j.dst = comm0; j.n_rows = (uint64_t)n_batch * s.n_rows;
   j.canon_out = c->comm_canon;
-  if (s.contiguous) {
+  // Brakedown below SDIG_T_MIN_ROWS stacked rows: the row-major kernels write no coeffs copy on the way, so the rows are placed first
+  const bool place_first = sdig && j.n_rows < SDIG_T_MIN_ROWS && !s.borrow;
+  if (s.contiguous && !place_first) {
     // read in place; the first pass writes the members' coeffs copies as it streams the source (unless they are borrowed)
     j.src = reinterpret_cast<const uint32_t*>(coeffs_dev);
     j.copy_dst = s.borrow ? nullptr : coeffs0;
@@ -145,7 +199,9 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
     launches[0]++;
     j.src = coeffs0;
   }
-  if ((rc = encode_rows_device(c, &sl->ws, j, st, &m0->err, &launches[0]))) return rc;
+  if (s.pos_major) rc = encode_batch_t(c, &m0->err, sl.get(), j.src, j.copy_dst, st, &launches[0]);
+  else rc = encode_rows_device(c, &sl->ws, j, st, &m0->err, &launches[0]);
+  if (rc) return rc;
   if (timing) HIPCHK(m0, hipEventRecord(m0->ev[1], st));
 
   // ---- column hash + tree: the launches of one commit, each over the whole batch (commit.cpp merkleize_device)
@@ -153,32 +209,56 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   uint32_t* hashes0 = sl->seg(sl->off_hashes, sl->hashes_stride, 0);
   const uint32_t dw = digest_words(c);
   uint32_t levels_done = 0;
-  if (s.chained) {
+  hipEvent_t ev_end = m0->ev[3];
+  float hash_ms = 0.f, merkle_ms = 0.f;
+  if (s.member_hash) {
+    // the one-shot hash and tree on each member's views; phase times are sums over the members (between the members' own events)
+    for (uint32_t i = 0; i < n_batch; i++) {
+      lcpc_commit_t* m = cms[i];
+      const bool own_timing = m->timing;
+      m->timing = timing;            // (merkleize_device records m->ev[2] between its hash and its tree)
+      rc = merkleize_device(m, st);
+      m->timing = own_timing;
+      if (rc) { if (m != m0) m0->err = m->err.c_str(); return rc; }
+      if (timing) HIPCHK(m0, hipEventRecord(m->ev[3], st));
+      launches[1] += m->launches[1]; launches[2] += m->launches[2];
+    }
+    if (timing) {
+      ev_end = cms[n_batch - 1]->ev[3];
+      HIPCHK(m0, hipEventSynchronize(ev_end));
+      for (uint32_t i = 0; i < n_batch; i++) {
+        float h = 0.f, t = 0.f;
+        (void)hipEventElapsedTime(&h, i ? cms[i - 1]->ev[3] : m0->ev[1], cms[i]->ev[2]);
+        (void)hipEventElapsedTime(&t, cms[i]->ev[2], cms[i]->ev[3]);
+        hash_ms += h; merkle_ms += t;
+      }
+    }
+  } else if (s.chained) {
     // one serial chain per column over the whole leaf message: the digests themselves, in one launch
     la.out = hashes0;
-    if (is_sha3(c)) HIPCHK(m0, launch_sha3_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
-    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
-    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
-    else HIPCHK(m0, launch_blake2b_leaves_batch(c->NL, la, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    if (is_sha3(c)) HIPCHK(m0, launch_sha3_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
+    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
+    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
+    else HIPCHK(m0, launch_blake2b_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
     launches[1]++;
   } else if (s.tree) {
-    HIPCHK(m0, launch_leaf_tree_batch(c->NL, la, hashes0, c->np2, n_batch, sl->comm_stride, sl->hashes_stride, st));
+    HIPCHK(m0, launch_leaf_tree_batch(c->NL, la, hashes0, c->np2, n_batch, comm_stride, sl->hashes_stride, st));
     launches[1]++;
     levels_done = 6;
   } else {
     uint32_t* cvs0 = s.need_cvs() ? sl->seg(sl->off_cvs, sl->cvs_stride, 0) : nullptr;
     la.out = cvs0 ? cvs0 : hashes0;              // (one chunk: the digests themselves)
-    HIPCHK(m0, launch_leaf_chunks_batch(c->NL, la, n_batch, sl->comm_stride, cvs0 ? sl->cvs_stride : sl->hashes_stride, st));
+    HIPCHK(m0, launch_leaf_chunks_batch(c->NL, la, n_batch, comm_stride, cvs0 ? sl->cvs_stride : sl->hashes_stride, st));
     launches[1]++;
     if (cvs0) {
       HIPCHK(m0, launch_leaf_finish_batch(cvs0, (uint32_t)s.n_chunks, c->n_cols, hashes0, n_batch, sl->cvs_stride, sl->hashes_stride, st));
       launches[1]++;
     }
   }
-  if (timing) HIPCHK(m0, hipEventRecord(m0->ev[2], st));
-  if (c->np2 > c->n_cols)          // hashes[n_cols..np2) of every member stay zero (lib.rs:656-666)
+  if (timing && !s.member_hash) HIPCHK(m0, hipEventRecord(m0->ev[2], st));
+  if (c->np2 > c->n_cols && !s.member_hash)          // hashes[n_cols..np2) of every member stay zero (lib.rs:656-666)
     HIPCHK(m0, hipMemset2DAsync(hashes0 + c->n_cols * dw, (size_t)sl->hashes_stride * 4, 0, (size_t)(c->np2 - c->n_cols) * digest_len(c), n_batch, st));
-  if (c->np2 > 1) {
+  if (c->np2 > 1 && !s.member_hash) {
     if (is_sha3(c)) HIPCHK(m0, launch_sha3_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
     else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
     else if (is_sha256(c)) HIPCHK(m0, launch_sha256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
@@ -189,13 +269,16 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
 
   // ---- seal (commit.cpp seal_commit, for every member)
   if (timing) {
-    HIPCHK(m0, hipEventRecord(m0->ev[3], st));
-    HIPCHK(m0, hipEventSynchronize(m0->ev[3]));
+    if (!s.member_hash) HIPCHK(m0, hipEventRecord(ev_end, st));
+    HIPCHK(m0, hipEventSynchronize(ev_end));
     lcpc_timings t{};
     (void)hipEventElapsedTime(&t.encode_ms, m0->ev[0], m0->ev[1]);
-    (void)hipEventElapsedTime(&t.hash_ms, m0->ev[1], m0->ev[2]);
-    (void)hipEventElapsedTime(&t.merkle_ms, m0->ev[2], m0->ev[3]);
-    (void)hipEventElapsedTime(&t.total_ms, m0->ev[0], m0->ev[3]);
+    if (s.member_hash) { t.hash_ms = hash_ms; t.merkle_ms = merkle_ms; }
+    else {
+      (void)hipEventElapsedTime(&t.hash_ms, m0->ev[1], m0->ev[2]);
+      (void)hipEventElapsedTime(&t.merkle_ms, m0->ev[2], m0->ev[3]);
+    }
+    (void)hipEventElapsedTime(&t.total_ms, m0->ev[0], ev_end);
     for (uint32_t i = 0; i < n_batch; i++) {     // phase times and launch counts only: the other fields are the member's own (begin_commit reset them)
       lcpc_timings& l = cms[i]->last;
       l.encode_ms = t.encode_ms; l.hash_ms = t.hash_ms; l.merkle_ms = t.merkle_ms; l.total_ms = t.total_ms;
@@ -210,10 +293,11 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
     HIPCHK(m0, hipEventRecord(m->ev_done, st));
   }
   for (uint32_t i = 0; i < n_batch; i++) cms[i]->committed = true;
-  return roots ? fetch_roots(cms, n_batch, sl.get(), st, roots) : 0;
+  return roots ? fetch_roots(cms, n_batch, s.member_hash ? nullptr : sl.get(), st, roots) : 0;   // (member_hash: each member's own root slot)
 }
 
-// Brakedown: the single-commit pipeline member by member on st; the batch's timings are the sums
+// a Brakedown batch of more stacked rows than the batch launchers take: the single-commit pipeline member by member on st; the
+// batch's timings are the sums
 int commit_batch_each(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs, uint64_t poly_stride,
                       hipStream_t st, uint32_t flags, uint8_t* roots) {
   lcpc_commit_t* m0 = cms[0];
@@ -271,7 +355,9 @@ int lcpcx_commit_batch_device(lcpc_commit_t* const* cms, uint32_t n_batch, const
   for (lcpc_commit_t* m : order) mus.emplace_back(m->mu);
   HIPCHK(m0, hipSetDevice(c->prm.device));
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = c->prm.encoding == LCPC_ENC_LIGERO;
+  // Brakedown: the stacked rows are one grid dimension of the transposes, in tiles of 32 (kernels.h launch_transpose_to_t_batch)
+  const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
+  const bool fast = c->prm.encoding == LCPC_ENC_LIGERO || (uint64_t)n_batch * n_rows <= (uint64_t)65535 * 32;
   int rc = fast ? commit_batch_fast(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots)
                 : commit_batch_each(cms, n_batch, coeffs_dev, n_coeffs, poly_stride, st, flags, roots);
   if (rc)                          // a failed batch leaves no member committed

@@ -51,14 +51,27 @@ int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks) {
 // (unless borrowed), hashes
 void leave_slab(lcpc_commit_t* m) {
   if (!m->slab) return;
-  m->d_comm = m->d_coeffs = m->d_hashes = nullptr;
-  m->cap_comm_rows = m->cap_coeff_rows = 0;
+  if (m->slab->comm_stride) { m->d_comm = nullptr; m->cap_comm_rows = 0; }   // (else null, or the member's own: ensure_comm_rows)
+  if (m->slab->t_stride) { m->ws.d_t = nullptr; m->ws.t_cap = 0; }           // the position-major commitment was a view too
+  m->d_coeffs = m->d_hashes = nullptr;
+  m->cap_coeff_rows = 0;
   m->slab.reset();                 // (the last member frees the slab: hipFree waits for whatever still reads it)
+}
+
+int ensure_comm_rows(lcpc_commit_t* m) {
+  const lcpc_ctx* c = m->enc;
+  const uint64_t rows = m->n_rows_local ? m->n_rows_local : 1;
+  if (rows > m->cap_comm_rows || !m->d_comm) {
+    dev_free(m->d_comm); m->d_comm = nullptr; m->cap_comm_rows = 0;
+    if (int rc = dev_alloc(&m->err, &m->d_comm, (size_t)rows * c->n_cols * elem_bytes(c))) return rc;
+    m->cap_comm_rows = rows;
+  }
+  return 0;
 }
 
 int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows) {
   const lcpc_ctx* c = m->enc;
-  leave_slab(m);                   // a fill of this object alone: buffers of its own again (readers never come here with a slab: Ligero only)
+  leave_slab(m);                   // a fill of this object alone: buffers of its own again (no reader comes here: lcpc_get_comm has ensure_comm_rows)
   const size_t eb = elem_bytes(c);
   const uint64_t rows = n_rows_local ? n_rows_local : 1;
   int rc;
@@ -167,7 +180,7 @@ static int finish_leaves(lcpc_commit_t* m, hipStream_t st) {
 }
 
 // hash_columns + merkle_tree on the local comm (unsharded) -- lib.rs:690-704
-static int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
+int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
   LeafArgs la = leaf_args(m);
   if (!is_blake3(c)) {
@@ -941,7 +954,8 @@ static int get_comm(lcpc_commit_t* m, uint64_t row0, uint64_t n, uint64_t* out) 
   { int orc = order_after_commit(m, nullptr); if (orc) return orc; }
   const size_t eb = elem_bytes(c);
   if (m->comm_t && !m->comm_rows_valid) {      // Brakedown: the commitment is position-major; make the row-major view once
-    int rc = ensure_commit_buffers(m, m->n_rows_local, false, true);
+    // (a copy of the member's own: a member of a batched commit stays in its slab, where ws.d_t, d_coeffs and d_hashes point)
+    int rc = ensure_comm_rows(m);
     if (rc) return rc;
     HIPCHK(m, launch_transpose_from_t(c->NL, m->ws.d_t, c->n_cols, m->n_rows_local, m->d_comm, c->n_cols, nullptr));
     HIPCHK(m, hipStreamSynchronize(nullptr));

@@ -299,29 +299,6 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
     if (e__ != hipSuccess) return fail_hip(err, e__, #call);              \
   } while (0)
 
-// The level walk of a Brakedown encode (encode.rs:36-94) over the segments of a codeword: precodes down, the last one into ws->d_tmp,
-// the R-S base case from d_tmp, postcodes up.  mat(m, in_off, out_off, into_tmp) and rs(out_off, n_out) each launch one step.
-template <class Mat, class Rs> static int sdig_walk(const lcpc_ctx* c, Mat&& mat, Rs&& rs) {
-  const size_t t = c->d_pre.size();
-  const DevCsr& pl = c->d_pre[t - 1];
-  uint64_t in_start = 0;
-  for (size_t i = 0; i + 1 < t; i++) {
-    if (int rc = mat(c->d_pre[i], in_start, in_start + c->d_pre[i].n_in, false)) return rc;
-    in_start += c->d_pre[i].n_in;
-  }
-  if (int rc = mat(pl, in_start, 0, true)) return rc;
-  const uint64_t in_end = in_start + pl.n_in;
-  if (int rc = rs(in_end, c->d_post[t - 1].n_in)) return rc;
-  in_start = in_end + pl.n_out;
-  uint64_t out_start = in_end + c->d_post[t - 1].n_in;
-  for (size_t ii = t; ii-- > 0;) {
-    in_start -= c->d_pre[ii].n_out;
-    if (int rc = mat(c->d_post[ii], in_start, out_start, false)) return rc;
-    out_start += c->d_post[ii].n_out;
-  }
-  return 0;
-}
-
 // ---- encode rows: LcEncoding::encode, batched over rows -----------------------------------------------
 int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipStream_t st, ErrText* err, uint32_t* launches) {
   uint32_t dummy = 0;

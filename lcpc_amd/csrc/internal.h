@@ -230,11 +230,16 @@ template <typename S> struct SetLease {
 // every member in ONE device allocation, member-major, so that the row encode sees one matrix of n_batch * n_rows rows and the batched
 // hash / tree kernels reach member i at a fixed stride.  The members share it (lcpc_commit_s::slab); the last one to leave frees it.
 // A hashes slot is digest_words(c) words (8; BLAKE2b 16); only BLAKE3 has chunk chaining values.
-// A member's d_comm / d_coeffs / d_hashes are then views into it: leave_slab before anything frees or regrows them.
+// Two regimes: a slab with a `comm` segment (Ligero; Brakedown members of < SDIG_T_MIN_ROWS rows) holds row-major commitment
+// matrices, and a member's d_comm / d_coeffs / d_hashes are views into it.  A slab with a `t` segment instead (Brakedown members
+// of >= SDIG_T_MIN_ROWS rows) holds every member's position-major T[pos][row]: the member's ws.d_t is the view (comm_t), and its
+// d_comm is null or the member's OWN row-major copy made on demand (lcpc_get_comm).  leave_slab before anything frees or regrows
+// a view.
 struct BatchSlab {
   uint8_t* d = nullptr;
-  uint64_t off_comm = 0, off_coeffs = 0, off_hashes = 0, off_cvs = 0;   // bytes; a segment is member-major
-  uint64_t comm_stride = 0, coeffs_stride = 0, hashes_stride = 0, cvs_stride = 0;   // 32-bit words per member (0: no such segment)
+  uint64_t off_comm = 0, off_t = 0, off_coeffs = 0, off_hashes = 0, off_cvs = 0;   // bytes; a segment is member-major
+  uint64_t comm_stride = 0, t_stride = 0, coeffs_stride = 0, hashes_stride = 0, cvs_stride = 0;   // 32-bit words per member (0: no such segment)
+  uint64_t tmp_stride = 0;         // t regime: words per member of ws.d_tmp (the last precode's [o][row] of every member)
   uint32_t n_batch = 0;
   uint64_t n_rows = 0;
   uint32_t* h_roots = nullptr;     // pinned, device-mapped [n_batch][digest_words]: written by the launch that produces the roots
@@ -243,6 +248,8 @@ struct BatchSlab {
   uint32_t* seg(uint64_t off, uint64_t stride, uint32_t i) const { return reinterpret_cast<uint32_t*>(d + off) + (size_t)i * stride; }
   ~BatchSlab() {
     if (d) (void)hipFree(d);
+    if (ws.d_tmp) (void)hipFree(ws.d_tmp);
+    if (ws.d_t) (void)hipFree(ws.d_t);
     if (ws.d_mid) (void)hipFree(ws.d_mid);
     if (h_roots) (void)hipHostFree(h_roots);
   }
@@ -335,8 +342,8 @@ struct lcpc_commit_s {
   const uint32_t* coeffs_view = nullptr;   // LcCommit.coeffs as prove/collapse read it: d_coeffs, or the caller's buffer
                                            // when the commit was made with LCPC_COMMIT_BORROW_COEFFS
   uint64_t cap_coeff_rows = 0, cap_comm_rows = 0, cap_cvs = 0;
-  std::shared_ptr<lcpc::BatchSlab> slab;   // member of a batched commit: d_comm / d_coeffs / d_hashes are views into it, not allocations
-  uint32_t slab_index = 0;                 // (leave_slab, commit.cpp)
+  std::shared_ptr<lcpc::BatchSlab> slab;   // member of a batched commit: d_comm (or ws.d_t: BatchSlab) / d_coeffs / d_hashes are views into it,
+  uint32_t slab_index = 0;                 // not allocations (leave_slab, commit.cpp)
   uint32_t* d_chain = nullptr;     // host-memory commit under SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: every column's chaining value between
   uint64_t cap_chain = 0;          // the row batches (kernels.h launch_*_leaves_range), word-major; capacity in bytes; kept across refills
   lcpc::EncodeWs ws;
@@ -472,6 +479,30 @@ int encode_rows_device(const lcpc_ctx* c, EncodeWs* ws, const EncodeJob& j, hipS
 
 int encode_msgs_host(lcpc_ctx* c, const uint64_t* const* msgs, uint64_t n_rows, uint64_t* out);
 
+// The level walk of a Brakedown encode (encode.rs:36-94) over the segments of a codeword: precodes down, the last one into the encode's d_tmp,
+// the R-S base case from d_tmp, postcodes up.  mat(m, in_off, out_off, into_tmp) and rs(out_off, n_out) each launch one step
+// (ctx.cpp encode_rows_device; batch.cpp over the batch launchers).
+template <class Mat, class Rs> int sdig_walk(const lcpc_ctx* c, Mat&& mat, Rs&& rs) {
+  const size_t t = c->d_pre.size();
+  const DevCsr& pl = c->d_pre[t - 1];
+  uint64_t in_start = 0;
+  for (size_t i = 0; i + 1 < t; i++) {
+    if (int rc = mat(c->d_pre[i], in_start, in_start + c->d_pre[i].n_in, false)) return rc;
+    in_start += c->d_pre[i].n_in;
+  }
+  if (int rc = mat(pl, in_start, 0, true)) return rc;
+  const uint64_t in_end = in_start + pl.n_in;
+  if (int rc = rs(in_end, c->d_post[t - 1].n_in)) return rc;
+  in_start = in_end + pl.n_out;
+  uint64_t out_start = in_end + c->d_post[t - 1].n_in;
+  for (size_t ii = t; ii-- > 0;) {
+    in_start -= c->d_pre[ii].n_out;
+    if (int rc = mat(c->d_post[ii], in_start, out_start, false)) return rc;
+    out_start += c->d_post[ii].n_out;
+  }
+  return 0;
+}
+
 // ---- commit.cpp -------------------------------------------------------------------------------------
 int ensure_scratch(lcpc_commit_t* m, DevScratch* sc, uint64_t bytes);
 int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks);
@@ -486,8 +517,13 @@ int ensure_cvs(lcpc_commit_t* m, uint64_t n_chunks);
 int begin_commit(lcpc_commit_t* m, hipStream_t st, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end, uint64_t chunk_begin,
                  uint64_t chunk_end);
 int ensure_commit_buffers(lcpc_commit_t* m, uint64_t n_rows_local, bool own_coeffs, bool comm_rows);
-// a member of a batched commit gives up its views of the shared slab (and its share of it): it owns no comm / coeffs / hashes then
+// a member of a batched commit gives up its views of the shared slab (and its share of it): it owns no coeffs / hashes then, and no
+// comm or T that was a view (a row-major copy of its own, made by ensure_comm_rows, it keeps)
 void leave_slab(lcpc_commit_t* m);
+// a row-major d_comm of the member's OWN for the rows it holds (lcpc_get_comm on a position-major commitment); touches nothing else
+int ensure_comm_rows(lcpc_commit_t* m);
+// hash_columns + merkle_tree of m's commitment matrix, wherever it lives (leaf_args), by the one-shot launchers
+int merkleize_device(lcpc_commit_t* m, hipStream_t st);
 // lcpc_commit_device behind its argument checks and locks (the caller holds m->fill_mu exclusively and m->mu; the device is current)
 int commit_device_locked(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_coeffs, hipStream_t st, uint32_t flags, uint8_t* root);
 int encode_coeffs(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src, bool borrow, hipStream_t st);

@@ -259,6 +259,23 @@ struct SpmmTArgs {
 hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st);
 hipError_t launch_sdig_rs_t(int nl, const uint32_t* in_t, uint32_t n_in, uint32_t* t, uint64_t out_off, uint32_t n_out,
                             uint64_t n_rows, const uint32_t* r2, hipStream_t st);
+// ---- the same for a batch of n_batch equal-shape members (kernels.hip K2b): lane = batch row R = member * n_rows + row.  The
+// arguments of the one-shot launcher describe member 0; member i's T (leading dimension n_rows, as a single commit's) starts
+// i * t_stride words behind it, its out_alt / in_t i * out_alt_stride / in_stride words.  Same values as the one-shot launchers run
+// member by member, bit for bit.  A stride must be at least one member's extent and keep the members' elements aligned as member
+// 0's are; nothing here checks that members do not overlap.  n_batch == 0 or > 65535, or more batch rows than the grid's second
+// dimension carries (65535 x 32 for the transpose, 65535 x 128 for the others), is hipErrorInvalidValue, checked before any launch;
+// Ft255 with null vals29 likewise; otherwise empty work is hipSuccess.
+// transpose: src is the members' rows STACKED (batch row R at src + R * src_stride elements; copy_dst likewise); n_src_total
+// counts a member's own flat elements
+hipError_t launch_transpose_to_t_batch(int nl, const uint32_t* src, uint64_t src_stride, uint64_t n_valid, uint64_t n_rows, uint32_t* t,
+                                       uint32_t n_batch, uint64_t t_stride, hipStream_t st, uint64_t n_src_total = ~(uint64_t)0,
+                                       uint32_t* copy_dst = nullptr, bool canon = false);
+// launch_spmm_t's selection by m, without the packed-tail kernel: the whole batch has at most one partial wave
+hipError_t launch_spmm_t_batch(int nl, const SpmmTArgs& a, uint32_t n_batch, uint64_t t_stride, uint64_t out_alt_stride, hipStream_t st);
+hipError_t launch_sdig_rs_t_batch(int nl, const uint32_t* in_t, uint32_t n_in, uint32_t* t, uint64_t out_off, uint32_t n_out,
+                                  uint64_t n_rows, const uint32_t* r2, uint32_t n_batch, uint64_t in_stride, uint64_t t_stride,
+                                  hipStream_t st);
 
 // Reed-Solomon base case (encode.rs:97-110): out[row][out_off + k] = sum_j in[row][j] (k+1)^j
 hipError_t launch_sdig_rs(int nl, const uint32_t* in, uint64_t in_stride, uint32_t n_in, uint32_t* mat, uint64_t stride,

@@ -4,6 +4,7 @@
 //                               LcEncoding::encode for Ligero = fffft fft_io_pc, precomp_fft (ligero lib.rs:140, 162-164)
 //   K2  transpose_to/from_t, spmm_t, sdig_rs_t (>= 24 rows); spmv, sdig_rs (fewer rows)
 //                               LcEncoding::encode for Brakedown                   (brakedown encode.rs:36-110)
+//   K2b transpose_to_t_batch, spmm_t_batch, sdig_rs_t_batch: the same for the stacked rows of a batch of commitments (batch.cpp)
 //   K3  leaf_chunk / leaf_finish hash_columns (+ subtree pre-merge for sharding)    (lcpc-2d lib.rs:706-745)
 //   K4  merkle_subtree           merkle_tree / merkle_layer                         (lib.rs:747-785)
 //   K5  collapse / collapse29 / field_sum / to_r29   collapse_columns               (lib.rs:1095-1123)
@@ -1451,6 +1452,185 @@ hipError_t launch_sdig_rs_t(int nl, const u32* in_t, u32 n_in, u32* t, u64 out_o
   if (!n_out || !n_rows) return hipSuccess;
   dim3 grid(n_out, (unsigned)((n_rows + 127) / 128));
   LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(sdig_rs_t_kernel<NLV>, grid, dim3(128), 0, st, in_t, n_in, t, out_off, n_out, n_rows, r2));
+  return hipGetLastError();
+}
+
+// =================================================================================================
+// K2b: the position-major path for a BATCH of equal-shape commitments of one encoder (batch.cpp).  The expander matrices are the
+// same for every row of every member, so the batch is one SpMM over n_batch * n_rows BATCH ROWS R = member * n_rows + row with
+// lane = batch row: the matrix entries stay wave-uniform scalar loads, the waves are full (the whole batch has at most one
+// partial wave, which is why the packed-tail kernel has no twin here), and a level is one launch.  Every member keeps its own
+// T_member[pos][row] with leading dimension n_rows, t_stride words behind its predecessor's, so that everything that reads a
+// single commit's T reads a member's unchanged.  A lane forms its own base pointers from (member, row); a wave may hold rows of
+// several members.  The dot products are spmm_t_terms', term for term: same values as the one-shot kernels, bit for bit.
+// =================================================================================================
+struct BatchRows {
+  u32 n_total;                  // n_batch * n_rows batch rows
+  u64 t_stride, alt_stride;     // words between members' T / out_alt (sdig_rs_t: in_t)
+};
+template <int NL>
+__global__ void __launch_bounds__(256) transpose_to_t_batch_kernel(const u32* src, u64 src_stride, u64 n_valid, u32 n_rows, u32* t,
+                                                                  u64 n_src_total, u32* copy_dst, u32 canon, BatchRows b) {
+  // transpose_to_t_kernel with tiles over batch rows (a 32-row tile may straddle members): src is the members' rows stacked,
+  // row R at src + R * src_stride; n_src_total counts inside a member
+  __shared__ u32 tile[32 * 33 * NL];
+  const u64 p0 = (u64)blockIdx.x * 32;
+  const u32 r0 = blockIdx.y * 32;
+  const u32 tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+  for (u32 rr = ty; rr < 32; rr += 8) {
+    const u32 R = r0 + rr;
+    const u64 p = p0 + tx;
+    if (R < b.n_total && p < n_valid) {
+      const u32 row = R % n_rows;
+      const u64 e = (u64)R * src_stride + p;
+      const Fe<NL> v = ((u64)row * src_stride + p < n_src_total) ? fe_load<NL>(src + e * NL) : fe_zero<NL>();
+      if (copy_dst != nullptr) fe_store<NL>(copy_dst + e * NL, v);
+      Fe<NL> u = v;
+      if (canon) {
+        if constexpr (NL == 8) u = fe_canon_r29(v);
+        else u = fe_canon<NL>(v);
+      }
+#pragma unroll
+      for (int w = 0; w < NL; w++) tile[(rr * 33 + tx) * NL + w] = u.v[w];
+    }
+  }
+  __syncthreads();
+  const u32 R = r0 + tx;
+  const u32 member = R / n_rows, row = R - member * n_rows;
+  u32* tm = t + (u64)member * b.t_stride;
+  for (u32 pp = ty; pp < 32; pp += 8) {
+    const u64 p = p0 + pp;
+    if (R < b.n_total && p < n_valid) {
+      Fe<NL> v;
+#pragma unroll
+      for (int w = 0; w < NL; w++) v.v[w] = tile[(tx * 33 + pp) * NL + w];
+      fe_store<NL>(tm + (p * n_rows + row) * NL, v);
+    }
+  }
+}
+// the grid's second dimension carries the batch rows: tiles of 32 (transpose) or workgroups of 128 lanes (spmm, sdig_rs)
+static bool batch_rows_ok(u32 n_batch, u64 n_rows, u32 rows_per_block, BatchRows* b) {
+  if (n_batch == 0 || n_batch > 65535) return false;
+  const u64 total = (u64)n_batch * n_rows;
+  if (total > (u64)65535 * rows_per_block) return false;
+  b->n_total = (u32)total;
+  return true;
+}
+hipError_t launch_transpose_to_t_batch(int nl, const u32* src, u64 src_stride, u64 n_valid, u64 n_rows, u32* t, u32 n_batch,
+                                       u64 t_stride, hipStream_t st, u64 n_src_total, u32* copy_dst, bool canon) {
+  BatchRows b{0, t_stride, 0};
+  if (!batch_rows_ok(n_batch, n_rows, 32, &b)) return hipErrorInvalidValue;
+  if (!n_valid || !n_rows) return hipSuccess;
+  dim3 grid((unsigned)((n_valid + 31) / 32), (b.n_total + 31) / 32);
+  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(transpose_to_t_batch_kernel<NLV>, grid, dim3(256), 0, st, src, src_stride, n_valid, (u32)n_rows,
+                                          t, n_src_total, copy_dst, canon ? 1u : 0u, b));
+  return hipGetLastError();
+}
+
+// a lane's member and row, and from them its gather base and its output slot.  Dead lanes (behind the last batch row) shadow
+// batch row 0 and do not store, as in the one-shot kernels
+template <int NL> struct BatchLane {
+  const u32* xin;
+  u32* out0;                    // output o of this lane at out0 + o * pstride
+  size_t pstride;
+  __device__ __forceinline__ BatchLane(const SpmmTArgs& a, const BatchRows& b, u32 R) {
+    const u32 n_rows = (u32)a.n_rows;
+    const u32 member = R / n_rows, row = R - member * n_rows;
+    pstride = (size_t)n_rows * NL;
+    u32* tm = a.t + (u64)member * b.t_stride;
+    xin = tm + (a.in_off * n_rows + row) * NL;
+    out0 = a.out_alt ? a.out_alt + (u64)member * b.alt_stride + (size_t)row * NL : tm + (a.out_off * n_rows + row) * NL;
+  }
+};
+template <int NL, int SPMM_OPW>
+__global__ void __launch_bounds__(128) spmm_t_batch_kernel(SpmmTArgs a, BatchRows b) {
+  const u32 R = blockIdx.y * 128 + threadIdx.x;
+  if ((R & ~63u) >= b.n_total) return;               // a wave with no batch row at all
+  const bool live = R < b.n_total;
+  const BatchLane<NL> ln(a, b, live ? R : 0);
+  for (u32 oo = 0; oo < SPMM_OPW; oo++) {
+    const u64 o = (u64)blockIdx.x * SPMM_OPW + oo;
+    if (o >= a.m) break;
+    const u32 k0 = __builtin_amdgcn_readfirstlane(a.rowptr[o]);
+    const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
+    const Fe<NL> res = spmm_t_terms<NL>(a, ln.xin, ln.pstride, k0, k1);
+    if (live) fe_store<NL>(ln.out0 + o * ln.pstride, res);
+  }
+}
+template <int NL, int SL>
+__global__ void __launch_bounds__(128 * SL) spmm_t_sliced_batch_kernel(SpmmTArgs a, BatchRows b) {
+  __shared__ u32 part[(SL - 1) * 128 * NL];
+  const u32 lane = threadIdx.x & 127;
+  const u32 sl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
+  const u32 R = blockIdx.y * 128 + lane;
+  const bool live = R < b.n_total;
+  const BatchLane<NL> ln(a, b, live ? R : 0);
+  const u64 o = blockIdx.x;
+  const u32 k0 = __builtin_amdgcn_readfirstlane(a.rowptr[o]);
+  const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
+  const u32 len = k1 - k0;
+  const u32 ks = k0 + (u32)(((u64)len * sl) / SL), ke = k0 + (u32)(((u64)len * (sl + 1)) / SL);
+  const bool wave_live = (R & ~63u) < b.n_total;       // (a wave with no batch row at all still has to reach the barrier)
+  Fe<NL> res = wave_live ? spmm_t_terms<NL>(a, ln.xin, ln.pstride, ks, ke) : fe_zero<NL>();
+  if (sl) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) part[((sl - 1) * NL + i) * 128 + lane] = res.v[i];
+  }
+  __syncthreads();
+  if (sl == 0) {
+#pragma unroll
+    for (int s = 0; s < SL - 1; s++) {
+      Fe<NL> p;
+#pragma unroll
+      for (int i = 0; i < NL; i++) p.v[i] = part[(s * NL + i) * 128 + lane];
+      res = fe_add<NL>(res, p);
+    }
+    if (live) fe_store<NL>(ln.out0 + o * ln.pstride, res);
+  }
+}
+hipError_t launch_spmm_t_batch(int nl, const SpmmTArgs& a, u32 n_batch, u64 t_stride, u64 out_alt_stride, hipStream_t st) {
+  BatchRows b{0, t_stride, out_alt_stride};
+  if (!batch_rows_ok(n_batch, a.n_rows, 128, &b)) return hipErrorInvalidValue;
+  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // as launch_spmm_t
+  if (a.m == 0 || a.n_rows == 0) return hipSuccess;
+  const unsigned gy = (b.n_total + 127) / 128;
+  // launch_spmm_t's selection by m; no packed-tail form: the whole batch has at most one partial wave
+  if (a.m >= 8192) {
+    dim3 grid((unsigned)((a.m + 3) / 4), gy);
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_batch_kernel<NLV, 4>), grid, dim3(128), 0, st, a, b));
+  } else if (a.m > 2048) {
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 2>), dim3((unsigned)a.m, gy), dim3(256), 0, st, a, b));
+  } else if (a.m > 256) {
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 4>), dim3((unsigned)a.m, gy), dim3(512), 0, st, a, b));
+  } else {
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 8>), dim3((unsigned)a.m, gy), dim3(1024), 0, st, a, b));
+  }
+  return hipGetLastError();
+}
+
+template <int NL>
+__global__ void __launch_bounds__(128) sdig_rs_t_batch_kernel(const u32* in_t, u32 n_in, u32* t, u64 out_off, u32 n_rows, const u32* r2,
+                                                             BatchRows b) {
+  const u32 R = blockIdx.y * 128 + threadIdx.x;
+  if (R >= b.n_total) return;
+  const u32 member = R / n_rows, row = R - member * n_rows;
+  in_t += (u64)member * b.alt_stride;
+  t += (u64)member * b.t_stride;
+  const u32 k = blockIdx.x;
+  Fe<NL> raw = fe_zero<NL>();
+  raw.v[0] = k + 1;
+  const Fe<NL> x = fe_mul<NL>(raw, fe_load<NL>(r2));          // (k+1) in Montgomery form
+  Fe<NL> r = fe_zero<NL>();
+  for (u32 j = n_in; j-- > 0;) r = fe_add<NL>(fe_mul<NL>(r, x), fe_load<NL>(in_t + ((u64)j * n_rows + row) * NL));
+  fe_store<NL>(t + ((out_off + k) * n_rows + row) * NL, r);
+}
+hipError_t launch_sdig_rs_t_batch(int nl, const u32* in_t, u32 n_in, u32* t, u64 out_off, u32 n_out, u64 n_rows, const u32* r2,
+                                  u32 n_batch, u64 in_stride, u64 t_stride, hipStream_t st) {
+  BatchRows b{0, t_stride, in_stride};
+  if (!batch_rows_ok(n_batch, n_rows, 128, &b)) return hipErrorInvalidValue;
+  if (!n_out || !n_rows) return hipSuccess;
+  dim3 grid(n_out, (b.n_total + 127) / 128);
+  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(sdig_rs_t_batch_kernel<NLV>, grid, dim3(128), 0, st, in_t, n_in, t, out_off, (u32)n_rows, r2, b));
   return hipGetLastError();
 }
 

@@ -7,9 +7,11 @@ process -- a, b, a, b, ... after a warm-up of both -- so that clocks and the all
 host (enqueue + drain), medians and min / max of --steps rounds.  One JSON line per shape on stdout, appended to --out
 (profiles/r10_batch.jsonl by default).
 
-  python tools/bench_batch.py [--shape FIELD:LOG2N[:DIGEST] ...] [--n-batch B] [--steps K] [--warmup W] [--out PATH]
+  python tools/bench_batch.py [--shape FIELD:LOG2N[:DIGEST] ...] [--encoding ligero|brakedown] [--code C] [--seed S]
+                              [--n-batch B] [--steps K] [--warmup W] [--out PATH]
 
-FIELD: ft63 / ft127 / ft191 / ft255; default shapes: ft63:16 (BASELINE's C1) and ft255:16."""
+FIELD: ft63 / ft127 / ft191 / ft255; default shapes: ft63:16 (BASELINE's C1) and ft255:16.  --encoding brakedown: SdigEncoding.new of
+--code (1 / 3 / 6) and --seed; the sequential loop is then the single-commit Brakedown pipeline."""
 import argparse
 import json
 import os
@@ -23,14 +25,17 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
-from lcpc_amd import LcCommit, LigeroEncoding, commit_batch  # noqa: E402
+from lcpc_amd import LcCommit, LigeroEncoding, SdigEncoding, commit_batch  # noqa: E402
 
 FIELDS = {"ft63": 0, "ft127": 1, "ft191": 2, "ft255": 3}
 
 
-def run(field, log_n, digest, n_batch, steps, warmup):
+def run(field, log_n, digest, n_batch, steps, warmup, encoding="ligero", code=3, seed=0):
     n = 1 << log_n
-    enc = LigeroEncoding.new(FIELDS[field], n, digest=digest)
+    if encoding == "brakedown":
+        enc = SdigEncoding.new(FIELDS[field], n, seed, code, digest=digest)
+    else:
+        enc = LigeroEncoding.new(FIELDS[field], n, digest=digest)
     x = enc.random_coeffs_device(n_batch * n, seed=0).reshape(n_batch, n * enc.L)
     seq = [LcCommit(enc) for _ in range(n_batch)]
     bat = [LcCommit(enc) for _ in range(n_batch)]
@@ -60,7 +65,8 @@ def run(field, log_n, digest, n_batch, steps, warmup):
     commit_batch(enc, x, into=bat)
     t = bat[0].timings()
     ms, mb = statistics.median(ts), statistics.median(tb)
-    return dict(tool="bench_batch", field=field, log_n=log_n, digest=digest, n_batch=n_batch, n_rows=bat[0].n_rows, n_cols=bat[0].n_cols,
+    extra = dict(code=code, seed=seed) if encoding == "brakedown" else {}
+    return dict(tool="bench_batch", encoding=encoding, **extra, field=field, log_n=log_n, digest=digest, n_batch=n_batch, n_rows=bat[0].n_rows, n_cols=bat[0].n_cols,
                 steps=steps, warmup=warmup, seq_ms=ms, seq_min_ms=min(ts), seq_max_ms=max(ts), batch_ms=mb, batch_min_ms=min(tb),
                 batch_max_ms=max(tb), seq_over_batch=ms / mb, batch_encode_ms=t.encode_ms, batch_hash_ms=t.hash_ms,
                 batch_merkle_ms=t.merkle_ms, batch_launches=[t.encode_launches, t.hash_launches, t.merkle_launches])
@@ -69,6 +75,9 @@ def run(field, log_n, digest, n_batch, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", nargs="*", default=["ft63:16", "ft255:16"], help="FIELD:LOG2N[:DIGEST]")
+    ap.add_argument("--encoding", choices=["ligero", "brakedown"], default="ligero")
+    ap.add_argument("--code", type=int, default=3, help="brakedown: SdigCode 1 / 3 / 6")
+    ap.add_argument("--seed", type=int, default=0, help="brakedown: matgen seed")
     ap.add_argument("--n-batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -76,7 +85,7 @@ def main():
     a = ap.parse_args()
     for sh in a.shape:
         parts = sh.split(":")
-        r = run(parts[0], int(parts[1]), parts[2] if len(parts) > 2 else "blake3", a.n_batch, a.steps, a.warmup)
+        r = run(parts[0], int(parts[1]), parts[2] if len(parts) > 2 else "blake3", a.n_batch, a.steps, a.warmup, a.encoding, a.code, a.seed)
         line = json.dumps(r)
         print(line, flush=True)
         if a.out:
