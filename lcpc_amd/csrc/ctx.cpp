@@ -205,6 +205,15 @@ static uint32_t ntt_tile_group_of(uint32_t log_n, int L, uint32_t log_tj) {
 // If the device cannot hold the tables (the first pack of a three-pass plan is ~2.3 x one row: 4.9 GB at 2^26 columns), everything
 // made here is freed and the general kernel's plan stays -- slower, not an error.  Ft255's d_rootsl / d_rootslc / d_qpl / d_wq_w
 // were made with d_roots and belong to that plan as well.
+// K1s pure / coset form, LCPC_NTT_MUL unset: does a pass of the plan with s0 first-pass stages multiply its lane-varying twiddles by
+// ln::mul2 (split packs)?  Each pass was switched alone (LCPC_NTT_MUL=split-pure / split-coset) against ln::mul, same box, interleaved,
+// 5 alternations, and keeps ln::mul2 only where the gain clears the larger run-to-run spread of the two sides (LABNOTES.md):
+//   coset pass: 2^16 x 512 rows 2.138 -> 2.086 ms per commit (spread 0.018), 2^18 x 512 9.159 -> 8.938 (0.041), 2^20 x 128 10.141 -> 9.905
+//               (0.101); it is the only split pass at 2^17 (2.305 -> 2.238) and 2^19 (5.051 -> 4.919): every size from 2^16 columns on;
+//   pure pass:  2^18 9.159 -> 9.052 (0.079; 3.270 -> 3.162 ms per launch in the kernel trace): kept.  2^16 2.138 -> 2.120 (0.023) and
+//               2^20 10.141 -> 10.066 (0.101) stay inside the spread: ln::mul.
+// Below 2^16 columns (the coset form forced by LCPC_NTT_FORM) nothing was measured and ln::mul stays.
+static bool ntt_mul_split_default(unsigned s0, bool first) { return first ? s0 == 8 : s0 >= 6; }
 static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
   std::vector<uint32_t**> made;                                // what this function allocated
   std::vector<NttStep> plan(n_pass);
@@ -267,7 +276,11 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
       const bool nf = c->L == 4 && n_pass == 2 && (c->sw_ntt_form == 1 || (c->sw_ntt_form < 0 && s0 >= 6));
       p.a.form = nf ? 1u : 0u;
       if (nf && last) p.blk0_gone = 1u;
-      p.pack_info = nf ? ntt_l9s_form_pack_info(p.a.s, p.first) : ntt_lns_pack_info(c->NL, p.a.s, p.first);
+      // the multiplier of the pass's lane-varying rounds (LCPC_NTT_MUL, ntt_l9s.hip M2): ln::mul on one pack entry or ln::mul2 on the
+      // two-table pair of a split pack (twice the twiddle bytes, 148 instructions against 188).  Pure / coset form only, and only the
+      // passes whose mul2 instantiation fits 128 VGPRs without scratch (ntt_l9s_mul2_supported); unset: ntt_mul_split_default
+      const bool m2 = nf && ntt_l9s_mul2_supported(p.a.s, p.first) && (c->sw_ntt_mul == 1 || c->sw_ntt_mul == (p.first ? 2 : 3) || (c->sw_ntt_mul < 0 && ntt_mul_split_default(s0, p.first)));
+      p.pack_info = nf ? ntt_l9s_form_pack_info(p.a.s, p.first, m2) : ntt_lns_pack_info(c->NL, p.a.s, p.first);
       const uint32_t n_classes = p.first != nf ? 1u << (p.a.log_n - 10) : 1u;  // DIF first pass, coset last pass: one class per tile position
 #ifdef LCPC_TEST_HOOKS
       if (n_pass == 3 && i == 0 && c->sw_test_fail_3pass) return LCPC_ERR_NOMEM;   // (the fallback below)
@@ -279,6 +292,10 @@ static int build_limb_plan(lcpc_ctx* c, unsigned n_pass) {
       else HIPCHK(c, launch_ntt_lns_pack(c->NL, pa, p.first, p.pack_info, n_classes, p.pack, nullptr));
     }
     HIPCHK(c, hipDeviceSynchronize());
+    if (c->sw_debug_timing)                                    // (the plan, for a reader and for tests/test_gpu_ntt_mul2.py)
+      for (unsigned i = 0; i < n_pass; i++)
+        fprintf(stderr, "lcpc: ntt plan 2^%u pass %u/%u: %s s=%u form=%u mul2=%u\n", k, i + 1, n_pass, plan[i].kernel == NttStep::K1S ? "K1s" : "K1n",
+                plan[i].a.s, plan[i].a.form, plan[i].pack_info.mul2);
     return 0;
   }();
   if (rc == 0) {
@@ -623,6 +640,7 @@ int lcpc_ctx_create(const lcpc_params* p, lcpc_ctx** out) {
   // the switches: read here, once per context, never on a launch path
   c->sw_ntt_general = getenv("LCPC_NTT_GENERAL") != nullptr;
   if (const char* ev = getenv("LCPC_NTT_FORM")) c->sw_ntt_form = !strcmp(ev, "dif") ? 0 : (!strcmp(ev, "coset") ? 1 : -1);
+  if (const char* ev = getenv("LCPC_NTT_MUL")) c->sw_ntt_mul = !strcmp(ev, "mont") ? 0 : (!strcmp(ev, "split") ? 1 : (!strcmp(ev, "split-pure") ? 2 : (!strcmp(ev, "split-coset") ? 3 : -1)));
   if (const char* ev = getenv("LCPC_NTT_MID_MAX_MB")) c->sw_ntt_mid_max_mb = (int64_t)strtoull(ev, nullptr, 10);
   if (const char* ev = getenv("LCPC_HOST_STAGE")) c->sw_host_stage = (int32_t)strtol(ev, nullptr, 10);
   c->sw_debug_timing = getenv("LCPC_DEBUG_TIMING") != nullptr;

@@ -53,7 +53,7 @@ template <> struct LnField<FT255> {
 };
 
 #include "field_ln_gen.h"    // ln_mul1s_ft63 / _ft127 / _ft191
-#include "field_r29_gen.h"   // Ft255: r29_columns (fe_mul_r29's Comba/Montgomery chain as asm blocks), r29_mul1s
+#include "field_r29_gen.h"   // Ft255: r29_columns (fe_mul_r29's Comba/Montgomery chain as asm blocks), r29_mul1s, r29_mul2s
 #include "field_wmul_gen.h"  // wmul_u / _ft127 / _ft191: x * w mod p for a WAVE-UNIFORM w given as its shifted multiples (scalar operands)
 
 template <int N> struct LN {
@@ -167,6 +167,41 @@ template <class FT> LCPC_DEV LN<FT::N> mul(const LN<FT::N>& a, const LN<FT::N>& 
   else if constexpr (FT::FID == FT191) ln_mul1s_ft191(a.v, w.v, r.v);
   else r29_mul1s(a.v, w.v, r.v);
   return r;
+}
+// Ft255, the two-table form of the same multiply for a lane-varying twiddle (K1s's split plans, ntt_l9s.hip): a = AL + 2^145 AH (limbs
+// 0-4 | 5-8) and the twiddle as TWO entries b0 = w c 2^145 mod p, b1 = w c 2^290 mod p, both normalised in [0, p) (c: the scale of the
+// table entry w c R', 1 or 2^5 / R'; the packs of ntt_lns.hip hold both).  Z = AL b0 + AH b1 == a w c 2^145 fills 13 columns, so five
+// Montgomery digits instead of nine bring it back to nine limbs: 81 + 40 mads against 81 + 72 (field_r29_gen.h r29_mul2s, 148
+// instructions against 188).  a: limbs in (-2^30, 2^30) -- no bound on the value beyond that.  Column sums stay inside i64 (9 * 2^59 +
+// 5 * 2^58 + 2^35 < 2^63).  Result == a w c (mod p), normalised, in (Z / 2^145 - p, Z / 2^145]:
+//   limbs in (-2^30, 2^30):                                          (-3.01p, 2.01p)
+//   a difference of two normalised values (limbs 0-7 in (-2^29, 2^29)): (-2.01p, 1.01p)
+//   a normalised value:                                              (-1.01p, 1.01p)
+// (wider than mul()'s (-1.2p, 0.2p] because only 2^145, not 2^261, is divided out; tests/test_gen_r29_mul2.py proves and checks them).
+template <class FT> LCPC_DEV LN<FT::N> mul2(const LN<FT::N>& a, const LN<FT::N>& b0, const LN<FT::N>& b1) {
+  static_assert(FT::FID == FT255, "the two-table multiply exists for Ft255 only");
+  LN<FT::N> r = b1;                                            // (b1 arrives in the result registers: it is dead before they are written)
+  r29_mul2s(a.v, b0.v, r.v);
+  return r;
+}
+// a table entry e = w c R' in [0, p) -> the pair (b0, b1) of mul2: e 2^-116 and e 2^29, fully reduced (pack kernels, ntt_lns.hip)
+template <class FT> LCPC_DEV void mul2_pair(const LN<FT::N>& e, LN<FT::N>& b0, LN<FT::N>& b1) {
+  static_assert(FT::FID == FT255, "the two-table multiply exists for Ft255 only");
+#pragma unroll
+  for (int t = 0; t < 2; t++) {
+    LN<FT::N> kk;
+#pragma unroll
+    for (int z = 0; z < FT::N; z++) kk.v[z] = t ? R29_MUL2_KB[z] : R29_MUL2_KA[z];
+    LN<FT::N> x = mul<FT>(kk, e);                              // (-1.2p, 0.2p], normalised: + p while negative lands in [0, p)
+    for (int it = 0; it < 2; it++) {
+      if ((int32_t)x.v[FT::N - 1] < 0) {
+#pragma unroll
+        for (int z = 0; z < FT::N; z++) x.v[z] += FT::limb(z);
+        normalize<FT>(x);
+      }
+    }
+    (t ? b1 : b0) = x;
+  }
 }
 // a * w mod p for a wave-uniform w given as its N shifted multiples W_j = balanced(w 2^(W j) mod p) (N^2 words t = N k + j, host:
 // ctx.cpp wmul_table; field_wmul_gen.h).  a: limbs of a normalised value or of a difference of two (sum |limb| < N 2^W).  Result:

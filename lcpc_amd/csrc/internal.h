@@ -267,6 +267,9 @@ struct lcpc_ctx {
   // A/B switches, read from the environment ONCE, when the context is created (never on a launch path: getenv next to a
   // setenv of another thread is undefined behaviour, and a context must not change plans under a running commit)
   bool sw_ntt_general = false;     // LCPC_NTT_GENERAL: every Ligero row on the general kernel (K1) instead of the shape-specialised plans
+  int sw_ntt_mul = -1;             // LCPC_NTT_MUL=mont|split: the lane-varying multiplier of the K1s pure / coset plans (ntt_l9s.hip M2): 0 = ln::mul,
+                                   // 1 = ln::mul2 on split packs in every pass that has the instantiation, 2 / 3 (split-pure / split-coset) = in that pass alone,
+                                   // -1 (unset) = per pass (build_limb_plan)
   int sw_ntt_form = -1;            // LCPC_NTT_FORM=dif|coset: the K1s two-pass plans' factorisation (ntt_l9s.hip): 0 = DIF, 1 = pure first pass + coset
                                    // last pass at every size, -1 (unset) = coset from 2^16 columns on (build_limb_plan)
   int64_t sw_ntt_mid_max_mb = -1;  // LCPC_NTT_MID_MAX_MB: -1 = the default rule of ntt_mid_rows

@@ -47,6 +47,8 @@ struct NttPackInfo {
   uint32_t round_off[8];    // word offset of round slot r inside a class block
   uint32_t class_words;     // words per tile class
   uint32_t u_off;           // passes with a uniform round (ntt_ln_dev.h Shape::RU): word offset of its 4 x 3 shifted-multiples tables
+  uint32_t mul2;            // K1s pure / coset form only: 1 = every lane-varying slot holds the two-table pair of ln::mul2 (twice the
+                            // variants: b0 of variant v at v, b1 at NV + v) and the pass kernel multiplies by it; 0 = ln::mul entries
 };
 bool ntt_l9s_supported(uint32_t log_n, uint32_t n_passes, int log_tile);
 // three passes for 2^21 .. 2^26 columns: s0 = log_n - 20 stages with the first-pass kernel on the whole rows (element stride 2^20),
@@ -56,7 +58,14 @@ bool ntt_l9s3_supported(uint32_t log_n);
 hipError_t launch_ntt_pass_l9s(const NttPassArgs& a, bool first, const uint32_t* pack, const NttPackInfo& pi, hipStream_t st);
 // the packs of the pure / coset form (NttPassArgs.form == 1; built in ntt_lns.hip beside the other packs).  First pass: one class;
 // last pass: one class per tile position, 2^(log_n - 10).  a: log_n, s, roots29, roots29c
-NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first);
+NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first, bool mul2);
+// mul2 (NttPackInfo.mul2, ln::mul2 on two-table packs) exists for these passes of the pure / coset form only: the coset pass, and the
+// pure passes but S = 2 (2^12 columns: no lane-varying round, I alone) and S = 7, 9 (2^17, 2^19 columns), which are not built: with 18
+// words per twiddle the ln::mul2 builds of <7, 3, first, packed intermediate> and of both <9, 1, first> need 12 / 12 / 20 bytes of scratch
+// per lane at 128 VGPRs, where every other ln::mul2 build needs none.  (The ln::mul builds of <9, 1, first, packed intermediate> carry 12 /
+// 20 bytes as well, DIF / pure form: those are what the plan ran before and runs still; they are not a reason to add spilling kernels.)
+// One predicate for the launcher's instantiations (ntt_l9s.hip) and the plan (ctx.cpp)
+constexpr bool ntt_l9s_mul2_supported(uint32_t s, bool first) { return !first ? s == 10 : (s >= 1 && s <= 10 && s != 2 && s != 7 && s != 9); }
 hipError_t launch_ntt_l9s_form_pack(const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st);
 
 // ---- shape-specialised lazy-limb NTT for Ft63 / Ft127 / Ft191, two-pass plans on 1024-element tiles (ntt_lns.hip) ----

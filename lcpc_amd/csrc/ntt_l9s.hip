@@ -65,13 +65,36 @@ namespace {
 // Per quad chain of the headline (8 + 10): 6 + 9 lane-varying and 7 + 11 uniform multiplies against 9 + 9 and 7 + 8.
 // Canonical output: block 0 of the pure pass is the low sub-block of EVERY tile; it leaves through the converting twiddles as before,
 // and the pure sum that would carry it on is converted in round RC (PureShape), so the coset pass sees canonical values only.
-template <int S, int LTJ, bool FIRST, bool MID, bool NF>
+// M2, the multiplier of the lane-varying rounds of the pure / coset form (NttPackInfo.mul2; the plan chooses it per pass, ctx.cpp
+// build_limb_plan): ln::mul on one pack entry w c 2^261 (188 instructions), or ln::mul2 on the pair b0 = w c 2^145, b1 = w c 2^290 that a
+// split pack holds for every lane-varying slot (148).  Where the bounds below name the output of ln::mul, (-1.2p, 0.2p], mul2 returns
+// (-3.01p, 2.01p) for limbs in (-2^30, 2^30) -- still |value| < 4p, invariant I; the rounds that depend on more say so.
+template <bool M2> struct Tw { LN<9> b0, b1; };
+template <> struct Tw<false> { LN<9> b0; };
+template <bool M2, u32 NV> LCPC_DEV Tw<M2> tw_get(const u32* blk, u32 period, u32 variant, u32 jl) {
+  using FT = LnField<FT255>;
+  Tw<M2> t;
+  if constexpr (M2) {
+    t.b0 = pack_get<FT, 2 * NV>(blk, period, variant, jl);
+    t.b1 = pack_get<FT, 2 * NV>(blk, period, NV + variant, jl);
+  } else {
+    t.b0 = pack_get<FT, NV>(blk, period, variant, jl);
+  }
+  return t;
+}
+template <bool M2> LCPC_DEV LN<9> tw_mul(const LN<9>& x, const Tw<M2>& w) {
+  if constexpr (M2) return ln::mul2<LnField<FT255>>(x, w.b0, w.b1);
+  else return ln::mul<LnField<FT255>>(x, w.b0);
+}
+
+template <int S, int LTJ, bool FIRST, bool MID, bool NF, bool M2>
 __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, const u32* __restrict__ pack, NttPackInfo pi) {
   using FT = LnField<FT255>;
   constexpr int NL = 8, LT = S + LTJ, LBT = LTJ;
   constexpr bool LAST = !FIRST;
   static_assert(LT == 10, "1024-element tiles: one radix-4 quad (two radix-2 pairs) per thread and round");
   static_assert(FIRST || (LTJ == 0 && S % 2 == 0), "the last pass works on contiguous tiles and ends with the trivial stages k-2, k-1");
+  static_assert(NF || !M2, "the two-table multiply serves the pure / coset form only");
   using SH = Shape<S, LBT>;
   using SP = PureShape<S>;
   constexpr int RU = NF ? (FIRST ? SP::RU : -1) : SH::RU;   // (the coset pass's two uniform rounds need no deal of the lanes)
@@ -194,20 +217,20 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     for (u32 pp = 0; pp < 2; pp++) {
       const u32 e1 = tid + 256u * pp;                        // slots with the top stage bit clear are [0, half)
       // pure form: w_{2^S}^i for the pair's i = e1 >> LBT, whatever the tile and lp
-      const LN<9> w = NF ? pack_get<FT, 2>(blk, 1u << (S - 1), canon ? 1u : 0u, e1 >> LBT) : pack_get<FT, 2>(blk, SH::period2, canon ? 1u : 0u, e1);
+      const Tw<M2> w = NF ? tw_get<M2, 2>(blk, 1u << (S - 1), canon ? 1u : 0u, e1 >> LBT) : tw_get<M2, 2>(blk, SH::period2, canon ? 1u : 0u, e1);
       const LN<9> x = DIRECT ? xin[pp] : planes_get<FT>(lds, T, SWZ(e1));
       if (pp == 0) mem_phase(false);
       // pure form, S = 1 and 3: no later round reads the pack, so the sum half is converted here as well (RC < 0, ntt_ln_dev.h)
       const bool cvs = NF && canon && SH::NR4 <= 1;
       if (zero_hi) {
         if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e1), cvs ? ln::mul<FT>(x, k32) : x);
-        planes_put<FT>(lds, T, SWZ(e1 + half), ln::mul<FT>(x, w));         // (x, 0) -> (x, x w)
+        planes_put<FT>(lds, T, SWZ(e1 + half), tw_mul<M2>(x, w));           // (x, 0) -> (x, x w)
       } else {
         const LN<9> y = DIRECT ? xin[pp + 2] : planes_get<FT>(lds, T, SWZ(e1 + half));
         LN<9> sum = ln::add(x, y);                              // [0, 2p)
         ln::normalize<FT>(sum);
         planes_put<FT>(lds, T, SWZ(e1), cvs ? ln::mul<FT>(sum, k32) : sum);
-        planes_put<FT>(lds, T, SWZ(e1 + half), ln::mul<FT>(ln::sub(x, y), w));
+        planes_put<FT>(lds, T, SWZ(e1 + half), tw_mul<M2>(ln::sub(x, y), w));
       }
     }
     mem_phase(true);
@@ -218,20 +241,23 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   if constexpr (NF && LAST) {
     // ---- the coset form (head comment): five multiply-then-butterfly rounds, thread q on quad q of its round throughout.
     //      What the tile holds between rounds is NOT invariant I: y1, y2, y3 are stored as they come out, un-normalised.  Per round:
-    //        x0            round 0: a load (< 2^256, or the limb intermediate: normalised, |value| < 10.8p -- the pure pass's I-only
-    //                      round) ; later: limbs in (-2^30, 2^30), |value| < 12.1p.  Clamped first (but for the packed loads): [0, p + 2^239).
+    //      (M2: where two figures stand as a / b, a is ln::mul's and b ln::mul2's, whose products lie in (-3.01p, 2.01p).)
+    //        x0            round 0: a load (< 2^256, or the limb intermediate: normalised, |value| < 10.8p / 12.04p -- the pure pass's
+    //                      I-only round) ; later: limbs in (-2^30, 2^30), |value| < 12.1p.  Clamped first (but for the packed loads): [0, p + 2^239).
     //                      ln::clamp_apply's carry pass is signed, and its quotient estimate from the un-normalised top limb is off by
     //                      the carries still below it, here in [-2, 2] instead of [0, 3]: V - q p >= (QBIAS - |q| - 2.01) B > 0 and
     //                      < (PTOP + 1 + QBIAS + |q| + 3.01) B < p + 64 B for |q| <= 18, the margins field_ln.h states
     //        x1, x2, x3    rounds 0, 1 (ln::mul_u): normalised -- round 0's inputs are loads, and round 0 normalises all four outputs
     //                      for round 1 (mul_u wants sum |limb| < 9 * 2^29; top limb: |value| < 12.1p is < 2^27);
-    //                      rounds 2 .. 4 (ln::mul): limbs in (-2^30, 2^30), |value| < 9.1p < 16p
-    //        p1, p2, p3    normalised; mul_u: (-2p, 2.7p), mul: (-1.2p, 0.2p]
+    //                      rounds 2 .. 4 (ln::mul / ln::mul2): limbs in (-2^30, 2^30), |value| < 9.1p < 16p (mul2 asks for the limbs only)
+    //        p1, p2, p3    normalised; mul_u: (-2p, 2.7p), mul: (-1.2p, 0.2p], mul2: (-3.01p, 2.01p)
     //        t             mul_u of p1 - p3 (a difference of two normalised values): normalised, (-2p, 2.7p)
     //        y0            x0 + p2 + p1 + p3: limbs [0, 2^31 - 4] -- normalised before it is stored (the one output that needs headroom)
     //        y1            (x0 + p2) - (p1 + p3): limbs (-2^30, 2^30);  y2, y3 = (x0 - p2) +- t: limbs (-2^30, 2^30)
     //        |y|           round 0: < 4p + 3 * 2.7p = 12.1p (x0 un-clamped from the packed loads: < 2.5p + 8.1p); round 1: < 1.001p + 8.1p = 9.1p;
-    //                      rounds 2 .. 4: < 1.001p + 3.6p = 4.6p
+    //                      rounds 2 .. 4: < 1.001p + 3.6p = 4.6p; M2: y0 in (-9.03p, 7.04p), y1 in (-7.03p, 9.04p) (x0 + p2 in (-3.01p, 3.02p),
+    //                      p1 + p3 in (-6.02p, 4.02p)), y2, y3 in (-4.71p, 6.72p) (x0 - p2 in (-2.01p, 4.02p), t in (-2p, 2.7p)): |y| < 9.04p,
+    //                      inside the clamp's |q| <= 18 and mul_u's limb sums (p1 - p3: a difference of two normalised values)
     //      The final round reduces and stores its four consecutive elements from the registers, as the DIF form's does.
 #pragma unroll
     for (int r = 0; r < 5; r++) {
@@ -255,13 +281,13 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         p3 = ln::mul_u<FT>(x3, wu + 2 * U_SLOT<FT>);
       } else {
         const u32* blk = cls_pack + pi.round_off[r];
-        const LN<9> w1 = pack_get<FT, 3>(blk, coset_sets(r), 0, m), w2 = pack_get<FT, 3>(blk, coset_sets(r), 1, m);
-        const LN<9> w3 = pack_get<FT, 3>(blk, coset_sets(r), 2, m);
+        const Tw<M2> w1 = tw_get<M2, 3>(blk, coset_sets(r), 0, m), w2 = tw_get<M2, 3>(blk, coset_sets(r), 1, m);
+        const Tw<M2> w3 = tw_get<M2, 3>(blk, coset_sets(r), 2, m);
         mem_phase(false);
         ln::clamp_apply<FT>(x0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x0.v[8])));
-        p2 = ln::mul<FT>(x2, w2);
-        p1 = ln::mul<FT>(x1, w1);
-        p3 = ln::mul<FT>(x3, w3);
+        p2 = tw_mul<M2>(x2, w2);
+        p1 = tw_mul<M2>(x1, w1);
+        p3 = tw_mul<M2>(x3, w3);
       }
       const LN<9> s02 = ln::add(x0, p2), d02 = ln::sub(x0, p2), s13 = ln::add(p1, p3);
       LN<9> y0 = ln::add(s02, s13), y1 = ln::sub(s02, s13);
@@ -277,7 +303,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         planes_put<FT>(lds, T, SWZ(e0 + 3 * D), y3);
         __syncthreads();
       } else {
-        // D == 1: four consecutive elements of the row, normalised, |value| < 4.6p: clamp, pack, the rare conditional subtract, store
+        // D == 1: four consecutive elements of the row, normalised, |value| < 4.6p (M2: 9.04p): clamp, pack, the rare conditional subtract, store
         u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
         LN<9> cc[4] = {y0, y1, y2, y3};
 #pragma unroll
@@ -313,7 +339,9 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     if (triv) {
       // ---- pure form, the last stage pair: c0 = b0 + b1, c1 = b0 - b1, c2, c3 = (x0 - x2) +- (x1 - x3) I.  Inputs: normalised,
       //      |value| < 2.7p (the uniform round before it: clamped sums and mul_u outputs; a lane-varying round: < 2.4p; loads and the
-      //      radix-2 round's sums: < 2p), so |c0|, |c1| < 10.8p and |c2|, |c3| < 5.4p + 2.7p = 8.1p.  Stored normalised: the successor's
+      //      radix-2 round's sums: < 2p), so |c0|, |c1| < 10.8p and |c2|, |c3| < 5.4p + 2.7p = 8.1p.  M2, S = 4, 5 (a lane-varying round
+      //      straight before this one) and S = 3 (the radix-2 round's products): inputs < 3.01p, so |c0|, |c1| < 12.04p and |c2|, |c3| <
+      //      6.02p + 2.7p = 8.72p -- the clamp takes |value| < 16p, the successor clamps x0 and multiplies the rest by mul_u.  Stored normalised: the successor's
       //      first round multiplies three of four by scalar operands (mul_u)
       const bool fr = DIRECT && SH::U0 == 0 && r == 0;       // S == 2: the thread's own loads
       const LN<9> x0 = fr ? xin[0] : planes_get<FT>(lds, T, SWZ(e0)), x1 = fr ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + dq));
@@ -380,24 +408,24 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       // zero-padded first round (rate <= 1/2): x2 = x3 = 0, the stage-0 butterflies are (x, x w); inputs < p; everything
       // is block 0, so with canonical output the three multiplies leaving it (w0, w3, and w2 for c1) take the converting set
       const u32 vb = canon ? 3u : 0u;
-      const LN<9> w0 = pack_get<FT, 6>(blk, period, vb + 0, jl), w3 = pack_get<FT, 6>(blk, period, vb + 1, jl), w2 = pack_get<FT, 6>(blk, period, vb + 2, jl);
+      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, vb + 0, jl), w3 = tw_get<M2, 6>(blk, period, vb + 1, jl), w2 = tw_get<M2, 6>(blk, period, vb + 2, jl);
       mem_phase(false);
       const bool cv0 = NF && canon && r == RC;               // pure form: the round that converts the pure sum as well (below)
       if (a.n_valid <= (1ull << (k - 2))) {                  // rate <= 1/4: x1 is zero too
         const LN<9> x0 = DIRECT ? xin[0] : planes_get<FT>(lds, T, SWZ(e0));
         if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(x0, k32) : x0);
-        planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(x0, w2));
-        planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(x0, w0));
-        planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), ln::mul<FT>(x0, w3));
+        planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(x0, w2));
+        planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(x0, w0));
+        planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(x0, w3));
       } else {
         const LN<9> x0 = DIRECT ? xin[0] : planes_get<FT>(lds, T, SWZ(e0)), x1 = DIRECT ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + dq));
         LN<9> c0 = ln::add(x0, x1);                                                           // [0, 2p)
         ln::normalize<FT>(c0);
         planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(c0, k32) : c0);
-        planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(ln::sub(x0, x1), w2));
+        planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(ln::sub(x0, x1), w2));
         const LN<9> t = ln::mul_u<FT>(x1, a.wq_w);                                                // x1 I (plain constant: t keeps x1's form); (-2p, 2.7p)
-        planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(ln::add(x0, t), w0));                  // in: limbs (-2^29, 2^30), |value| < 3.7p
-        planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), ln::mul<FT>(ln::sub(x0, t), w3));
+        planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(x0, t), w0));                   // in: limbs (-2^29, 2^30), |value| < 3.7p
+        planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(x0, t), w3));
       }
       mem_phase(true);
       __syncthreads();
@@ -461,15 +489,30 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         }
       }
       const u32 vb = blk0c ? 3u : 0u;
-      const LN<9> w0 = pack_get<FT, 6>(blk, period, vb + 0, jl), w3 = pack_get<FT, 6>(blk, period, vb + 1, jl);
-      const LN<9> w2 = pack_get<FT, 6>(blk, period, vb + 2, jl);
+      if constexpr (M2) {
+        // the same butterfly as below on 18 words per twiddle: w3's are asked for behind the first product, under whose chain they
+        // arrive, and the two differences are taken before it, so that x0 .. x3 are dead when the first chain starts (all three pairs
+        // up front spill at 128 VGPRs)
+        const Tw<M2> w2 = tw_get<M2, 6>(blk, period, vb + 2, jl), w0 = tw_get<M2, 6>(blk, period, vb + 0, jl);
+        const LN<9> d1 = ln::sub(b0, b1);
+        const LN<9> d13 = ln::sub(x1, x3), e2 = ln::sub(x0, x2);
+        planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(d1, w2));                                   // normalised, (-3.01p, 2.01p)
+        __builtin_amdgcn_sched_barrier(0);
+        const Tw<M2> w3 = tw_get<M2, 6>(blk, period, vb + 1, jl);
+        const LN<9> t = ln::mul_u<FT>(d13, a.wq_w);                                                // normalised, (-2p, 2.7p)
+        planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(e2, t), w0));
+        planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(e2, t), w3));
+      } else {
+      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, vb + 0, jl), w3 = tw_get<M2, 6>(blk, period, vb + 1, jl);
+      const Tw<M2> w2 = tw_get<M2, 6>(blk, period, vb + 2, jl);
       const LN<9> d1 = ln::sub(b0, b1);                                                       // limbs (-2^30, 2^30), |value| < 16p
-      planes_put<FT>(lds, T, SWZ(e0 + dq), ln::mul<FT>(d1, w2));                                    // normalised, (-1.2p, 0.2p]
+      planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(d1, w2));                                     // normalised, (-1.2p, 0.2p]
       // t = (x1 - x3) I by the plain constant: in block 0 it stays in the form of its inputs and the two products below convert
       const LN<9> t = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);                                     // normalised, (-2p, 2.7p)
       const LN<9> e2 = ln::sub(x0, x2);                                                       // limbs (-2^29, 2^29), |value| < 8p
-      planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), ln::mul<FT>(ln::add(e2, t), w0));                    // in: limbs (-2^29, 2^30), |value| < 10.7p
-      planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), ln::mul<FT>(ln::sub(e2, t), w3));
+      planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(e2, t), w0));                     // in: limbs (-2^29, 2^30), |value| < 10.7p
+      planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(e2, t), w3));
+      }
     }
     mem_phase(true);                                         // the barrier, then the next round's reads and twiddle loads (or the store phase)
     __syncthreads();
@@ -508,22 +551,27 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   }
 }
 
-template <int S, int LTJ, bool FIRST, bool MID, bool NF>
+template <int S, int LTJ, bool FIRST, bool MID, bool NF, bool M2>
 hipError_t launch_tm(const NttPassArgs& a, const u32* pack, const NttPackInfo& pi, hipStream_t st) {
   constexpr int LT = S + LTJ;
   const u64 tiles = ((u64)1 << (a.log_n - LT)) * a.n_rows;
   const size_t lds_bytes = (((size_t)1 << LT) * 9 + 64 * LnField<FT255>::STRIDE) * 4;   // tile + q*p table
   // hipFuncSetAttribute is idempotent and cheap; calling it on every launch keeps this free of unsynchronised caches
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF, M2>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF>), dim3((unsigned)tiles), dim3(256), lds_bytes, st, a, pack, pi);
+  hipLaunchKernelGGL((ntt_pass_l9s_kernel<S, LTJ, FIRST, MID, NF, M2>), dim3((unsigned)tiles), dim3(256), lds_bytes, st, a, pack, pi);
   return hipGetLastError();
 }
 template <int S, int LTJ, bool FIRST>
 hipError_t launch_t(const NttPassArgs& a, const u32* pack, const NttPackInfo& pi, hipStream_t st) {
-  if (a.form) return a.mid ? launch_tm<S, LTJ, FIRST, true, true>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, true>(a, pack, pi, st);
-  return a.mid ? launch_tm<S, LTJ, FIRST, true, false>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, false>(a, pack, pi, st);
+  if (pi.mul2) {
+    // the split packs exist for the pure / coset form only, and only for the passes that ntt_l9s_mul2_supported names
+    if constexpr (ntt_l9s_mul2_supported(S, FIRST)) { if (a.form) return a.mid ? launch_tm<S, LTJ, FIRST, true, true, true>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, true, true>(a, pack, pi, st); }
+    return hipErrorInvalidValue;
+  }
+  if (a.form) return a.mid ? launch_tm<S, LTJ, FIRST, true, true, false>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, true, false>(a, pack, pi, st);
+  return a.mid ? launch_tm<S, LTJ, FIRST, true, false, false>(a, pack, pi, st) : launch_tm<S, LTJ, FIRST, false, false, false>(a, pack, pi, st);
 }
 
 }  // namespace

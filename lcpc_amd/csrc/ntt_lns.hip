@@ -318,6 +318,20 @@ template <class FT> LCPC_DEV LN<FT::N> tab_entry_neg(const u32* tab, u32 ix, u32
   }
   return m;
 }
+// a lane-varying slot of a pack: the table entry itself, or (NttPackInfo.mul2, Ft255's K1s split plans) the pair of ln::mul2 made from
+// it -- b0 at variant v, b1 at NV + v of a slot with twice the variants
+template <class FT, u32 NV> LCPC_DEV void pack_put_tw(u32* blk, u32 period, u32 variant, u32 jl, const LN<FT::N>& e, u32 mul2) {
+  if constexpr (FT::FID == FT255) {
+    if (mul2) {
+      LN<FT::N> b0, b1;
+      ln::mul2_pair<FT>(e, b0, b1);
+      pack_put<FT, 2 * NV>(blk, period, variant, jl, b0);
+      pack_put<FT, 2 * NV>(blk, period, NV + variant, jl, b1);
+      return;
+    }
+  }
+  pack_put<FT, NV>(blk, period, variant, jl, e);
+}
 // one thread per (class, round slot, position): copies the table entries a quad / pair will ask for into lane order
 template <class FT, int S, int LBT>
 __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPackInfo pi, u32 n_classes, bool first, u32* pack) {
@@ -335,8 +349,8 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
       const u32 lp = jl & ((1u << LBT) - 1), i = jl >> LBT;
       const u32 g1 = (i << lb) | lo | lp;
       const u32 gm = (1u << (k - t0 - 1)) - 1;
-      pack_put<FT, 2>(blk, SH::period2, 0, jl, tab_entry<FT>(a.roots29, (g1 & gm) << t0));
-      pack_put<FT, 2>(blk, SH::period2, 1, jl, tab_entry<FT>(a.roots29c, (g1 & gm) << t0));
+      pack_put_tw<FT, 2>(blk, SH::period2, 0, jl, tab_entry<FT>(a.roots29, (g1 & gm) << t0), pi.mul2);
+      pack_put_tw<FT, 2>(blk, SH::period2, 1, jl, tab_entry<FT>(a.roots29c, (g1 & gm) << t0), pi.mul2);
       continue;
     }
     const u32 r = slot - SH::U0, u = SH::U0 + 2 * r, hb = S - u - 1, period = 1u << (hb - 1 + LBT);
@@ -350,7 +364,7 @@ __global__ void __launch_bounds__(256) ntt_lns_pack_kernel(NttPassArgs a, NttPac
     // w1 = w^(e + n/4) = I w0 is never read).  The tables hold w^i for i < n / 2 and w^(n/2) = -1: past that, the negated entry
     const u32 ex = (g0 & gm0) << t, half_n = 1u << (k - 1);
     const u32 idx[3] = {ex, 3 * ex, 2 * ex};
-    for (u32 v = 0; v < 6; v++) pack_put<FT, 6>(blk, period, v, jl, tab_entry_neg<FT>(v < 3 ? a.roots29 : a.roots29c, idx[v % 3], half_n));
+    for (u32 v = 0; v < 6; v++) pack_put_tw<FT, 6>(blk, period, v, jl, tab_entry_neg<FT>(v < 3 ? a.roots29 : a.roots29c, idx[v % 3], half_n), pi.mul2);
   }
 }
 
@@ -443,7 +457,7 @@ __global__ void __launch_bounds__(256) l9s_coset_pack_kernel(NttPassArgs a, NttP
     const u32 r = x < 16 ? 2u : (x < 80 ? 3u : 4u), m = x < 16 ? x : (x < 80 ? x - 16 : x - 80);
     const u32 E = coset_exp(k, cls, r, m);
     u32* blk = pack + (size_t)cls * pi.class_words + pi.round_off[r];
-    for (u32 v = 0; v < 3; v++) pack_put<F255, 3>(blk, coset_sets(r), v, m, tab_entry_neg<F255>(a.roots29, (v + 1) * E, half_n));
+    for (u32 v = 0; v < 3; v++) pack_put_tw<F255, 3>(blk, coset_sets(r), v, m, tab_entry_neg<F255>(a.roots29, (v + 1) * E, half_n), pi.mul2);
   }
 }
 // rounds 0 (one triple) and 1 (four): shifted multiples, table (r * 4 + m) * 3 + v
@@ -491,18 +505,20 @@ __global__ void __launch_bounds__(256) roots_ln_kernel(const u32* roots, u64 n, 
 
 #define LNS_FIRST_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 
-NttPackInfo form_pack_info(uint32_t s, bool first) {
+NttPackInfo form_pack_info(uint32_t s, bool first, bool mul2) {
   NttPackInfo pi{};
   u32 off = 0;
+  const u32 nb = mul2 ? 2u : 1u;                               // entries per lane-varying twiddle (ln::mul2: b0 | b1)
+  pi.mul2 = mul2 ? 1u : 0u;
   if (first) {
     // as pack_info_t<F255, S, 0>: the radix-2 slot, then 6 variants x sets(r) per radix-4 round; then the uniform round's 4 x 3 tables
     const u32 u0 = s & 1, nr4 = s / 2;
     u32 slot = 0;
-    if (u0) { pi.round_off[slot++] = off; off += 2 * (1u << (s - 1)) * 9; off = (off + 3) & ~3u; }
-    for (u32 r = 0; r < nr4; r++) { pi.round_off[slot++] = off; off += 6 * (1u << (s - u0 - 2 * r - 2)) * 9; off = (off + 3) & ~3u; }
+    if (u0) { pi.round_off[slot++] = off; off += nb * 2 * (1u << (s - 1)) * 9; off = (off + 3) & ~3u; }
+    for (u32 r = 0; r < nr4; r++) { pi.round_off[slot++] = off; off += nb * 6 * (1u << (s - u0 - 2 * r - 2)) * 9; off = (off + 3) & ~3u; }
     if (nr4 >= 3) { pi.u_off = off; off += 4 * 3 * U_SLOT<F255>; }
   } else {
-    for (u32 r = 2; r < 5; r++) { pi.round_off[r] = off; off += 3 * coset_sets(r) * 9; }
+    for (u32 r = 2; r < 5; r++) { pi.round_off[r] = off; off += nb * 3 * coset_sets(r) * 9; }
     pi.u_off = off;
     off += 2 * 4 * 3 * U_SLOT<F255>;
   }
@@ -569,7 +585,7 @@ template <class FT> hipError_t launch_pass_f(const NttPassArgs& a, bool first, c
 // 0.73 / 1.43 / 2.30 ms against 0.76 / 1.63 / 2.90; 2^20 columns 1.97 / 2.26 ms against 2.02 / 3.26 for Ft127 / Ft191.  Ft63's
 // 8-byte first-pass runs lost at 2^20 columns until the first pass ran the tiles that share cache lines back to back on one
 // XCD (NttPassArgs.tile_group): 512 rows x 2^20 columns 12.9 ms on the general plan, 23.3 ungrouped, 11.2 grouped.
-NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first) { return form_pack_info(s, first); }
+NttPackInfo ntt_l9s_form_pack_info(uint32_t s, bool first, bool mul2) { return form_pack_info(s, first, mul2); }
 hipError_t launch_ntt_l9s_form_pack(const NttPassArgs& a, bool first, const NttPackInfo& pi, uint32_t n_classes, uint32_t* pack, hipStream_t st) {
   if (a.log_n < 11 || a.log_n > 20 || a.s != (first ? a.log_n - 10 : 10u)) return hipErrorInvalidValue;
   if (!first) {

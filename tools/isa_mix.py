@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""tools/isa_mix.py [out.json] -- the VALU instruction mix of the headline's two row-NTT kernels (ntt_pass_l9s_kernel<8, 2, true, false, true> and
-<10, 0, false, false, true>: LcEncoding::encode of lcpc-ligero-pc/src/lib.rs:162-164 at 2^18 columns) from the gfx950 disassembly, priced with
+"""tools/isa_mix.py [out.json] -- the VALU instruction mix of the headline's two row-NTT kernels (ntt_pass_l9s_kernel<8, 2, true, false, true, true> and
+<10, 0, false, false, true, true>: LcEncoding::encode of lcpc-ligero-pc/src/lib.rs:162-164 at 2^18 columns) from the gfx950 disassembly, priced with
 the issue cost of each instruction class measured on an MI355X (profiles/r06_ubench_mix.txt = `tools/ubench_valu mix`, 4 waves per SIMD
 like the kernels; profiles/r02_ubench_valu.txt for the rest), to state ONE ceiling for "how many wave instructions per second could this
 stream issue": VERDICT r5 item 5.  Runs without a GPU (hipcc -S --cuda-device-only).
@@ -27,8 +27,8 @@ sys.path.insert(0, ROOT)
 CSRC = os.path.join(ROOT, "lcpc_amd", "csrc")
 COST = {"mad64": 4.79, "mad64_s": 4.46, "mul32": 4.32, "vop3": 4.30, "vop2": 2.45}
 UBENCH_CLOCK_GHZ = 2.36          # rocm-smi while the same microbenchmark kernels loop (profiles/r01f_ubench_power.txt: 2.33-2.39)
-# (the last template argument: the pure / coset form, which the headline runs)
-KERNELS = {"first pass, 8 stages": "ntt_pass_l9s_kernelILi8ELi2ELb1ELb0ELb1E", "last pass, 10 stages": "ntt_pass_l9s_kernelILi10ELi0ELb0ELb0ELb1E"}
+# (the last two template arguments: the pure / coset form and the two-table multiply ln::mul2, which the headline runs)
+KERNELS = {"first pass, 8 stages": "ntt_pass_l9s_kernelILi8ELi2ELb1ELb0ELb1ELb1E", "last pass, 10 stages": "ntt_pass_l9s_kernelILi10ELi0ELb0ELb0ELb1ELb1E"}
 VOP2_NAMES = {"v_and_b32", "v_or_b32", "v_xor_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_mov_b32", "v_lshlrev_b32", "v_lshrrev_b32",
               "v_ashrrev_i32", "v_not_b32", "v_min_u32", "v_max_u32", "v_mul_u32_u24", "v_mul_i32_i24"}
 CARRY = ("v_add_co_u32", "v_addc_co_u32", "v_sub_co_u32", "v_subb_co_u32", "v_subrev_co_u32", "v_subbrev_co_u32")
