@@ -5,7 +5,7 @@
 // once over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as batched kernels
 // -- as many launches as ONE commit of the shape.  BLAKE3: batch_kernels.hip (K3b / K4b: chunk CVs, fold, or leaf digests with the
 // first six tree levels).  SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: one serial chain per column, so one leaf launch and one tree
-// call over the batch (the batch forms in sha3.hip, sha256.hip, blake2b.hip); hashes slots are digest_words(c) words.
+// call over the batch (the batch forms of chain_dev.h); hashes slots are digest_words(c) words.
 //
 // Brakedown: the expander matrices are the same for every row of every member, so the encode is one pass over the n_batch * n_rows
 // stacked rows, in one commit's launches.  Members of < SDIG_T_MIN_ROWS rows keep a row-major comm, as a single commit of theirs
@@ -236,10 +236,7 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   } else if (s.chained) {
     // one serial chain per column over the whole leaf message: the digests themselves, in one launch
     la.out = hashes0;
-    if (is_sha3(c)) HIPCHK(m0, launch_sha3_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
-    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
-    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
-    else HIPCHK(m0, launch_blake2b_leaves_batch(c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
+    HIPCHK(m0, launch_chain_leaves_batch(chain_hash(c), c->NL, la, n_batch, comm_stride, sl->hashes_stride, st));
     launches[1]++;
   } else if (s.tree) {
     HIPCHK(m0, launch_leaf_tree_batch(c->NL, la, hashes0, c->np2, n_batch, comm_stride, sl->hashes_stride, st));
@@ -259,10 +256,7 @@ int commit_batch_fast(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   if (c->np2 > c->n_cols && !s.member_hash)          // hashes[n_cols..np2) of every member stay zero (lib.rs:656-666)
     HIPCHK(m0, hipMemset2DAsync(hashes0 + c->n_cols * dw, (size_t)sl->hashes_stride * 4, 0, (size_t)(c->np2 - c->n_cols) * digest_len(c), n_batch, st));
   if (c->np2 > 1 && !s.member_hash) {
-    if (is_sha3(c)) HIPCHK(m0, launch_sha3_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
-    else if (is_keccak256(c)) HIPCHK(m0, launch_keccak256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
-    else if (is_sha256(c)) HIPCHK(m0, launch_sha256_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
-    else if (is_blake2b(c)) HIPCHK(m0, launch_blake2b_merkle_tree_batch(hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
+    if (!is_blake3(c)) HIPCHK(m0, launch_chain_merkle_tree_batch(chain_hash(c), hashes0, c->np2, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
     else HIPCHK(m0, launch_merkle_tree_from_batch(hashes0, c->np2, levels_done, n_batch, sl->hashes_stride, st, sl->d_roots_alias));
     launches[2]++;
   }

@@ -1,7 +1,7 @@
 // lcpc_amd/csrc/batch_kernels.hip -- gfx950 kernels of the batched commit (batch.cpp, include/lcpc_hip_batch.h): the BLAKE3 batch forms
 // of leaf_chunk_kernel, leaf_tree_kernel, leaf_finish_kernel and merkle_subtree_kernel (kernels.hip), and the placement of strided /
 // ragged polynomials into the padded coeffs rows (every digest).  The batch forms of the SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b
-// leaf and subtree kernels sit beside their namesakes in sha3.hip, sha256.hip and blake2b.hip, whose step functions they share.
+// leaf and subtree kernels are chain_dev.h's.
 // Launchers: kernels.h.
 #include "kernels.h"
 #include "field_dev.h"

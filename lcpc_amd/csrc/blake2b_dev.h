@@ -86,4 +86,43 @@ __device__ __forceinline__ void init(uint64_t h[8]) {
 }
 
 }  // namespace b2b
+
+// the chain traits (chain_dev.h): Output<Blake2b>::default() is 64 zero bytes, so the prefix is 8 words; every message word is one
+// BLAKE2b message word, 16 to a block.  A message that fills its last block exactly gets no extra block: the final compression is the
+// full last block with t = the message length and f0 = ~0.  The byte counter of a block that is not the last is 128 (blk + 1), so the
+// chaining value is all a later launch needs.  Digests are 64 bytes = 16 u32 words.
+struct Blake2bChain {
+  static constexpr int PREFIX = 8, BLOCK = 16, DIGEST_WORDS = 16, STATE_WORDS = 16, N_ELEMS = 8;
+  using Elem = uint64_t;
+  using Word = uint64_t;       // the state pointer must be 8-byte aligned
+  struct Msg { uint64_t w[16]; };
+  static constexpr uint64_t n_blocks(uint64_t n_words) { return (n_words + 15) / 16; }   // no padding block
+  // no occupancy bound on the batch leaf kernel: held to the one-shot twin's 5 / 4 waves per SIMD the register allocator spills 36 .. 116
+  // bytes per lane; left alone it takes 116 .. 136 VGPRs -- one wave per SIMD fewer -- and no scratch
+  static constexpr int batch_waves(int, bool) { return 0; }
+  static __device__ __forceinline__ Word word(Elem e) { return e; }
+  static __device__ __forceinline__ Elem elem(Word w) { return w; }
+  static __device__ __forceinline__ void init(Elem h[8]) { b2b::init(h); }
+  static __device__ __forceinline__ void absorb(Elem*, Msg& m, int p, uint32_t lo, uint32_t hi) { m.w[p] = b2b::pack(lo, hi); }
+  static __device__ __forceinline__ void finish_block(Elem h[8], Msg& m, uint64_t blk, uint64_t n_words, uint64_t n_blocks) {
+    const bool last = blk + 1 == n_blocks;
+    b2b::compress(h, m.w, last ? 8 * n_words : 128 * (blk + 1), last);
+  }
+  static __device__ __forceinline__ void store_digest(uint32_t* o, const Elem h[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; i += 2)
+      *reinterpret_cast<uint4*>(o + 2 * i) = make_uint4(b2b::lo32(h[i]), b2b::hi32(h[i]), b2b::lo32(h[i + 1]), b2b::hi32(h[i + 1]));
+  }
+  // parent = BLAKE2b(left || right): 16 words, one compression with t = 128 and the last-block flag
+  static __device__ __forceinline__ void node(uint32_t o[16], const uint32_t* l, const uint32_t* r) {
+    uint64_t m[16], h[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { m[i] = b2b::pack(l[2 * i], l[2 * i + 1]); m[8 + i] = b2b::pack(r[2 * i], r[2 * i + 1]); }
+    b2b::init(h);
+    b2b::compress(h, m, 128, true);
+#pragma unroll
+    for (int i = 0; i < 8; i++) { o[2 * i] = b2b::lo32(h[i]); o[2 * i + 1] = b2b::hi32(h[i]); }
+  }
+};
+
 }  // namespace lcpc

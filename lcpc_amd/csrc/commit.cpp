@@ -124,10 +124,7 @@ int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done) {
       }
       if (!m->h_root) (void)hipGetLastError();   // the failed call's error must not surface at the next launch check
     }
-    if (is_sha3(c)) HIPCHK(m, launch_sha3_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
-    else if (is_blake2b(c)) HIPCHK(m, launch_blake2b_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
-    else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));
-    else if (is_sha256(c)) HIPCHK(m, launch_sha256_merkle_tree(m->d_hashes, c->np2, st, m->d_root_alias));
+    if (!is_blake3(c)) HIPCHK(m, launch_chain_merkle_tree(chain_hash(c), m->d_hashes, c->np2, st, m->d_root_alias));   // (levels_done == 0)
     else HIPCHK(m, launch_merkle_tree_from(m->d_hashes, c->np2, levels_done, st, m->d_root_alias));
     m->launches[2]++;
   }
@@ -147,23 +144,14 @@ static int fetch_root(lcpc_commit_t* m, hipStream_t st, uint8_t* root) {
 }
 
 // SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b on the host-memory path: a column's chain is resumed behind every row batch
-// (kernels.h launch_*_leaves_range), its chaining value kept in d_chain between the launches
-struct ChainShape { uint32_t prefix_words, block_words, state_words; uint64_t n_blocks; };   // 64-bit words; state in 32-bit words
-static ChainShape chain_shape(const lcpc_ctx* c, uint64_t n_rows) {
-  if (is_blake2b(c)) return {8, 16, BLAKE2B_STATE_WORDS, blake2b_leaf_blocks(c->NL, n_rows)};
-  if (is_sha256(c)) return {4, 8, SHA256_STATE_WORDS, sha256_leaf_blocks(c->NL, n_rows)};
-  return {4, 17, SHA3_STATE_WORDS, sha3_leaf_blocks(c->NL, n_rows)};
-}
+// (kernels.h launch_chain_leaves_range), its chaining value kept in d_chain between the launches
 // blocks [b0, b1) of every column's leaf message, all of whose rows are in d_comm
 static int hash_block_range(lcpc_commit_t* m, uint64_t b0, uint64_t b1, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
   if (b0 == b1) return 0;
   LeafArgs la = leaf_args(m);
   la.out = m->d_hashes;
-  if (is_sha3(c)) HIPCHK(m, launch_sha3_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
-  else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
-  else if (is_sha256(c)) HIPCHK(m, launch_sha256_leaves_range(c->NL, la, b0, b1, m->d_chain, st));
-  else HIPCHK(m, launch_blake2b_leaves_range(c->NL, la, b0, b1, reinterpret_cast<uint64_t*>(m->d_chain), st));
+  HIPCHK(m, launch_chain_leaves_range(chain_hash(c), c->NL, la, b0, b1, m->d_chain, st));
   m->launches[1]++;
   return 0;
 }
@@ -184,13 +172,9 @@ int merkleize_device(lcpc_commit_t* m, hipStream_t st) {
   const lcpc_ctx* c = m->enc;
   LeafArgs la = leaf_args(m);
   if (!is_blake3(c)) {
-    // SHA3-256 / BLAKE2b / Keccak-256 / SHA-256: one serial chain per column over the whole leaf message (sha3.hip, blake2b.hip,
-    // sha256.hip), then the tree
+    // SHA3-256 / BLAKE2b / Keccak-256 / SHA-256: one serial chain per column over the whole leaf message (chain_dev.h), then the tree
     la.out = m->d_hashes;
-    if (is_sha3(c)) HIPCHK(m, launch_sha3_leaves(c->NL, la, st));
-    else if (is_keccak256(c)) HIPCHK(m, launch_keccak256_leaves(c->NL, la, st));
-    else if (is_sha256(c)) HIPCHK(m, launch_sha256_leaves(c->NL, la, st));
-    else HIPCHK(m, launch_blake2b_leaves(c->NL, la, st));
+    HIPCHK(m, launch_chain_leaves(chain_hash(c), c->NL, la, st));
     m->launches[1]++;
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[2], st));
     return merkle_top(m, st);
@@ -457,8 +441,7 @@ int open_columns_device(lcpc_commit_t* m, const uint64_t* d_cols, uint32_t n, ui
       HIPCHK(m, launch_gather_columns(c->NL, m->d_comm, m->n_rows_local, c->n_cols, 1, d_cols, n, d_vals, c->comm_canon ? c->d_r2 : nullptr, st));
   }
   if (d_paths && c->path_len) {
-    if (is_blake2b(c)) HIPCHK(m, launch_blake2b_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, st));
-    else HIPCHK(m, launch_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, st));
+    HIPCHK(m, launch_gather_paths(m->d_hashes, c->np2, c->path_len, d_cols, n, d_paths, digest_words(c), st));
   }
   return 0;
 }
@@ -715,7 +698,7 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   // every digest but BLAKE3: a column's hash is one serial chain over all rows.  It is resumed behind every batch for the blocks
   // that batch completed, the chaining values waiting in d_chain; the last batch's launch ends the chain and writes the digests
   const bool chained = !is_blake3(c);
-  const ChainShape cs = chained ? chain_shape(c, n_rows) : ChainShape{};
+  const ChainShape cs = chained ? chain_shape(chain_hash(c), c->NL, n_rows) : ChainShape{};
   uint64_t blocks_hashed = 0;
   if (chained && (rc = ensure_dev(&m->err, &m->d_chain, &m->cap_chain, (uint64_t)cs.state_words * 4 * c->n_cols))) return rc;
   for (int b = 0; b < NB; b++) {

@@ -348,7 +348,7 @@ struct lcpc_commit_s {
   std::shared_ptr<lcpc::BatchSlab> slab;   // member of a batched commit: d_comm (or ws.d_t: BatchSlab) / d_coeffs / d_hashes are views into it,
   uint32_t slab_index = 0;                 // not allocations (leave_slab, commit.cpp)
   uint32_t* d_chain = nullptr;     // host-memory commit under SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: every column's chaining value between
-  uint64_t cap_chain = 0;          // the row batches (kernels.h launch_*_leaves_range), word-major; capacity in bytes; kept across refills
+  uint64_t cap_chain = 0;          // the row batches (kernels.h launch_chain_leaves_range), word-major; capacity in bytes; kept across refills
   lcpc::EncodeWs ws;
   bool comm_t = false;             // Brakedown commit with >= sdig_t_min_rows() local rows: the commitment matrix lives in ws.d_t (position-major,
                                    // element (row, col) at (col * n_rows_local + row)); hash / open read it there, d_comm is only
@@ -452,6 +452,10 @@ inline bool is_sha256(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA25
 // BLAKE3 is the only digest whose leaf hash splits into chunks (row batches, row shards); SHA3-256, BLAKE2b, Keccak-256 and SHA-256
 // are one serial chain
 inline bool is_blake3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE3; }
+// the serial-chain digest of an encoder that is not BLAKE3's (kernels.h launch_chain_*)
+inline ChainHash chain_hash(const lcpc_ctx* c) {
+  return is_sha3(c) ? ChainHash::Sha3_256 : is_keccak256(c) ? ChainHash::Keccak256 : is_sha256(c) ? ChainHash::Sha256 : ChainHash::Blake2b;
+}
 // bytes of one Output<D>: a hashes slot, a root, a path entry (32; BLAKE2b 64)
 inline uint32_t digest_len(const lcpc_ctx* c) { return is_blake2b(c) ? 64u : 32u; }
 inline uint32_t digest_words(const lcpc_ctx* c) { return digest_len(c) / 4; }

@@ -82,4 +82,53 @@ __device__ __forceinline__ void keccak_f(Lane a[25]) {
 }
 
 }  // namespace kc
+
+// the chain traits (chain_dev.h) of the two sponges: rate 17 lanes, every message word one lane, 32-byte output.  DOM = KC_DOM_SHA3 /
+// KC_DOM_KECCAK
+template <uint32_t DOM> struct KeccakChain {
+  static constexpr int PREFIX = 4, BLOCK = 17, DIGEST_WORDS = 8, STATE_WORDS = 50, N_ELEMS = 25;
+  using Elem = kc::Lane;
+  using Word = uint2;          // one lane: the state pointer must be 8-byte aligned
+  struct Msg {};               // a sponge absorbs into its state
+  static constexpr uint64_t n_blocks(uint64_t n_words) { return n_words / 17 + 1; }   // the padding always fits: a message of 17 k words takes a block of its own
+  static constexpr int batch_waves(int, bool) { return 0; }
+  static __device__ __forceinline__ Word word(Elem e) { return make_uint2(e.lo, e.hi); }
+  static __device__ __forceinline__ Elem elem(Word w) { return {w.x, w.y}; }
+  static __device__ __forceinline__ void init(Elem s[25]) {
+#pragma unroll
+    for (int i = 0; i < 25; i++) s[i] = {0u, 0u};
+  }
+  static __device__ __forceinline__ void absorb(Elem s[25], Msg&, int p, uint32_t lo, uint32_t hi) { s[p].lo ^= lo; s[p].hi ^= hi; }
+  static __device__ __forceinline__ void finish_block(Elem s[25], Msg&, uint64_t blk, uint64_t n_words, uint64_t) {
+    if (17 * blk + 17 > n_words) {
+      // the block that holds the end of the message: pad10*1 behind the domain bits (DOM ... 0x80); the message is whole words, so the
+      // DOM byte starts lane n_words - 17 blk.  The byte comes from a scalar register the compiler cannot see through, so that it does not
+      // turn `? 1 : 0` (Keccak-256) into a per-lane boolean and allocate the whole kernel differently from the SHA3-256 instantiation
+      const uint32_t q = (uint32_t)(n_words - 17 * blk);
+      uint32_t dom = DOM;
+      asm volatile("" : "+s"(dom));
+#pragma unroll
+      for (uint32_t p = 0; p < 17; p++) s[p].lo ^= (p == q) ? dom : 0u;
+      s[16].hi ^= 0x80000000u;
+    }
+    kc::keccak_f(s);
+  }
+  static __device__ __forceinline__ void store_digest(uint32_t* o, const Elem s[25]) {
+    *reinterpret_cast<uint4*>(o) = make_uint4(s[0].lo, s[0].hi, s[1].lo, s[1].hi);
+    *reinterpret_cast<uint4*>(o + 4) = make_uint4(s[2].lo, s[2].hi, s[3].lo, s[3].hi);
+  }
+  // parent = D(left || right): 8 words, one permutation
+  static __device__ __forceinline__ void node(uint32_t o[8], const uint32_t* l, const uint32_t* r) {
+    Elem s[25];
+    init(s);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { s[i] = {l[2 * i], l[2 * i + 1]}; s[4 + i] = {r[2 * i], r[2 * i + 1]}; }
+    s[8].lo = DOM;
+    s[16].hi = 0x80000000u;
+    kc::keccak_f(s);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { o[2 * i] = s[i].lo; o[2 * i + 1] = s[i].hi; }
+  }
+};
+
 }  // namespace lcpc

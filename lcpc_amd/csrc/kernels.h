@@ -137,69 +137,46 @@ hipError_t launch_merkle_tree_from_batch(uint32_t* hashes, uint64_t np2, uint32_
 hipError_t launch_batch_place(const uint64_t* src, uint64_t src_stride, uint64_t n_valid, uint64_t* dst, uint64_t dst_stride, uint32_t n_batch,
                               hipStream_t st);
 
-// ---- batched column hash and tree of the serial-chain digests (sha3.hip, sha256.hip, blake2b.hip): the batch forms of the
-// launch_*_leaves / launch_*_merkle_tree launchers below, n_batch <= 65535 members with the member index a grid dimension.  `a` and
-// `hashes` describe member 0; member i's comm, a.out and hashes start i * (the given stride, in 32-bit words) behind it.  Same digests
-// as the single launchers, bit for bit; alignment and stride rules as for the BLAKE3 batch launchers above.  Empty work (n_batch == 0,
-// no columns) is hipSuccess; nl == 8 with a.canon_in == 0 is hipErrorInvalidValue (a Ligero comm over Ft255 is always canonical, so
-// that kernel is not instantiated).
-hipError_t launch_sha3_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
-hipError_t launch_keccak256_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
-hipError_t launch_sha256_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
-hipError_t launch_blake2b_leaves_batch(int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride, hipStream_t st);
-// root_out (may be null): [n_batch][8] words ([n_batch][16] for BLAKE2b), member i's root written by the launch that produces it
-hipError_t launch_sha3_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st, uint32_t* root_out);
-hipError_t launch_keccak256_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
-                                              uint32_t* root_out);
-hipError_t launch_sha256_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
-                                           uint32_t* root_out);
-hipError_t launch_blake2b_merkle_tree_batch(uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
-                                            uint32_t* root_out);
+// ---- the serial-chain digests SHA3-256, Keccak-256, SHA-256 and BLAKE2b (chain.hip; kernels: chain_dev.h over the traits of keccak_dev.h,
+// sha256_dev.h, blake2b_dev.h; instantiated in sha3.hip, sha256.hip, blake2b.hip): the same leaves and tree for an encoder built with
+// LCPC_HASH_SHA3_256 / _KECCAK256 / _SHA256 / _BLAKE2B.  Keccak-256 is SHA3-256 with the padding's first byte 0x01 instead of 0x06.
+enum class ChainHash { Sha3_256, Keccak256, Sha256, Blake2b };
+// the leaf message of n_rows_total rows: zero prefix and block in 64-bit words, a column's chaining value and a digest (a hashes slot, a
+// root, a path entry) in 32-bit words, the blocks of the whole message, padding blocks included.  nl = 2 / 4 / 6 / 8
+struct ChainShape { uint32_t prefix_words, block_words, state_words, digest_words; uint64_t n_blocks; };
+constexpr ChainShape chain_shape(ChainHash h, int nl, uint64_t n_rows_total) {
+  const uint64_t L = (uint64_t)(nl / 2);
+  switch (h) {
+    case ChainHash::Sha256: { const uint64_t w = 4 + L * n_rows_total; return {4, 8, 8, 8, w / 8 + 1 + ((w & 7) == 7 ? 1 : 0)}; }
+    case ChainHash::Blake2b: return {8, 16, 16, 16, (8 + L * n_rows_total + 15) / 16};
+    default: return {4, 17, 50, 8, (4 + L * n_rows_total) / 17 + 1};          // the two sponges
+  }
+}
+// leaf digests [n_cols][digest_words] of the whole column (a.n_chunks_* unused: a chain is not split); a.out = LcCommit.hashes
+hipError_t launch_chain_leaves(ChainHash h, int nl, const LeafArgs& a, hipStream_t st);
+// the whole tree above the np2 leaf digests; root_out (may be null): digest_words more words the root is written to by the launch that
+// produces it (host-mapped memory)
+hipError_t launch_chain_merkle_tree(ChainHash h, uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
 
-// ---- SHA3-256 digest (sha3.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA3_256 ----
-// leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a sponge is not split); a.out = LcCommit.hashes
-hipError_t launch_sha3_leaves(int nl, const LeafArgs& a, hipStream_t st);
-// the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
-hipError_t launch_sha3_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
-// Keccak-256 (LCPC_HASH_KECCAK256): the same kernels with the padding's first byte 0x01 instead of 0x06
-hipError_t launch_keccak256_leaves(int nl, const LeafArgs& a, hipStream_t st);
-hipError_t launch_keccak256_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
+// The batch forms: n_batch <= 65535 members with the member index a grid dimension.  `a` and `hashes` describe member 0; member i's comm,
+// a.out and hashes start i * (the given stride, in 32-bit words) behind it.  Same digests as the single launchers, bit for bit; alignment
+// and stride rules as for the BLAKE3 batch launchers above.  Empty work (n_batch == 0, no columns) is hipSuccess; nl == 8 with
+// a.canon_in == 0 is hipErrorInvalidValue (a Ligero comm over Ft255 is always canonical, so that kernel is not instantiated).
+hipError_t launch_chain_leaves_batch(ChainHash h, int nl, const LeafArgs& a, uint32_t n_batch, uint64_t comm_stride, uint64_t out_stride,
+                                     hipStream_t st);
+// root_out (may be null): [n_batch][digest_words] words, member i's root written by the launch that produces it
+hipError_t launch_chain_merkle_tree_batch(ChainHash h, uint32_t* hashes, uint64_t np2, uint32_t n_batch, uint64_t hashes_stride, hipStream_t st,
+                                          uint32_t* root_out);
 
-// ---- SHA-256 digest (sha256.hip): the same leaves and tree for an encoder built with LCPC_HASH_SHA256 ----
-// leaf digests [n_cols][8] of the whole column (a.n_chunks_* unused: a Merkle-Damgard chain is not split); a.out = LcCommit.hashes
-hipError_t launch_sha256_leaves(int nl, const LeafArgs& a, hipStream_t st);
-// the whole tree above the np2 leaf digests; root_out as for launch_merkle_tree
-hipError_t launch_sha256_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
-
-// ---- BLAKE2b-512 digest (blake2b.hip): the same leaves and tree with 64-byte digests (16 words per hashes slot) ----
-// leaf digests [n_cols][16] of the whole column (a.n_chunks_* unused: the chain is not split); a.out = LcCommit.hashes
-hipError_t launch_blake2b_leaves(int nl, const LeafArgs& a, hipStream_t st);
-// the whole tree above the np2 leaf digests; root_out (may be null): 16 more words the root is written to
-hipError_t launch_blake2b_merkle_tree(uint32_t* hashes, uint64_t np2, hipStream_t st, uint32_t* root_out);
-// launch_gather_paths for 64-byte digests: paths [n][path_len][16]
-hipError_t launch_blake2b_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
-                                       uint32_t* paths, hipStream_t st);
-
-// ---- resumable column hash of the three serial-chain families (sha3.hip, sha256.hip, blake2b.hip) ----
-// The same leaf message hashed a block range at a time: a launch runs blocks [blk_begin, blk_end) of every column's chain.  It
-// starts from the IV / the zero sponge when blk_begin == 0 and from `state` otherwise; it leaves the chaining value in `state`
-// when blk_end is not the message's last block and the digest in a.out (the one-shot layout) when it is.  An empty range launches
+// The resumable column hash.  The same leaf message hashed a block range at a time: a launch runs blocks [blk_begin, blk_end) of every
+// column's chain.  It starts from the IV / the zero sponge when blk_begin == 0 and from `state` otherwise; it leaves the chaining value in
+// `state` when blk_end is not the message's last block and the digest in a.out (the one-shot layout) when it is.  An empty range launches
 // nothing; a range past the last block is hipErrorInvalidValue.  A launch loads only the rows its blocks hold bytes of, so comm
 // needs nothing behind them yet (the host-memory commit hashes behind each row batch: commit.cpp).
-// state: the chaining value alone, word-major so that consecutive columns are consecutive addresses -- word i of column c at
-// state[i * n_cols + c]: 25 x u64 lanes (sponges), 8 x u32 (SHA-256), 8 x u64 (BLAKE2b; its byte counter is 128 (blk + 1)).
-// blocks of the whole leaf message of n_rows_total rows (padding blocks included); nl = 2 / 4 / 6 / 8
-inline uint64_t sha3_leaf_blocks(int nl, uint64_t n_rows_total) { return (4 + (uint64_t)(nl / 2) * n_rows_total) / 17 + 1; }
-inline uint64_t sha256_leaf_blocks(int nl, uint64_t n_rows_total) {
-  const uint64_t w = 4 + (uint64_t)(nl / 2) * n_rows_total;
-  return w / 8 + 1 + ((w & 7) == 7 ? 1 : 0);
-}
-inline uint64_t blake2b_leaf_blocks(int nl, uint64_t n_rows_total) { return (8 + (uint64_t)(nl / 2) * n_rows_total + 15) / 16; }
-constexpr uint32_t SHA3_STATE_WORDS = 50, SHA256_STATE_WORDS = 8, BLAKE2B_STATE_WORDS = 16;     // u32 words per column
-hipError_t launch_sha3_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
-hipError_t launch_keccak256_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
-hipError_t launch_sha256_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint32_t* state, hipStream_t st);
-hipError_t launch_blake2b_leaves_range(int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint64_t* state, hipStream_t st);
+// state: the chaining value alone, state_words * n_cols words, 8-byte aligned, word-major so that consecutive columns are consecutive
+// addresses -- word i of column c at state[i * n_cols + c]: 25 x u64 lanes (sponges), 8 x u32 (SHA-256), 8 x u64 (BLAKE2b; its byte
+// counter is 128 (blk + 1)).
+hipError_t launch_chain_leaves_range(ChainHash h, int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint32_t* state, hipStream_t st);
 
 struct CollapseArgs {
   const uint32_t* coeffs;      // local rows x n_per_row
@@ -230,8 +207,9 @@ hipError_t launch_to_canon(int nl, const uint32_t* in, uint64_t n, uint32_t* out
 // sharded open_column: [rank][k][rows of rank] (blocks of block_words) -> [k][all rows]; rb: G + 1 row boundaries on the device
 hipError_t launch_assemble_columns(int nl, const uint32_t* recv, uint64_t block_words, const uint64_t* rb, uint32_t G, uint32_t n,
                                    uint64_t n_rows, uint32_t* out, hipStream_t st);
+// digest_words = 8 or 16 (ChainShape.digest_words; BLAKE3: 8): paths [n][path_len][digest_words]
 hipError_t launch_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
-                               uint32_t* paths, hipStream_t st);
+                               uint32_t* paths, uint32_t digest_words, hipStream_t st);
 
 // Brakedown: y[row][out_off + o] = sum_k vals[k] * x[row][in_off + colidx[k]], k in [rowptr[o], rowptr[o+1])
 struct SpmvArgs {

@@ -962,6 +962,8 @@ hipError_t launch_gather_columns(int nl, const u32* comm, u64 n_rows, u64 row_st
   }
   return hipSuccess;
 }
+// DW = words per digest, 8 or 16: 16-byte moves
+template <int DW>
 __global__ void __launch_bounds__(256) gather_paths_kernel(const u32* hashes, u64 np2, u32 path_len, const u64* cols, u32 n,
                                                           u32* paths) {
   const u64 id = (u64)blockIdx.x * 256 + threadIdx.x;
@@ -970,9 +972,10 @@ __global__ void __launch_bounds__(256) gather_paths_kernel(const u32* hashes, u6
   u64 base = 0, w = np2;
   for (u32 i = 0; i < lvl; i++) { base += w; w >>= 1; }
   const u64 node = (cols[k] >> lvl) ^ 1;
-  u32 d[8];
-  ld8(d, hashes + (base + node) * 8);
-  st8(paths + id * 8, d);
+  const uint4* s = reinterpret_cast<const uint4*>(hashes + (base + node) * DW);
+  uint4* d = reinterpret_cast<uint4*>(paths + id * DW);
+#pragma unroll
+  for (int i = 0; i < DW / 4; i++) d[i] = s[i];
 }
 // sharded open_column: rank g's block of the all-gather holds its rows of the n opened columns as [k][rows of g]; the proof
 // wants [k][all rows].  rb[0..G]: first row of every rank (rb[G] = n_rows), device-resident.  One element per thread.
@@ -994,11 +997,14 @@ hipError_t launch_assemble_columns(int nl, const u32* recv, u64 block_words, con
   hipLaunchKernelGGL(assemble_columns_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, recv, block_words, rb, G, n, n_rows, (u32)nl, out);
   return hipGetLastError();
 }
-hipError_t launch_gather_paths(const u32* hashes, u64 np2, u32 path_len, const u64* cols, u32 n, u32* paths, hipStream_t st) {
+hipError_t launch_gather_paths(const u32* hashes, u64 np2, u32 path_len, const u64* cols, u32 n, u32* paths, u32 digest_words,
+                               hipStream_t st) {
+  if (digest_words != 8 && digest_words != 16) return hipErrorInvalidValue;
   const u64 tot = (u64)n * path_len;
   if (tot == 0) return hipSuccess;
-  hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, hashes, np2, path_len, cols, n,
-                     paths);
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (digest_words == 8) hipLaunchKernelGGL(gather_paths_kernel<8>, grid, dim3(256), 0, st, hashes, np2, path_len, cols, n, paths);
+  else hipLaunchKernelGGL(gather_paths_kernel<16>, grid, dim3(256), 0, st, hashes, np2, path_len, cols, n, paths);
   return hipGetLastError();
 }
 

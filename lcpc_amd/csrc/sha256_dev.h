@@ -131,4 +131,57 @@ __device__ __forceinline__ void compress_pad64(uint32_t h[8]) {
 }
 
 }  // namespace s256
+
+// the chain traits (chain_dev.h): a 64-byte block is 8 message words; word p goes into words 2 p, 2 p + 1 of the block, each half
+// byte-swapped.  Padding: the byte 0x80, zeros, the bit length as a big-endian 64-bit word at the end of a block.  With q = n_words mod 8
+// words in the block that holds the end of the message, 0x80 opens word q and the length is word 7 of the same block -- except q = 7,
+// where the length takes one more block; q = 0 is a block of padding alone.
+struct Sha256Chain {
+  static constexpr int PREFIX = 4, BLOCK = 8, DIGEST_WORDS = 8, STATE_WORDS = 8, N_ELEMS = 8;
+  using Elem = uint32_t;       // the working h[], not byte-swapped
+  using Word = uint32_t;
+  struct Msg { uint32_t w[16]; };
+  static constexpr uint64_t n_blocks(uint64_t n_words) { return n_words / 8 + 1 + ((n_words & 7) == 7 ? 1 : 0); }   // 0x80 and the length need two words
+  // the batch leaf kernel's second launch bound is the one-shot twin's occupancy in waves per SIMD: without it the register allocator
+  // spreads the same instruction stream over twice the VGPRs
+  static constexpr int batch_waves(int nl, bool canon) { return (nl == 6 && !canon) ? 7 : 8; }
+  static __device__ __forceinline__ Word word(Elem e) { return e; }
+  static __device__ __forceinline__ Elem elem(Word w) { return w; }
+  static __device__ __forceinline__ void init(Elem h[8]) { s256::init(h); }
+  static __device__ __forceinline__ void absorb(Elem*, Msg& m, int p, uint32_t lo, uint32_t hi) {
+    m.w[2 * p] = s256::bswap(lo);
+    m.w[2 * p + 1] = s256::bswap(hi);
+  }
+  static __device__ __forceinline__ void finish_block(Elem h[8], Msg& m, uint64_t blk, uint64_t n_words, uint64_t n_blocks) {
+    if (blk == n_words / 8) {
+      // the block that holds the end of the message: the message is whole words, so the 0x80 byte is the first byte of word
+      // n_words - 8 blk, i.e. the top byte of its first big-endian half (that word is zero so far)
+      const uint32_t q = (uint32_t)(n_words - 8 * blk);
+#pragma unroll
+      for (uint32_t p = 0; p < 8; p++) m.w[2 * p] |= (p == q) ? 0x80000000u : 0u;
+    }
+    if (blk + 1 == n_blocks) {
+      const uint64_t bits = 64 * n_words;
+      m.w[14] = (uint32_t)(bits >> 32);
+      m.w[15] = (uint32_t)bits;
+    }
+    s256::compress(h, m.w);
+  }
+  static __device__ __forceinline__ void store_digest(uint32_t* o, const Elem h[8]) {
+    *reinterpret_cast<uint4*>(o) = make_uint4(s256::bswap(h[0]), s256::bswap(h[1]), s256::bswap(h[2]), s256::bswap(h[3]));
+    *reinterpret_cast<uint4*>(o + 4) = make_uint4(s256::bswap(h[4]), s256::bswap(h[5]), s256::bswap(h[6]), s256::bswap(h[7]));
+  }
+  // parent = SHA-256(left || right): 64 message bytes are one block, the padding a second one that is the same for every node
+  static __device__ __forceinline__ void node(uint32_t o[8], const uint32_t* l, const uint32_t* r) {
+    uint32_t m[16], h[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { m[i] = s256::bswap(l[i]); m[8 + i] = s256::bswap(r[i]); }
+    s256::init(h);
+    s256::compress(h, m);
+    s256::compress_pad64(h);
+#pragma unroll
+    for (int i = 0; i < 8; i++) o[i] = s256::bswap(h[i]);
+  }
+};
+
 }  // namespace lcpc

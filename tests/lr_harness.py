@@ -1,8 +1,8 @@
-"""ctypes side of tests/native/lr_harness.cpp (lcpc_amd/lib/liblcpc_lr_harness.so, built by lcpc_amd/csrc/Makefile): the resumable column
-hash of SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b (launch_*_leaves_range of lcpc_amd/csrc/kernels.h) on buffers a test builds.  Elements
-cross as (.., L) uint64 arrays of limbs, the chaining state and the digests as flat uint32 arrays that are modified in place.  Every call
-returns after the device has finished and raises on any hipError_t; BadArgs means the harness refused the call before touching the
-device."""
+"""ctypes side of tests/native/lr_harness.cpp (lcpc_amd/lib/liblcpc_lr_harness.so, built by lcpc_amd/csrc/Makefile): the column hash of
+SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b -- resumable, one-shot and batched -- and their Merkle tree (launch_chain_* of
+lcpc_amd/csrc/kernels.h) on buffers a test builds.  Elements cross as (.., L) uint64 arrays of limbs, the chaining state, the digests
+and the hashes as flat uint32 arrays that are modified in place.  Every call returns after the device has finished and raises on any
+hipError_t; BadArgs means the harness refused the call before touching the device."""
 import ctypes as C
 import os
 
@@ -26,11 +26,13 @@ class HipError(RuntimeError):
         self.code = code
 
 
-_vp, _u64, _i32 = C.c_void_p, C.c_uint64, C.c_int
+_vp, _u64, _i32, _u32 = C.c_void_p, C.c_uint64, C.c_int, C.c_uint32
 SYMBOLS = {
     "lrh_device_count": (_i32, []),
     "lrh_leaf_blocks": (_u64, [_i32, _i32, _u64]),
     "lrh_leaf_range": (_i32, [_i32, _i32, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _u64, _i32, _vp, _u64, _u64, _vp, _u64, _u64]),
+    "lrh_leaves": (_i32, [_i32, _i32, _vp, _u64, _u64, _u64, _u64, _u64, _i32, _u32, _u64, _u64, _vp, _u64, _u64]),
+    "lrh_merkle_tree": (_i32, [_i32, _u64, _u32, _u64, _vp, _u64, _u64, _vp, _u64, _u64]),
 }
 _lib = None
 
@@ -71,3 +73,29 @@ def leaf_range(digest, fid, comm, row_stride, col_stride, n_cols, n_rows_total, 
         raise BadArgs("lrh_leaf_range")
     if rc:
         raise HipError("lrh_leaf_range", rc)
+
+
+def _check(what, rc):
+    if rc == -1:
+        raise BadArgs(what)
+    if rc:
+        raise HipError(what, rc)
+
+
+def leaves(digest, fid, comm, row_stride, col_stride, n_cols, n_rows_total, canon_in, out, out_off, n_batch=0, comm_stride=0, out_stride=0):
+    """the whole column hash in one launch: the one-shot launcher (n_batch == 0) or the batch launcher over n_batch members.  comm: flat
+    uint32 words of all members, member i starting comm_stride * i words in; its digests start at word out_off + i * out_stride of out"""
+    assert comm.dtype == np.uint32 and comm.flags.c_contiguous and comm.ndim == 1
+    assert out.dtype == np.uint32 and out.flags.c_contiguous and out.ndim == 1
+    _check("lrh_leaves", lib().lrh_leaves(FAMILY[digest], NL[fid], comm.ctypes.data_as(_vp), comm.size, row_stride, col_stride, n_cols, n_rows_total,
+                                          int(canon_in), n_batch, comm_stride, out_stride, out.ctypes.data_as(_vp), out.size, out_off))
+
+
+def merkle_tree(digest, np2, hashes, hashes_off, root=None, root_off=0, n_batch=0, hashes_stride=0):
+    """the tree above np2 leaf digests: the one-shot launcher (n_batch == 0) or the batch launcher.  hashes: flat uint32, member i's
+    [2 np2 - 1][digest words] starting at word hashes_off + i * hashes_stride; root (None: a null root_out): member i's root at word
+    root_off + i * digest words"""
+    assert hashes.dtype == np.uint32 and hashes.flags.c_contiguous and hashes.ndim == 1
+    assert root is None or (root.dtype == np.uint32 and root.flags.c_contiguous and root.ndim == 1)
+    _check("lrh_merkle_tree", lib().lrh_merkle_tree(FAMILY[digest], np2, n_batch, hashes_stride, hashes.ctypes.data_as(_vp), hashes.size, hashes_off,
+                                                    None if root is None else root.ctypes.data_as(_vp), 0 if root is None else root.size, root_off))

@@ -200,7 +200,7 @@ K3H_EXPORT int k3h_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t p
   K3H_TRY(d_hashes.put(hashes, (size_t)(2 * np2 - 1) * 32));
   K3H_TRY(d_cols.put(cols, (size_t)n * 8));
   K3H_TRY(d_paths.put(paths, p_bytes));
-  K3H_TRY(lcpc::launch_gather_paths(d_hashes.p, np2, path_len, reinterpret_cast<const uint64_t*>(d_cols.p), n, d_paths.p, nullptr));
+  K3H_TRY(lcpc::launch_gather_paths(d_hashes.p, np2, path_len, reinterpret_cast<const uint64_t*>(d_cols.p), n, d_paths.p, 8, nullptr));
   K3H_TRY(hipDeviceSynchronize());
   return (int)d_paths.get(paths, p_bytes);
 }
