@@ -132,11 +132,18 @@ template <class FT> LCPC_DEV void normalize(LN<FT::N>& a) {
   }
 }
 // ---- normalise + clamp in ONE carry pass -----------------------------------------------------------------------------------------
-// a: limbs 0..N-2 in [0, 2^31 - 4] (the sum of four normalised values), top limb signed, |value| < 16p.  With
-// B = 2^(W(N-1)), V = t B + low, q = floor((t - QBIAS) / (PTOP + 1)) estimated from the UN-normalised top limb (the
-// carries still in the lower limbs, c in [0, 3], are not in it yet):
-//   V - q p = q (B - plow) + (rem + QBIAS + c) B + low   >= (QBIAS - |q|) B >= 0   for |q| <= 17 + 1,
-//                                                         <  (PTOP + 1 + QBIAS + |q| + 1 + 3) B  <  p + 64 B.
+// a: |value| < 16p, the top limb signed, and limbs 0..N-2 of one of two classes (W = 29):
+//   (a) in [0, 2^31 - 4]: the sum of four normalised values.  The carries still in the lower limbs are c in [0, 3];
+//   (b) signed, in (-2^30, 2^30): differences and sums of up to two differences of normalised values, un-normalised (K1s, ntt_l9s.hip:
+//       the outputs of a butterfly as they leave it).  c in [-2, 2]: the lower limbs hold a value in (-2.01 B, 2.01 B).
+// With B = 2^(W(N-1)), V = t B + low, q = floor((t - QBIAS) / (PTOP + 1)) estimated from the UN-normalised top limb (c is not in it yet):
+//   V - q p = q (B - plow) + (rem + QBIAS + c) B + low'  (0 <= low' < B, 0 <= rem <= PTOP, 0 < B - plow <= B)
+//   (a)  >= (QBIAS - |q|) B >= 0,         <  (PTOP + 1 + QBIAS + |q| + 3) B        for |q| <= 17 + 1,
+//   (b)  >= (QBIAS - |q| - 2.01) B > 0,   <  (PTOP + 1 + QBIAS + |q| + 2.01) B     for |q| <= 18:   both inside [0, p + 64 B).
+// The carry pass is signed: d below stays inside an i32 for either class ((a): < 2^31 - 4 + 3; (b): the row's limbs lie in (-2^W, 0],
+// so d > -2^30 - 2^29 - 4), and leaves limbs 0..N-2 in [0, 2^W) and a top limb in [0, PTOP + 64]: a normalised value that to_packed takes.
+// The table index n / (PTOP + 1) lies in [0, 64): |t| < 16 (PTOP + 1) + 3.  tests/test_clamp_lazy_inputs.py runs this on integers at the
+// extremes of both classes.
 // The row -(q p) comes from a table in LDS (the kernel negates ctx.cpp's (i - QOFF) p table when it copies it).
 template <class FT> LCPC_DEV u32 clamp_q(u32 top) {
   constexpr u32 PTOP1 = FT::limb(FT::N - 1) + 1;

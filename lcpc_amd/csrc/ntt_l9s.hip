@@ -20,6 +20,9 @@
 //   * (round 6) a tile makes no LDS round trip it does not need: the four elements a thread loads are its first round's quad, which
 //     therefore runs from the registers with no barrier before it; the last pass's final round owns four consecutive elements and
 //     reduces and stores them itself;
+//   * the pure first pass's final round (I only) does the same for the packed intermediate: its quad is four elements of one column,
+//     clamped, packed and stored from the registers; and every round that stores from registers clamps each output once, straight
+//     from the butterfly's sums (ntt_ln_dev.h clamp_store; the bounds: field_ln.h clamp_apply);
 //   * (round 6) a wave holds priority 1 while it issues memory instructions and 0 inside the multiplier chains (field_dev.h mem_phase).
 // Exact modular arithmetic: any stage grouping gives the same fully-reduced bits as the reference's radix-2 loop.
 #include "kernels.h"
@@ -258,7 +261,8 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     //                      rounds 2 .. 4: < 1.001p + 3.6p = 4.6p; M2: y0 in (-9.03p, 7.04p), y1 in (-7.03p, 9.04p) (x0 + p2 in (-3.01p, 3.02p),
     //                      p1 + p3 in (-6.02p, 4.02p)), y2, y3 in (-4.71p, 6.72p) (x0 - p2 in (-2.01p, 4.02p), t in (-2p, 2.7p)): |y| < 9.04p,
     //                      inside the clamp's |q| <= 18 and mul_u's limb sums (p1 - p3: a difference of two normalised values)
-    //      The final round reduces and stores its four consecutive elements from the registers, as the DIF form's does.
+    //      The final round reduces and stores its four consecutive elements from the registers, as the DIF form's does: each is clamped
+    //      as it comes out of the butterfly, y0 included, by the argument given for x0 (nothing normalises in front of the clamp).
 #pragma unroll
     for (int r = 0; r < 5; r++) {
       const int hb = 9 - 2 * r;                              // quarter distance D = 2^(hb - 1) = 256, 64, 16, 4, 1
@@ -291,10 +295,10 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       }
       const LN<9> s02 = ln::add(x0, p2), d02 = ln::sub(x0, p2), s13 = ln::add(p1, p3);
       LN<9> y0 = ln::add(s02, s13), y1 = ln::sub(s02, s13);
-      ln::normalize<FT>(y0);
+      if (r < 4) ln::normalize<FT>(y0);
       const LN<9> t = ln::mul_u<FT>(ln::sub(p1, p3), a.wq_w);
       LN<9> y2 = ln::add(d02, t), y3 = ln::sub(d02, t);
-      if (r == 0 || r == 4) { ln::normalize<FT>(y1); ln::normalize<FT>(y2); ln::normalize<FT>(y3); }
+      if (r == 0) { ln::normalize<FT>(y1); ln::normalize<FT>(y2); ln::normalize<FT>(y3); }
       mem_phase(true);
       if (r < 4) {
         planes_put<FT>(lds, T, SWZ(e0), y0);
@@ -303,21 +307,14 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         planes_put<FT>(lds, T, SWZ(e0 + 3 * D), y3);
         __syncthreads();
       } else {
-        // D == 1: four consecutive elements of the row, normalised, |value| < 4.6p (M2: 9.04p): clamp, pack, the rare conditional subtract, store
+        // D == 1: four consecutive elements of the row, |value| < 4.6p (M2: 9.04p), NOT normalised: y0's limbs lie in [0, 2^31 - 4] (a
+        // clamped x0 plus three normalised products), those of y1, y2, y3 in (-2^30, 2^30) -- the two classes ln::clamp_apply takes as
+        // they are (the bound the x0 of rounds 1 .. 4 goes by, above).  Clamp, pack, the rare conditional subtract, store
         u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
-        LN<9> cc[4] = {y0, y1, y2, y3};
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          LN<9> x = cc[c];
-          ln::clamp_apply<FT>(x, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x.v[8])));      // [0, p + 2^239) < 2^256
-          u32 w[8];
-          ln::to_packed<FT>(w, x.v);
-          Fe<NL> v;
-#pragma unroll
-          for (int i = 0; i < 8; i++) v.v[i] = w[i];
-          if (__any((int)(x.v[8] >= FT::limb(8)))) v = fe_reduce_once<8>(w);
-          fe_store<NL>(dstq + (size_t)c * NL, v);
-        }
+        clamp_store<FT, true>(dstq, y0, nqp);
+        clamp_store<FT, true>(dstq + (size_t)1 * NL, y1, nqp);
+        clamp_store<FT, true>(dstq + (size_t)2 * NL, y2, nqp);
+        clamp_store<FT, true>(dstq + (size_t)3 * NL, y3, nqp);
       }
     }
     return;
@@ -341,8 +338,15 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       //      |value| < 2.7p (the uniform round before it: clamped sums and mul_u outputs; a lane-varying round: < 2.4p; loads and the
       //      radix-2 round's sums: < 2p), so |c0|, |c1| < 10.8p and |c2|, |c3| < 5.4p + 2.7p = 8.1p.  M2, S = 4, 5 (a lane-varying round
       //      straight before this one) and S = 3 (the radix-2 round's products): inputs < 3.01p, so |c0|, |c1| < 12.04p and |c2|, |c3| <
-      //      6.02p + 2.7p = 8.72p -- the clamp takes |value| < 16p, the successor clamps x0 and multiplies the rest by mul_u.  Stored normalised: the successor's
-      //      first round multiplies three of four by scalar operands (mul_u)
+      //      6.02p + 2.7p = 8.72p -- the clamp takes |value| < 16p, the successor clamps x0 and multiplies the rest by mul_u.
+      //      With the carries counted: c0, a sum of four normalised values, has limbs in [0, 2^31 - 4]; c1 = b0 - b1 (two sums of two) and
+      //      c2, c3 = (x0 - x2) +- t have limbs in (-2^30, 2^30); |value| < 12.04p for all four -- ln::clamp_apply's two input classes.
+      //      Packed intermediate (!MID): this round is the tile's last, and the quad is elements i = 4 j .. 4 j + 3 of column lp.  Each
+      //      output is clamped ONCE, straight from its sum, packed and stored from the registers (ntt_ln_dev.h clamp_store): no
+      //      normalise, no LDS round trip, no barrier, no store loop.  The lanes of consecutive lp store 2^LBT x 32 contiguous bytes,
+      //      the segments the store loop wrote.
+      //      Limb intermediate (MID): stored to LDS normalised, as before -- the successor's first round multiplies three of four by
+      //      scalar operands (mul_u) -- and the plane-store loop below takes the tile
       const bool fr = DIRECT && SH::U0 == 0 && r == 0;       // S == 2: the thread's own loads
       const LN<9> x0 = fr ? xin[0] : planes_get<FT>(lds, T, SWZ(e0)), x1 = fr ? xin[1] : planes_get<FT>(lds, T, SWZ(e0 + dq));
       const LN<9> x2 = fr ? xin[2] : planes_get<FT>(lds, T, SWZ(e0 + 2 * dq)), x3 = fr ? xin[3] : planes_get<FT>(lds, T, SWZ(e0 + 3 * dq));
@@ -352,6 +356,24 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       const LN<9> b2 = ln::sub(x0, x2);
       const LN<9> t = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);                                    // normalised, (-2p, 2.7p)
       LN<9> c2 = ln::add(b2, t), c3 = ln::sub(b2, t);
+      if constexpr (!MID && SH::NR4 >= 1) {                  // (S == 1 has no such round: its instantiation keeps a single exit)
+        if (RC < 0 && SH::U0 == 0 && canon) {
+          // S == 2: no round before this one, every lane still holds Montgomery form: all four outputs are converted here
+          ln::normalize<FT>(c0); ln::normalize<FT>(c1); ln::normalize<FT>(c2); ln::normalize<FT>(c3);
+          c0 = ln::mul<FT>(c0, k32); c1 = ln::mul<FT>(c1, k32); c2 = ln::mul<FT>(c2, k32); c3 = ln::mul<FT>(c3, k32);
+        }
+        // S == 2: the storing round is the first round and no barrier has run yet; this one makes the q*p table, copied into LDS at
+        // the kernel's top, visible to every wave before the first clamp reads it (the old route normalised c0 to stay off the table
+        // and met the barrier behind its puts: one barrier then, one now)
+        if constexpr (SH::U0 == 0 && SH::NR4 == 1) __syncthreads();
+        mem_phase(true);
+        u32* dstq = a.dst + row * a.dst_stride * NL;
+        clamp_store<FT, false>(dstq + (size_t)gindex(e0) * NL, c0, nqp);            // [0, p + 2^239) < 2^256: what the successor reads
+        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + dq) * NL, c1, nqp);
+        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + 2 * dq) * NL, c2, nqp);
+        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + 3 * dq) * NL, c3, nqp);
+        return;
+      }
       ln::normalize<FT>(c1); ln::normalize<FT>(c2); ln::normalize<FT>(c3);
       if (RC < 0 && SH::U0 == 0 && canon) {
         // S == 2: no round before this one, every lane still holds Montgomery form: all four outputs are converted here
@@ -438,33 +460,23 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);                                   // limbs [0, 2^30), |value| < 8p
     LN<9> c0 = ln::add(b0, b1);                                                               // limbs [0, 2^31), |value| < 16p
     if (last_two) {
-      // outputs go straight to the store path (normalised, |value| < 16p)
-      ln::normalize<FT>(c0);
+      // outputs go straight to the store path, as the sums leave them: c0 limbs [0, 2^31 - 4], c1, c2, c3 limbs (-2^30, 2^30) (b0 - b1: two
+      // sums of two normalised values; (x0 - x2) +- b3: a difference of two and a normalised product), |value| < 16p -- ln::clamp_apply's
+      // two input classes; its carry pass is the only one they get
       LN<9> c1 = ln::sub(b0, b1);
       const LN<9> b2 = ln::sub(x0, x2);
       // w^(n/4) is the one twiddle every lane shares: its multiply takes the shifted-multiples form (scalar operands)
       const LN<9> b3 = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);
       LN<9> c2 = ln::add(b2, b3);
       LN<9> c3 = ln::sub(b2, b3);
-      ln::normalize<FT>(c1); ln::normalize<FT>(c2); ln::normalize<FT>(c3);
       // dq == 1 here: the quad is four CONSECUTIVE elements of the row, 128 bytes -- reduced and stored from the registers (no LDS round
-      // trip, no barrier; -0.2 ... -0.8 % by shape).  -> [0, p): after the clamp, value >= p needs the top limb to reach floor(p / 2^232)
-      // -- about one element in 2^17; the conditional subtract runs only in the waves that hold such an element
+      // trip, no barrier; -0.2 ... -0.8 % by shape).  -> [0, p): ntt_ln_dev.h clamp_store
       mem_phase(true);
       u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
-      LN<9> cc[4] = {c0, c1, c2, c3};
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        LN<9> x = cc[c];                                                     // normalised, |value| < 16p
-        ln::clamp_apply<FT>(x, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x.v[8])));      // [0, p + 2^239) < 2^256
-        u32 w[8];
-        ln::to_packed<FT>(w, x.v);
-        Fe<NL> v;
-#pragma unroll
-        for (int i = 0; i < 8; i++) v.v[i] = w[i];
-        if (__any((int)(x.v[8] >= FT::limb(8)))) v = fe_reduce_once<8>(w);
-        fe_store<NL>(dstq + (size_t)c * NL, v);
-      }
+      clamp_store<FT, true>(dstq, c0, nqp);
+      clamp_store<FT, true>(dstq + (size_t)1 * NL, c1, nqp);
+      clamp_store<FT, true>(dstq + (size_t)2 * NL, c2, nqp);
+      clamp_store<FT, true>(dstq + (size_t)3 * NL, c3, nqp);
       return;
     } else {
       // clamp the pure sum at once: c0 leaves the registers before the multiplier chains start (holding it and its

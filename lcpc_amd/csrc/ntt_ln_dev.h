@@ -90,6 +90,26 @@ template <class FT, class C = u32> LCPC_DEV void planes_put(u32* base, C cnt, u3
   }
 }
 
+// ---- an element leaves its tile from the registers (K1s: the pure first pass's I-only round, both last passes' final rounds): clamped
+//      straight from the butterfly's sums -- ln::clamp_apply IS the carry pass, so nothing normalises in front of it; x is of one of the
+//      two input classes field_ln.h names there -- to [0, p + 64 B) < 2^(32 NL), packed and stored.  REDUCE (a last pass): -> [0, p).
+//      After the clamp, value >= p needs the top limb to reach floor(p / B) -- Ft255: about one element in 2^17; the conditional
+//      subtract runs only in the waves that hold such an element.  nqp: the NEGATED q*p rows in LDS, visible to the wave (a barrier
+//      has run since the kernel copied them)
+template <class FT, bool REDUCE> LCPC_DEV void clamp_store(u32* dst, LN<FT::N> x, const u32* nqp) {
+  constexpr int N = FT::N, NL = FT::NL;
+  ln::clamp_apply<FT>(x, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x.v[N - 1])));
+  u32 w[NL];
+  ln::to_packed<FT>(w, x.v);
+  Fe<NL> v;
+#pragma unroll
+  for (int i = 0; i < NL; i++) v.v[i] = w[i];
+  if constexpr (REDUCE) {
+    if (__any((int)(x.v[N - 1] >= FT::limb(N - 1)))) v = fe_reduce_once<NL>(w);
+  }
+  fe_store<NL>(dst, v);
+}
+
 // one entry of a limb-form table (twiddles w^i R' mod p, STRIDE words per entry).  Ft255's 12-word entries are 16-byte aligned:
 // two uint4 loads and a word
 template <class FT> LCPC_DEV LN<FT::N> tab_entry(const u32* tab, u32 idx) {
