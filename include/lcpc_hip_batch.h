@@ -61,6 +61,39 @@
  * under BLAKE3 all of them are the batch's; under the four chained digests encode_ms and encode_launches are the batch's, hash_ms /
  * merkle_ms and their launch counts are sums over the members (the members' hashes and trees alternate on the stream).  On the
  * member-by-member path every figure is the sum over the members.
+ *
+ * Contract of the batch prove (version 2)
+ *  The prover that committed a batch opens all of it.  One call runs the core header's prove for every member in lockstep: all members
+ *  draw their degree-test tensors, ONE launch chain collapses for all, all members absorb side by side on the host pool, all draw
+ *  their columns, ONE launch chain opens for all.  Every proof is byte for byte what the core header's prove call returns for that
+ *  member alone, and every transcript is left in exactly the state that call leaves it in.
+ *  - members: cms[0 .. n_batch) are distinct, committed, unsharded commitments of ONE encoder with the same n_rows.  They need not come
+ *    from one batch commit, or from a batch commit at all: slab members, single device / host / from_parts / from_bincode commits,
+ *    borrowed coefficients and position-major Brakedown members may be mixed in any order.  The kernels reach every member through a
+ *    per-member descriptor (coeffs, comm and its two strides, hashes), never through a slab stride.
+ *  - outer tensor: member i's is the n_outer elements at outer_tensors + i * outer_stride * L.  outer_stride == 0 means ONE tensor
+ *    shared by all members (all polynomials opened at one point); a nonzero stride must be >= n_outer.
+ *  - transcripts and proofs: trs[i] is member i's transcript; the transcripts are distinct objects.  proofs[i] / proof_lens[i]
+ *    receive the bincode bytes, each released with lcpc_free like a single proof.  cols_opened: NULL, or [n_batch][n_col_opens].
+ *  - errors: LCPC_ERR_ARG for a NULL cms / member / trs / transcript / outer_tensors / proofs / proof_lens, n_batch == 0 or > 65535, a
+ *    member or a transcript listed twice, members of different encoders or different n_rows, 0 < outer_stride < n_outer;
+ *    LCPC_ERR_STATE for an uncommitted member or a sharded encoder; LCPC_ERR_OUTER_TENSOR for n_outer != n_rows; LCPC_ERR_COMMIT where
+ *    the single prove returns it; device errors as usual (the detail text is on cms[0]).  After a failure no proof is returned --
+ *    every proofs[i] is NULL, nothing leaks -- and the transcripts are in an unspecified state, as after a failed single prove.
+ *  - threads: the call is a READER of every member.  It holds every member's fill lock shared for its duration, taken in address
+ *    order as the batch commit takes its exclusive locks, so it runs next to single proves, other batch proves that overlap in
+ *    members, collapses and opens; a refill of any member waits for it.  It works in ONE working set of cms[0] (stream, pinned arena,
+ *    device scratch, sized for a group); the stream is ordered behind every member's commit.
+ *  - stats (may be NULL): how the call ran.  Within one group the launch and synchronisation counts do not depend on n_batch.
+ *  - groups: the pinned arena per member is
+ *        A = (2 n_rows + 4 n_per_row) F + n_col_opens (8 + n_rows F + path_len D)   bytes  (F = 8 L, D = the digest length)
+ *    -- tensors, polynomials and their canonical forms; the drawn columns and the opened columns and paths, which are staged.
+ *    LIMITATION -- the arena is bounded by LCPCX_PROVE_ARENA_BUDGET (64 MiB): a batch runs in consecutive groups of
+ *    max(1, floor(budget / A)) members, ceil(n_batch / that) groups in all, each a lockstep pipeline of its own.  Same results;
+ *    stats.groups says how many.  (The arena stays with cms[0]'s working set until that object is destroyed.)
+ *  - timing: with LCPC_DEBUG_TIMING set when the encoder was created the call prints one line for the batch to stderr.
+ *  Out of scope: sharded encoders (LCPC_ERR_STATE); a batched verify; any change to proof format or protocol, such as a random linear
+ *  combination of the members into one proof -- the reference has none, and byte parity would have nothing to stand on.
  */
 #ifndef LCPC_HIP_BATCH_H
 #define LCPC_HIP_BATCH_H
@@ -69,13 +102,27 @@
 extern "C" {
 #endif
 
-#define LCPCX_BATCH_VERSION 1
+#define LCPCX_BATCH_VERSION 2
 int lcpcx_batch_version(void);
 /* cms[0..n_batch): distinct LcCommit objects of ONE unsharded encoder.  Polynomial i = n_coeffs elements at
  * coeffs_dev + i * poly_stride * L  (poly_stride in elements, >= n_coeffs; 0 means n_coeffs).
  * roots: n_batch * D bytes (D = the encoder's digest length) or NULL; non-NULL synchronises `stream` once. */
 int lcpcx_commit_batch_device(lcpc_commit_t *const *cms, uint32_t n_batch, const uint64_t *coeffs_dev,
                               uint64_t n_coeffs, uint64_t poly_stride, void *stream, uint32_t flags, uint8_t *roots);
+
+#define LCPCX_PROVE_ARENA_BUDGET ((uint64_t)64 << 20)
+typedef struct {
+  uint32_t groups;            /* lockstep groups the batch was cut into */
+  uint32_t collapse_launches; /* kernel launches of all collapse rounds: to_r29 + collapse + split sum + to_canon */
+  uint32_t open_launches;     /* column + path gather launches */
+  uint32_t host_syncs;        /* stream / event synchronisations the call made */
+} lcpcx_prove_stats;
+/* cms[0..n_batch): distinct committed LcCommit objects of ONE unsharded encoder, equal n_rows; trs[0..n_batch): distinct transcripts.
+ * Member i's outer tensor: n_outer elements at outer_tensors + i * outer_stride * L (0: one tensor for all).
+ * proofs / proof_lens: [n_batch]; cols_opened: [n_batch][n_col_opens] or NULL; stats: NULL or filled on success. */
+int lcpcx_prove_batch(lcpc_commit_t *const *cms, uint32_t n_batch, const uint64_t *outer_tensors, uint64_t n_outer,
+                      uint64_t outer_stride, lcpc_transcript *const *trs, uint8_t **proofs, uint64_t *proof_lens,
+                      uint64_t *cols_opened, lcpcx_prove_stats *stats);
 
 #ifdef __cplusplus
 }

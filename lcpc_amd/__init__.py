@@ -452,6 +452,39 @@ def commit_batch(enc, coeffs, n_coeffs=None, stream=0, sync=True, borrow=False, 
     return cms
 
 
+def prove_batch(cms, outer_tensor, trs, return_stats=False):
+    """lcpcx_prove_batch (include/lcpc_hip_batch.h): LcCommit::prove for every member of `cms` in one lockstep pipeline -- the
+    collapse and the open of all members in the launches of one prove, the members' transcript absorbs side by side on the host
+    pool.  cms: committed LcCommit objects of ONE encoder with the same n_rows, of any origin; trs: one Transcript per member.
+    outer_tensor: (n_rows, L) -- one tensor for all members -- or (n_batch, n_rows, L), one per member.  Returns the list of
+    LcEvalProof, each byte for byte what cms[i].prove(outer_i, enc, trs[i]) returns (return_stats: and the call's
+    LcpcxProveStats: groups, collapse_launches, open_launches, host_syncs)."""
+    cms, trs = list(cms), list(trs)
+    n_batch = len(cms)
+    if n_batch == 0 or len(trs) != n_batch:
+        raise LcpcError(ERR_ARG)
+    enc = cms[0].enc
+    t = np.ascontiguousarray(outer_tensor, dtype=np.uint64)
+    if t.ndim == 3:
+        if t.shape[0] != n_batch or t.shape[2] != enc.L:
+            raise LcpcError(ERR_OUTER_TENSOR)
+        n_outer = stride = t.shape[1]
+    else:
+        t = _elems(t, enc.L)
+        n_outer, stride = t.size // enc.L, 0
+    handles = (C.c_void_p * n_batch)(*[cm._h for cm in cms])
+    th = (C.c_void_p * n_batch)(*[tr._h for tr in trs])
+    pp, plen = (C.c_void_p * n_batch)(), (C.c_uint64 * n_batch)()
+    n_open = enc.get_n_col_opens()
+    cols = np.zeros((n_batch, n_open), np.uint64)
+    stats = _lib.LcpcxProveStats()
+    rc = _lib.lib().lcpcx_prove_batch(handles, n_batch, _ptr(t), n_outer, stride, th, pp, plen, _ptr(cols), C.byref(stats))
+    if rc:
+        raise LcpcError(rc, _lib.lib().lcpc_commit_last_error(cms[0]._h).decode())
+    pfs = [LcEvalProof(_OwnedBuffer(C.c_void_p(pp[i]), plen[i]), enc.L, cols[i]) for i in range(n_batch)]
+    return (pfs, stats) if return_stats else pfs
+
+
 class _OwnedBuffer:
     """a malloc'ed buffer handed out by the library (lcpc_prove): viewed in place, released with lcpc_free"""
 

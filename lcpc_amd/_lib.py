@@ -92,10 +92,19 @@ SYMBOLS = {
 }
 
 # the batch extension (include/lcpc_hip_batch.h): its own prefix, table and version -- SYMBOLS and ABI_VERSION above are the core header's
-BATCH_VERSION = 1
+BATCH_VERSION = 2
+
+
+class LcpcxProveStats(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("collapse_launches", C.c_uint32), ("open_launches", C.c_uint32), ("host_syncs", C.c_uint32)]
+
+
+PROVE_ARENA_BUDGET = 64 << 20      # LCPCX_PROVE_ARENA_BUDGET
 BATCH_SYMBOLS = {
     "lcpcx_batch_version": (_i32, []),
     "lcpcx_commit_batch_device": (_i32, [C.POINTER(_vp), _u32, _vp, _u64, _u64, _vp, _u32, _vp]),
+    "lcpcx_prove_batch": (_i32, [C.POINTER(_vp), _u32, _vp, _u64, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _vp,
+                                 C.POINTER(LcpcxProveStats)]),
 }
 
 

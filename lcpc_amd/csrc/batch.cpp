@@ -16,6 +16,8 @@
 // Brakedown batch run member by member through the one-shot launchers (merkleize_device):
 // tests/test_gpu_commit_batch_digests.py::test_brakedown_under_a_chained_digest pins that launch count.  A batch with more stacked
 // rows than the batch launchers' grids carry runs the single-commit pipeline (commit.cpp commit_device_locked) member by member.
+//
+// lcpcx_prove_batch, the other half of the header, is at the end of this file: every member of a batch opened in lockstep.
 #include "internal.h"
 #include "../../include/lcpc_hip_batch.h"
 #include <functional>
@@ -323,11 +325,228 @@ int commit_batch_each(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_
   return roots ? fetch_roots(cms, n_batch, nullptr, st, roots) : 0;
 }
 
+// =====================================================================================================
+// lcpcx_prove_batch: LcCommit::prove (lcpc-2d lib.rs:1004-1093; prove.cpp prove_impl) for every member of a batch in lockstep.
+// Per group of members: each degree-test round is one upload of all tensors, the batched collapse chain (kernels.hip K5b), one
+// copy down and ONE synchronisation, then every member absorbs its p_random on the host pool; the open is one upload of all
+// column numbers, the two batched gathers (K6b), the copies down and ONE synchronisation.  Round 0 fuses the outer tensor as the
+// second tensor, as the sharded prove does.  A member's transcript work of one step -- absorb, the copy into its proof, the draw
+// for the next step -- is one task of the pool, so the members' serial STROBE absorbs overlap each other.
+// =====================================================================================================
+constexpr uint64_t PROVE_ARENA_BUDGET = LCPCX_PROVE_ARENA_BUDGET;      // pinned bytes of one group (include/lcpc_hip_batch.h, groups)
+
+// one member as the K5b / K6b kernels see it (commit.cpp collapse_prepare, open_columns_device)
+ProveMember describe_member(const lcpc_commit_t* m) {
+  const lcpc_ctx* c = m->enc;
+  ProveMember d{};
+  d.coeffs = m->coeffs_view; d.hashes = m->d_hashes;
+  if (m->comm_t) { d.comm = m->ws.d_t; d.comm_row_stride = 1; d.comm_col_stride = m->n_rows_local; d.comm_canon = 1u; }
+  else { d.comm = m->d_comm; d.comm_row_stride = c->n_cols; d.comm_col_stride = 1; d.comm_canon = c->comm_canon ? 1u : 0u; }
+  return d;
+}
+
+struct ProofBufs {                 // the proofs of a call that does not succeed go back, and the caller sees NULLs
+  uint8_t** p; uint32_t n; bool keep = false;
+  ~ProofBufs() {
+    if (keep) return;
+    for (uint32_t i = 0; i < n; i++) { proof_buf_free(p[i]); p[i] = nullptr; }
+  }
+};
+
+// every member's fill_mu held shared; arguments checked
+int prove_batch_locked(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* outer, uint64_t outer_stride, lcpc_transcript* const* trs,
+                       uint8_t** proofs, uint64_t* proof_lens, uint64_t* cols_opened, lcpcx_prove_stats* stats) {
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  const FieldDesc& f = *c->f;
+  const int L = f.L;
+  const uint64_t F = elem_bytes(c), nr = m0->n_rows, np = c->n_per_row;
+  const ProofLayout pl = proof_layout(c, nr);
+  const uint64_t n_deg = pl.n_deg, n_open = pl.n_open;
+  const uint32_t path_len = c->path_len, splits = collapse_splits(m0);
+  const bool dbg = c->sw_debug_timing;
+  const double t_start = now_ms();
+  double t_draw = 0, t_dev = 0, t_absorb = 0, t_open = 0, t_frame = 0;
+  // the pinned arena of one member (the header's A): tensors | polynomials and canonical forms | columns | opened values | paths
+  const uint64_t a_t = 2 * nr * F, a_p = 4 * np * F, a_c = n_open * 8, a_v = n_open * nr * F, a_h = n_open * path_len * pl.dl;
+  const uint64_t arena = a_t + a_p + a_c + a_v + a_h;
+  uint64_t gmax = PROVE_ARENA_BUDGET / arena;
+  if (gmax < 1) gmax = 1;
+  if (gmax > n_batch) gmax = n_batch;
+  lcpcx_prove_stats stt{};
+  stt.groups = (uint32_t)((n_batch + gmax - 1) / gmax);
+
+  std::vector<ProveMember> desc(n_batch);        // (outlives the working set's stream: it is the source of an asynchronous copy)
+  for (uint32_t i = 0; i < n_batch; i++) desc[i] = describe_member(cms[i]);
+  std::vector<uint64_t> eval_canon;              // to_repr of p_eval from round 0, absorbed after the last round
+  if (n_deg > 1) eval_canon.resize(gmax * np * L);
+  ProofBufs bufs{proofs, n_batch};
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (!(proofs[i] = static_cast<uint8_t*>(proof_buf_alloc(pl.total ? pl.total : 1)))) return LCPC_ERR_NOMEM;
+
+  SetLease<CallSet> ws{m0->sets};
+  int rc = take_call_set(m0, gmax * arena, &ws.s);
+  if (rc) return rc;
+  hipStream_t st = ws.s->st;
+  for (uint32_t i = 1; i < n_batch; i++)
+    if ((rc = order_after_commit(cms[i], st))) { m0->err = cms[i]->err.c_str(); return rc; }
+  // device scratch: [descriptors][tensors][polys | canon][partials][cols][vals][paths], each segment 256-byte aligned
+  const uint64_t s_desc = align256((uint64_t)n_batch * sizeof(ProveMember)), s_t = align256(gmax * a_t), s_p = align256(gmax * a_p);
+  const uint64_t s_part = splits > 1 ? align256(gmax * splits * 2 * np * F) : 0;
+  const uint64_t s_c = align256(gmax * a_c), s_v = align256(gmax * a_v), s_h = align256(gmax * a_h);
+  if ((rc = ensure_scratch(m0, &ws.s->sc, s_desc + s_t + s_p + s_part + s_c + s_v + s_h))) return rc;
+  uint8_t* base = reinterpret_cast<uint8_t*>(ws.s->sc.d);
+  const ProveMember* d_desc = reinterpret_cast<const ProveMember*>(base);
+  uint32_t* d_t = reinterpret_cast<uint32_t*>(base + s_desc);
+  uint32_t* d_p = reinterpret_cast<uint32_t*>(base + s_desc + s_t);
+  uint32_t* d_part = reinterpret_cast<uint32_t*>(base + s_desc + s_t + s_p);
+  uint64_t* d_cols = reinterpret_cast<uint64_t*>(base + s_desc + s_t + s_p + s_part);
+  uint32_t* d_vals = reinterpret_cast<uint32_t*>(base + s_desc + s_t + s_p + s_part + s_c);
+  uint32_t* d_paths = reinterpret_cast<uint32_t*>(base + s_desc + s_t + s_p + s_part + s_c + s_v);
+  if (c->NL == 8 && (rc = ensure_dev(&m0->err, &ws.s->sc.t29, &ws.s->sc.t29_cap, gmax * 2 * nr * 48))) return rc;
+  HIPCHK(m0, hipMemcpyAsync(base, desc.data(), (size_t)n_batch * sizeof(ProveMember), hipMemcpyHostToDevice, st));
+
+  for (uint32_t g0 = 0; g0 < n_batch; g0 += (uint32_t)gmax) {
+    const uint32_t g = (uint32_t)std::min<uint64_t>(gmax, n_batch - g0);
+    uint64_t* h_t = reinterpret_cast<uint64_t*>(ws.s->h_pin);
+    uint64_t* h_p = reinterpret_cast<uint64_t*>(ws.s->h_pin + g * a_t);
+    uint64_t* h_cols = reinterpret_cast<uint64_t*>(ws.s->h_pin + g * (a_t + a_p));
+    uint64_t* h_vals = reinterpret_cast<uint64_t*>(ws.s->h_pin + g * (a_t + a_p + a_c));
+    uint8_t* h_paths = ws.s->h_pin + g * (a_t + a_p + a_c + a_v);
+    // member i of the group draws the tensor of its next round ([member][tensor][n_rows]; round 0 takes the outer tensor second)
+    auto draw_tensor = [&](uint32_t i, uint32_t nt) {
+      uint8_t key[32];
+      trs[g0 + i]->t.challenge_bytes(LBL_DT, 6, key, 32);                       // lib.rs:1024-1043
+      ChaCha20Rng rng(key);
+      uint64_t* t = h_t + (size_t)i * nt * nr * L;
+      for (uint64_t r = 0; r < nr; r++) rng.field_random(f, &t[r * L]);
+      if (nt == 2) memcpy(t + nr * L, outer + (size_t)(g0 + i) * outer_stride * L, nr * F);
+    };
+    double t0 = now_ms();
+    parallel_for(g, 1, [&](uint64_t b, uint64_t e) { for (uint64_t i = b; i < e; i++) draw_tensor((uint32_t)i, 2); });
+    t_draw += now_ms() - t0;
+    for (uint64_t round = 0; round < n_deg; round++) {
+      const uint32_t nt = round == 0 ? 2 : 1;
+      const uint64_t n_poly = (uint64_t)g * nt * np;                               // elements of all polynomials of this round
+      t0 = now_ms();
+      HIPCHK(m0, hipMemcpyAsync(d_t, h_t, (size_t)g * nt * nr * F, hipMemcpyHostToDevice, st));
+      CollapseArgs b{};                                                           // the batch form: member = grid z
+      b.members = d_desc + g0; b.n_batch = g; b.tensors = d_t; b.out = splits == 1 ? d_p : d_part;
+      b.n_rows = nr; b.n_per_row = np; b.n_tensors = nt; b.n_splits = splits;
+      if (c->NL == 8) {
+        HIPCHK(m0, launch_to_r29(d_t, (uint64_t)g * nt * nr, ws.s->sc.t29, st));
+        b.tensors29 = ws.s->sc.t29;
+        stt.collapse_launches++;
+      }
+      HIPCHK(m0, launch_collapse(c->NL, b, st));
+      stt.collapse_launches++;
+      if (splits > 1) {
+        HIPCHK(m0, launch_field_sum_batch(c->NL, d_part, splits, (uint64_t)nt * np, d_p, g, st));
+        stt.collapse_launches++;
+      }
+      HIPCHK(m0, launch_to_canon(c->NL, d_p, n_poly, d_p + n_poly * c->NL, st));   // the canonical forms right behind the polynomials
+      stt.collapse_launches++;
+      HIPCHK(m0, hipMemcpyAsync(h_p, d_p, (size_t)2 * n_poly * F, hipMemcpyDeviceToHost, st));
+      HIPCHK(m0, hipStreamSynchronize(st));
+      stt.host_syncs++;
+      t_dev += now_ms() - t0;
+      t0 = now_ms();
+      const bool last = round + 1 == n_deg;
+      parallel_for(g, 1, [&](uint64_t mb, uint64_t me) {
+        for (uint64_t i = mb; i < me; i++) {
+          Transcript& tr = trs[g0 + i]->t;
+          uint8_t* out = proofs[g0 + i];
+          const uint64_t* polys = h_p + i * nt * np * L;
+          const uint64_t* canon = h_p + (n_poly + i * nt * np) * L;
+          tr.append_messages(LBL_PR, 6, reinterpret_cast<const uint8_t*>(canon), 8 * L, np);          // lib.rs:1045-1047
+          memcpy(out + pl.off_rand0 + round * (8 + pl.pbytes), polys, pl.pbytes);
+          if (round == 0) {
+            memcpy(out + pl.off_eval, polys + np * L, pl.pbytes);
+            if (n_deg > 1) memcpy(&eval_canon[i * np * L], canon + np * L, pl.pbytes);
+          }
+          if (!last) { draw_tensor((uint32_t)i, 1); continue; }
+          const uint64_t* pe = n_deg > 1 ? &eval_canon[i * np * L] : canon + np * L;
+          tr.append_messages(LBL_PE, 6, reinterpret_cast<const uint8_t*>(pe), 8 * L, np);             // lib.rs:1066-1068
+          draw_columns(tr, c, h_cols + i * n_open, n_open);
+          proof_write_head(pl, out);
+        }
+      });
+      t_absorb += now_ms() - t0;
+    }
+    t0 = now_ms();
+    HIPCHK(m0, hipMemcpyAsync(d_cols, h_cols, (size_t)g * a_c, hipMemcpyHostToDevice, st));
+    HIPCHK(m0, launch_gather_columns_batch(c->NL, d_desc + g0, g, nr, d_cols, (uint32_t)n_open, d_vals, c->d_r2, st));
+    stt.open_launches += (uint32_t)((n_open + 32767) / 32768);
+    HIPCHK(m0, hipMemcpyAsync(h_vals, d_vals, (size_t)g * a_v, hipMemcpyDeviceToHost, st));
+    if (path_len) {
+      HIPCHK(m0, launch_gather_paths_batch(d_desc + g0, g, c->np2, path_len, d_cols, (uint32_t)n_open, d_paths, digest_words(c), st));
+      stt.open_launches++;
+      HIPCHK(m0, hipMemcpyAsync(h_paths, d_paths, (size_t)g * a_h, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(m0, hipStreamSynchronize(st));
+    stt.host_syncs++;
+    t_open += now_ms() - t0;
+    t0 = now_ms();
+    // framing, values and paths of every opened column of every member: flat over (member, column)
+    parallel_for((uint64_t)g * n_open, 256, [&](uint64_t b, uint64_t e) {
+      while (b < e) {
+        const uint64_t i = b / n_open, k0 = b % n_open, k1 = std::min<uint64_t>(n_open, k0 + (e - b));
+        proof_write_columns(pl, proofs[g0 + i], h_paths + i * a_h, h_vals + i * n_open * nr * L, k0, k1);
+        b += k1 - k0;
+      }
+    });
+    if (cols_opened) memcpy(cols_opened + (size_t)g0 * n_open, h_cols, (size_t)g * a_c);
+    t_frame += now_ms() - t0;
+  }
+  for (uint32_t i = 0; i < n_batch; i++) proof_lens[i] = pl.total;
+  bufs.keep = true;
+  if (stats) *stats = stt;
+  if (dbg)
+    fprintf(stderr, "[lcpcx_prove_batch] %u members in %u groups: draw tensors %.2f ms, collapse (device + copies) %.2f, absorb + draw %.2f, "
+                    "open %.2f, bincode %.2f, total %.2f; %u collapse + %u open launches, %u syncs\n",
+            n_batch, stt.groups, t_draw, t_dev, t_absorb, t_open, t_frame, now_ms() - t_start, stt.collapse_launches, stt.open_launches,
+            stt.host_syncs);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int lcpcx_batch_version(void) { return LCPCX_BATCH_VERSION; }
+
+int lcpcx_prove_batch(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* outer_tensors, uint64_t n_outer, uint64_t outer_stride,
+                      lcpc_transcript* const* trs, uint8_t** proofs, uint64_t* proof_lens, uint64_t* cols_opened, lcpcx_prove_stats* stats) {
+  if (!proofs || n_batch == 0 || n_batch > 65535) return LCPC_ERR_ARG;
+  for (uint32_t i = 0; i < n_batch; i++) proofs[i] = nullptr;                 // whatever fails from here on, no proof is returned
+  if (!cms || !trs || !outer_tensors || !proof_lens || (outer_stride != 0 && outer_stride < n_outer)) return LCPC_ERR_ARG;
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (!cms[i] || !trs[i] || cms[i]->enc != cms[0]->enc) return LCPC_ERR_ARG;
+  lcpc_commit_t* m0 = cms[0];
+  const lcpc_ctx* c = m0->enc;
+  LCPC_TRY
+  std::vector<lcpc_commit_t*> order(cms, cms + n_batch);
+  std::sort(order.begin(), order.end(), std::less<lcpc_commit_t*>());
+  if (std::adjacent_find(order.begin(), order.end()) != order.end()) return LCPC_ERR_ARG;       // a member listed twice
+  {
+    std::vector<lcpc_transcript*> t(trs, trs + n_batch);
+    std::sort(t.begin(), t.end(), std::less<lcpc_transcript*>());
+    if (std::adjacent_find(t.begin(), t.end()) != t.end()) return LCPC_ERR_ARG;                 // a transcript listed twice
+  }
+  if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
+  // a reader of every member, in the batch commit's lock order: a refill of any member waits, readers run beside
+  std::vector<std::shared_lock<FillLock>> readers;
+  readers.reserve(n_batch);
+  for (lcpc_commit_t* m : order) readers.emplace_back(m->fill_mu);
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (!cms[i]->committed) return LCPC_ERR_STATE;
+  for (uint32_t i = 0; i < n_batch; i++)
+    if (cms[i]->n_rows != m0->n_rows) return LCPC_ERR_ARG;
+  if (!lcpc_dims_ok(c, c->n_per_row, c->n_cols)) return LCPC_ERR_COMMIT;      // check_comm lib.rs:1015
+  if (n_outer != m0->n_rows) return LCPC_ERR_OUTER_TENSOR;                     // lib.rs:1016-1018
+  return prove_batch_locked(cms, n_batch, outer_tensors, outer_stride, trs, proofs, proof_lens, cols_opened, stats);
+  LCPC_CATCH(m0)
+}
 
 int lcpcx_commit_batch_device(lcpc_commit_t* const* cms, uint32_t n_batch, const uint64_t* coeffs_dev, uint64_t n_coeffs,
                               uint64_t poly_stride, void* stream, uint32_t flags, uint8_t* roots) {

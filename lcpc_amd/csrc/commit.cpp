@@ -292,7 +292,7 @@ int order_after_commit(lcpc_commit_t* m, hipStream_t st) {
   return 0;
 }
 
-static uint32_t collapse_splits(const lcpc_commit_t* m) {
+uint32_t collapse_splits(const lcpc_commit_t* m) {
   const uint64_t col_blocks = (m->enc->n_per_row + 255) / 256;
   uint32_t n_splits = 1;   // split the row range so that the grid has >= ~2k workgroups even for narrow matrices
   while (n_splits < 64 && col_blocks * n_splits < 2048 && m->n_rows_local / (n_splits * 2) >= 16) n_splits *= 2;

@@ -540,6 +540,7 @@ int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);
 int order_after_commit(lcpc_commit_t* m, hipStream_t st);          // st waits for the commit that filled m (event; cheap)
 int collapse_run(lcpc_commit_t* m, DevScratch* sc, const uint32_t* d_tensors, uint32_t n_tensors, hipStream_t st, uint32_t* d_polys);
 size_t collapse_scratch_bytes(const lcpc_commit_t* m, uint32_t n_tensors);
+uint32_t collapse_splits(const lcpc_commit_t* m);                  // row splits of a whole-polynomial collapse (>= 16 rows each)
 // the host-entry readers (prove, lcpc_collapse, lcpc_open_columns) run in a working set `ws` of m->sets, taken by take_call_set
 // (the caller holds m->fill_mu shared): everything on ws->st, synchronised on that stream or its events
 int take_call_set(lcpc_commit_t* m, uint64_t pin_bytes, CallSet** ws);
@@ -575,5 +576,23 @@ int open_sharded(lcpc_commit_t* m, const ShardXchg& x, const uint64_t* cols, uin
 // ---- prove.cpp --------------------------------------------------------------------------------------
 int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_transcript* trw, uint8_t** proof, uint64_t* proof_len,
                uint64_t* cols_opened, const ShardXchg* xchg);
+// What the single prove and the batched one (batch.cpp) share.
+// bincode 1.3 of WrappedLcEvalProof (lib.rs:550-560): n_cols | p_eval | p_random_vec | columns, every size known up front
+struct ProofLayout {
+  uint64_t n_cols, np, nr, n_deg, n_open;
+  uint32_t path_len;
+  size_t pbytes;                   // one polynomial
+  size_t dl;                       // each path entry: u64 dl | dl bytes (lib.rs:354-372)
+  size_t col_bytes;                // one opened column: u64 nr | values | u64 path_len | entries
+  size_t off_eval, off_rand0;      // first element of p_eval / of p_random_vec[0]; p_random_vec[i] at off_rand0 + i * (8 + pbytes)
+  size_t head, total;              // the columns start at head; values of column k at head + k * col_bytes + 8
+};
+ProofLayout proof_layout(const lcpc_ctx* c, uint64_t n_rows);
+void proof_write_head(const ProofLayout& pl, uint8_t* out);      // every length prefix in front of the columns
+// framing and path of columns [k0, k1); their values are in place already, or (vals non-null, [n_open][nr] elements) copied here
+void proof_write_columns(const ProofLayout& pl, uint8_t* out, const uint8_t* paths, const uint64_t* vals, uint64_t k0, uint64_t k1);
+// the column challenge (lib.rs:1071-1080)
+void draw_columns(Transcript& tr, const lcpc_ctx* c, uint64_t* cols, uint64_t n_open);
+double now_ms();
 
 }  // namespace lcpc

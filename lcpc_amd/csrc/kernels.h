@@ -178,6 +178,16 @@ hipError_t launch_chain_merkle_tree_batch(ChainHash h, uint32_t* hashes, uint64_
 // counter is 128 (blk + 1)).
 hipError_t launch_chain_leaves_range(ChainHash h, int nl, const LeafArgs& a, uint64_t blk_begin, uint64_t blk_end, uint32_t* state, hipStream_t st);
 
+// ---- K5b / K6b: the batch forms for the batched prove (batch.cpp): the member index is a grid dimension ------------------------
+// What differs between the members of a batch, one record per member in device memory: a member's coefficients and commitment
+// matrix wherever they live.  Element (r, c) of comm at comm + (r * comm_row_stride + c * comm_col_stride) elements.
+struct ProveMember {
+  const uint32_t* coeffs;      // n_rows x n_per_row
+  const uint32_t* comm;
+  uint64_t comm_row_stride, comm_col_stride;   // row-major: n_cols, 1; position-major: 1, n_rows
+  const uint32_t* hashes;      // 2 np2 - 1 digests
+  uint32_t comm_canon;         // comm holds canonical values: open multiplies by R^2
+};
 struct CollapseArgs {
   const uint32_t* coeffs;      // local rows x n_per_row
   const uint32_t* tensors;     // [n_tensors][n_rows_local]
@@ -188,6 +198,10 @@ struct CollapseArgs {
   // column range [j0, j1) of this launch (j1 == 0: all of them) and the element stride between the output rows: a range's outputs sit
   // at out + ((split * n_tensors + tensor) * out_stride + (j - j0)) elements (prove collapses p_random in two ranges: commit.cpp)
   uint64_t j0 = 0, j1 = 0, out_stride = 0;
+  // the batch form (K5b): members non-null -> grid z = member (n_batch <= 65535).  Member z reads members[z].coeffs (`coeffs` is not
+  // read), its tensors at tensors / tensors29 + z * n_tensors * n_rows elements, and writes at out + z * n_splits * n_tensors * out_stride
+  const ProveMember* members = nullptr;
+  uint32_t n_batch = 0;
 };
 hipError_t launch_collapse(int nl, const CollapseArgs& a, hipStream_t st);
 // Ft255 tensors (Montgomery) -> the 29-bit-limb / 2^261 form used by the lazy dot-product kernels
@@ -210,6 +224,18 @@ hipError_t launch_assemble_columns(int nl, const uint32_t* recv, uint64_t block_
 // digest_words = 8 or 16 (ChainShape.digest_words; BLAKE3: 8): paths [n][path_len][digest_words]
 hipError_t launch_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
                                uint32_t* paths, uint32_t digest_words, hipStream_t st);
+
+// ---- K5b / K6b: the batch forms of the split sum and the gathers (the batch form of collapse: CollapseArgs.members) -------------
+// out[member][e] = sum_p parts[member][p][e] mod p (member = blockIdx.y)
+hipError_t launch_field_sum_batch(int nl, const uint32_t* parts, uint32_t n_parts, uint64_t n_elems, uint32_t* out, uint32_t n_batch,
+                                  hipStream_t st);
+// vals[member][k][r] = comm_member[r][cols[member][k]]; grid (row blocks, opened column, member), n_open in slices of 32768.
+// r2 is applied to the members whose descriptor says comm_canon
+hipError_t launch_gather_columns_batch(int nl, const ProveMember* members, uint32_t n_batch, uint64_t n_rows, const uint64_t* cols,
+                                       uint32_t n_open, uint32_t* vals, const uint32_t* r2, hipStream_t st);
+// paths[member][k][lvl][digest_words]: one flat launch over n_batch * n_open * path_len entries
+hipError_t launch_gather_paths_batch(const ProveMember* members, uint32_t n_batch, uint64_t np2, uint32_t path_len, const uint64_t* cols,
+                                     uint32_t n_open, uint32_t* paths, uint32_t digest_words, hipStream_t st);
 
 // Brakedown: y[row][out_off + o] = sum_k vals[k] * x[row][in_off + colidx[k]], k in [rowptr[o], rowptr[o+1])
 struct SpmvArgs {

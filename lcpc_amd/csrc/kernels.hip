@@ -752,11 +752,23 @@ hipError_t launch_merkle_tree_from(u32* hashes, u64 np2, u32 levels_done, hipStr
 // over coeffs.  Lane = column j (coalesced row reads); the tensor entry is wave-uniform.  Products
 // are accumulated unreduced (2NL+1 limbs) in batches and Montgomery-reduced once per batch.
 // =================================================================================================
+// K5b, the batch form (the batched prove, batch.cpp): the same kernels with the member of a batch as grid dimension z.  a.members
+// non-null: workgroup z reads member z's coefficients through its descriptor, member z's tensors ([member][tensor][n_rows]) and
+// writes member z's outputs ([member][split][tensor][out_stride]).  The member is uniform per workgroup, so the pointers stay scalar.
 template <int NL, int NT>
 __global__ void __launch_bounds__(256) collapse_kernel(CollapseArgs a) {
   const u64 j = a.j0 + (u64)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.j1) return;
   const u32 z = blockIdx.y;
+  const u32* coeffs = a.coeffs;
+  const u32* tensors = a.tensors;
+  u32* out = a.out;
+  if (a.members != nullptr) {
+    const u64 m = blockIdx.z;
+    coeffs = a.members[m].coeffs;
+    tensors += m * NT * a.n_rows * NL;
+    out += m * a.n_splits * NT * a.out_stride * NL;
+  }
   const u64 rows_per = (a.n_rows + a.n_splits - 1) / a.n_splits;
   const u64 r0 = (u64)z * rows_per;
   const u64 r1 = (r0 + rows_per < a.n_rows) ? r0 + rows_per : a.n_rows;
@@ -770,10 +782,10 @@ __global__ void __launch_bounds__(256) collapse_kernel(CollapseArgs a) {
     for (int t = 0; t < NT; t++) w[t] = wide_zero<NL>();
     const u64 re = (rb + BATCH < r1) ? rb + BATCH : r1;
     for (u64 r = rb; r < re; r++) {
-      const Fe<NL> c = fe_load<NL>(a.coeffs + (r * a.n_per_row + j) * NL);
+      const Fe<NL> c = fe_load<NL>(coeffs + (r * a.n_per_row + j) * NL);
 #pragma unroll
       for (int t = 0; t < NT; t++) {
-        const Fe<NL> tv = fe_load<NL>(a.tensors + ((u64)t * a.n_rows + r) * NL);
+        const Fe<NL> tv = fe_load<NL>(tensors + ((u64)t * a.n_rows + r) * NL);
         wide_mac<NL>(w[t], c, tv);
       }
     }
@@ -781,15 +793,24 @@ __global__ void __launch_bounds__(256) collapse_kernel(CollapseArgs a) {
     for (int t = 0; t < NT; t++) acc[t] = fe_add<NL>(acc[t], wide_reduce<NL>(w[t]));
   }
 #pragma unroll
-  for (int t = 0; t < NT; t++) fe_store<NL>(a.out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * NL, acc[t]);
+  for (int t = 0; t < NT; t++) fe_store<NL>(out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * NL, acc[t]);
 }
 // Ft255: carry-free lazy dot products (ln::lazy_mac); the tensor entry is wave-uniform, so its nine 29-bit limbs
-// (pre-converted to the 2^261 form, a.tensors29) are scalar operands of the 81 v_mad_u64_u32 per term.
+// (pre-converted to the 2^261 form, tensors29) are scalar operands of the 81 v_mad_u64_u32 per term.
 template <int NT>
 __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
   const u64 j = a.j0 + (u64)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.j1) return;
   const u32 z = blockIdx.y;
+  const u32* coeffs = a.coeffs;
+  const u32* tensors29 = a.tensors29;
+  u32* out = a.out;
+  if (a.members != nullptr) {                    // K5b: member = blockIdx.z
+    const u64 m = blockIdx.z;
+    coeffs = a.members[m].coeffs;
+    tensors29 += m * NT * a.n_rows * 12;
+    out += m * a.n_splits * NT * a.out_stride * 8;
+  }
   const u64 rows_per = (a.n_rows + a.n_splits - 1) / a.n_splits;
   const u64 r0 = (u64)z * rows_per;
   const u64 r1 = (r0 + rows_per < a.n_rows) ? r0 + rows_per : a.n_rows;
@@ -802,20 +823,20 @@ __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
 #pragma unroll
     for (int t = 0; t < NT; t++) ln::lazy_zero(w[t]);
     u32 since = 0;
-    Fe<8> c = fe_load<8>(a.coeffs + (rb * a.n_per_row + j) * 8);
+    Fe<8> c = fe_load<8>(coeffs + (rb * a.n_per_row + j) * 8);
     for (u64 r = rb; r < re; r++) {
       Fe<8> cn = c;
       // (field_dev.h) one tensor: the next row's load goes out ahead of this row's 81 mads (0.425 -> 0.401 ms at the headline shape);
       // with two tensors fused the same costs 10 % (0.66 -> 0.73): the longer arithmetic stretch already covers the load
       if constexpr (NT == 1) mem_phase(true);
-      if (r + 1 < re) cn = fe_load<8>(a.coeffs + ((r + 1) * a.n_per_row + j) * 8);     // next row in flight
+      if (r + 1 < re) cn = fe_load<8>(coeffs + ((r + 1) * a.n_per_row + j) * 8);     // next row in flight
       if constexpr (NT == 1) mem_phase(false);
       const LN<9> x = ln::from_packed<L255>(c);
 #pragma unroll
       for (int t = 0; t < NT; t++) {
         LN<9> v;
 #pragma unroll
-        for (int i = 0; i < 9; i++) v.v[i] = __builtin_amdgcn_readfirstlane(a.tensors29[((u64)t * a.n_rows + r) * 12 + i]);
+        for (int i = 0; i < 9; i++) v.v[i] = __builtin_amdgcn_readfirstlane(tensors29[((u64)t * a.n_rows + r) * 12 + i]);
         ln::lazy_mac(w[t], x, v);
       }
       if (++since == 6) {
@@ -829,7 +850,7 @@ __global__ void __launch_bounds__(256) collapse29_kernel(CollapseArgs a) {
     for (int t = 0; t < NT; t++) acc[t] = fe_add<8>(acc[t], ln::lazy_reduce(w[t]));
   }
 #pragma unroll
-  for (int t = 0; t < NT; t++) fe_store<8>(a.out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * 8, acc[t]);
+  for (int t = 0; t < NT; t++) fe_store<8>(out + (((u64)z * NT + t) * a.out_stride + (j - a.j0)) * 8, acc[t]);
 }
 // tensors (Montgomery, R = 2^256) -> 9 x 29-bit limbs of t * 2^261 mod p, 12-word stride
 __global__ void __launch_bounds__(256) to_r29_kernel(const u32* in, u64 n, u32* out) {
@@ -851,7 +872,7 @@ hipError_t launch_to_r29(const u32* in, u64 n, u32* out, hipStream_t st) {
 
 template <int NL>
 static hipError_t launch_collapse_t(const CollapseArgs& a, hipStream_t st) {
-  dim3 grid((unsigned)((a.j1 - a.j0 + 255) / 256), a.n_splits);
+  dim3 grid((unsigned)((a.j1 - a.j0 + 255) / 256), a.n_splits, a.members ? a.n_batch : 1);
   switch (a.n_tensors) {
     case 1: hipLaunchKernelGGL((collapse_kernel<NL, 1>), grid, dim3(256), 0, st, a); break;
     case 2: hipLaunchKernelGGL((collapse_kernel<NL, 2>), grid, dim3(256), 0, st, a); break;
@@ -864,8 +885,9 @@ hipError_t launch_collapse(int nl, const CollapseArgs& a_in, hipStream_t st) {
   if (a.j1 == 0) { a.j0 = 0; a.j1 = a.n_per_row; }            // the whole polynomial
   if (a.out_stride == 0) a.out_stride = a.n_per_row;
   if (a.j1 > a.n_per_row || a.j0 >= a.j1) return hipErrorInvalidValue;
+  if (a.members != nullptr && (a.n_batch == 0 || a.n_batch > 65535)) return hipErrorInvalidValue;   // the batch form: grid z
   if (nl == 8 && a.tensors29 != nullptr) {
-    dim3 grid((unsigned)((a.j1 - a.j0 + 255) / 256), a.n_splits);
+    dim3 grid((unsigned)((a.j1 - a.j0 + 255) / 256), a.n_splits, a.members ? a.n_batch : 1);
     switch (a.n_tensors) {
       case 1: hipLaunchKernelGGL(collapse29_kernel<1>, grid, dim3(256), 0, st, a); break;
       case 2: hipLaunchKernelGGL(collapse29_kernel<2>, grid, dim3(256), 0, st, a); break;
@@ -883,12 +905,16 @@ hipError_t launch_collapse(int nl, const CollapseArgs& a_in, hipStream_t st) {
 }
 
 template <int NL>
-__global__ void __launch_bounds__(256) field_sum_kernel(const u32* parts, u32 n_parts, u64 n_elems, u32* out) {
+__device__ __forceinline__ void field_sum_elem(const u32* parts, u32 n_parts, u64 n_elems, u32* out) {
   const u64 e = (u64)blockIdx.x * 256 + threadIdx.x;
   if (e >= n_elems) return;
   Fe<NL> acc = fe_load<NL>(parts + e * NL);
   for (u32 p = 1; p < n_parts; p++) acc = fe_add<NL>(acc, fe_load<NL>(parts + ((u64)p * n_elems + e) * NL));
   fe_store<NL>(out + e * NL, acc);
+}
+template <int NL>
+__global__ void __launch_bounds__(256) field_sum_kernel(const u32* parts, u32 n_parts, u64 n_elems, u32* out) {
+  field_sum_elem<NL>(parts, n_parts, n_elems, out);
 }
 hipError_t launch_field_sum(int nl, const u32* parts, u32 n_parts, u64 n_elems, u32* out, hipStream_t st) {
   dim3 grid((unsigned)((n_elems + 255) / 256));
@@ -905,16 +931,20 @@ hipError_t launch_field_sum(int nl, const u32* parts, u32 n_parts, u64 n_elems, 
 // =================================================================================================
 // K6: open_column gathers
 // =================================================================================================
+// column c of one commitment matrix -> vals_k[0 .. n_rows) (shared with the batch form, K6b)
+template <int NL>
+__device__ __forceinline__ void gather_column(const u32* comm, u64 n_rows, u64 row_stride, u64 col_stride, u64 c, u32* vals_k, const u32* r2) {
+  for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (u64)gridDim.x * 256) {
+    Fe<NL> v = fe_load<NL>(comm + (r * row_stride + c * col_stride) * NL);
+    if (r2 != nullptr) v = fe_mul<NL>(v, fe_load<NL>(r2));  // canonical comm -> Montgomery form
+    fe_store<NL>(vals_k + r * NL, v);
+  }
+}
 template <int NL>
 __global__ void __launch_bounds__(256) gather_columns_kernel(const u32* comm, u64 n_rows, u64 row_stride, u64 col_stride, const u64* cols,
                                                             u32* vals, const u32* r2) {
   const u32 k = blockIdx.y;
-  const u64 c = cols[k];
-  for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (u64)gridDim.x * 256) {
-    Fe<NL> v = fe_load<NL>(comm + (r * row_stride + c * col_stride) * NL);
-    if (r2 != nullptr) v = fe_mul<NL>(v, fe_load<NL>(r2));  // canonical comm -> Montgomery form
-    fe_store<NL>(vals + ((u64)k * n_rows + r) * NL, v);
-  }
+  gather_column<NL>(comm, n_rows, row_stride, col_stride, cols[k], vals + (u64)k * n_rows * NL, r2);
 }
 template <int NL>
 __global__ void __launch_bounds__(256) to_mont_kernel(const u32* in, u64 n, const u32* r2, u32* out) {
@@ -962,20 +992,24 @@ hipError_t launch_gather_columns(int nl, const u32* comm, u64 n_rows, u64 row_st
   }
   return hipSuccess;
 }
-// DW = words per digest, 8 or 16: 16-byte moves
+// DW = words per digest, 8 or 16: 16-byte moves.  The sibling of column col's ancestor at level lvl -> dst
+template <int DW>
+__device__ __forceinline__ void gather_path_entry(const u32* hashes, u64 np2, u32 lvl, u64 col, u32* dst) {
+  u64 base = 0, w = np2;
+  for (u32 i = 0; i < lvl; i++) { base += w; w >>= 1; }
+  const u64 node = (col >> lvl) ^ 1;
+  const uint4* s = reinterpret_cast<const uint4*>(hashes + (base + node) * DW);
+  uint4* d = reinterpret_cast<uint4*>(dst);
+#pragma unroll
+  for (int i = 0; i < DW / 4; i++) d[i] = s[i];
+}
 template <int DW>
 __global__ void __launch_bounds__(256) gather_paths_kernel(const u32* hashes, u64 np2, u32 path_len, const u64* cols, u32 n,
                                                           u32* paths) {
   const u64 id = (u64)blockIdx.x * 256 + threadIdx.x;
   if (id >= (u64)n * path_len) return;
   const u32 k = (u32)(id / path_len), lvl = (u32)(id % path_len);
-  u64 base = 0, w = np2;
-  for (u32 i = 0; i < lvl; i++) { base += w; w >>= 1; }
-  const u64 node = (cols[k] >> lvl) ^ 1;
-  const uint4* s = reinterpret_cast<const uint4*>(hashes + (base + node) * DW);
-  uint4* d = reinterpret_cast<uint4*>(paths + id * DW);
-#pragma unroll
-  for (int i = 0; i < DW / 4; i++) d[i] = s[i];
+  gather_path_entry<DW>(hashes, np2, lvl, cols[k], paths + id * DW);
 }
 // sharded open_column: rank g's block of the all-gather holds its rows of the n opened columns as [k][rows of g]; the proof
 // wants [k][all rows].  rb[0..G]: first row of every rank (rb[G] = n_rows), device-resident.  One element per thread.
@@ -1005,6 +1039,75 @@ hipError_t launch_gather_paths(const u32* hashes, u64 np2, u32 path_len, const u
   const dim3 grid((unsigned)((tot + 255) / 256));
   if (digest_words == 8) hipLaunchKernelGGL(gather_paths_kernel<8>, grid, dim3(256), 0, st, hashes, np2, path_len, cols, n, paths);
   else hipLaunchKernelGGL(gather_paths_kernel<16>, grid, dim3(256), 0, st, hashes, np2, path_len, cols, n, paths);
+  return hipGetLastError();
+}
+
+// =================================================================================================
+// K5b / K6b: collapse_columns and open_column for a BATCH of equal-shape commitments of one encoder (batch.cpp, the batched prove).
+// The member is a grid dimension -- uniform per workgroup, so every per-member pointer is a scalar operand -- and everything that
+// differs between members (a slab view, an own allocation, a borrowed buffer, a position-major T) is read from a device array of
+// ProveMember descriptors.  The row loops, the split sum, the column and the path moves are the bodies of K5 / K6 above.
+// =================================================================================================
+// member = blockIdx.y: out[member][e] = sum_p parts[member][p][e]
+template <int NL>
+__global__ void __launch_bounds__(256) field_sum_batch_kernel(const u32* parts, u32 n_parts, u64 n_elems, u32* out) {
+  const u64 m = blockIdx.y;
+  field_sum_elem<NL>(parts + m * n_parts * n_elems * NL, n_parts, n_elems, out + m * n_elems * NL);
+}
+hipError_t launch_field_sum_batch(int nl, const u32* parts, u32 n_parts, u64 n_elems, u32* out, u32 n_batch, hipStream_t st) {
+  if (n_batch == 0 || n_elems == 0) return hipSuccess;
+  if (n_batch > 65535 || n_parts == 0) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n_elems + 255) / 256), n_batch);
+  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(field_sum_batch_kernel<NLV>, grid, dim3(256), 0, st, parts, n_parts, n_elems, out));
+  return hipGetLastError();
+}
+// grid (row blocks, opened column of this slice, member); cols / vals point at the slice's first column of member 0
+template <int NL>
+__global__ void __launch_bounds__(256) gather_columns_batch_kernel(const ProveMember* members, u64 n_rows, const u64* cols, u32 n_open,
+                                                                  u32* vals, const u32* r2) {
+  const u32 k = blockIdx.y, m = blockIdx.z;
+  const ProveMember d = members[m];
+  gather_column<NL>(d.comm, n_rows, d.comm_row_stride, d.comm_col_stride, cols[(u64)m * n_open + k],
+                    vals + ((u64)m * n_open + k) * n_rows * NL, d.comm_canon ? r2 : nullptr);
+}
+hipError_t launch_gather_columns_batch(int nl, const ProveMember* members, u32 n_batch, u64 n_rows, const u64* cols, u32 n_open, u32* vals,
+                                       const u32* r2, hipStream_t st) {
+  if (n_batch == 0 || n_open == 0 || n_rows == 0) return hipSuccess;
+  if (n_batch > 65535) return hipErrorInvalidValue;
+  unsigned gx = (unsigned)((n_rows + 255) / 256);
+  if (gx > 64) gx = 64;
+  constexpr u32 SLICE = 32768;                 // grid.y limit: columns in slices, as in launch_gather_columns
+  for (u32 s0 = 0; s0 < n_open; s0 += SLICE) {
+    const u32 cnt = n_open - s0 < SLICE ? n_open - s0 : SLICE;
+    const dim3 grid(gx, cnt, n_batch);
+    const u64* c = cols + s0;
+    u32* v = vals + (u64)s0 * n_rows * nl;
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(gather_columns_batch_kernel<NLV>, grid, dim3(256), 0, st, members, n_rows, c, n_open, v, r2));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// one flat launch over [member][opened column][level]
+template <int DW>
+__global__ void __launch_bounds__(256) gather_paths_batch_kernel(const ProveMember* members, u64 np2, u32 path_len, const u64* cols,
+                                                                u64 total, u64 per_member, u32* paths) {
+  const u64 id = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (id >= total) return;
+  const u64 m = id / per_member;
+  const u32 lvl = (u32)(id % path_len);
+  gather_path_entry<DW>(members[m].hashes, np2, lvl, cols[id / path_len], paths + id * DW);   // cols is [member][n_open]: entry id / path_len
+}
+hipError_t launch_gather_paths_batch(const ProveMember* members, u32 n_batch, u64 np2, u32 path_len, const u64* cols, u32 n_open, u32* paths,
+                                     u32 digest_words, hipStream_t st) {
+  if (digest_words != 8 && digest_words != 16) return hipErrorInvalidValue;
+  const u64 per_member = (u64)n_open * path_len, total = per_member * n_batch;
+  if (total == 0) return hipSuccess;
+  const u64 blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)blocks);
+  if (digest_words == 8) hipLaunchKernelGGL(gather_paths_batch_kernel<8>, grid, dim3(256), 0, st, members, np2, path_len, cols, total, per_member, paths);
+  else hipLaunchKernelGGL(gather_paths_batch_kernel<16>, grid, dim3(256), 0, st, members, np2, path_len, cols, total, per_member, paths);
   return hipGetLastError();
 }
 

@@ -13,7 +13,47 @@ using namespace lcpc;
 
 namespace lcpc {
 
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+ProofLayout proof_layout(const lcpc_ctx* c, uint64_t n_rows) {
+  ProofLayout pl{};
+  pl.n_cols = c->n_cols; pl.np = c->n_per_row; pl.nr = n_rows;
+  pl.n_deg = lcpc_get_n_degree_tests(c); pl.n_open = lcpc_get_n_col_opens(c);
+  pl.path_len = c->path_len;
+  pl.pbytes = pl.np * c->f->L * 8;
+  pl.dl = digest_len(c);
+  pl.col_bytes = 8 + pl.nr * c->f->L * 8 + 8 + (size_t)pl.path_len * (8 + pl.dl);
+  pl.off_eval = 8 + 8; pl.off_rand0 = pl.off_eval + pl.pbytes + 8 + 8;
+  pl.head = 8 + (8 + pl.pbytes) + 8 + pl.n_deg * (8 + pl.pbytes) + 8;
+  pl.total = pl.head + pl.n_open * pl.col_bytes;
+  return pl;
+}
+void proof_write_head(const ProofLayout& pl, uint8_t* out) {
+  auto put64 = [&](size_t off, uint64_t v) { memcpy(out + off, &v, 8); };
+  put64(0, pl.n_cols);
+  put64(8, pl.np);
+  put64(pl.off_eval + pl.pbytes, pl.n_deg);
+  for (uint64_t i = 0; i < pl.n_deg; i++) put64(pl.off_rand0 - 8 + i * (8 + pl.pbytes), pl.np);
+  put64(pl.head - 8, pl.n_open);
+}
+void proof_write_columns(const ProofLayout& pl, uint8_t* out, const uint8_t* paths, const uint64_t* vals, uint64_t k0, uint64_t k1) {
+  const size_t vb = pl.col_bytes - 16 - (size_t)pl.path_len * (8 + pl.dl);     // the values of one column
+  for (uint64_t k = k0; k < k1; k++) {
+    uint8_t* q = out + pl.head + k * pl.col_bytes;
+    auto q64 = [&](uint64_t v) { memcpy(q, &v, 8); q += 8; };
+    q64(pl.nr);
+    if (vals) memcpy(q, reinterpret_cast<const uint8_t*>(vals) + k * vb, vb);
+    q += vb;
+    q64(pl.path_len);
+    for (uint32_t l = 0; l < pl.path_len; l++) { q64(pl.dl); memcpy(q, &paths[((size_t)k * pl.path_len + l) * pl.dl], pl.dl); q += pl.dl; }
+  }
+}
+void draw_columns(Transcript& tr, const lcpc_ctx* c, uint64_t* cols, uint64_t n_open) {
+  uint8_t key[32];
+  tr.challenge_bytes(LBL_CO, 6, key, 32);
+  ChaCha20Rng rng(key);
+  for (uint64_t i = 0; i < n_open; i++) cols[i] = rng.uniform(c->n_cols);
+}
 
 // tr.append_message(label, to_repr(poly[i])) for every coefficient (lib.rs:1045-1047, 1066-1068).  to_repr (Montgomery ->
 // canonical little-endian, lib.rs:47-57) is independent per element: prove (sharded or not) gets it from the device with the
@@ -101,12 +141,9 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   // bincode 1.3 of WrappedLcEvalProof (lib.rs:550-560): n_cols, p_eval, p_random_vec, columns.  The size is known up
   // front, so the proof is written once, straight into the buffer the caller receives: the polynomials by a helper
   // thread while this one runs the (serial) transcript, the opened columns by the device-to-host copy itself.
-  const size_t pbytes = np * L * 8;
-  const size_t dl = digest_len(c);                                            // each path entry: u64 dl | dl bytes (lib.rs:354-372)
-  const size_t col_bytes = 8 + nr * L * 8 + 8 + (size_t)c->path_len * (8 + dl);
-  const size_t off_eval = 8 + 8, off_rand0 = off_eval + pbytes + 8 + 8;      // first element of p_eval / of p_random_vec[0]
-  const size_t head = 8 + (8 + pbytes) + 8 + n_deg * (8 + pbytes) + 8;
-  const size_t total = head + n_open * col_bytes;
+  const ProofLayout pl = proof_layout(c, nr);
+  const size_t pbytes = pl.pbytes, dl = pl.dl, col_bytes = pl.col_bytes, off_eval = pl.off_eval, off_rand0 = pl.off_rand0, head = pl.head,
+               total = pl.total;
   struct Buf { uint8_t* p = nullptr; ~Buf() { proof_buf_free(p); } } out;
   out.p = static_cast<uint8_t*>(proof_buf_alloc(total ? total : 1));
   if (!out.p) return LCPC_ERR_NOMEM;
@@ -120,7 +157,6 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   uint64_t* polys = tensors + a_t;
   uint64_t* canon = polys + a_p;
   std::vector<uint64_t> p_eval_canon;                                         // only when the eval tensor could not be fused
-  auto put64 = [&](size_t off, uint64_t v) { memcpy(out.p + off, &v, 8); };
   std::thread filler;
   JoinGuard join{filler};
   bool have_eval = false;
@@ -185,11 +221,8 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
     absorb_canon(tr, LBL_PE, f, n_deg > 1 ? p_eval_canon.data() : canon + np * L, np);   // lib.rs:1066-1068
   }
   tp[2] = now_ms();
-  uint8_t key[32];
-  tr.challenge_bytes(LBL_CO, 6, key, 32);                                     // lib.rs:1071-1080
-  ChaCha20Rng rng(key);
   std::vector<uint64_t> cols(n_open);
-  for (auto& x : cols) x = rng.uniform(c->n_cols);
+  draw_columns(tr, c, cols.data(), n_open);                                   // lib.rs:1071-1080
   if (cols_opened) memcpy(cols_opened, cols.data(), n_open * 8);
   std::unique_ptr<uint8_t[]> paths(new uint8_t[(size_t)n_open * c->path_len * dl + dl]);
   if (filler.joinable()) filler.join();
@@ -203,21 +236,8 @@ int prove_impl(lcpc_commit_t* m, const uint64_t* outer, uint64_t n_outer, lcpc_t
   }
   if (rc) return rc;
   tp[4] = now_ms();
-  put64(0, c->n_cols);
-  put64(8, np);
-  put64(off_eval + pbytes, n_deg);
-  for (uint64_t i = 0; i < n_deg; i++) put64(off_rand0 - 8 + i * (8 + pbytes), np);
-  put64(head - 8, n_open);
-  parallel_for(n_open, 256, [&](uint64_t b, uint64_t e) {
-    for (uint64_t k = b; k < e; k++) {
-      uint8_t* q = out.p + head + k * col_bytes;
-      auto q64 = [&](uint64_t v) { memcpy(q, &v, 8); q += 8; };
-      q64(nr);
-      q += nr * L * 8;                                                        // the values are already there
-      q64(c->path_len);
-      for (uint32_t l = 0; l < c->path_len; l++) { q64(dl); memcpy(q, &paths[((size_t)k * c->path_len + l) * dl], dl); q += dl; }
-    }
-  });
+  proof_write_head(pl, out.p);
+  parallel_for(n_open, 256, [&](uint64_t b, uint64_t e) { proof_write_columns(pl, out.p, paths.get(), nullptr, b, e); });   // the values are already there
   *proof = out.p; *proof_len = total;
   out.p = nullptr;
   if (dbg)
