@@ -92,7 +92,7 @@
  *    max(1, floor(budget / A)) members, ceil(n_batch / that) groups in all, each a lockstep pipeline of its own.  Same results;
  *    stats.groups says how many.  (The arena stays with cms[0]'s working set until that object is destroyed.)
  *  - timing: with LCPC_DEBUG_TIMING set when the encoder was created the call prints one line for the batch to stderr.
- *  Out of scope: sharded encoders (LCPC_ERR_STATE); a batched verify; any change to proof format or protocol, such as a random linear
+ *  Out of scope: sharded encoders (LCPC_ERR_STATE); the batched verify, which is lcpc_hip_verify.h's; any change to proof format or protocol, such as a random linear
  *  combination of the members into one proof -- the reference has none, and byte parity would have nothing to stand on.
  */
 #ifndef LCPC_HIP_BATCH_H

@@ -547,6 +547,55 @@ class LcEvalProof:
         return out
 
 
+def verify_batch(enc, roots, outer_tensor, inner_tensor, proofs, trs, return_stats=False):
+    """lcpcv_verify_batch (include/lcpc_hip_verify.h): LcEvalProof::verify for every proof of a batch in one lockstep pipeline -- one
+    row encode, one column-hash launch chain and one column-check kernel for all members, their transcripts side by side on the host
+    pool.  roots: one root per member; proofs: LcEvalProof objects or bytes; trs: one Transcript per member.  outer_tensor /
+    inner_tensor: (n, L) -- one tensor for all members -- or (n_batch, n, L), one per member.  Returns (evals (n_batch, L) uint64,
+    status (n_batch,) int32): status[i] is 0 or the VERR_* code proofs[i].verify(roots[i], outer_i, inner_i, enc, trs[i]) raises, and
+    evals[i] its evaluation when status[i] == 0 (return_stats: and the call's LcpcvVerifyStats).  Raises LcpcError only when the call
+    itself fails (arguments, device)."""
+    roots, proofs, trs = list(roots), list(proofs), list(trs)
+    n_batch = len(proofs)
+    if n_batch == 0 or len(trs) != n_batch or len(roots) != n_batch:
+        raise LcpcError(ERR_ARG)
+
+    def tensor(t):
+        t = np.ascontiguousarray(t, dtype=np.uint64)
+        if t.ndim == 3:
+            if t.shape[0] != n_batch or t.shape[2] != enc.L:
+                raise LcpcError(ERR_ARG)
+            return t, t.shape[1], t.shape[1]
+        t = _elems(t, enc.L)
+        return t, t.size // enc.L, 0
+
+    o, n_outer, o_stride = tensor(outer_tensor)
+    i, n_inner, i_stride = tensor(inner_tensor)
+    # the library reads the encoder's digest length of every root: a shorter one is zero-filled (it cannot match), a longer one cut
+    rootb = np.zeros((n_batch, enc.digest_len), np.uint8)
+    for k, r in enumerate(roots):
+        rb = bytes(r)[:enc.digest_len]
+        rootb[k, :len(rb)] = np.frombuffer(rb, np.uint8)
+    bufs = []
+    for pf in proofs:
+        if isinstance(pf, LcEvalProof):
+            bufs.append(np.frombuffer(pf._own.view if pf._own else pf._bytes, np.uint8))
+        else:
+            bufs.append(np.frombuffer(pf, np.uint8))
+    empty = np.zeros(8, np.uint8)             # (an empty proof is a member's VERR_MALFORMED, not a NULL argument)
+    pp = (C.c_void_p * n_batch)(*[b.ctypes.data if b.size else empty.ctypes.data for b in bufs])
+    plen = (C.c_uint64 * n_batch)(*[b.size for b in bufs])
+    th = (C.c_void_p * n_batch)(*[tr._h for tr in trs])
+    evals = np.zeros((n_batch, enc.L), np.uint64)
+    status = np.zeros(n_batch, np.int32)
+    stats = _lib.LcpcvVerifyStats()
+    rc = _lib.lib().lcpcv_verify_batch(enc._h, n_batch, _ptr(rootb), _ptr(o), n_outer, o_stride, _ptr(i), n_inner, i_stride, pp, plen, th,
+                                       _ptr(evals), _ptr(status), C.byref(stats))
+    if rc:
+        raise LcpcError(rc, _lib.lib().lcpc_last_error(enc._h).decode())
+    return (evals, status, stats) if return_stats else (evals, status)
+
+
 def root_bincode(root):
     """bincode of LcRoot (lib.rs:373-384): u64 len | the digest (40 bytes; 72 for a 64-byte BLAKE2b root)"""
     if len(root) == 64:

@@ -107,6 +107,22 @@ BATCH_SYMBOLS = {
                                  C.POINTER(LcpcxProveStats)]),
 }
 
+# the verifier-side extension (include/lcpc_hip_verify.h): again its own prefix, table and version
+VERIFY_VERSION = 1
+
+
+class LcpcvVerifyStats(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("encode_launches", C.c_uint32), ("hash_launches", C.c_uint32), ("check_launches", C.c_uint32),
+                ("host_syncs", C.c_uint32)]
+
+
+VERIFY_ARENA_BUDGET = 64 << 20     # LCPCV_ARENA_BUDGET
+VERIFY_SYMBOLS = {
+    "lcpcv_version": (_i32, []),
+    "lcpcv_verify_batch": (_i32, [_vp, _u32, _vp, _vp, _u64, _u64, _vp, _u64, _u64, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), _vp,
+                                  _vp, C.POINTER(LcpcvVerifyStats)]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -144,5 +160,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcx_batch_version() != BATCH_VERSION:
             raise RuntimeError("lcpc_amd: batch extension version mismatch")
+        for name, (res, args) in VERIFY_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcv_version() != VERIFY_VERSION:
+            raise RuntimeError("lcpc_amd: verify extension version mismatch")
         _lib = L
     return _lib

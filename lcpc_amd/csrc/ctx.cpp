@@ -25,6 +25,7 @@ static void ctx_free(lcpc_ctx* c) {
   dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_roots); dev_free(c->d_r2);
   dev_free(c->ws.d_tmp); dev_free(c->ws.d_t); dev_free(c->ws.d_mid); dev_free(c->d_scratch);
   c->verify_sets.clear();
+  c->verify_batch_sets.clear();
   if (c->s_verify) (void)hipStreamDestroy(c->s_verify);
   for (unsigned k = 0; k < lcpc_ctx::N_STAGE; k++) {
     if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);

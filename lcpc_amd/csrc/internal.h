@@ -6,6 +6,7 @@
 //   commit.cpp  lcpc_commit  = an LcCommit<D, E> (lcpc-2d lib.rs:172-184): comm / coeffs / hashes in HBM, created by
 //                              commit(), consumed by prove / open_column / collapse_columns.
 //   prove.cpp   transcript wrappers, prove (lib.rs:1004-1093), verify (lib.rs:832-1000), bincode (lib.rs:550-609)
+//   verify_batch.cpp  lcpcv_verify_batch (include/lcpc_hip_verify.h): the verifier's batch call over K7b
 //   shard.cpp   row-sharded commit / prove across GPUs and the RCCL exchange
 #pragma once
 #include "../../include/lcpc_hip.h"
@@ -159,6 +160,23 @@ struct VerifySet {
   int make() { return 0; }
   void quiesce() {}
   ~VerifySet() { if (h_pin) (void)hipHostFree(h_pin); }
+};
+
+// lcpcv_verify_batch's working set (verify_batch.cpp): its own non-blocking stream, the event behind the row encode, the pinned arena of
+// a group and the device buffers of a group.  Batch verifies under one encoder run side by side, each in its own.
+struct VerifyBatchSet {
+  bool busy = false;
+  uint8_t* h_pin = nullptr;
+  uint64_t h_pin_cap = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev_enc = nullptr;     // recorded behind the row encode: the encoder's lock is held until it has fired
+  uint8_t* d = nullptr;            // [polys][encoded rows][columns][canonical columns][tensors][drawn][status][digests (+ CVs)]
+  uint64_t d_cap = 0;
+  uint32_t* t29 = nullptr;         // Ft255: the tensors in the 29-bit-limb form
+  uint64_t t29_cap = 0;
+  int make();
+  void quiesce() { (void)hipStreamSynchronize(st); }
+  ~VerifyBatchSet();
 };
 
 // Working sets of concurrent calls on one object.  A call takes a set on entry (take) and hands it back on exit (SetLease).
@@ -323,6 +341,9 @@ struct lcpc_ctx {
   // verify run on s_verify under `mu` (ws / d_scratch above), which is held only around that encode's enqueue and synchronisation
   lcpc::SetPool<lcpc::VerifySet> verify_sets;
   hipStream_t s_verify = nullptr;  // non-blocking
+  // lcpcv_verify_batch (include/lcpc_hip_verify.h): one working set per running call; its row encode runs on the set's stream under
+  // `mu` (ws above), which is held until that encode's event has fired
+  lcpc::SetPool<lcpc::VerifyBatchSet> verify_batch_sets;
   // lcpc_commit from PAGEABLE host memory (commit.cpp upload_host): a ring of pinned bounce buffers the host pool fills while
   // the previous slices cross the bus.  stage_mu is held per upload call (one row batch of one commit); the buffers are kept between commits
   // (up to 4 x 64 MiB of pinned host memory per encoder that has taken a pageable source; LCPC_HOST_STAGE=1 pins the first two at lcpc_ctx_create).
@@ -594,5 +615,22 @@ void proof_write_columns(const ProofLayout& pl, uint8_t* out, const uint8_t* pat
 // the column challenge (lib.rs:1071-1080)
 void draw_columns(Transcript& tr, const lcpc_ctx* c, uint64_t* cols, uint64_t n_open);
 double now_ms();
+// What the single verify and the batched one (verify_batch.cpp) share.
+// A proof's bincode (lib.rs:550-560) read in place: every vector a view into the proof bytes (or into `realigned`, the one copy made of a
+// proof handed over at an odd address -- every field of the wire layout sits at a multiple of 8 bytes).
+struct ProofView {
+  struct Vec { const uint64_t* p = nullptr; uint64_t n = 0; const uint64_t* data() const { return p; } uint64_t size() const { return n; } };   // n: 64-bit words
+  struct Path { const uint8_t* p = nullptr; uint64_t n = 0; };   // n entries of (u64 dl, dl bytes): digest k at p + (8 + dl) k + 8
+  uint64_t n_cols = 0, n_per_row = 0, n_rows = 0;
+  Vec p_eval;
+  std::vector<Vec> p_random, cols;
+  std::vector<Path> paths;
+  std::vector<uint64_t> realigned;
+};
+// the wire layout, then the checks of lib.rs:845-860 against the encoder and the tensor lengths, in lcpc_verify's order: 0 or the
+// LCPC_VERR_* code lcpc_verify returns.  The limbs are not looked at (all_reduced, or the caller's own pass over them).
+int parse_proof(const lcpc_ctx* c, const uint8_t* proof, uint64_t proof_len, uint64_t n_outer, uint64_t n_inner, ProofView* out);
+// D(in) with the encoder's digest (LCPC_HASH_*): 32 bytes into out, 64 for BLAKE2b
+void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out);
 
 }  // namespace lcpc

@@ -237,6 +237,29 @@ hipError_t launch_gather_columns_batch(int nl, const ProveMember* members, uint3
 hipError_t launch_gather_paths_batch(const ProveMember* members, uint32_t n_batch, uint64_t np2, uint32_t path_len, const uint64_t* cols,
                                      uint32_t n_open, uint32_t* paths, uint32_t digest_words, hipStream_t st);
 
+// ---- K7b: the column check of the batched verify (verify_batch.cpp): verify_column_value (lib.rs:985-1000) for every opened column of
+// every member and every tensor in one launch.  acc_d = sum_k tensors[d][k] * cols[i][k] mod p is compared, as a fully reduced
+// Montgomery element, with enc[d][drawn[i]].  One wave per (member, opened column): the lanes run over consecutive rows of the column,
+// every column element is loaded once and multiplied with up to 4 tensors (n_t > 4: again for every further 4), the lanes' partial
+// sums are combined across the wave.  The member is grid dimension y; n_open is sliced at the grid limit of x.
+// Alignment: cols, tensors and enc are aligned as elements are (fe_load: 16 bytes for Ft127 / Ft255, 8 for Ft63 / Ft191), tensors29 to
+// 16 bytes; cols_stride counts whole elements, so every member's are.  A drawn column number >= n_cols reads nothing of enc and sets
+// every bit the launch can set.
+struct VerifyColsArgs {
+  const uint32_t* cols;        // [member][n_open][n_rows] Montgomery elements; member stride in elements
+  uint64_t cols_stride;
+  const uint32_t* tensors;     // [member][n_t][n_rows]
+  const uint32_t* tensors29;   // Ft255: the 29-bit-limb form (launch_to_r29), else null
+  const uint32_t* enc;         // [member][n_t][n_cols] encoded rows
+  const uint64_t* drawn;       // [member][n_open] column numbers
+  uint32_t* status;            // [member][n_open]: bit 0 = some degree-test row differs, bit 1 = the eval row differs
+  uint64_t n_rows, n_cols;
+  uint32_t n_open, n_t, n_batch;   // n_t = n_deg + 1, the LAST tensor is the outer tensor
+};
+// nl = 2 / 4 / 6 / 8; Ft255 needs tensors29.  n_batch > 65535 or n_t == 0 with work to do is hipErrorInvalidValue, checked before
+// any launch; empty work (n_batch == 0 or n_open == 0) is hipSuccess
+hipError_t launch_verify_columns_batch(int nl, const VerifyColsArgs& a, hipStream_t st);
+
 // Brakedown: y[row][out_off + o] = sum_k vals[k] * x[row][in_off + colidx[k]], k in [rowptr[o], rowptr[o+1])
 struct SpmvArgs {
   uint32_t* mat;                // comm (row-major, stride elements per row); in and out segments are disjoint

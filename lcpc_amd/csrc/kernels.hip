@@ -1112,6 +1112,129 @@ hipError_t launch_gather_paths_batch(const ProveMember* members, u32 n_batch, u6
 }
 
 // =================================================================================================
+// K7b: the column check of the batched verify (verify_batch.cpp): verify_column_value (lib.rs:985-1000) for every opened column of
+// every member.  One wave per (member, opened column i), four of them per workgroup; lane l takes rows l, l + 64, .. of the column, which
+// is contiguous, so a wave's loads of the column and of the tensors are whole lines.  A column element is loaded once and multiplied
+// with up to VC_NT tensors; a lane accumulates its terms unreduced as the collapse kernels do (K5: Wide<NL>, reduced every 8 terms;
+// Ft255: ln::lazy_mac on the tensors' 29-bit-limb form, normalised every 6 terms and reduced every 60), the lanes' sums -- exact field
+// elements -- are added across the wave with lane shuffles, and the total, a fully reduced Montgomery element like the encoded row's
+// entry, is compared limb by limb.  No barrier, no LDS of its own: a wave past the last column leaves at once.
+// =================================================================================================
+constexpr int VC_NT = 4;           // tensors per pass over a column (n_t = 1 + n_degree_tests <= 4 for every encoder the four fields give)
+template <int NL> LCPC_DEV Fe<NL> wave_sum(Fe<NL> a) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    Fe<NL> b;
+#pragma unroll
+    for (int i = 0; i < NL; i++) b.v[i] = (u32)__shfl_xor((int)a.v[i], off, 64);
+    a = fe_add<NL>(a, b);
+  }
+  return a;
+}
+// this lane's share of <tensor d0 + t, column>, t < NT: rows lane, lane + 64, ..
+template <int NL, int NT>
+LCPC_DEV void verify_cols_dots(const VerifyColsArgs& a, const u32* col, const u32* tens, const u32* tens29, u32 d0, u32 lane, Fe<NL>* acc) {
+#pragma unroll
+  for (int t = 0; t < NT; t++) acc[t] = fe_zero<NL>();
+  if constexpr (NL == 8) {
+    for (u64 rb = lane; rb < a.n_rows; rb += 64 * 60) {
+      ln::LazyN<L255> w[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) ln::lazy_zero(w[t]);
+      u32 since = 0;
+      for (u32 k = 0; k < 60; k++) {
+        const u64 r = rb + 64 * (u64)k;
+        if (r >= a.n_rows) break;
+        const LN<9> x = ln::from_packed<L255>(fe_load<8>(col + r * 8));
+#pragma unroll
+        for (int t = 0; t < NT; t++) ln::lazy_mac(w[t], x, ln::load_limbs<9>(tens29 + ((u64)(d0 + t) * a.n_rows + r) * 12));
+        if (++since == 6) {
+#pragma unroll
+          for (int t = 0; t < NT; t++) ln::lazy_normalize(w[t]);
+          since = 0;
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < NT; t++) acc[t] = fe_add<8>(acc[t], ln::lazy_reduce(w[t]));
+    }
+  } else {
+    constexpr u32 BATCH = 8;
+    for (u64 rb = lane; rb < a.n_rows; rb += 64 * BATCH) {
+      Wide<NL> w[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) w[t] = wide_zero<NL>();
+      for (u32 k = 0; k < BATCH; k++) {
+        const u64 r = rb + 64 * (u64)k;
+        if (r >= a.n_rows) break;
+        const Fe<NL> x = fe_load<NL>(col + r * NL);
+#pragma unroll
+        for (int t = 0; t < NT; t++) wide_mac<NL>(w[t], x, fe_load<NL>(tens + ((u64)(d0 + t) * a.n_rows + r) * NL));
+      }
+#pragma unroll
+      for (int t = 0; t < NT; t++) acc[t] = fe_add<NL>(acc[t], wide_reduce<NL>(w[t]));
+    }
+  }
+}
+// tensors [d0, d0 + NT) against column cn of the member's encoded rows -> the status bits they set
+template <int NL, int NT>
+LCPC_DEV u32 verify_cols_pass(const VerifyColsArgs& a, const u32* col, const u32* tens, const u32* tens29, const u32* enc, u64 cn, u32 d0, u32 lane) {
+  Fe<NL> acc[NT];
+  verify_cols_dots<NL, NT>(a, col, tens, tens29, d0, lane, acc);
+  u32 bits = 0;
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    const Fe<NL> s = wave_sum<NL>(acc[t]);
+    const Fe<NL> e = fe_load<NL>(enc + ((u64)(d0 + t) * a.n_cols + cn) * NL);
+    u32 diff = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) diff |= s.v[i] ^ e.v[i];
+    if (diff) bits |= d0 + t + 1 == a.n_t ? 2u : 1u;
+  }
+  return bits;
+}
+template <int NL>
+__global__ void __launch_bounds__(256) verify_columns_batch_kernel(VerifyColsArgs a, u32 open0) {
+  const u32 lane = threadIdx.x & 63;
+  const u64 i = (u64)open0 + (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n_open) return;                     // (wave-uniform)
+  const u64 m = blockIdx.y;
+  const u64 slot = m * a.n_open + i;
+  const u64 cn = a.drawn[slot];
+  if (cn >= a.n_cols) {                          // no such column: nothing of enc is read, every row counts as differing
+    if (lane == 0) a.status[slot] = (a.n_t > 1 ? 1u : 0u) | 2u;
+    return;
+  }
+  const u32* col = a.cols + (m * a.cols_stride + i * a.n_rows) * NL;
+  const u32* tens = a.tensors + m * a.n_t * a.n_rows * NL;
+  const u32* tens29 = NL == 8 ? a.tensors29 + m * a.n_t * a.n_rows * 12 : nullptr;
+  const u32* enc = a.enc + m * a.n_t * a.n_cols * NL;
+  u32 bits = 0;
+  for (u32 d0 = 0; d0 < a.n_t; d0 += VC_NT) {
+    switch (a.n_t - d0) {
+      case 1: bits |= verify_cols_pass<NL, 1>(a, col, tens, tens29, enc, cn, d0, lane); break;
+      case 2: bits |= verify_cols_pass<NL, 2>(a, col, tens, tens29, enc, cn, d0, lane); break;
+      case 3: bits |= verify_cols_pass<NL, 3>(a, col, tens, tens29, enc, cn, d0, lane); break;
+      default: bits |= verify_cols_pass<NL, VC_NT>(a, col, tens, tens29, enc, cn, d0, lane); break;
+    }
+  }
+  if (lane == 0) a.status[slot] = bits;
+}
+hipError_t launch_verify_columns_batch(int nl, const VerifyColsArgs& a, hipStream_t st) {
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
+  if (a.n_batch == 0 || a.n_open == 0) return hipSuccess;
+  if (a.n_batch > 65535 || a.n_t == 0 || (nl == 8 && a.tensors29 == nullptr)) return hipErrorInvalidValue;
+  constexpr u32 SLICE = 1u << 20;                // opened columns per launch: 2^18 workgroups of four
+  for (u32 o0 = 0; o0 < a.n_open; o0 += SLICE) {
+    const u32 cnt = a.n_open - o0 < SLICE ? a.n_open - o0 : SLICE;
+    const dim3 grid((cnt + 3) / 4, a.n_batch);
+    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(verify_columns_batch_kernel<NLV>, grid, dim3(256), 0, st, a, o0));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// =================================================================================================
 // K2: Brakedown expander code.  The reference multiplies a CSC matrix by one row at a time
 // (sprs CsMat::dot, encode.rs:50-55); here the matrix is stored CSR-by-output and applied to all
 // rows of the commitment in one launch: lane = output index o (consecutive lanes write consecutive

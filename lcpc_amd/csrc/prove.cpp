@@ -252,6 +252,7 @@ struct Rd {
   uint64_t u64_() { uint64_t v = 0; if (pos + 8 > len) { bad = true; return 0; } memcpy(&v, p + pos, 8); pos += 8; return v; }
   const uint8_t* take(uint64_t n) { if (n > len - pos) { bad = true; return nullptr; } const uint8_t* q = p + pos; pos += n; return q; }
 };
+}  // namespace
 // D(in) with the encoder's digest: 32 bytes into out, 64 for BLAKE2b
 void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out) {
   if (hash == LCPC_HASH_SHA3_256) sha3_256_host(in, len, out);
@@ -260,6 +261,67 @@ void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out) {
   else if (hash == LCPC_HASH_SHA256) sha256_host(in, len, out);
   else blake3_host(in, len, out);
 }
+int parse_proof(const lcpc_ctx* c, const uint8_t* proof, uint64_t proof_len, uint64_t n_outer, uint64_t n_inner, ProofView* out) {
+  const int L = c->f->L;
+  const uint64_t F = 8 * L, dl = digest_len(c);
+  ProofView& v = *out;
+  // every field of the wire layout sits at a multiple of 8 bytes, so the vectors are read in place (a proof handed over
+  // at an odd address is copied once)
+  if (reinterpret_cast<uintptr_t>(proof) % 8 != 0) {
+    v.realigned.resize((proof_len + 7) / 8);
+    memcpy(v.realigned.data(), proof, proof_len);
+    proof = reinterpret_cast<const uint8_t*>(v.realigned.data());
+  }
+  Rd r{proof, proof_len};
+  const uint64_t n_cols = r.u64_();
+  const uint64_t n_per_row = r.u64_();
+  if (r.bad || n_per_row > proof_len / F) return LCPC_VERR_MALFORMED;
+  using View = ProofView::Vec;
+  { const uint8_t* q = r.take(n_per_row * F); if (!q) return LCPC_VERR_MALFORMED; v.p_eval = View{reinterpret_cast<const uint64_t*>(q), n_per_row * L}; }
+  const uint64_t n_deg_pf = r.u64_();
+  if (r.bad || n_deg_pf > 4096) return LCPC_VERR_MALFORMED;
+  v.p_random.assign(n_deg_pf, View{});
+  for (auto& pv : v.p_random) {
+    const uint64_t l = r.u64_();
+    if (r.bad || l > proof_len / F) return LCPC_VERR_MALFORMED;
+    const uint8_t* q = r.take(l * F);
+    if (!q) return LCPC_VERR_MALFORMED;
+    pv = View{reinterpret_cast<const uint64_t*>(q), l * L};
+  }
+  const uint64_t n_columns = r.u64_();
+  if (r.bad || n_columns > proof_len / 8) return LCPC_VERR_MALFORMED;
+  v.cols.assign(n_columns, View{});
+  v.paths.assign(n_columns, ProofView::Path{});
+  for (uint64_t i = 0; i < n_columns; i++) {
+    const uint64_t l = r.u64_();
+    if (r.bad || l > proof_len / F) return LCPC_VERR_MALFORMED;
+    const uint8_t* q = r.take(l * F);
+    if (!q) return LCPC_VERR_MALFORMED;
+    v.cols[i] = View{reinterpret_cast<const uint64_t*>(q), l * L};
+    const uint64_t pl = r.u64_();
+    if (r.bad || pl > proof_len / (8 + dl)) return LCPC_VERR_MALFORMED;
+    v.paths[i].p = proof + r.pos;
+    v.paths[i].n = pl;
+    for (uint64_t k = 0; k < pl; k++) {
+      const uint64_t el = r.u64_();
+      if (r.bad || el != dl || !r.take(dl)) return LCPC_VERR_MALFORMED;     // every entry is one Output<D> of the encoder's digest
+    }
+  }
+  // (bytes after the last column are ignored, as by bincode::deserialize, whose legacy options allow trailing bytes)
+  const uint64_t n_col_opens = lcpc_get_n_col_opens(c);                        // lib.rs:845-860
+  if (n_col_opens != n_columns || n_col_opens == 0) return LCPC_VERR_NUM_COL_OPENS;
+  const uint64_t n_rows = v.cols[0].size() / L;
+  v.n_cols = n_cols; v.n_per_row = n_per_row; v.n_rows = n_rows;
+  if (n_inner != n_per_row) return LCPC_VERR_INNER_TENSOR;
+  if (n_outer != n_rows) return LCPC_VERR_OUTER_TENSOR;
+  if (!lcpc_dims_ok(c, n_per_row, n_cols)) return LCPC_VERR_ENCODING_DIMS;
+  const uint64_t n_deg = lcpc_get_n_degree_tests(c);
+  if (n_deg_pf < n_deg) return LCPC_VERR_MALFORMED;                            // reference indexes p_random_vec[i] (would panic)
+  for (uint64_t i = 0; i < n_deg; i++) if (v.p_random[i].size() != n_per_row * L) return LCPC_VERR_MALFORMED;
+  for (auto& cv : v.cols) if (cv.size() != n_rows * L) return LCPC_VERR_MALFORMED;
+  return 0;
+}
+namespace {
 // D(Output<D>::default() || to_repr(col[0]) || ...) with the encoder's digest (lib.rs:719-735): a prefix of dl zero bytes
 void hash_column_host(const FieldDesc& f, uint32_t hash, const uint64_t* col, uint64_t n_rows, uint8_t* out) {
   const size_t dl = hash == LCPC_HASH_BLAKE2B ? 64 : 32;
@@ -326,62 +388,14 @@ int lcpc_verify(lcpc_ctx* c, const uint8_t root[32], const uint64_t* outer, uint
   Transcript& tr = trw->t;
   const bool dbg = c->sw_debug_timing;
   double tv[6] = {now_ms(), 0, 0, 0, 0, 0};
-  // every field of the wire layout sits at a multiple of 8 bytes, so the vectors are read in place (a proof handed over
-  // at an odd address is copied once)
-  std::vector<uint64_t> realigned;
-  if (reinterpret_cast<uintptr_t>(proof) % 8 != 0) {
-    realigned.resize((proof_len + 7) / 8);
-    memcpy(realigned.data(), proof, proof_len);
-    proof = reinterpret_cast<const uint8_t*>(realigned.data());
-  }
-  Rd r{proof, proof_len};
-  const uint64_t n_cols = r.u64_();
-  const uint64_t n_per_row = r.u64_();
-  if (r.bad || n_per_row > proof_len / F) return LCPC_VERR_MALFORMED;
-  struct View { const uint64_t* p = nullptr; uint64_t n = 0; const uint64_t* data() const { return p; } uint64_t size() const { return n; } };
-  View p_eval;
-  { const uint8_t* q = r.take(n_per_row * F); if (!q) return LCPC_VERR_MALFORMED; p_eval = View{reinterpret_cast<const uint64_t*>(q), n_per_row * L}; }
-  const uint64_t n_deg_pf = r.u64_();
-  if (r.bad || n_deg_pf > 4096) return LCPC_VERR_MALFORMED;
-  std::vector<View> p_random(n_deg_pf);
-  for (auto& v : p_random) {
-    const uint64_t l = r.u64_();
-    if (r.bad || l > proof_len / F) return LCPC_VERR_MALFORMED;
-    const uint8_t* q = r.take(l * F);
-    if (!q) return LCPC_VERR_MALFORMED;
-    v = View{reinterpret_cast<const uint64_t*>(q), l * L};
-  }
-  const uint64_t n_columns = r.u64_();
-  if (r.bad || n_columns > proof_len / 8) return LCPC_VERR_MALFORMED;
-  std::vector<View> cols(n_columns);
-  struct PathView { const uint8_t* p = nullptr; uint64_t n = 0; };      // n entries of (u64 dl, dl bytes): digest k at p + (8 + dl) k + 8
-  std::vector<PathView> paths(n_columns);
-  for (uint64_t i = 0; i < n_columns; i++) {
-    const uint64_t l = r.u64_();
-    if (r.bad || l > proof_len / F) return LCPC_VERR_MALFORMED;
-    const uint8_t* q = r.take(l * F);
-    if (!q) return LCPC_VERR_MALFORMED;
-    cols[i] = View{reinterpret_cast<const uint64_t*>(q), l * L};
-    const uint64_t pl = r.u64_();
-    if (r.bad || pl > proof_len / (8 + dl)) return LCPC_VERR_MALFORMED;
-    paths[i].p = proof + r.pos;
-    paths[i].n = pl;
-    for (uint64_t k = 0; k < pl; k++) {
-      const uint64_t el = r.u64_();
-      if (r.bad || el != dl || !r.take(dl)) return LCPC_VERR_MALFORMED;     // every entry is one Output<D> of the encoder's digest
-    }
-  }
-  // (bytes after the last column are ignored, as by bincode::deserialize, whose legacy options allow trailing bytes)
-  const uint64_t n_col_opens = lcpc_get_n_col_opens(c);                        // lib.rs:845-860
-  if (n_col_opens != n_columns || n_col_opens == 0) return LCPC_VERR_NUM_COL_OPENS;
-  const uint64_t n_rows = cols[0].size() / L;
-  if (n_inner != n_per_row) return LCPC_VERR_INNER_TENSOR;
-  if (n_outer != n_rows) return LCPC_VERR_OUTER_TENSOR;
-  if (!lcpc_dims_ok(c, n_per_row, n_cols)) return LCPC_VERR_ENCODING_DIMS;
+  ProofView pv;
+  if (const int prc = parse_proof(c, proof, proof_len, n_outer, n_inner, &pv)) return prc;
+  const uint64_t n_cols = pv.n_cols, n_per_row = pv.n_per_row, n_rows = pv.n_rows;
+  const ProofView::Vec& p_eval = pv.p_eval;
+  const std::vector<ProofView::Vec>&p_random = pv.p_random, &cols = pv.cols;
+  const std::vector<ProofView::Path>& paths = pv.paths;
+  const uint64_t n_deg_pf = p_random.size(), n_columns = cols.size();
   const uint64_t n_deg = lcpc_get_n_degree_tests(c);
-  if (n_deg_pf < n_deg) return LCPC_VERR_MALFORMED;                            // reference indexes p_random_vec[i] (would panic)
-  for (uint64_t i = 0; i < n_deg; i++) if (p_random[i].size() != n_per_row * L) return LCPC_VERR_MALFORMED;
-  for (auto& cv : cols) if (cv.size() != n_rows * L) return LCPC_VERR_MALFORMED;
   // untrusted limbs: nothing >= p reaches the device arithmetic (the polynomials are checked before they are sent; the
   // columns, which only meet host arithmetic, are checked by the side thread below)
   if (!all_reduced(f, p_eval.data(), n_per_row)) return LCPC_VERR_MALFORMED;
