@@ -203,37 +203,59 @@ struct CollapseArgs {
   const ProveMember* members = nullptr;
   uint32_t n_batch = 0;
 };
+// Every launcher of K5 / K6 below settles what it will not run BEFORE any launch: empty work is hipSuccess with nothing launched, a
+// job no grid can carry (or no kernel is built for) is hipErrorInvalidValue with nothing launched.  Each states its own cases.
+//
+// nl = 2 / 4 / 6 / 8, n_tensors = 1 or 2, 1 <= n_splits <= 65535 (grid y), j0 < j1 <= n_per_row after the defaults, and with members
+// non-null 1 <= n_batch <= 65535 (grid z): anything else is hipErrorInvalidValue, checked before any launch.  A split that holds no
+// row (ceil(n_rows / n_splits) * split >= n_rows) writes zeros.  Ft255 with tensors29 == null runs the Montgomery-word kernel of the
+// other fields: same values, slower.
 hipError_t launch_collapse(int nl, const CollapseArgs& a, hipStream_t st);
-// Ft255 tensors (Montgomery) -> the 29-bit-limb / 2^261 form used by the lazy dot-product kernels
+// Ft255 tensors (Montgomery) -> the 29-bit-limb / 2^261 form used by the lazy dot-product kernels: nine 29-bit limbs of 32 t mod p and
+// three zero words per entry.  n == 0 is hipSuccess, nothing launched
 hipError_t launch_to_r29(const uint32_t* in, uint64_t n, uint32_t* out, hipStream_t st);
-// out[e] = sum_p parts[p][e] mod p
+// out[e] = sum_p parts[p][e] mod p.  n_elems == 0 is hipSuccess, nothing launched; otherwise n_parts == 0 or a bad nl is
+// hipErrorInvalidValue, checked before any launch
 hipError_t launch_field_sum(int nl, const uint32_t* parts, uint32_t n_parts, uint64_t n_elems, uint32_t* out, hipStream_t st);
 
 // open_column: vals[k][r] = comm[r][cols[k]]; paths[k][lvl] = sibling digest.  r2 non-null: comm holds canonical
 // values, multiply by R^2 on the way out so that vals are Montgomery-form elements like everything else at the ABI
 // element (r, c) at comm + (r * row_stride + c * col_stride) elements (row-major comm: n_cols, 1; position-major: 1, n_rows)
+// n == 0 or n_rows == 0 is hipSuccess, nothing launched; otherwise a bad nl is hipErrorInvalidValue, checked before any launch.
+// n in slices of 32768 (grid y); more than 16384 rows: a grid-stride loop over 64 row blocks
 hipError_t launch_gather_columns(int nl, const uint32_t* comm, uint64_t n_rows, uint64_t row_stride, uint64_t col_stride,
                                  const uint64_t* cols, uint32_t n, uint32_t* vals, const uint32_t* r2, hipStream_t st);
 // elementwise representation change of n elements (in may equal out): to_mont = x * R (r2 = R^2 mod p, Montgomery
 // multiply), to_canon = x * R^-1 (Montgomery reduction = PrimeField::to_repr without the byte dump)
+// n == 0 is hipSuccess, nothing launched; otherwise a bad nl is hipErrorInvalidValue, checked before any launch
 hipError_t launch_to_mont(int nl, const uint32_t* in, uint64_t n, const uint32_t* r2, uint32_t* out, hipStream_t st);
 hipError_t launch_to_canon(int nl, const uint32_t* in, uint64_t n, uint32_t* out, hipStream_t st);
 // sharded open_column: [rank][k][rows of rank] (blocks of block_words) -> [k][all rows]; rb: G + 1 row boundaries on the device
+// (rb[0] = 0, non-decreasing, rb[G] = n_rows: a rank may hold no row).  n == 0 or n_rows == 0 is hipSuccess, nothing launched;
+// otherwise a bad nl is hipErrorInvalidValue, checked before any launch
 hipError_t launch_assemble_columns(int nl, const uint32_t* recv, uint64_t block_words, const uint64_t* rb, uint32_t G, uint32_t n,
                                    uint64_t n_rows, uint32_t* out, hipStream_t st);
 // digest_words = 8 or 16 (ChainShape.digest_words; BLAKE3: 8): paths [n][path_len][digest_words]
+// digest_words other than 8 or 16 is hipErrorInvalidValue, whatever else is asked; otherwise n == 0 or path_len == 0 is hipSuccess,
+// nothing launched
 hipError_t launch_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t path_len, const uint64_t* cols, uint32_t n,
                                uint32_t* paths, uint32_t digest_words, hipStream_t st);
 
 // ---- K5b / K6b: the batch forms of the split sum and the gathers (the batch form of collapse: CollapseArgs.members) -------------
 // out[member][e] = sum_p parts[member][p][e] mod p (member = blockIdx.y)
+// n_batch == 0 or n_elems == 0 is hipSuccess, nothing launched; otherwise n_batch > 65535, n_parts == 0 or a bad nl is
+// hipErrorInvalidValue, checked before any launch
 hipError_t launch_field_sum_batch(int nl, const uint32_t* parts, uint32_t n_parts, uint64_t n_elems, uint32_t* out, uint32_t n_batch,
                                   hipStream_t st);
 // vals[member][k][r] = comm_member[r][cols[member][k]]; grid (row blocks, opened column, member), n_open in slices of 32768.
 // r2 is applied to the members whose descriptor says comm_canon
+// n_batch == 0, n_open == 0 or n_rows == 0 is hipSuccess, nothing launched; otherwise n_batch > 65535 or a bad nl is
+// hipErrorInvalidValue, checked before any launch
 hipError_t launch_gather_columns_batch(int nl, const ProveMember* members, uint32_t n_batch, uint64_t n_rows, const uint64_t* cols,
                                        uint32_t n_open, uint32_t* vals, const uint32_t* r2, hipStream_t st);
 // paths[member][k][lvl][digest_words]: one flat launch over n_batch * n_open * path_len entries
+// digest_words other than 8 or 16 is hipErrorInvalidValue, whatever else is asked; otherwise an empty product is hipSuccess, nothing
+// launched
 hipError_t launch_gather_paths_batch(const ProveMember* members, uint32_t n_batch, uint64_t np2, uint32_t path_len, const uint64_t* cols,
                                      uint32_t n_open, uint32_t* paths, uint32_t digest_words, hipStream_t st);
 

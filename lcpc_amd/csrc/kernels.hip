@@ -886,6 +886,8 @@ hipError_t launch_collapse(int nl, const CollapseArgs& a_in, hipStream_t st) {
   if (a.out_stride == 0) a.out_stride = a.n_per_row;
   if (a.j1 > a.n_per_row || a.j0 >= a.j1) return hipErrorInvalidValue;
   if (a.members != nullptr && (a.n_batch == 0 || a.n_batch > 65535)) return hipErrorInvalidValue;   // the batch form: grid z
+  if (a.n_splits == 0 || a.n_splits > 65535) return hipErrorInvalidValue;                            // grid y
+  if (a.n_tensors != 1 && a.n_tensors != 2) return hipErrorInvalidValue;
   if (nl == 8 && a.tensors29 != nullptr) {
     dim3 grid((unsigned)((a.j1 - a.j0 + 255) / 256), a.n_splits, a.members ? a.n_batch : 1);
     switch (a.n_tensors) {
@@ -917,6 +919,8 @@ __global__ void __launch_bounds__(256) field_sum_kernel(const u32* parts, u32 n_
   field_sum_elem<NL>(parts, n_parts, n_elems, out);
 }
 hipError_t launch_field_sum(int nl, const u32* parts, u32 n_parts, u64 n_elems, u32* out, hipStream_t st) {
+  if (n_elems == 0) return hipSuccess;
+  if (n_parts == 0) return hipErrorInvalidValue;             // the kernel starts from parts[0]
   dim3 grid((unsigned)((n_elems + 255) / 256));
   switch (nl) {
     case 2: hipLaunchKernelGGL(field_sum_kernel<2>, grid, dim3(256), 0, st, parts, n_parts, n_elems, out); break;
@@ -971,7 +975,8 @@ hipError_t launch_to_canon(int nl, const u32* in, u64 n, u32* out, hipStream_t s
 }
 hipError_t launch_gather_columns(int nl, const u32* comm, u64 n_rows, u64 row_stride, u64 col_stride, const u64* cols, u32 n, u32* vals,
                                  const u32* r2, hipStream_t st) {
-  if (n == 0) return hipSuccess;
+  if (n == 0 || n_rows == 0) return hipSuccess;
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;
   unsigned gx = (unsigned)((n_rows + 255) / 256);
   if (gx > 64) gx = 64;
   constexpr u32 SLICE = 32768;                 // grid.y limit: columns in slices
@@ -1028,6 +1033,7 @@ __global__ void __launch_bounds__(256) assemble_columns_kernel(const u32* recv, 
 hipError_t launch_assemble_columns(int nl, const u32* recv, u64 block_words, const u64* rb, u32 G, u32 n, u64 n_rows, u32* out, hipStream_t st) {
   const u64 tot = (u64)n * n_rows;
   if (tot == 0) return hipSuccess;
+  if (nl != 2 && nl != 4 && nl != 6 && nl != 8) return hipErrorInvalidValue;   // the kernel moves an element as nl / 2 uint2
   hipLaunchKernelGGL(assemble_columns_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, recv, block_words, rb, G, n, n_rows, (u32)nl, out);
   return hipGetLastError();
 }
