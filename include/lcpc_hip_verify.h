@@ -35,8 +35,8 @@
  *    members' 1 + n_degree_tests polynomials, whose result stays on the device; the leaf digests of all opened columns (the batch forms
  *    of the column-hash kernels; under SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b over Ft255, one representation change in front of them);
  *    beside that the members' transcripts on the host pool; ONE upload of tensors and drawn columns; the column check (all dot products
- *    and their comparison with the encoded rows, one kernel); ONE download of the status words and leaf digests; the Merkle paths on
- *    the host pool.
+ *    and their comparison with the encoded rows, one kernel); the Merkle path folds (one more kernel, below); ONE download of the status words and leaf
+ *    digests; the verdicts on the host pool.
  *  - stats (may be NULL, filled when the call returns 0): how the call ran.  host_syncs is 2 per group: one event wait behind the row
  *    encode, for which the encoder's lock is held, and one stream synchronisation at the end.  Within one group the launch and
  *    synchronisation counts do not depend on n_batch for a Ligero encoder; a Brakedown row encode changes kernels at 24 stacked rows, as
@@ -52,9 +52,15 @@
  *    n_outer == 0 fits no honest proof (a column has at least one row): such a call is judged member by member by the single verify,
  *    and stats is all zero.
  *  - timing: with LCPC_DEBUG_TIMING set when the encoder was created the call prints one line to stderr: parse + stage, transcripts,
- *    device, path folds.
- *  LIMITATION -- the Merkle path folds stay on the host (one task per opened column on the host pool): moving them to the device needs
- *  a node-compress kernel per digest.
+ *    device, path folds (the host's share), and how many columns folded on the device and how many on the host.
+ *  - path folds: the Merkle path of every opened column is folded on the device, by one more kernel behind the column check (one lane per
+ *    opened column: the leaf digest, path_len node hashes, the comparison with the member's root; a mismatch sets bit 4 of the
+ *    column's status word, beside the column check's 1 = degree and 2 = eval).  The siblings are staged level-major in a second pinned
+ *    buffer of the working set and cross the bus behind the polynomials; they are P = n_col_opens * path_len * D bytes per member
+ *    (path_len = the encoder's tree depth) and are NOT part of A.  They are bounded by LCPCV_PATH_BUDGET (64 MiB): the first
+ *    min(g, max(1, floor(budget / P))) members of a group of g fold on the device, the rest of that group on the host pool (one task per
+ *    opened column, from the downloaded leaf digest).  A column whose path has another number of entries than path_len (the parser
+ *    accepts any count) is folded on the host as well.  Same verdicts either way.
  *  Out of scope: sharded encoders (LCPC_ERR_STATE); any change to the proof format or the protocol, such as a random linear combination
  *  of the proofs -- the reference has none.
  */
@@ -69,10 +75,11 @@ extern "C" {
 int lcpcv_version(void);
 
 #define LCPCV_ARENA_BUDGET ((uint64_t)64 << 20)
+#define LCPCV_PATH_BUDGET ((uint64_t)64 << 20)
 typedef struct {
   uint32_t groups;           /* lockstep groups the batch was cut into */
   uint32_t encode_launches;  /* kernel launches of the row encode(s) */
-  uint32_t hash_launches;    /* leaf-digest launches (and representation changes in front of them) */
+  uint32_t hash_launches;    /* leaf-digest launches (and representation changes in front of them), and the path-fold launch */
   uint32_t check_launches;   /* tensor conversions + the column-check kernel */
   uint32_t host_syncs;       /* stream / event synchronisations the call made */
 } lcpcv_verify_stats;

@@ -596,6 +596,37 @@ def verify_batch(enc, roots, outer_tensor, inner_tensor, proofs, trs, return_sta
     return (evals, status, stats) if return_stats else (evals, status)
 
 
+def check_columns(enc, root, cols, col_vals, paths, out=None):
+    """lcpcp_check_columns (include/lcpc_hip_columns.h): verify_column_path for columns opened outside a proof -- what
+    LcCommit.open_columns(cols) returns, checked against a root on the device.  cols: (n,) column numbers; col_vals: (n, n_rows, L)
+    stored limbs; paths: (n, path_len, digest_len) bytes.  Returns an (n,) bool array: True where the column's leaf digest folds to
+    root (out: an (n,) uint8 array the library writes instead, returned as it is).  Raises LcpcError when the call itself fails
+    (ERR_COLUMN_NUMBER for a column number >= n_cols: nothing is judged)."""
+    cols = np.ascontiguousarray(cols, np.uint64).reshape(-1)
+    n = cols.size
+    vals = np.ascontiguousarray(col_vals, np.uint64)
+    pth = np.ascontiguousarray(paths, np.uint8)
+    if vals.ndim != 3 or vals.shape[0] != n or vals.shape[2] != enc.L or pth.ndim != 3 or pth.shape[0] != n or pth.shape[2] != enc.digest_len:
+        raise LcpcError(ERR_ARG)
+    path_len = max(0, (enc.n_cols - 1).bit_length())
+    if pth.shape[1] != path_len:
+        raise LcpcError(ERR_ARG)
+    rootb = np.zeros(enc.digest_len, np.uint8)
+    rb = bytes(root)[:enc.digest_len]
+    rootb[:len(rb)] = np.frombuffer(rb, np.uint8)
+    ok = np.zeros(n, np.uint8) if out is None else out
+    if ok.dtype != np.uint8 or ok.shape != (n,) or not ok.flags.c_contiguous:
+        raise LcpcError(ERR_ARG)
+    if n == 0:
+        return ok.astype(bool) if out is None else ok
+    if pth.size == 0:
+        pth = np.zeros(1, np.uint8)           # (a tree of one leaf has no siblings; the library still wants a pointer)
+    rc = _lib.lib().lcpcp_check_columns(enc._h, _ptr(rootb), _ptr(cols), n, vals.shape[1], _ptr(vals), _ptr(pth), _ptr(ok))
+    if rc:
+        raise LcpcError(rc, _lib.lib().lcpc_last_error(enc._h).decode())
+    return ok.astype(bool) if out is None else ok
+
+
 def root_bincode(root):
     """bincode of LcRoot (lib.rs:373-384): u64 len | the digest (40 bytes; 72 for a 64-byte BLAKE2b root)"""
     if len(root) == 64:

@@ -117,10 +117,18 @@ class LcpcvVerifyStats(C.Structure):
 
 
 VERIFY_ARENA_BUDGET = 64 << 20     # LCPCV_ARENA_BUDGET
+VERIFY_PATH_BUDGET = 64 << 20      # LCPCV_PATH_BUDGET
 VERIFY_SYMBOLS = {
     "lcpcv_version": (_i32, []),
     "lcpcv_verify_batch": (_i32, [_vp, _u32, _vp, _vp, _u64, _u64, _vp, _u64, _u64, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), _vp,
                                   _vp, C.POINTER(LcpcvVerifyStats)]),
+}
+
+# the column-check extension (include/lcpc_hip_columns.h): again its own prefix, table and version
+COLUMNS_VERSION = 1
+COLUMNS_SYMBOLS = {
+    "lcpcp_version": (_i32, []),
+    "lcpcp_check_columns": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp]),
 }
 
 
@@ -166,5 +174,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcv_version() != VERIFY_VERSION:
             raise RuntimeError("lcpc_amd: verify extension version mismatch")
+        for name, (res, args) in COLUMNS_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcp_version() != COLUMNS_VERSION:
+            raise RuntimeError("lcpc_amd: column-check extension version mismatch")
         _lib = L
     return _lib

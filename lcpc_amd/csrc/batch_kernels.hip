@@ -7,6 +7,7 @@
 #include "field_dev.h"
 #include "blake3_dev.h"
 #include "leaf_dev.h"
+#include "fold_dev.h"
 
 namespace lcpc {
 
@@ -271,6 +272,22 @@ hipError_t launch_merkle_tree_from_batch(u32* hashes, u64 np2, u32 levels_done, 
     for (u32 j = 0; j < lsub; j++) { in_off += width; width >>= 1; }
   }
   return hipSuccess;
+}
+
+// K8b under BLAKE3 (kernels.h FoldPathsArgs, fold_dev.h): a tree node is the 64-byte message left || right hashed as one whole chunk, with
+// the flags merkle_subtree_batch_kernel passes
+struct B3Node {
+  static constexpr int DIGEST_WORDS = 8;
+  static __device__ __forceinline__ void node(u32 o[8], const u32* l, const u32* r) { b3_hash64(o, l, r, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT); }
+};
+__global__ void __launch_bounds__(256) fold_paths_b3_kernel(FoldPathsArgs a) {
+  fold_path_lane<B3Node>(a);
+}
+hipError_t launch_fold_paths_b3(const FoldPathsArgs& a, hipStream_t st) {
+  const int job = fold_paths_job(a);
+  if (job <= 0) return job ? hipErrorInvalidValue : hipSuccess;
+  hipLaunchKernelGGL(fold_paths_b3_kernel, dim3((a.n_open + 255) / 256, a.n_batch), dim3(256), 0, st, a);
+  return hipGetLastError();
 }
 
 // the polynomials of a batch into the padded coeffs rows of the slab: member i's n_valid 64-bit words from src + i * src_stride to

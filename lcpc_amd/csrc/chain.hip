@@ -54,5 +54,8 @@ hipError_t launch_chain_merkle_tree(ChainHash h, u32* hashes, u64 np2, hipStream
 hipError_t launch_chain_merkle_tree_batch(ChainHash h, u32* hashes, u64 np2, u32 n_batch, u64 hashes_stride, hipStream_t st, u32* root_out) {
   return with_chain(h, [&](auto d) { return chain_merkle_tree<decltype(d), true>(hashes, np2, n_batch, hashes_stride, st, root_out); });
 }
+hipError_t launch_chain_fold_paths(ChainHash h, const FoldPathsArgs& a, hipStream_t st) {
+  return with_chain(h, [&](auto d) { return chain_fold_paths<decltype(d)>(a, st); });
+}
 
 }  // namespace lcpc

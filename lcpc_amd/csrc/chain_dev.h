@@ -20,6 +20,7 @@
 #pragma once
 #include "kernels.h"
 #include "field_ln.h"
+#include "fold_dev.h"
 
 namespace lcpc {
 
@@ -167,6 +168,12 @@ __global__ void __launch_bounds__(256) chain_merkle_subtree_kernel(u32* hashes, 
   }
 }
 
+// K8b (kernels.h FoldPathsArgs, fold_dev.h): one lane folds one opened column's path with D::node and compares with the member's root
+template <class D>
+__global__ void __launch_bounds__(256) chain_fold_paths_kernel(FoldPathsArgs a) {
+  fold_path_lane<D>(a);
+}
+
 // ---- the launchers of one digest: chain.hip switches over ChainHash to these; each is instantiated in its digest's .hip ----
 // F<NL, CANON>: a functor that launches one instantiation; the nl / canon_in switch written once
 template <class F>
@@ -243,12 +250,20 @@ template <class D, bool BATCH> hipError_t chain_merkle_tree(u32* hashes, u64 np2
   return hipSuccess;
 }
 
-// LCPC_CHAIN_LAUNCHERS(, D) in D's .hip instantiates the five; LCPC_CHAIN_LAUNCHERS(extern, D) in chain.hip names them without compiling them
+template <class D> hipError_t chain_fold_paths(const FoldPathsArgs& a, hipStream_t st) {
+  const int job = fold_paths_job(a);
+  if (job <= 0) return job ? hipErrorInvalidValue : hipSuccess;
+  hipLaunchKernelGGL((chain_fold_paths_kernel<D>), dim3((a.n_open + 255) / 256, a.n_batch), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// LCPC_CHAIN_LAUNCHERS(, D) in D's .hip instantiates the six; LCPC_CHAIN_LAUNCHERS(extern, D) in chain.hip names them without compiling them
 #define LCPC_CHAIN_LAUNCHERS(EXT, D)                                                                                    \
   EXT template hipError_t chain_leaves<D>(int, const LeafArgs&, hipStream_t);                                           \
   EXT template hipError_t chain_leaves_batch<D>(int, const LeafArgs&, u32, u64, u64, hipStream_t);                      \
   EXT template hipError_t chain_leaves_range<D>(int, const LeafArgs&, u64, u64, u32*, hipStream_t);                     \
   EXT template hipError_t chain_merkle_tree<D, false>(u32*, u64, u32, u64, hipStream_t, u32*);                          \
-  EXT template hipError_t chain_merkle_tree<D, true>(u32*, u64, u32, u64, hipStream_t, u32*);
+  EXT template hipError_t chain_merkle_tree<D, true>(u32*, u64, u32, u64, hipStream_t, u32*);                           \
+  EXT template hipError_t chain_fold_paths<D>(const FoldPathsArgs&, hipStream_t);
 
 }  // namespace lcpc

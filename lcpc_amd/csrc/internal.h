@@ -174,7 +174,13 @@ struct VerifyBatchSet {
   uint64_t d_cap = 0;
   uint32_t* t29 = nullptr;         // Ft255: the tensors in the 29-bit-limb form
   uint64_t t29_cap = 0;
+  // the Merkle path siblings the device folds (K8b): a pinned buffer and its device mirror, beside the arena and not part of its
+  // formula; grown on demand (ensure_paths)
+  uint8_t* h_path = nullptr;
+  uint8_t* d_path = nullptr;
+  uint64_t h_path_cap = 0, d_path_cap = 0;
   int make();
+  int ensure_paths(ErrText* err, uint64_t bytes);
   void quiesce() { (void)hipStreamSynchronize(st); }
   ~VerifyBatchSet();
 };
@@ -632,5 +638,27 @@ struct ProofView {
 int parse_proof(const lcpc_ctx* c, const uint8_t* proof, uint64_t proof_len, uint64_t n_outer, uint64_t n_inner, ProofView* out);
 // D(in) with the encoder's digest (LCPC_HASH_*): 32 bytes into out, 64 for BLAKE2b
 void digest_host(uint32_t hash, const uint8_t* in, size_t len, uint8_t* out);
+
+// ---- verify_batch.cpp: what lcpcv_verify_batch and lcpcp_check_columns (columns.cpp) share --------------------------------------------
+// verify_column_path (lib.rs:955-982) on the device for opened columns staged position-major: the leaf digests by the batch forms of the
+// column-hash launchers, then the path folds (K8b).  Two calls, because the batched verify knows the drawn column numbers only after
+// the transcripts, which run beside the leaf digests.
+struct StagedColumns {
+  uint32_t* cols;                  // [member][n_open][n_rows] stored (Montgomery) elements, every limb < p; member stride in words
+  uint64_t cols_stride_w;          // (whole elements and a multiple of 16 bytes: kernels.h, the batch hash launchers)
+  uint32_t* canon;                 // a chained digest over Ft255: room for n_batch * cols_stride_w words, the canonical copy; else unused
+  uint32_t* cvs;                   // BLAKE3 leaves of more than one chunk: [member][n_chunks][n_open][8]; else unused
+  uint64_t cvs_stride_w;
+  uint32_t* digests;               // out: [member][n_open][digest words]
+  uint64_t dig_stride_w;
+  uint64_t n_open, n_rows;
+  uint32_t n_batch;
+};
+// bytes of the canon and cvs segments a member needs (0: the segment is not used)
+uint64_t staged_canon_bytes(const lcpc_ctx* c, uint64_t cols_bytes);
+uint64_t staged_cvs_bytes(const lcpc_ctx* c, uint64_t n_open, uint64_t n_rows);
+// enqueue on st; *launches (may be null) is advanced by the kernels launched
+int enqueue_leaf_digests(lcpc_ctx* c, const StagedColumns& sc, hipStream_t st, uint32_t* launches);
+int enqueue_fold_paths(lcpc_ctx* c, const FoldPathsArgs& fa, hipStream_t st, uint32_t* launches);
 
 }  // namespace lcpc

@@ -282,6 +282,42 @@ struct VerifyColsArgs {
 // any launch; empty work (n_batch == 0 or n_open == 0) is hipSuccess
 hipError_t launch_verify_columns_batch(int nl, const VerifyColsArgs& a, hipStream_t st);
 
+// ---- K8b: the Merkle path folds of the batched verify and of the column check (fold.cpp): verify_column_path (lib.rs:955-982) for every
+// opened column of every member in one launch.  One lane per (member, opened column): h = the column's leaf digest; for lvl = 0 ..
+// depth - 1: h = node(cc even ? h || sib : sib || h), cc >>= 1, cc starting at the drawn column number; h is then compared with the
+// member's root.  On a mismatch the lane ORs FOLD_PATH_BIT into ITS status word (plain load, OR, store: one lane owns one word), otherwise
+// the word is neither read nor written.  depth is uniform for a launch; depth == 0 compares the leaf digest with the root.  Grid: x =
+// columns in blocks of 256, y = member; no LDS.
+// The sibling of (member m, opened column k, level lvl) is the digest at sibs + m * sib_member + k * sib_col + lvl * sib_lvl words, so
+// both layouts run without a transposition: level-major [lvl][column] (sib_col = DW, sib_lvl = n_open * DW: consecutive lanes read
+// consecutive digests; what verify_batch.cpp stages) and column-major [column][lvl] (sib_col = depth * DW, sib_lvl = DW: what the core
+// header's open-columns call returns).  DW = digest words, 8 or 16 (Blake2b).
+// Alignment: digests move as uint4 -- every base pointer is 16-byte aligned and every stride a multiple of 4 words.  Nothing checks that
+// members do not overlap.
+constexpr uint32_t FOLD_PATH_BIT = 4;    // beside K7b's 1 = degree, 2 = eval
+struct FoldPathsArgs {
+  const uint32_t* leaves;      // [member][n_open][DW] leaf digests; member stride in words
+  uint64_t leaves_stride;
+  const uint64_t* drawn;       // [member][n_open] column numbers (member stride n_open)
+  const uint32_t* sibs;        // the sibling base and its three word strides
+  uint64_t sib_member, sib_col, sib_lvl;
+  const uint32_t* roots;       // [member][DW]
+  uint32_t* status;            // [member][n_open] at member stride status_stride words
+  uint64_t status_stride;
+  uint32_t n_open, depth, n_batch;
+};
+// n_batch == 0 or > 65535, depth > 63, or a null leaves / drawn / sibs / roots / status with n_open > 0 (sibs is not read when depth ==
+// 0, and must still be a pointer) is hipErrorInvalidValue, checked before any launch; n_open == 0 is hipSuccess, nothing launched
+hipError_t launch_fold_paths_b3(const FoldPathsArgs& a, hipStream_t st);                    // BLAKE3 (batch_kernels.hip)
+hipError_t launch_chain_fold_paths(ChainHash h, const FoldPathsArgs& a, hipStream_t st);    // the chain digests (chain_dev.h)
+// what both settle before a launch: -1 = refuse, 0 = nothing to do, 1 = launch
+constexpr int fold_paths_job(const FoldPathsArgs& a) {
+  if (a.n_batch == 0 || a.n_batch > 65535 || a.depth > 63) return -1;
+  if (a.n_open == 0) return 0;
+  if (!a.leaves || !a.drawn || !a.sibs || !a.roots || !a.status) return -1;
+  return 1;
+}
+
 // Brakedown: y[row][out_off + o] = sum_k vals[k] * x[row][in_off + colidx[k]], k in [rowptr[o], rowptr[o+1])
 struct SpmvArgs {
   uint32_t* mat;                // comm (row-major, stride elements per row); in and out segments are disjoint

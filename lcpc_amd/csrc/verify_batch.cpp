@@ -9,10 +9,15 @@
 //      leaf digests of the g n_col_opens opened columns -- each member's columns are a position-major matrix of n_col_opens columns -- by
 //      the batch forms of the column-hash launchers.
 //   3. host pool beside the hashes, one task per member: the whole transcript (tensors, absorbs, column draw), <inner, p_eval>.
-//   4. device: one upload (tensors | drawn columns), K7b (kernels.hip: all dot products against the encoded rows), one download
-//      (status words | leaf digests), one synchronisation.
-//   5. host pool over all g n_col_opens columns: the Merkle path from the downloaded leaf digest, combined with K7b's bits into the
-//      member's verdict under lcpc_verify's precedence.
+//      Stage 1 also copies each member's root and path siblings, level-major, into the working set's second pinned buffer (not part of
+//      the arena formula); they go up behind the hashes.
+//   4. device: one upload (tensors | drawn columns), K7b (kernels.hip: all dot products against the encoded rows), K8b (kernels.h
+//      FoldPathsArgs: every Merkle path folded from its leaf digest and compared with the root), one download (status words | leaf
+//      digests), one synchronisation.
+//   5. host pool over all g n_col_opens columns: K7b's and K8b's bits combined into the member's verdict under lcpc_verify's
+//      precedence.  The columns K8b did not judge -- members past the header's path budget, paths of another length than the tree's
+//      depth -- are folded here from the downloaded leaf digest.
+// enqueue_leaf_digests / enqueue_fold_paths are shared with lcpcp_check_columns (columns.cpp).
 #include "internal.h"
 #include "../../include/lcpc_hip_verify.h"
 
@@ -26,10 +31,68 @@ int VerifyBatchSet::make() {
 }
 VerifyBatchSet::~VerifyBatchSet() {
   if (st) (void)hipStreamSynchronize(st);
-  dev_free(d); dev_free(t29);
+  dev_free(d); dev_free(t29); dev_free(d_path);
   if (ev_enc) (void)hipEventDestroy(ev_enc);
   if (st) (void)hipStreamDestroy(st);
   if (h_pin) (void)hipHostFree(h_pin);
+  if (h_path) (void)hipHostFree(h_path);
+}
+int VerifyBatchSet::ensure_paths(ErrText* err, uint64_t bytes) {
+  bytes = (bytes + 255) & ~(uint64_t)255;
+  if (bytes > h_path_cap || !h_path) {
+    if (h_path) (void)hipHostFree(h_path);
+    h_path = nullptr; h_path_cap = 0;
+    void* hp = nullptr;
+    hipError_t e = hipHostMalloc(&hp, (size_t)bytes, hipHostMallocDefault);
+    if (e != hipSuccess) return fail_hip(err, e, "hipHostMalloc");
+    h_path = static_cast<uint8_t*>(hp); h_path_cap = bytes;
+  }
+  return ensure_dev(err, &d_path, &d_path_cap, bytes);
+}
+
+uint64_t staged_canon_bytes(const lcpc_ctx* c, uint64_t cols_bytes) { return !is_blake3(c) && c->NL == 8 ? cols_bytes : 0; }
+uint64_t staged_cvs_bytes(const lcpc_ctx* c, uint64_t n_open, uint64_t n_rows) {
+  const uint64_t n_chunks = is_blake3(c) ? leaf_chunks(c, n_rows) : 1;
+  return n_chunks > 1 ? n_chunks * n_open * 32 : 0;
+}
+
+// each member's columns are a position-major matrix of n_open columns: element (row r, column k) at k * n_rows + r
+int enqueue_leaf_digests(lcpc_ctx* c, const StagedColumns& sc, hipStream_t st, uint32_t* launches) {
+  const int NL = c->NL;
+  uint32_t n = 0;
+  LeafArgs la{};
+  la.comm = sc.cols; la.row_stride = 1; la.col_stride = sc.n_rows; la.n_cols = sc.n_open; la.row_base = 0; la.n_rows_total = sc.n_rows;
+  la.canon_in = 0;
+  if (is_blake3(c)) {
+    const uint64_t n_chunks = leaf_chunks(c, sc.n_rows);
+    la.chunk_begin = 0; la.n_chunks_local = la.n_chunks_total = (uint32_t)n_chunks;
+    la.out = n_chunks > 1 ? sc.cvs : sc.digests;
+    HIPCHK(c, launch_leaf_chunks_batch(NL, la, sc.n_batch, sc.cols_stride_w, n_chunks > 1 ? sc.cvs_stride_w : sc.dig_stride_w, st));
+    n += (uint32_t)((n_chunks + 32767) / 32768);
+    if (n_chunks > 1) {
+      HIPCHK(c, launch_leaf_finish_batch(sc.cvs, (uint32_t)n_chunks, sc.n_open, sc.digests, sc.n_batch, sc.cvs_stride_w, sc.dig_stride_w, st));
+      n++;
+    }
+  } else {
+    la.chunk_begin = 0; la.n_chunks_local = la.n_chunks_total = 1;
+    if (NL == 8) {                 // the chained batch kernels over Ft255 read canonical values only (kernels.h)
+      HIPCHK(c, launch_to_canon(NL, sc.cols, (uint64_t)sc.n_batch * sc.cols_stride_w / NL, sc.canon, st));
+      n++;
+      la.comm = sc.canon; la.canon_in = 1;
+    }
+    la.out = sc.digests;
+    HIPCHK(c, launch_chain_leaves_batch(chain_hash(c), NL, la, sc.n_batch, sc.cols_stride_w, sc.dig_stride_w, st));
+    n++;
+  }
+  if (launches) *launches += n;
+  return 0;
+}
+
+int enqueue_fold_paths(lcpc_ctx* c, const FoldPathsArgs& fa, hipStream_t st, uint32_t* launches) {
+  if (is_blake3(c)) HIPCHK(c, launch_fold_paths_b3(fa, st));
+  else HIPCHK(c, launch_chain_fold_paths(chain_hash(c), fa, st));
+  if (launches) *launches += 1;
+  return 0;
 }
 }  // namespace lcpc
 
@@ -119,14 +182,24 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
   if (int rc = c->verify_batch_sets.take(lay.total, &ws.s)) return rc;
   hipStream_t st = ws.s->st;
   // device: the mirrored segments, then [encoded rows][canonical columns: a chained digest over Ft255][chunk CVs: BLAKE3 leaves of > 1 chunk]
-  const bool b3 = is_blake3(c);
-  const bool canon_cols = !b3 && NL == 8;        // the chained batch kernels over Ft255 read canonical values only (kernels.h)
-  const uint64_t n_chunks = b3 ? leaf_chunks(c, nr) : 1;
-  const uint64_t enc_b = align256(gmax * nt * n_cols * F), ccols_b = canon_cols ? align256(gmax * lay.cols_b) : 0;
-  const uint64_t cvs_member_b = n_chunks > 1 ? n_chunks * n_open * 32 : 0, cvs_b = align256(gmax * cvs_member_b);
+  const uint64_t enc_b = align256(gmax * nt * n_cols * F), ccols_b = align256(gmax * staged_canon_bytes(c, lay.cols_b));
+  const uint64_t cvs_member_b = staged_cvs_bytes(c, n_open, nr), cvs_b = align256(gmax * cvs_member_b);
   if (int rc = ensure_dev(&c->err, &ws.s->d, &ws.s->d_cap, lay.total + enc_b + ccols_b + cvs_b)) return rc;
   if (NL == 8)
     if (int rc = ensure_dev(&c->err, &ws.s->t29, &ws.s->t29_cap, gmax * nt * nr * 48)) return rc;
+  // the path buffer, beside the arena: [roots of the group][siblings of the members that fold on the device, level-major].  The first
+  // n_fold members of a group fold on the device (the header's path budget); a group's last members and every column whose path has
+  // another number of entries than the tree's depth fold on the host
+  const uint32_t path_len = c->path_len;
+  const uint64_t path_b = n_open * path_len * dl;                // P
+  const uint64_t n_fold_max = path_b ? std::min<uint64_t>(gmax, std::max<uint64_t>(1, LCPCV_PATH_BUDGET / path_b)) : gmax;
+  const uint64_t o_sibs = align256(gmax * dl);
+  if (int rc = ws.s->ensure_paths(&c->err, o_sibs + n_fold_max * path_b)) return rc;
+  uint8_t* const hp = ws.s->h_path;
+  uint8_t* const dp = ws.s->d_path;
+  std::unique_ptr<uint8_t[]> host_fold(new uint8_t[(size_t)gmax * n_open]);      // 1: this column's path is folded on the host
+  std::vector<uint64_t> n_host_fold(gmax);
+  uint64_t cols_dev = 0, cols_host = 0;
   uint8_t* const hb = ws.s->h_pin;
   uint8_t* const db = ws.s->d;
   auto d32 = [&](uint64_t off) { return reinterpret_cast<uint32_t*>(db + off); };
@@ -140,6 +213,7 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
   for (uint32_t g0 = 0; g0 < A.n_batch; g0 += (uint32_t)gmax) {
     const uint32_t g = (uint32_t)std::min<uint64_t>(gmax, A.n_batch - g0);
     int32_t* const status = A.status + g0;
+    const uint64_t n_fold = std::min<uint64_t>(g, n_fold_max);
     // ---- 1. parse, check, stage ---------------------------------------------------------------------------------------------------
     double t0 = now_ms();
     parallel_for(g, 1, [&](uint64_t mb, uint64_t me) {
@@ -171,6 +245,33 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
         }
         if (rc) { memset(polys, 0, lay.poly_b); memset(cols, 0, lay.cols_b); }     // the hole: zeros, never read as data
         else if (lay.cols_b > n_open * nr * F) memset(reinterpret_cast<uint8_t*>(cols) + n_open * nr * F, 0, lay.cols_b - n_open * nr * F);
+        // the root and the path siblings, level-major: entry lvl of column k at (lvl * n_open + k) * D of the member's slot
+        memcpy(hp + i * dl, A.roots + (size_t)(g0 + i) * dl, dl);
+        uint8_t* const hf = host_fold.get() + i * n_open;
+        n_host_fold[i] = 0;
+        if (i >= n_fold) {
+          memset(hf, 1, n_open);
+          n_host_fold[i] = n_open;
+        } else if (rc) {
+          memset(hp + o_sibs + i * path_b, 0, path_b);
+          memset(hf, 0, n_open);
+        } else {
+          uint8_t* const sibs = hp + o_sibs + i * path_b;
+          for (uint64_t k = 0; k < n_open; k++) {
+            hf[k] = pv.paths[k].n != path_len;
+            n_host_fold[i] += hf[k];
+          }
+          // level by level, so that the writes run through the slot in order (the reads step from column to column of the proof)
+          for (uint64_t lvl = 0; lvl < path_len; lvl++) {
+            uint8_t* dst = sibs + lvl * n_open * dl;
+            const uint64_t off = (8 + dl) * lvl + 8;
+            for (uint64_t k = 0; k < n_open; k++, dst += dl) {
+              if (hf[k]) memset(dst, 0, dl);
+              else if (dl == 32) memcpy(dst, pv.paths[k].p + off, 32);
+              else memcpy(dst, pv.paths[k].p + off, 64);
+            }
+          }
+        }
         status[i] = rc;
       }
     });
@@ -178,10 +279,9 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
     // ---- 2. upload, row encode, leaf digests --------------------------------------------------------------------------------------
     t0 = now_ms();
     HIPCHK(c, hipMemcpyAsync(db + lay.o_poly, hb + lay.o_poly, lay.o_cols + (size_t)g * lay.cols_b, hipMemcpyHostToDevice, st));
-    LeafArgs la{};
-    la.comm = d32(lay.o_cols); la.row_stride = 1; la.col_stride = nr; la.n_cols = n_open; la.row_base = 0; la.n_rows_total = nr;
-    la.chunk_begin = 0; la.n_chunks_local = la.n_chunks_total = (uint32_t)n_chunks; la.canon_in = 0;
-    const uint64_t cols_stride_w = lay.cols_b / 4, dig_stride_w = n_open * dw;
+    StagedColumns sc{};
+    sc.cols = d32(lay.o_cols); sc.cols_stride_w = lay.cols_b / 4; sc.canon = d_ccols; sc.cvs = d_cvs; sc.cvs_stride_w = cvs_member_b / 4;
+    sc.digests = d32(lay.o_dig); sc.dig_stride_w = n_open * dw; sc.n_open = n_open; sc.n_rows = nr; sc.n_batch = g;
     {
       EncodeLock lk(c, st);
       EncodeJob j;
@@ -189,28 +289,13 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
       if (int rc = encode_rows_device(c, &c->ws, j, st, &c->err, &stt.encode_launches)) return rc;
       HIPCHK(c, hipEventRecord(ws.s->ev_enc, st));
       // the hashes do not touch the encode workspace; they are enqueued before the wait so that they run behind the encode at once
-      if (b3) {
-        la.out = n_chunks > 1 ? d_cvs : d32(lay.o_dig);
-        HIPCHK(c, launch_leaf_chunks_batch(NL, la, g, cols_stride_w, n_chunks > 1 ? cvs_member_b / 4 : dig_stride_w, st));
-        stt.hash_launches += (uint32_t)((n_chunks + 32767) / 32768);
-        if (n_chunks > 1) {
-          HIPCHK(c, launch_leaf_finish_batch(d_cvs, (uint32_t)n_chunks, n_open, d32(lay.o_dig), g, cvs_member_b / 4, dig_stride_w, st));
-          stt.hash_launches++;
-        }
-      } else {
-        if (canon_cols) {
-          HIPCHK(c, launch_to_canon(NL, la.comm, (uint64_t)g * lay.cols_b / F, d_ccols, st));
-          stt.hash_launches++;
-          la.comm = d_ccols; la.canon_in = 1;
-        }
-        la.out = d32(lay.o_dig);
-        HIPCHK(c, launch_chain_leaves_batch(chain_hash(c), NL, la, g, cols_stride_w, dig_stride_w, st));
-        stt.hash_launches++;
-      }
+      if (int rc = enqueue_leaf_digests(c, sc, st, &stt.hash_launches)) return rc;
       HIPCHK(c, hipEventSynchronize(ws.s->ev_enc));
       stt.host_syncs++;
       lk.drained = true;
     }
+    // roots and paths go up behind the polynomials on the same stream, beside the transcripts: nothing waits for them before the fold
+    HIPCHK(c, hipMemcpyAsync(dp, hp, o_sibs + (size_t)n_fold * path_b, hipMemcpyHostToDevice, st));
     t_dev += now_ms() - t0;
     // ---- 3. transcripts, beside the hashes ------------------------------------------------------------------------------------------
     t0 = now_ms();
@@ -256,6 +341,13 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
     }
     HIPCHK(c, launch_verify_columns_batch(NL, va, st));
     stt.check_launches += (uint32_t)((n_open + (1u << 20) - 1) >> 20);
+    // K8b behind K7b, which has written every status word: the path bit of the first n_fold members' columns
+    FoldPathsArgs fa{};
+    fa.leaves = d32(lay.o_dig); fa.leaves_stride = n_open * dw; fa.drawn = va.drawn;
+    fa.sibs = reinterpret_cast<const uint32_t*>(dp + o_sibs); fa.sib_member = path_b / 4; fa.sib_col = dw; fa.sib_lvl = n_open * dw;
+    fa.roots = reinterpret_cast<const uint32_t*>(dp); fa.status = va.status; fa.status_stride = n_open;
+    fa.n_open = (uint32_t)n_open; fa.depth = path_len; fa.n_batch = (uint32_t)n_fold;
+    if (int rc = enqueue_fold_paths(c, fa, st, &stt.hash_launches)) return rc;
     HIPCHK(c, hipMemcpyAsync(hb + lay.o_stat, db + lay.o_stat, lay.o_dig - lay.o_stat + (size_t)g * lay.dig_b, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     stt.host_syncs++;
@@ -272,23 +364,28 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
         const uint64_t i = id / n_open, k = id % n_open;
         if (status[i]) { col_code[id] = 0; continue; }
         const uint32_t bits = h_stat[i * n_open + k];
-        const ProofView::Path& path = views[i].paths[k];
-        uint8_t h[64], blk[128];                                                   // verify_column_path lib.rs:955-982
-        memcpy(h, h_dig + i * lay.dig_b + k * dl, dl);
-        uint64_t cc = h_drawn[i * n_open + k];
-        for (uint64_t lvl = 0; lvl < path.n; lvl++) {
-          const uint8_t* pk = path.p + (8 + dl) * lvl + 8;
-          if (cc % 2 == 0) { memcpy(blk, h, dl); memcpy(blk + dl, pk, dl); } else { memcpy(blk, pk, dl); memcpy(blk + dl, h, dl); }
-          digest_host(hash, blk, 2 * dl, h);
-          cc >>= 1;
+        bool pth = !(bits & FOLD_PATH_BIT);                                        // K8b's verdict
+        if (host_fold[id]) {                                                       // verify_column_path lib.rs:955-982
+          const ProofView::Path& path = views[i].paths[k];
+          uint8_t h[64], blk[128];
+          memcpy(h, h_dig + i * lay.dig_b + k * dl, dl);
+          uint64_t cc = h_drawn[i * n_open + k];
+          for (uint64_t lvl = 0; lvl < path.n; lvl++) {
+            const uint8_t* pk = path.p + (8 + dl) * lvl + 8;
+            if (cc % 2 == 0) { memcpy(blk, h, dl); memcpy(blk + dl, pk, dl); } else { memcpy(blk, pk, dl); memcpy(blk + dl, h, dl); }
+            digest_host(hash, blk, 2 * dl, h);
+            cc >>= 1;
+          }
+          pth = memcmp(h, A.roots + (size_t)(g0 + i) * dl, dl) == 0;
         }
-        const bool pth = memcmp(h, A.roots + (size_t)(g0 + i) * dl, dl) == 0;
         const int code = (bits & 1u) ? LCPC_VERR_COLUMN_DEGREE : ((bits & 2u) ? LCPC_VERR_COLUMN_EVAL : (!pth ? LCPC_VERR_COLUMN_PATH : 0));
         col_code[id] = (uint8_t)(-code);
       }
     });
     for (uint32_t i = 0; i < g; i++) {
       if (status[i]) continue;
+      cols_host += n_host_fold[i];
+      cols_dev += n_open - n_host_fold[i];
       for (uint64_t k = 0; k < n_open; k++)
         if (col_code[(size_t)i * n_open + k]) { status[i] = -(int)col_code[(size_t)i * n_open + k]; break; }
       if (!status[i]) memcpy(A.evals + (size_t)(g0 + i) * L, &eval_acc[i * MAXL], F);
@@ -298,9 +395,10 @@ int verify_batch_run(const Args& A, lcpcv_verify_stats* stats) {
   if (stats) *stats = stt;
   if (dbg)
     fprintf(stderr, "[lcpcv_verify_batch] %u members in %u groups: parse + stage %.2f ms, transcripts %.2f, device (uploads, encode wait, check, "
-                    "download) %.2f, path folds %.2f, total %.2f; %u encode + %u hash + %u check launches, %u syncs\n",
+                    "download) %.2f, path folds %.2f, total %.2f; %u encode + %u hash + %u check launches, %u syncs; %llu columns folded on the "
+                    "device, %llu on the host\n",
             A.n_batch, stt.groups, t_stage, t_tr, t_dev, t_fold, now_ms() - t_start, stt.encode_launches, stt.hash_launches, stt.check_launches,
-            stt.host_syncs);
+            stt.host_syncs, (unsigned long long)cols_dev, (unsigned long long)cols_host);
   return 0;
 }
 
