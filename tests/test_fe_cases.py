@@ -9,7 +9,9 @@ sets against the models alone: every operand is in contract, the models agree wi
 branches it was built for.
 
 The tables the limb primitives read (the clamp table (i - QOFF) p, its limb-wise negation, the shifted multiples of mul_u) are built
-here from the layouts field_ln.h and ctx.cpp describe, not by ctx.cpp."""
+here from the layouts field_ln.h and ctx.cpp describe, not by ctx.cpp: the primitives are tested on these models of the tables.  That
+the tables the product builds for itself (ctx.cpp, kernels.hip, ntt_lns.hip) ARE these models, word for word, is what
+tests/test_gpu_k1_tables.py checks on real contexts, with clamp_table and shifted_multiples below as its references."""
 import functools
 import os
 import random
