@@ -35,7 +35,7 @@
  *
  * Which encoders are batched
  *  - Ligero encoders, all four fields, all five digests: ONE row encode over n_batch * n_rows rows (the row NTT is row-independent),
- *    then batched column-hash and tree kernels, the member index a grid dimension.  BLAKE3: batch_kernels.hip (K3b / K4b).  SHA3-256,
+ *    then batched column-hash and tree kernels, the member index a grid dimension.  BLAKE3: kernels.hip (K3b / K4b).  SHA3-256,
  *    Keccak-256, SHA-256 and BLAKE2b -- one serial chain per column -- run the batch forms of their leaf and subtree kernels (sha3.hip,
  *    sha256.hip, blake2b.hip): one leaf launch and one tree call for the whole batch, roots and hashes slots of D bytes.
  *    The hash and tree of the whole batch cost as many launches as one member's; the encode costs one member's when n_coeffs fills

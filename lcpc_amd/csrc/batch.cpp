@@ -3,7 +3,7 @@
 //
 // Ligero, under every digest: the members' comm / coeffs / hashes live member-major in one slab (internal.h BatchSlab), the row NTT runs
 // once over n_batch * n_rows rows (encode_rows_device: rows are independent), and the column hash and the tree run as batched kernels
-// -- as many launches as ONE commit of the shape.  BLAKE3: batch_kernels.hip (K3b / K4b: chunk CVs, fold, or leaf digests with the
+// -- as many launches as ONE commit of the shape.  BLAKE3: kernels.hip (K3b / K4b: chunk CVs, fold, or leaf digests with the
 // first six tree levels).  SHA3-256 / Keccak-256 / SHA-256 / BLAKE2b: one serial chain per column, so one leaf launch and one tree
 // call over the batch (the batch forms of chain_dev.h); hashes slots are digest_words(c) words.
 //

@@ -1,5 +1,5 @@
 // lcpc_amd/csrc/fold_dev.h -- K8b, the Merkle path fold (kernels.h FoldPathsArgs): one lane's work, written once over the node function.
-// N supplies DIGEST_WORDS and node(o, l, r): the chain digests' traits (chain_dev.h) and BLAKE3's (batch_kernels.hip).
+// N supplies DIGEST_WORDS and node(o, l, r): the chain digests' traits (chain_dev.h) and BLAKE3's (kernels.hip).
 #pragma once
 #include "kernels.h"
 

@@ -118,7 +118,7 @@ hipError_t launch_merkle_tree_from(uint32_t* hashes, uint64_t np2, uint32_t leve
 bool leaf_tree_supported(const LeafArgs& a, uint64_t np2);
 hipError_t launch_leaf_tree(int nl, const LeafArgs& a, uint32_t* hashes, uint64_t np2, hipStream_t st);
 
-// ---- batched BLAKE3 column hash and tree (batch_kernels.hip K3b / K4b): n_batch <= 65535 equal-shape commitments of one encoder in one
+// ---- batched BLAKE3 column hash and tree (kernels.hip K3b / K4b: the K3 / K4 kernels' BATCH = true forms): n_batch <= 65535 equal-shape commitments of one encoder in one
 // launch each, the member index a grid dimension.  `a`, `hashes`, `cvs`, `digests` describe member 0; member i's comm, a.out, hashes,
 // cvs and digests start i * (the given stride, in 32-bit words) behind it.  Same digests as the single launchers, bit for bit.
 // Alignment: every stride must be a multiple of 4 words (16 bytes), and member 0's pointers 16-byte aligned as for the single launchers --
@@ -308,7 +308,7 @@ struct FoldPathsArgs {
 };
 // n_batch == 0 or > 65535, depth > 63, or a null leaves / drawn / sibs / roots / status with n_open > 0 (sibs is not read when depth ==
 // 0, and must still be a pointer) is hipErrorInvalidValue, checked before any launch; n_open == 0 is hipSuccess, nothing launched
-hipError_t launch_fold_paths_b3(const FoldPathsArgs& a, hipStream_t st);                    // BLAKE3 (batch_kernels.hip)
+hipError_t launch_fold_paths_b3(const FoldPathsArgs& a, hipStream_t st);                    // BLAKE3 (kernels.hip)
 hipError_t launch_chain_fold_paths(ChainHash h, const FoldPathsArgs& a, hipStream_t st);    // the chain digests (chain_dev.h)
 // what both settle before a launch: -1 = refuse, 0 = nothing to do, 1 = launch
 constexpr int fold_paths_job(const FoldPathsArgs& a) {

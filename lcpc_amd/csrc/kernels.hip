@@ -4,9 +4,11 @@
 //                               LcEncoding::encode for Ligero = fffft fft_io_pc, precomp_fft (ligero lib.rs:140, 162-164)
 //   K2  transpose_to/from_t, spmm_t, sdig_rs_t (>= 24 rows); spmv, sdig_rs (fewer rows)
 //                               LcEncoding::encode for Brakedown                   (brakedown encode.rs:36-110)
-//   K2b transpose_to_t_batch, spmm_t_batch, sdig_rs_t_batch: the same for the stacked rows of a batch of commitments (batch.cpp)
+//   K2b transpose_to_t_batch, and spmm_t / spmm_t_sliced / sdig_rs_t<.., BATCH = true>: the same for the stacked rows of a batch of
+//       commitments (batch.cpp)
 //   K3  leaf_chunk / leaf_finish hash_columns (+ subtree pre-merge for sharding)    (lcpc-2d lib.rs:706-745)
 //   K4  merkle_subtree           merkle_tree / merkle_layer                         (lib.rs:747-785)
+//   K3b / K4b  the same kernels' BATCH = true forms, the member of a batch one more grid dimension; fold_paths_b3 (K8b), batch_place
 //   K5  collapse / collapse29 / field_sum / to_r29   collapse_columns               (lib.rs:1095-1123)
 //   K6  gather_columns / gather_paths                open_column                    (lib.rs:788-825)
 //
@@ -16,7 +18,7 @@
 #include "field_dev.h"
 #include "ntt_ln_dev.h"
 #include "blake3_dev.h"
-#include "leaf_dev.h"
+#include "fold_dev.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -459,12 +461,125 @@ hipError_t launch_ntt_pass(int nl, int log_tile, const NttPassArgs& a, hipStream
 // unit a row-sharded multi-GPU commit exchanges.  A second tiny kernel folds the CVs of a column with
 // BLAKE3's parent rule.  Element -> canonical little-endian bytes is one Montgomery reduction.
 // =================================================================================================
-// (ld8 / st8 and the leaf message's block loads and chunk chaining value, leaf_chunk_cv: leaf_dev.h, shared with batch_kernels.hip)
-template <int NL, bool CANON = false, bool QUAD = false>
-__global__ void __launch_bounds__(256) leaf_chunk_kernel(LeafArgs a) {
+__device__ __forceinline__ void ld8(u32 d[8], const u32* p) {
+  uint4 x = *reinterpret_cast<const uint4*>(p), y = *reinterpret_cast<const uint4*>(p + 4);
+  d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w; d[4] = y.x; d[5] = y.y; d[6] = y.z; d[7] = y.w;
+}
+__device__ __forceinline__ void st8(u32* p, const u32 d[8]) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(d[0], d[1], d[2], d[3]);
+  *reinterpret_cast<uint4*>(p + 4) = make_uint4(d[4], d[5], d[6], d[7]);
+}
+template <int NL, int PH> struct LeafRaw {
+  static constexpr int NEL = (PH + 16 + NL - 1) / NL;     // elements a 16-word block touches
+  Fe<NL> el[NEL];
+};
+// issue the global loads of one 64-byte block's elements (Montgomery form, not yet converted)
+template <int NL, int PH>
+__device__ __forceinline__ void leaf_load_raw(LeafRaw<NL, PH>& r, const LeafArgs& a, u64 col, int64_t row0) {
+#pragma unroll
+  for (int x = 0; x < LeafRaw<NL, PH>::NEL; x++) {
+    const int64_t row = row0 + x;
+    if (row >= 0 && (u64)row < a.n_rows_total) r.el[x] = fe_load<NL>(a.comm + ((u64)(row - a.row_base) * a.row_stride + col * a.col_stride) * NL);
+    else r.el[x] = fe_zero<NL>();        // the 32-byte zero prefix (rows -1, -2, ..) and the tail past the message
+  }
+}
+// Montgomery -> canonical little-endian words (PrimeField::to_repr), laid out as the block's 16 message words
+template <int NL, int PH, bool CANON = false>
+__device__ __forceinline__ void leaf_build_block(u32 m[16], const LeafRaw<NL, PH>& r) {
+  Fe<NL> c[LeafRaw<NL, PH>::NEL];
+#pragma unroll
+  for (int x = 0; x < LeafRaw<NL, PH>::NEL; x++) {
+    if constexpr (CANON) c[x] = r.el[x];                    // comm already canonical (LeafArgs::canon_in)
+    else if constexpr (NL == 8) c[x] = fe_canon_r29(r.el[x]);
+    else c[x] = fe_canon<NL>(r.el[x]);
+  }
+#pragma unroll
+  for (int p = 0; p < 16; p++) m[p] = c[(PH + p) / NL].v[(PH + p) % NL];
+}
+template <int NL, int PH, bool CANON = false>
+__device__ __forceinline__ void leaf_fill_block(u32 m[16], const LeafArgs& a, u64 col, int64_t row0) {
+  LeafRaw<NL, PH> r;
+  leaf_load_raw<NL, PH>(r, a, col, row0);
+  leaf_build_block<NL, PH, CANON>(m, r);
+}
+
+// QUAD: four lanes per column, one compression per quad (b3_compress_quad): a small commitment has fewer (column, chunk)
+// pairs than the chip has lanes, and a chunk is a chain of up to 16 dependent compressions -- ~300 instead of ~700 dependent
+// instructions each.  The four lanes build the same message block (their loads coalesce to one); 64 columns per workgroup.
+// Chaining value of chunk `chunk` of column `col`'s leaf message: in cv[8] (one lane per column), or spread over the quad
+// (lane q: words q and 4 + q in cv_lo / cv_hi).
+template <int NL, bool CANON, bool QUAD>
+__device__ __forceinline__ void leaf_chunk_cv(const LeafArgs& a, u64 col, u32 chunk, u32 q, u32 cv[8], u32& cv_lo, u32& cv_hi) {
+  const u64 total_len = 32 + (u64)NL * 4 * a.n_rows_total;
+  const u64 chunk_off = (u64)chunk * 1024;
+  const u32 chunk_len = (u32)((total_len - chunk_off) < 1024 ? (total_len - chunk_off) : 1024);
+  const u32 nblocks = (chunk_len + 63) / 64;
+  b3_set_iv(cv);
+  cv_lo = b3_sel4(q, B3_IV0, B3_IV1, B3_IV2, B3_IV3); cv_hi = b3_sel4(q, B3_IV4, B3_IV5, B3_IV6, B3_IV7);   // QUAD: this lane's two words
+  auto compress = [&](const u32* m, u32 blen, u32 flags) {
+    if constexpr (QUAD) b3_compress_quad(q, cv_lo, cv_hi, m, chunk, blen, flags);
+    else b3_compress(cv, m, chunk, blen, flags);
+  };
+  // element-word offset of block b's first word is 16*(16*chunk + b) - 8 (the zero prefix is words -8..-1)
+  auto block_row0 = [&](u32 b, int& ph) -> int64_t {
+    const int64_t s0 = ((int64_t)chunk * 16 + b) * 16 - 8;
+    const int64_t r0 = s0 >= 0 ? s0 / NL : -((-s0 + NL - 1) / NL);
+    ph = (int)(s0 - r0 * NL);
+    return r0;
+  };
+  if constexpr (NL != 6) {
+    // every block starts on an element boundary (PH == 0): software-pipeline the loads one block ahead
+    // (two blocks per trip, their operands in two register sets that swap roles: no copy of the block fetched ahead)
+    int ph;
+    LeafRaw<NL, 0> ra, rb;
+    auto one = [&](const LeafRaw<NL, 0>& r, u32 b) {
+      u32 m[16];
+      leaf_build_block<NL, 0, CANON>(m, r);
+      const u32 rem = chunk_len - 64 * b;
+      const u32 blen = rem < 64 ? rem : 64;
+      u32 flags = (b == 0 ? B3_CHUNK_START : 0u);
+      if (b == nblocks - 1) flags |= B3_CHUNK_END | (a.n_chunks_total == 1 ? B3_ROOT : 0u);
+      compress(m, blen, flags);
+    };
+    leaf_load_raw<NL, 0>(ra, a, col, block_row0(0, ph));
+    for (u32 b = 0; b < nblocks; b += 2) {
+      if (b + 1 < nblocks) leaf_load_raw<NL, 0>(rb, a, col, block_row0(b + 1, ph));
+      one(ra, b);
+      if (b + 1 < nblocks) {
+        if (b + 2 < nblocks) leaf_load_raw<NL, 0>(ra, a, col, block_row0(b + 2, ph));
+        one(rb, b + 1);
+      }
+    }
+  } else {
+    for (u32 b = 0; b < nblocks; b++) {
+      int ph;
+      const int64_t row0 = block_row0(b, ph);
+      u32 m[16];
+      if (ph == 0) leaf_fill_block<NL, 0, CANON>(m, a, col, row0);
+      else if (ph == 2) leaf_fill_block<NL, 2, CANON>(m, a, col, row0);
+      else leaf_fill_block<NL, 4, CANON>(m, a, col, row0);
+      const u32 rem = chunk_len - 64 * b;
+      const u32 blen = rem < 64 ? rem : 64;
+      u32 flags = (b == 0 ? B3_CHUNK_START : 0u);
+      if (b == nblocks - 1) flags |= B3_CHUNK_END | (a.n_chunks_total == 1 ? B3_ROOT : 0u);
+      compress(m, blen, flags);
+    }
+  }
+}
+// BATCH (K3b / K4b, here and in the three kernels below): the column hash and the tree of a batch of equal-shape commitments of one
+// encoder (batch.cpp), the member index one more grid dimension (z here, y below).  Member i's comm, chaining values and hashes sit
+// at a fixed word stride behind member 0's, and the per-member work is the same code on shifted pointers -- so one launch holds
+// n_batch times as many workgroups, where a small commitment's own launch leaves most of the chip idle.  A single commit runs the
+// instantiation that never reads the strides: its instructions are those of the kernel without them.
+template <int NL, bool CANON = false, bool QUAD = false, bool BATCH = false>
+__global__ void __launch_bounds__(256) leaf_chunk_kernel(LeafArgs a, u64 comm_stride, u64 out_stride) {
   const u64 col = QUAD ? (u64)blockIdx.x * 64 + (threadIdx.x >> 2) : (u64)blockIdx.x * 256 + threadIdx.x;
   const u32 q = threadIdx.x & 3u;
   if (col >= a.n_cols) return;
+  if constexpr (BATCH) {
+    a.comm += (u64)blockIdx.z * comm_stride;
+    a.out += (u64)blockIdx.z * out_stride;
+  }
   const u32 chunk = a.chunk_begin + blockIdx.y;
   u32 cv[8];
   u32 cv_lo, cv_hi;
@@ -484,9 +599,13 @@ __global__ void __launch_bounds__(256) leaf_chunk_kernel(LeafArgs a) {
 // parent rule -- and then folds its 64 leaf digests six levels up through LDS, one compression per quad, writing every level to
 // its slot of `hashes`.  The launches it replaces (chunk CVs, their fold, the 512-leaf subtree kernel) are each a latency chain on
 // a nearly empty chip; the tail of the tree (launch_merkle_tree_from level 6) follows.  Needs np2 == n_cols, n_cols % 64 == 0.
-template <int NL, bool CANON>
-__global__ void __launch_bounds__(256) leaf_tree_kernel(LeafArgs a, u32* hashes, u64 np2) {
+template <int NL, bool CANON, bool BATCH = false>
+__global__ void __launch_bounds__(256) leaf_tree_kernel(LeafArgs a, u32* hashes, u64 np2, u64 comm_stride, u64 hashes_stride) {
   __shared__ u32 buf[64 * 8];
+  if constexpr (BATCH) {
+    a.comm += (u64)blockIdx.y * comm_stride;
+    hashes += (u64)blockIdx.y * hashes_stride;
+  }
   const u32 tid = threadIdx.x, qd = tid >> 2, q = tid & 3u;
   const u64 base = (u64)blockIdx.x * 64;
   const u64 col = base + qd;
@@ -537,11 +656,14 @@ bool leaf_tree_supported(const LeafArgs& a, u64 np2) {
   return a.n_chunks_total <= 2 && a.n_chunks_local == a.n_chunks_total && a.chunk_begin == 0 && np2 == a.n_cols && a.n_cols >= 128 &&
          (a.n_cols & 63) == 0 && a.n_cols * a.n_chunks_total <= 65536;
 }
-hipError_t launch_leaf_tree(int nl, const LeafArgs& a, u32* hashes, u64 np2, hipStream_t st) {
-  if (!leaf_tree_supported(a, np2)) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(a.n_cols / 64));
-#define LT_CASE(NLV) case NLV: if (a.canon_in) hipLaunchKernelGGL((leaf_tree_kernel<NLV, true>), grid, dim3(256), 0, st, a, hashes, np2); \
-                               else hipLaunchKernelGGL((leaf_tree_kernel<NLV, false>), grid, dim3(256), 0, st, a, hashes, np2); break;
+// (n_batch members, or the one of a single commit: BATCH = false is called with n_batch = 1, so the refusals below are the batch form's)
+template <bool BATCH>
+static hipError_t launch_leaf_tree_t(int nl, const LeafArgs& a, u32* hashes, u64 np2, u32 n_batch, u64 comm_stride, u64 hashes_stride,
+                                     hipStream_t st) {
+  if (!leaf_tree_supported(a, np2) || n_batch == 0 || n_batch > 65535) return hipErrorInvalidValue;      // grid.y
+  const dim3 grid((unsigned)(a.n_cols / 64), n_batch);
+#define LT_CASE(NLV) case NLV: if (a.canon_in) hipLaunchKernelGGL((leaf_tree_kernel<NLV, true, BATCH>), grid, dim3(256), 0, st, a, hashes, np2, comm_stride, hashes_stride); \
+                               else hipLaunchKernelGGL((leaf_tree_kernel<NLV, false, BATCH>), grid, dim3(256), 0, st, a, hashes, np2, comm_stride, hashes_stride); break;
   switch (nl) {
     LT_CASE(2) LT_CASE(4) LT_CASE(6) LT_CASE(8)
     default: return hipErrorInvalidValue;
@@ -549,44 +671,57 @@ hipError_t launch_leaf_tree(int nl, const LeafArgs& a, u32* hashes, u64 np2, hip
 #undef LT_CASE
   return hipGetLastError();
 }
+hipError_t launch_leaf_tree(int nl, const LeafArgs& a, u32* hashes, u64 np2, hipStream_t st) {
+  return launch_leaf_tree_t<false>(nl, a, hashes, np2, 1, 0, 0, st);
+}
+// leaf digests and the first six tree levels of every member in one launch
+hipError_t launch_leaf_tree_batch(int nl, const LeafArgs& a, u32* hashes, u64 np2, u32 n_batch, u64 comm_stride, u64 hashes_stride, hipStream_t st) {
+  return launch_leaf_tree_t<true>(nl, a, hashes, np2, n_batch, comm_stride, hashes_stride, st);
+}
+template <int NL, bool BATCH>
+static void launch_leaf_chunks_nl(const LeafArgs& a, u32 n_batch, u64 comm_stride, u64 out_stride, hipStream_t st) {
+  // few (column, chunk) pairs: four lanes per column (latency); else one lane per column (throughput).  The threshold was measured
+  // on single commits; counting the pairs of ALL members of a batch against the same number is an assumption that no measurement
+  // backs yet (tools/bench_batch.py is where to check it).  A batch may therefore run the other form of the kernel than a single
+  // commit of its shape does -- both give the same chaining values.
+  const bool quad = (u64)a.n_cols * a.n_chunks_local * n_batch <= 65536;
+  const dim3 grid((unsigned)((a.n_cols + (quad ? 63 : 255)) / (quad ? 64 : 256)), a.n_chunks_local, n_batch);
+  if (a.canon_in) {
+    if (quad) hipLaunchKernelGGL((leaf_chunk_kernel<NL, true, true, BATCH>), grid, dim3(256), 0, st, a, comm_stride, out_stride);
+    else hipLaunchKernelGGL((leaf_chunk_kernel<NL, true, false, BATCH>), grid, dim3(256), 0, st, a, comm_stride, out_stride);
+  } else {
+    if (quad) hipLaunchKernelGGL((leaf_chunk_kernel<NL, false, true, BATCH>), grid, dim3(256), 0, st, a, comm_stride, out_stride);
+    else hipLaunchKernelGGL((leaf_chunk_kernel<NL, false, false, BATCH>), grid, dim3(256), 0, st, a, comm_stride, out_stride);
+  }
+}
 // grid.y is limited to 65535: a commitment with millions of short rows (new_from_dims with a small n_per_row) has more
 // leaf-message chunks than that, so the chunk range is launched in slices
-template <int NL> static void launch_leaf_chunks_nl(const LeafArgs& a, hipStream_t st) {
-  // few (column, chunk) pairs: four lanes per column (latency); else one lane per column (throughput)
-  const bool quad = (u64)a.n_cols * a.n_chunks_local <= 65536;
-  const dim3 grid((unsigned)((a.n_cols + (quad ? 63 : 255)) / (quad ? 64 : 256)), a.n_chunks_local);
-  if (a.canon_in) {
-    if (quad) hipLaunchKernelGGL((leaf_chunk_kernel<NL, true, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((leaf_chunk_kernel<NL, true, false>), grid, dim3(256), 0, st, a);
-  } else {
-    if (quad) hipLaunchKernelGGL((leaf_chunk_kernel<NL, false, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((leaf_chunk_kernel<NL, false, false>), grid, dim3(256), 0, st, a);
-  }
-}
-static hipError_t launch_leaf_chunks_slice(int nl, const LeafArgs& a, hipStream_t st) {
-  switch (nl) {
-    case 2: launch_leaf_chunks_nl<2>(a, st); break;
-    case 4: launch_leaf_chunks_nl<4>(a, st); break;
-    case 6: launch_leaf_chunks_nl<6>(a, st); break;
-    case 8: launch_leaf_chunks_nl<8>(a, st); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-hipError_t launch_leaf_chunks(int nl, const LeafArgs& a, hipStream_t st) {
-  if (a.n_chunks_local == 0 || a.n_cols == 0) return hipSuccess;
+template <bool BATCH>
+static hipError_t launch_leaf_chunks_t(int nl, const LeafArgs& a, u32 n_batch, u64 comm_stride, u64 out_stride, hipStream_t st) {
+  if (a.n_chunks_local == 0 || a.n_cols == 0 || n_batch == 0) return hipSuccess;
+  if (n_batch > 65535) return hipErrorInvalidValue;          // grid.z
   constexpr u32 SLICE = 32768;
   for (u32 s0 = 0; s0 < a.n_chunks_local; s0 += SLICE) {
     LeafArgs b = a;
     b.chunk_begin = a.chunk_begin + s0;
     b.n_chunks_local = a.n_chunks_local - s0 < SLICE ? a.n_chunks_local - s0 : SLICE;
     b.out = a.out + (u64)s0 * a.n_cols * 8;
-    hipError_t e = launch_leaf_chunks_slice(nl, b, st);
+    switch (nl) {
+      case 2: launch_leaf_chunks_nl<2, BATCH>(b, n_batch, comm_stride, out_stride, st); break;
+      case 4: launch_leaf_chunks_nl<4, BATCH>(b, n_batch, comm_stride, out_stride, st); break;
+      case 6: launch_leaf_chunks_nl<6, BATCH>(b, n_batch, comm_stride, out_stride, st); break;
+      case 8: launch_leaf_chunks_nl<8, BATCH>(b, n_batch, comm_stride, out_stride, st); break;
+      default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
-
+hipError_t launch_leaf_chunks(int nl, const LeafArgs& a, hipStream_t st) { return launch_leaf_chunks_t<false>(nl, a, 1, 0, 0, st); }
+hipError_t launch_leaf_chunks_batch(int nl, const LeafArgs& a, u32 n_batch, u64 comm_stride, u64 out_stride, hipStream_t st) {
+  return launch_leaf_chunks_t<true>(nl, a, n_batch, comm_stride, out_stride, st);
+}
 
 // BLAKE3 tree over the subtree CVs ("nodes") of each column.  Node j covers 2^node_log[j] consecutive chunks
 // starting at a multiple of its size (aligned power-of-two chunk groups are subtrees of the BLAKE3 tree); its CV
@@ -594,10 +729,16 @@ hipError_t launch_leaf_chunks(int nl, const LeafArgs& a, hipStream_t st) {
 // adding a node of 2^l chunks, merge while bit l, l+1, ... of the running chunk count is clear.  The
 // (wave-uniform) stack is kept in the slots of already-consumed nodes.  root_flag = B3_ROOT for a whole leaf
 // message, 0 when this call only pre-merges a rank's chunk range into one subtree CV (row-sharded commit).
+// BATCH: member blockIdx.y, whole leaf messages only (launch_leaf_finish_batch: null node tables -- chunk j's CV in slot j -- and ROOT).
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256) leaf_finish_kernel(u32* cvs, const u32* node_slot, const u32* node_log, u32 n_nodes,
-                                                         u64 n_cols, u32* out, u32 root_flag) {
+                                                         u64 n_cols, u32* out, u32 root_flag, u64 cvs_stride, u64 out_stride) {
   const u64 col = (u64)blockIdx.x * 256 + threadIdx.x;
   if (col >= n_cols) return;
+  if constexpr (BATCH) {
+    cvs += (u64)blockIdx.y * cvs_stride;
+    out += (u64)blockIdx.y * out_stride;
+  }
   auto slot = [&](u32 j) -> u64 { return node_slot ? node_slot[j] : j; };
   u32 cv[8], left[8];
   u32 len = 0;
@@ -631,14 +772,21 @@ __global__ void __launch_bounds__(256) leaf_finish_kernel(u32* cvs, const u32* n
   st8(out + col * 8, cv);
 }
 hipError_t launch_leaf_finish(u32* cvs, u32 n_chunks, u64 n_cols, u32* digests, hipStream_t st) {
-  hipLaunchKernelGGL(leaf_finish_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, cvs, (const u32*)nullptr,
-                     (const u32*)nullptr, n_chunks, n_cols, digests, (u32)B3_ROOT);
+  hipLaunchKernelGGL(leaf_finish_kernel<false>, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, cvs, (const u32*)nullptr,
+                     (const u32*)nullptr, n_chunks, n_cols, digests, (u32)B3_ROOT, (u64)0, (u64)0);
   return hipGetLastError();
 }
 hipError_t launch_leaf_finish_nodes(u32* cvs, const u32* node_slot, const u32* node_log, u32 n_nodes, u64 n_cols, u32* out,
                                     bool root, hipStream_t st) {
-  hipLaunchKernelGGL(leaf_finish_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, cvs, node_slot, node_log, n_nodes,
-                     n_cols, out, root ? (u32)B3_ROOT : 0u);
+  hipLaunchKernelGGL(leaf_finish_kernel<false>, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, cvs, node_slot, node_log, n_nodes,
+                     n_cols, out, root ? (u32)B3_ROOT : 0u, (u64)0, (u64)0);
+  return hipGetLastError();
+}
+// (refuses empty work, where launch_leaf_finish launches)
+hipError_t launch_leaf_finish_batch(u32* cvs, u32 n_chunks, u64 n_cols, u32* digests, u32 n_batch, u64 cvs_stride, u64 digests_stride, hipStream_t st) {
+  if (n_chunks == 0 || n_cols == 0 || n_batch == 0 || n_batch > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(leaf_finish_kernel<true>, dim3((unsigned)((n_cols + 255) / 256), n_batch), dim3(256), 0, st, cvs, (const u32*)nullptr,
+                     (const u32*)nullptr, n_chunks, n_cols, digests, (u32)B3_ROOT, cvs_stride, digests_stride);
   return hipGetLastError();
 }
 
@@ -650,9 +798,11 @@ hipError_t launch_leaf_finish_nodes(u32* cvs, const u32* node_slot, const u32* n
 // =================================================================================================
 // layers: `width` nodes at `hashes + in_off*8`; each WG reduces SUB = 2^lsub consecutive nodes down
 // `lsub` layers.  Layer j (1-based) of the subtree lands at hashes[layer_off_j + wg * (SUB >> j) + ...].
-template <u32 BS>
-__global__ void __launch_bounds__(BS) merkle_subtree_kernel(u32* hashes, u64 in_off, u64 width, u32 lsub, u32* root_out) {
+// BATCH: member blockIdx.y's hashes; root_out (may be null): [n_batch][8], member i's root at root_out + 8 i
+template <u32 BS, bool BATCH = false>
+__global__ void __launch_bounds__(BS) merkle_subtree_kernel(u32* hashes, u64 in_off, u64 width, u32 lsub, u32* root_out, u64 hashes_stride) {
   __shared__ u32 buf[BS * 8];
+  if constexpr (BATCH) hashes += (u64)blockIdx.y * hashes_stride;
   constexpr u32 NQ = BS / 4;                    // quads per workgroup
   const u32 tid = threadIdx.x;
   const u64 sub = (u64)1 << lsub;               // nodes consumed per WG (<= 2 BS)
@@ -720,12 +870,14 @@ __global__ void __launch_bounds__(BS) merkle_subtree_kernel(u32* hashes, u64 in_
   // the 32-byte device-to-host copy was a blit kernel of its own (4.3 us + its launch) behind every commit that returns a root
   if (root_out != nullptr) {
     __syncthreads();
-    if (tid < 8) root_out[tid] = buf[tid];      // node 0 of the last level
+    if (tid < 8) root_out[(BATCH ? (u64)blockIdx.y * 8 : 0) + tid] = buf[tid];      // node 0 of the last level
   }
 }
-hipError_t launch_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) { return launch_merkle_tree_from(hashes, np2, 0, st, root_out); }
-// ... from level `levels_done` on (the levels below it are in `hashes` already: leaf_tree_kernel)
-hipError_t launch_merkle_tree_from(u32* hashes, u64 np2, u32 levels_done, hipStream_t st, u32* root_out) {
+// ... from level `levels_done` on (the levels below it are in `hashes` already: leaf_tree_kernel), for every member: the launches of
+// one tree, each over the whole batch (BATCH = false is called with n_batch = 1)
+template <bool BATCH>
+static hipError_t merkle_tree_from_t(u32* hashes, u64 np2, u32 levels_done, u32 n_batch, u64 hashes_stride, hipStream_t st, u32* root_out) {
+  if (n_batch == 0 || n_batch > 65535) return hipErrorInvalidValue;       // grid.y
   u64 in_off = 0, width = np2;
   for (u32 j = 0; j < levels_done; j++) { in_off += width; width >>= 1; }
   while (width > 1) {
@@ -734,17 +886,42 @@ hipError_t launch_merkle_tree_from(u32* hashes, u64 np2, u32 levels_done, hipStr
     if (lw <= 9) {
       // <= 512 nodes left: the rest of the tree in ONE workgroup of 1024 threads, one compression per quad of lanes from
       // its first level on (wider levels belong on many CUs: 2048 leaves in one workgroup took 17 us against 9 + 6)
-      hipLaunchKernelGGL(merkle_subtree_kernel<1024>, dim3(1), dim3(1024), 0, st, hashes, in_off, width, lw, root_out);
+      hipLaunchKernelGGL((merkle_subtree_kernel<1024, BATCH>), dim3(1, n_batch), dim3(1024), 0, st, hashes, in_off, width, lw, root_out,
+                         hashes_stride);
       return hipGetLastError();
     }
     const u32 lsub = 9;
     const u64 nwg = width >> lsub;
-    hipLaunchKernelGGL(merkle_subtree_kernel<256>, dim3((unsigned)nwg), dim3(256), 0, st, hashes, in_off, width, lsub, (u32*)nullptr);
+    hipLaunchKernelGGL((merkle_subtree_kernel<256, BATCH>), dim3((unsigned)nwg, n_batch), dim3(256), 0, st, hashes, in_off, width, lsub,
+                       (u32*)nullptr, hashes_stride);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     for (u32 j = 0; j < lsub; j++) { in_off += width; width >>= 1; }
   }
   return hipSuccess;
+}
+hipError_t launch_merkle_tree(u32* hashes, u64 np2, hipStream_t st, u32* root_out) { return launch_merkle_tree_from(hashes, np2, 0, st, root_out); }
+hipError_t launch_merkle_tree_from(u32* hashes, u64 np2, u32 levels_done, hipStream_t st, u32* root_out) {
+  return merkle_tree_from_t<false>(hashes, np2, levels_done, 1, 0, st, root_out);
+}
+hipError_t launch_merkle_tree_from_batch(u32* hashes, u64 np2, u32 levels_done, u32 n_batch, u64 hashes_stride, hipStream_t st, u32* root_out) {
+  return merkle_tree_from_t<true>(hashes, np2, levels_done, n_batch, hashes_stride, st, root_out);
+}
+
+// K8b under BLAKE3 (kernels.h FoldPathsArgs, fold_dev.h): a tree node is the 64-byte message left || right hashed as one whole chunk, with
+// the flags merkle_subtree_kernel passes
+struct B3Node {
+  static constexpr int DIGEST_WORDS = 8;
+  static __device__ __forceinline__ void node(u32 o[8], const u32* l, const u32* r) { b3_hash64(o, l, r, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT); }
+};
+__global__ void __launch_bounds__(256) fold_paths_b3_kernel(FoldPathsArgs a) {
+  fold_path_lane<B3Node>(a);
+}
+hipError_t launch_fold_paths_b3(const FoldPathsArgs& a, hipStream_t st) {
+  const int job = fold_paths_job(a);
+  if (job <= 0) return job ? hipErrorInvalidValue : hipSuccess;
+  hipLaunchKernelGGL(fold_paths_b3_kernel, dim3((a.n_open + 255) / 256, a.n_batch), dim3(256), 0, st, a);
+  return hipGetLastError();
 }
 
 // =================================================================================================
@@ -1521,14 +1698,44 @@ __device__ __forceinline__ Fe<NL> spmm_t_terms(const SpmmTArgs& a, const u32* xi
   return res;
 }
 
+// =================================================================================================
+// K2b: the position-major path for a BATCH of equal-shape commitments of one encoder (batch.cpp).  The expander matrices are the
+// same for every row of every member, so the batch is one SpMM over n_batch * n_rows BATCH ROWS R = member * n_rows + row with
+// lane = batch row: the matrix entries stay wave-uniform scalar loads, the waves are full (the whole batch has at most one
+// partial wave, which is why the packed-tail kernel has no batch form), and a level is one launch.  Every member keeps its own
+// T_member[pos][row] with leading dimension n_rows, t_stride words behind its predecessor's, so that everything that reads a
+// single commit's T reads a member's unchanged.  A lane forms its own base pointers from (member, row); a wave may hold rows of
+// several members.  spmm_t_kernel, spmm_t_sliced_kernel and sdig_rs_t_kernel are each ONE body, the batch form (BATCH = true) with
+// an addressing prologue in front: the same dot products term for term, so the same values bit for bit, and the single forms'
+// instructions are those they had before they had a batch form.
+// =================================================================================================
+struct BatchRows {
+  u32 n_total;                  // n_batch * n_rows batch rows
+  u64 t_stride, alt_stride;     // words between members' T / out_alt (sdig_rs_t: in_t)
+};
+// The batch forms' addressing prologue: batch row R -> its row in its member (one division, in 32-bit arithmetic: n_total fits the
+// grid, batch_rows_ok), with a.t shifted to that member's T and a.out_alt made the base of that member's outputs wherever they go
+// (its out_alt, or position out_off of its T) -- so the batch forms store through out_alt always.  Behind it a lane runs the single
+// form's code on its own (member, row); the shifted pointers differ from lane to lane, the matrix pointers do not.
+template <int NL> __device__ __forceinline__ u32 batch_member_row(SpmmTArgs& a, const BatchRows& b, u32 R) {
+  const u32 n_rows = (u32)a.n_rows;
+  const u32 member = R / n_rows;
+  a.t += (u64)member * b.t_stride;
+  a.out_alt = a.out_alt ? a.out_alt + (u64)member * b.alt_stride : a.t + a.out_off * n_rows * NL;
+  return R - member * n_rows;
+}
+
 // OPW = outputs per workgroup (4: the wide levels; narrower ones go to spmm_t_sliced_kernel)
-// n_main: the rows this launch covers, [0, n_main) (all of them, or the whole 64-row groups when spmm_t_tail_kernel takes the rest)
-template <int NL, int SPMM_OPW>
-__global__ void __launch_bounds__(128) spmm_t_kernel(SpmmTArgs a, u32 n_main) {
-  const u64 row = (u64)blockIdx.y * 128 + threadIdx.x;
-  if ((row & ~(u64)63) >= n_main) return;            // a wave with no row at all (<= 64 rows: the workgroup's second wave)
+// n_main: the rows this launch covers, [0, n_main) (all of them, or the whole 64-row groups when spmm_t_tail_kernel takes the rest;
+// the batch form: all n_total batch rows)
+template <int NL, int SPMM_OPW, bool BATCH = false>
+__global__ void __launch_bounds__(128) spmm_t_kernel(SpmmTArgs a, u32 n_main, BatchRows b) {
+  typedef std::conditional_t<BATCH, u32, u64> row_t;
+  row_t row = (row_t)blockIdx.y * 128 + threadIdx.x;
+  if ((row & ~(row_t)63) >= n_main) return;          // a wave with no row at all (<= 64 rows: the workgroup's second wave)
   const bool live = row < n_main;
-  const u64 rr = live ? row : 0;                     // dead lanes recompute row 0 and do not store
+  if constexpr (BATCH) row = batch_member_row<NL>(a, b, live ? row : 0);
+  const row_t rr = live ? row : 0;                   // dead lanes recompute row 0 and do not store
   const u32* xin = a.t + (a.in_off * a.n_rows + rr) * NL;
   const size_t pstride = (size_t)a.n_rows * NL;      // words between consecutive positions
   for (u32 oo = 0; oo < SPMM_OPW; oo++) {
@@ -1538,7 +1745,7 @@ __global__ void __launch_bounds__(128) spmm_t_kernel(SpmmTArgs a, u32 n_main) {
     const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
     const Fe<NL> res = spmm_t_terms<NL>(a, xin, pstride, k0, k1);
     if (live) {
-      u32* dst = a.out_alt ? a.out_alt + (o * a.n_rows + row) * NL : a.t + ((a.out_off + o) * a.n_rows + row) * NL;
+      u32* dst = BATCH || a.out_alt ? a.out_alt + (o * a.n_rows + row) * NL : a.t + ((a.out_off + o) * a.n_rows + row) * NL;
       fe_store<NL>(dst, res);
     }
   }
@@ -1606,14 +1813,18 @@ __global__ void __launch_bounds__(256) spmm_t_tail_kernel(SpmmTArgs a, u32 n_mai
 // The tail levels of the recursion have a few hundred outputs or fewer, each a dependent chain of up to ~100 gathered
 // terms: the launch is bound by that chain's latency, not by throughput.  SL wave-groups per output each take 1/SL of the
 // terms; the partial sums (field elements: addition is exact, so the split does not change the result) meet in LDS.
-template <int NL, int SL>
-__global__ void __launch_bounds__(128 * SL) spmm_t_sliced_kernel(SpmmTArgs a) {
+template <int NL, int SL, bool BATCH = false>
+__global__ void __launch_bounds__(128 * SL) spmm_t_sliced_kernel(SpmmTArgs a, BatchRows b) {
+  typedef std::conditional_t<BATCH, u32, u64> row_t;
   __shared__ u32 part[(SL - 1) * 128 * NL];
   const u32 lane = threadIdx.x & 127;
   const u32 sl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
-  const u64 row = (u64)blockIdx.y * 128 + lane;
-  const bool live = row < a.n_rows;
-  const u64 rr = live ? row : 0;
+  const row_t lane_row = (row_t)blockIdx.y * 128 + lane;          // BATCH: the batch row
+  const row_t n_lanes = BATCH ? b.n_total : a.n_rows;
+  const bool live = lane_row < n_lanes;
+  row_t row = lane_row;
+  if constexpr (BATCH) row = batch_member_row<NL>(a, b, live ? lane_row : 0);
+  const row_t rr = live ? row : 0;
   const u32* xin = a.t + (a.in_off * a.n_rows + rr) * NL;
   const size_t pstride = (size_t)a.n_rows * NL;
   const u64 o = blockIdx.x;
@@ -1621,7 +1832,7 @@ __global__ void __launch_bounds__(128 * SL) spmm_t_sliced_kernel(SpmmTArgs a) {
   const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
   const u32 len = k1 - k0;
   const u32 ks = k0 + (u32)(((u64)len * sl) / SL), ke = k0 + (u32)(((u64)len * (sl + 1)) / SL);
-  const bool wave_live = (row & ~(u64)63) < a.n_rows;  // (a wave with no row at all still has to reach the barrier)
+  const bool wave_live = (lane_row & ~(row_t)63) < n_lanes;  // (a wave with no row at all still has to reach the barrier)
   Fe<NL> res = wave_live ? spmm_t_terms<NL>(a, xin, pstride, ks, ke) : fe_zero<NL>();
   if (sl) {
 #pragma unroll
@@ -1637,46 +1848,82 @@ __global__ void __launch_bounds__(128 * SL) spmm_t_sliced_kernel(SpmmTArgs a) {
       res = fe_add<NL>(res, p);
     }
     if (live) {
-      u32* dst = a.out_alt ? a.out_alt + (o * a.n_rows + row) * NL : a.t + ((a.out_off + o) * a.n_rows + row) * NL;
+      u32* dst = BATCH || a.out_alt ? a.out_alt + (o * a.n_rows + row) * NL : a.t + ((a.out_off + o) * a.n_rows + row) * NL;
       fe_store<NL>(dst, res);
     }
   }
 }
-hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st) {
-  if (a.m == 0 || a.n_rows == 0) return hipSuccess;
-  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // Ft255 has the limb path only here (spmm_t_terms reads vals29 unasked)
+// the grid's second dimension carries the batch rows: tiles of 32 (transpose) or workgroups of 128 lanes (spmm, sdig_rs)
+static bool batch_rows_ok(u32 n_batch, u64 n_rows, u32 rows_per_block, BatchRows* b) {
+  if (n_batch == 0 || n_batch > 65535) return false;
+  const u64 total = (u64)n_batch * n_rows;
+  if (total > (u64)65535 * rows_per_block) return false;
+  b->n_total = (u32)total;
+  return true;
+}
+// ONE selection by the number of outputs m, for a single commit (b == nullptr; the entry point of kernels.h below) and for the
+// stacked rows of a batch (launch_spmm_t_batch): the thresholds, slices and block sizes stand here once, each form of a kernel
+// beside its other.  tests/test_lazy_bounds.py reads them out of this body.
+static hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st, const BatchRows* b) {
+  const u64 n_lanes = b ? b->n_total : a.n_rows;
+  const dim3 sliced((unsigned)a.m, (unsigned)((n_lanes + 127) / 128));
+  const BatchRows none{};
   if (a.m >= 8192) {
-    // a last group of <= 48 rows goes to the packed-tail kernel (Ft255 limb path), the whole 64-row groups stay lane = row
-    u32 n_main = (u32)a.n_rows;
+    // a single commit's last group of <= 48 rows goes to the packed-tail kernel (Ft255 limb path), the whole 64-row groups stay
+    // lane = row; a batch has at most one partial wave in all, and no packed-tail form
+    u32 n_main = (u32)n_lanes;
     const u32 tail = (u32)(a.n_rows & 63);
-    if (nl == 8 && a.vals29 != nullptr && tail != 0 && tail <= 48) n_main -= tail;
+    if (!b) {
+      if (nl == 8 && a.vals29 != nullptr && tail != 0 && tail <= 48) n_main -= tail;
+    }
     if (n_main) {
       dim3 grid((unsigned)((a.m + 3) / 4), (unsigned)((n_main + 127) / 128));
-      LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_kernel<NLV, 4>), grid, dim3(128), 0, st, a, n_main));
+      if (b) { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_kernel<NLV, 4, true>), grid, dim3(128), 0, st, a, n_main, *b)); }
+      else { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_kernel<NLV, 4>), grid, dim3(128), 0, st, a, n_main, none)); }
     }
-    if (n_main != (u32)a.n_rows) {
+    if (n_main != (u32)n_lanes) {
       const u64 total = a.m * (a.n_rows - n_main);
       const dim3 tg((unsigned)((total + 255) / 256));
       hipLaunchKernelGGL(spmm_t_tail_kernel, tg, dim3(256), 0, st, a, n_main);
     }
   } else if (a.m > 2048) {
-    dim3 grid((unsigned)a.m, (unsigned)((a.n_rows + 127) / 128));
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 2>), grid, dim3(256), 0, st, a));
+    if (b) { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 2, true>), sliced, dim3(256), 0, st, a, *b)); }
+    else { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 2>), sliced, dim3(256), 0, st, a, none)); }
   } else if (a.m > 256) {
-    dim3 grid((unsigned)a.m, (unsigned)((a.n_rows + 127) / 128));
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 4>), grid, dim3(512), 0, st, a));
+    if (b) { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 4, true>), sliced, dim3(512), 0, st, a, *b)); }
+    else { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 4>), sliced, dim3(512), 0, st, a, none)); }
   } else {
-    dim3 grid((unsigned)a.m, (unsigned)((a.n_rows + 127) / 128));
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 8>), grid, dim3(1024), 0, st, a));
+    if (b) { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 8, true>), sliced, dim3(1024), 0, st, a, *b)); }
+    else { LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_kernel<NLV, 8>), sliced, dim3(1024), 0, st, a, none)); }
   }
   return hipGetLastError();
 }
+hipError_t launch_spmm_t(int nl, const SpmmTArgs& a, hipStream_t st) {
+  if (a.m == 0 || a.n_rows == 0) return hipSuccess;
+  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // Ft255 has the limb path only here (spmm_t_terms reads vals29 unasked)
+  return launch_spmm_t(nl, a, st, nullptr);
+}
+hipError_t launch_spmm_t_batch(int nl, const SpmmTArgs& a, u32 n_batch, u64 t_stride, u64 out_alt_stride, hipStream_t st) {
+  BatchRows b{0, t_stride, out_alt_stride};
+  if (!batch_rows_ok(n_batch, a.n_rows, 128, &b)) return hipErrorInvalidValue;
+  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // as launch_spmm_t
+  if (a.m == 0 || a.n_rows == 0) return hipSuccess;
+  return launch_spmm_t(nl, a, st, &b);
+}
 
-template <int NL>
+// BATCH: lane = batch row, member and row by one division in 32-bit arithmetic, as batch_member_row (b.alt_stride: words between members' in_t)
+template <int NL, bool BATCH = false>
 __global__ void __launch_bounds__(128) sdig_rs_t_kernel(const u32* in_t, u32 n_in, u32* t, u64 out_off, u32 n_out, u64 n_rows,
-                                                       const u32* r2) {
-  const u64 row = (u64)blockIdx.y * 128 + threadIdx.x;
-  if (row >= n_rows) return;
+                                                       const u32* r2, BatchRows b) {
+  typedef std::conditional_t<BATCH, u32, u64> row_t;
+  row_t row = (row_t)blockIdx.y * 128 + threadIdx.x;
+  if (row >= (BATCH ? b.n_total : n_rows)) return;
+  if constexpr (BATCH) {
+    const u32 member = row / (u32)n_rows;
+    row -= member * (u32)n_rows;
+    in_t += (u64)member * b.alt_stride;
+    t += (u64)member * b.t_stride;
+  }
   const u32 k = blockIdx.x;
   Fe<NL> raw = fe_zero<NL>();
   raw.v[0] = k + 1;
@@ -1689,23 +1936,13 @@ hipError_t launch_sdig_rs_t(int nl, const u32* in_t, u32 n_in, u32* t, u64 out_o
                             hipStream_t st) {
   if (!n_out || !n_rows) return hipSuccess;
   dim3 grid(n_out, (unsigned)((n_rows + 127) / 128));
-  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(sdig_rs_t_kernel<NLV>, grid, dim3(128), 0, st, in_t, n_in, t, out_off, n_out, n_rows, r2));
+  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((sdig_rs_t_kernel<NLV, false>), grid, dim3(128), 0, st, in_t, n_in, t, out_off, n_out, n_rows, r2, BatchRows{}));
   return hipGetLastError();
 }
 
-// =================================================================================================
-// K2b: the position-major path for a BATCH of equal-shape commitments of one encoder (batch.cpp).  The expander matrices are the
-// same for every row of every member, so the batch is one SpMM over n_batch * n_rows BATCH ROWS R = member * n_rows + row with
-// lane = batch row: the matrix entries stay wave-uniform scalar loads, the waves are full (the whole batch has at most one
-// partial wave, which is why the packed-tail kernel has no twin here), and a level is one launch.  Every member keeps its own
-// T_member[pos][row] with leading dimension n_rows, t_stride words behind its predecessor's, so that everything that reads a
-// single commit's T reads a member's unchanged.  A lane forms its own base pointers from (member, row); a wave may hold rows of
-// several members.  The dot products are spmm_t_terms', term for term: same values as the one-shot kernels, bit for bit.
-// =================================================================================================
-struct BatchRows {
-  u32 n_total;                  // n_batch * n_rows batch rows
-  u64 t_stride, alt_stride;     // words between members' T / out_alt (sdig_rs_t: in_t)
-};
+// K2b's transpose keeps a kernel of its own: its member split is not a prologue (the ragged-row test needs a row's place in its
+// member on every trip of the load loop, and the store loop's rows are another split), so one body would carry the batch form's
+// branches through both loops
 template <int NL>
 __global__ void __launch_bounds__(256) transpose_to_t_batch_kernel(const u32* src, u64 src_stride, u64 n_valid, u32 n_rows, u32* t,
                                                                   u64 n_src_total, u32* copy_dst, u32 canon, BatchRows b) {
@@ -1746,14 +1983,6 @@ __global__ void __launch_bounds__(256) transpose_to_t_batch_kernel(const u32* sr
     }
   }
 }
-// the grid's second dimension carries the batch rows: tiles of 32 (transpose) or workgroups of 128 lanes (spmm, sdig_rs)
-static bool batch_rows_ok(u32 n_batch, u64 n_rows, u32 rows_per_block, BatchRows* b) {
-  if (n_batch == 0 || n_batch > 65535) return false;
-  const u64 total = (u64)n_batch * n_rows;
-  if (total > (u64)65535 * rows_per_block) return false;
-  b->n_total = (u32)total;
-  return true;
-}
 hipError_t launch_transpose_to_t_batch(int nl, const u32* src, u64 src_stride, u64 n_valid, u64 n_rows, u32* t, u32 n_batch,
                                        u64 t_stride, hipStream_t st, u64 n_src_total, u32* copy_dst, bool canon) {
   BatchRows b{0, t_stride, 0};
@@ -1765,110 +1994,13 @@ hipError_t launch_transpose_to_t_batch(int nl, const u32* src, u64 src_stride, u
   return hipGetLastError();
 }
 
-// a lane's member and row, and from them its gather base and its output slot.  Dead lanes (behind the last batch row) shadow
-// batch row 0 and do not store, as in the one-shot kernels
-template <int NL> struct BatchLane {
-  const u32* xin;
-  u32* out0;                    // output o of this lane at out0 + o * pstride
-  size_t pstride;
-  __device__ __forceinline__ BatchLane(const SpmmTArgs& a, const BatchRows& b, u32 R) {
-    const u32 n_rows = (u32)a.n_rows;
-    const u32 member = R / n_rows, row = R - member * n_rows;
-    pstride = (size_t)n_rows * NL;
-    u32* tm = a.t + (u64)member * b.t_stride;
-    xin = tm + (a.in_off * n_rows + row) * NL;
-    out0 = a.out_alt ? a.out_alt + (u64)member * b.alt_stride + (size_t)row * NL : tm + (a.out_off * n_rows + row) * NL;
-  }
-};
-template <int NL, int SPMM_OPW>
-__global__ void __launch_bounds__(128) spmm_t_batch_kernel(SpmmTArgs a, BatchRows b) {
-  const u32 R = blockIdx.y * 128 + threadIdx.x;
-  if ((R & ~63u) >= b.n_total) return;               // a wave with no batch row at all
-  const bool live = R < b.n_total;
-  const BatchLane<NL> ln(a, b, live ? R : 0);
-  for (u32 oo = 0; oo < SPMM_OPW; oo++) {
-    const u64 o = (u64)blockIdx.x * SPMM_OPW + oo;
-    if (o >= a.m) break;
-    const u32 k0 = __builtin_amdgcn_readfirstlane(a.rowptr[o]);
-    const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
-    const Fe<NL> res = spmm_t_terms<NL>(a, ln.xin, ln.pstride, k0, k1);
-    if (live) fe_store<NL>(ln.out0 + o * ln.pstride, res);
-  }
-}
-template <int NL, int SL>
-__global__ void __launch_bounds__(128 * SL) spmm_t_sliced_batch_kernel(SpmmTArgs a, BatchRows b) {
-  __shared__ u32 part[(SL - 1) * 128 * NL];
-  const u32 lane = threadIdx.x & 127;
-  const u32 sl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
-  const u32 R = blockIdx.y * 128 + lane;
-  const bool live = R < b.n_total;
-  const BatchLane<NL> ln(a, b, live ? R : 0);
-  const u64 o = blockIdx.x;
-  const u32 k0 = __builtin_amdgcn_readfirstlane(a.rowptr[o]);
-  const u32 k1 = __builtin_amdgcn_readfirstlane(a.rowptr[o + 1]);
-  const u32 len = k1 - k0;
-  const u32 ks = k0 + (u32)(((u64)len * sl) / SL), ke = k0 + (u32)(((u64)len * (sl + 1)) / SL);
-  const bool wave_live = (R & ~63u) < b.n_total;       // (a wave with no batch row at all still has to reach the barrier)
-  Fe<NL> res = wave_live ? spmm_t_terms<NL>(a, ln.xin, ln.pstride, ks, ke) : fe_zero<NL>();
-  if (sl) {
-#pragma unroll
-    for (int i = 0; i < NL; i++) part[((sl - 1) * NL + i) * 128 + lane] = res.v[i];
-  }
-  __syncthreads();
-  if (sl == 0) {
-#pragma unroll
-    for (int s = 0; s < SL - 1; s++) {
-      Fe<NL> p;
-#pragma unroll
-      for (int i = 0; i < NL; i++) p.v[i] = part[(s * NL + i) * 128 + lane];
-      res = fe_add<NL>(res, p);
-    }
-    if (live) fe_store<NL>(ln.out0 + o * ln.pstride, res);
-  }
-}
-hipError_t launch_spmm_t_batch(int nl, const SpmmTArgs& a, u32 n_batch, u64 t_stride, u64 out_alt_stride, hipStream_t st) {
-  BatchRows b{0, t_stride, out_alt_stride};
-  if (!batch_rows_ok(n_batch, a.n_rows, 128, &b)) return hipErrorInvalidValue;
-  if (nl == 8 && a.vals29 == nullptr) return hipErrorInvalidValue;   // as launch_spmm_t
-  if (a.m == 0 || a.n_rows == 0) return hipSuccess;
-  const unsigned gy = (b.n_total + 127) / 128;
-  // launch_spmm_t's selection by m; no packed-tail form: the whole batch has at most one partial wave
-  if (a.m >= 8192) {
-    dim3 grid((unsigned)((a.m + 3) / 4), gy);
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_batch_kernel<NLV, 4>), grid, dim3(128), 0, st, a, b));
-  } else if (a.m > 2048) {
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 2>), dim3((unsigned)a.m, gy), dim3(256), 0, st, a, b));
-  } else if (a.m > 256) {
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 4>), dim3((unsigned)a.m, gy), dim3(512), 0, st, a, b));
-  } else {
-    LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((spmm_t_sliced_batch_kernel<NLV, 8>), dim3((unsigned)a.m, gy), dim3(1024), 0, st, a, b));
-  }
-  return hipGetLastError();
-}
-
-template <int NL>
-__global__ void __launch_bounds__(128) sdig_rs_t_batch_kernel(const u32* in_t, u32 n_in, u32* t, u64 out_off, u32 n_rows, const u32* r2,
-                                                             BatchRows b) {
-  const u32 R = blockIdx.y * 128 + threadIdx.x;
-  if (R >= b.n_total) return;
-  const u32 member = R / n_rows, row = R - member * n_rows;
-  in_t += (u64)member * b.alt_stride;
-  t += (u64)member * b.t_stride;
-  const u32 k = blockIdx.x;
-  Fe<NL> raw = fe_zero<NL>();
-  raw.v[0] = k + 1;
-  const Fe<NL> x = fe_mul<NL>(raw, fe_load<NL>(r2));          // (k+1) in Montgomery form
-  Fe<NL> r = fe_zero<NL>();
-  for (u32 j = n_in; j-- > 0;) r = fe_add<NL>(fe_mul<NL>(r, x), fe_load<NL>(in_t + ((u64)j * n_rows + row) * NL));
-  fe_store<NL>(t + ((out_off + k) * n_rows + row) * NL, r);
-}
 hipError_t launch_sdig_rs_t_batch(int nl, const u32* in_t, u32 n_in, u32* t, u64 out_off, u32 n_out, u64 n_rows, const u32* r2,
                                   u32 n_batch, u64 in_stride, u64 t_stride, hipStream_t st) {
   BatchRows b{0, t_stride, in_stride};
   if (!batch_rows_ok(n_batch, n_rows, 128, &b)) return hipErrorInvalidValue;
   if (!n_out || !n_rows) return hipSuccess;
   dim3 grid(n_out, (b.n_total + 127) / 128);
-  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL(sdig_rs_t_batch_kernel<NLV>, grid, dim3(128), 0, st, in_t, n_in, t, out_off, (u32)n_rows, r2, b));
+  LCPC_DISPATCH_NL(nl, hipLaunchKernelGGL((sdig_rs_t_kernel<NLV, true>), grid, dim3(128), 0, st, in_t, n_in, t, out_off, n_out, n_rows, r2, b));
   return hipGetLastError();
 }
 
@@ -1935,6 +2067,24 @@ hipError_t launch_pad_rows(int nl, const u32* src, u64 src_stride, u32* dst, u64
     case 8: hipLaunchKernelGGL(pad_rows_kernel<8>, grid, dim3(256), 0, st, src, src_stride, dst, dst_stride, n_valid); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// the polynomials of a batch into the padded coeffs rows of the slab (batch.cpp, every digest): member i's n_valid 64-bit words from
+// src + i * src_stride to dst + i * dst_stride, the rest of its dst_stride words zero (a ragged last row; poison between strided
+// polynomials is not read)
+__global__ void __launch_bounds__(256) batch_place_kernel(const uint2* src, u64 src_stride, u64 n_valid, uint2* dst, u64 dst_stride) {
+  const uint2* s = src + (u64)blockIdx.y * src_stride;
+  uint2* d = dst + (u64)blockIdx.y * dst_stride;
+  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < dst_stride; i += (u64)gridDim.x * 256)
+    d[i] = i < n_valid ? s[i] : make_uint2(0u, 0u);
+}
+hipError_t launch_batch_place(const uint64_t* src, u64 src_stride, u64 n_valid, uint64_t* dst, u64 dst_stride, u32 n_batch, hipStream_t st) {
+  if (n_batch == 0 || n_batch > 65535 || n_valid > dst_stride || n_valid > src_stride) return hipErrorInvalidValue;
+  if (dst_stride == 0) return hipSuccess;
+  const u64 blocks = (dst_stride + 255) / 256;
+  hipLaunchKernelGGL(batch_place_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096), n_batch), dim3(256), 0, st,
+                     reinterpret_cast<const uint2*>(src), src_stride, n_valid, reinterpret_cast<uint2*>(dst), dst_stride);
   return hipGetLastError();
 }
 

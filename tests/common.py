@@ -415,12 +415,12 @@ def leaf_quad(n_cols, n_chunks_local):
     return n_cols * n_chunks_local <= K3_QUAD_MAX
 
 
-K3B_QUAD_MAX = 65536       # batch_kernels.hip launch_leaf_chunks_batch_nl: the (column, chunk) pairs of ALL members against the same number
+K3B_QUAD_MAX = 65536       # kernels.hip launch_leaf_chunks_nl with n_batch members: the (column, chunk) pairs of ALL members against the same number
 K3B_MAX_BATCH = 65535      # the batch launchers: members per launch (a grid dimension)
 
 
 def leaf_quad_batch(n_cols, n_chunks_local, n_batch):
-    """launch_leaf_chunks_batch_nl: QUAD or one lane per column, for the whole batch"""
+    """launch_leaf_chunks_nl: QUAD or one lane per column, for the whole batch"""
     return n_cols * n_chunks_local * n_batch <= K3B_QUAD_MAX
 
 

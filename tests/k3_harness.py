@@ -133,7 +133,7 @@ def gather_paths(hashes, np2, path_len, cols, paths):
     _check("k3h_gather_paths", lib().k3h_gather_paths(_words(hashes, (2 * np2 - 1) * 8), np2, path_len, _ptr(cols), len(cols), _words(paths)))
 
 
-# ---- the batch forms (lcpc_amd/csrc/batch_kernels.hip).  A batched buffer is an (n_batch, stride) uint32 array -- member i in the first
+# ---- the batch forms (lcpc_amd/csrc/kernels.hip, BATCH = true).  A batched buffer is an (n_batch, stride) uint32 array -- member i in the first
 # words of row i, its gap behind it -- and a stride is in 32-bit words, as kernels.h defines it
 def batch_comm(comms, comm_stride, fill=0xFFFFFFFF):
     """the members' comms, (n_batch, comm_elems, L) uint64 (Leaf's layout per member) -> (n_batch, comm_stride) uint32, the gaps all ones:

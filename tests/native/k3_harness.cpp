@@ -1,5 +1,5 @@
 // tests/native/k3_harness.cpp -- test-only C entry points over the BLAKE3 column-hash (K3), Merkle-tree (K4) and path-gather launchers of
-// lcpc_amd/csrc/kernels.h and their batch forms (batch_kernels.hip), so that a test can hand a kernel a commitment matrix, a chunk range,
+// lcpc_amd/csrc/kernels.h and their batch forms (kernels.hip, BATCH = true), so that a test can hand a kernel a commitment matrix, a chunk range,
 // a node table or a leaf layer of its own making (tests/k3_harness.py, tests/test_gpu_k3_kernels.py, tests/test_gpu_k3_batch.py).  Built by
 // lcpc_amd/csrc/Makefile into lcpc_amd/lib/liblcpc_k3_harness.so and linked against the product library, which gains nothing by it.
 //
@@ -205,7 +205,7 @@ K3H_EXPORT int k3h_gather_paths(const uint32_t* hashes, uint64_t np2, uint32_t p
   return (int)d_paths.get(paths, p_bytes);
 }
 
-// ---- the batch forms (lcpc_amd/csrc/batch_kernels.hip): member i of a buffer starts i * stride 32-bit words behind member 0 and the
+// ---- the batch forms (lcpc_amd/csrc/kernels.hip, BATCH = true): member i of a buffer starts i * stride 32-bit words behind member 0 and the
 // buffer is n_batch * stride words, so every member -- the last one too -- is followed by its gap.  Refused before anything is launched:
 // n_batch outside 1 .. 65535 (a grid dimension), a stride smaller than one member (a member's region would reach into the next), and a
 // stride that is no multiple of 4 words (kernels.h: the kernels load and store 16 bytes at a time at member offsets).

@@ -46,7 +46,7 @@ def test_position_major_members(oracle, fid, n_rows):
 
 def test_wide_levels_without_the_packed_tail_kernel(oracle):
     """levels of >= 8192 outputs, 37 rows: every single commit runs spmm_t_tail_kernel (tests/test_gpu_edges.py
-    test_brakedown_packed_tail_rows), the batch of 74 stacked rows runs spmm_t_batch_kernel alone"""
+    test_brakedown_packed_tail_rows), the batch of 74 stacked rows runs spmm_t_kernel's batch form alone"""
     enc = sdig(oracle, 3, 70000, seed=9)
     check_batch(enc, 2, 37 * 70000, 37)
 

@@ -22,7 +22,7 @@ SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
 # 24 x 5: the first wave holds three members); 24 x 3 = 72 batch rows leaves the second wave partial; 65 x 2 puts the 128-lane
 # workgroup boundary inside member 1; 64 x n: members on wave boundaries; 101 x 5 = 505 rows: four workgroups
 ROWS, BATCHES = (24, 37, 63, 64, 65, 101), (1, 2, 3, 5)
-# m ON launch_spmm_t_batch's selection thresholds, as tests/test_k2_cases.py SPMM_CASES: spmm_t_batch_kernel<NL, 4> from 8192, the sliced
+# m ON launch_spmm_t_batch's selection thresholds, as tests/test_k2_cases.py SPMM_CASES: spmm_t_kernel<NL, 4, true> from 8192, the sliced
 # forms with 2 / 4 / 8 slices for (2048, 8192), (256, 2048], [.., 256]
 MS = (8192, 8191, 2049, 2048, 257, 256, 100)
 

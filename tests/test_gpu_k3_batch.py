@@ -1,4 +1,4 @@
-"""The batch forms of the BLAKE3 column-hash and Merkle-tree kernels and the placement kernel (lcpc_amd/csrc/batch_kernels.hip), launched
+"""The batch forms of the BLAKE3 column-hash and Merkle-tree kernels and the placement kernel (lcpc_amd/csrc/kernels.hip), launched
 directly through tests/k3_harness.py on the batch tables of tests/test_k3_cases.py and compared word for word with its references.  What
 lcpcx_commit_batch_device never hands them is handed here: strides with gaps, column counts that leave the last workgroup partly filled,
 chunk ranges, row bases, position-major comm, trees that are not the commitment's, member counts at the grid limit, and both forms of the

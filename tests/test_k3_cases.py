@@ -366,7 +366,7 @@ def leaf_tree_cases():
     return out
 
 
-# ---- batch cases (lcpc_amd/csrc/batch_kernels.hip, tests/test_gpu_k3_batch.py) ---------------------------------------------------------
+# ---- batch cases (lcpc_amd/csrc/kernels.hip's BATCH forms, tests/test_gpu_k3_batch.py) ---------------------------------------------------------
 # A batched buffer holds member i in the first words of row i of an (n_batch, stride) word array.  A gap is what a stride adds to one
 # member rounded up to 4 words (kernels.h: strides are multiples of 4 words); None: more than a member
 BATCH_SIZES = (1, 2, 3, 7)
@@ -431,8 +431,8 @@ BORDER_COLS = 257                                            # 255 members: 6553
 
 @functools.lru_cache(maxsize=None)
 def batch_lane_cases():
-    """either side of launch_leaf_chunks_batch_nl's 65536 (column, chunk) pairs: exactly that many and one member more; every
-    leaf_chunk_batch_kernel<NL, CANON, false> just above it on a column count that fills no workgroup; three chunks on one shape in both
+    """either side of launch_leaf_chunks_nl's 65536 (column, chunk) pairs of a whole batch: exactly that many and one member more; every
+    leaf_chunk_kernel<NL, CANON, false, true> just above it on a column count that fills no workgroup; three chunks on one shape in both
     forms; a batch whose range launch (1, 2) is one lane per column as well"""
     one = ((0, 1),)
     out = [BatchLeafCase(0, 1, 256, False, "row", one, 256, 0, 0), BatchLeafCase(0, 1, 256, False, "row", one, 257, 0, 0)]
@@ -580,11 +580,19 @@ def test_leaf_cases_reach_every_selection_axis(fid):
     assert {c.n_cols % 64 != 0 for c in cases} == {True, False} and any(c.n_cols % 256 for c in cases) and any(c.n_cols > 256 for c in cases)
 
 
+def _fn_body(src, head):
+    """the text of the function whose definition starts with `head`, up to its closing brace at column 0"""
+    i = src.index(head)
+    return src[i:src.index("\n}\n", i)]
+
+
 def test_selection_rules_match_the_sources():
     """the numbers tests/common.py restates are the ones in kernels.hip"""
     src = open(os.path.join(ROOT, "lcpc_amd", "csrc", "kernels.hip")).read()
-    assert int(re.search(r"const bool quad = \(u64\)a\.n_cols \* a\.n_chunks_local <= (\d+);", src).group(1)) == CM.K3_QUAD_MAX
-    assert int(re.search(r"constexpr u32 SLICE = (\d+);", src).group(1)) == CM.K3_SLICE
+    # one rule for single and batched commits: launch_leaf_chunks calls it with n_batch = 1
+    assert [int(v) for v in re.findall(r"const bool quad = \(u64\)a\.n_cols \* a\.n_chunks_local \* n_batch <= (\d+);", src)] == [CM.K3_QUAD_MAX]
+    assert "hipError_t launch_leaf_chunks(int nl, const LeafArgs& a, hipStream_t st) { return launch_leaf_chunks_t<false>(nl, a, 1, 0, 0, st); }" in src
+    assert int(re.search(r"constexpr u32 SLICE = (\d+);", _fn_body(src, "static hipError_t launch_leaf_chunks_t(")).group(1)) == CM.K3_SLICE
     m = re.search(r"bool leaf_tree_supported\(const LeafArgs& a, u64 np2\) \{\s*return (.*?);\s*\}", src, re.S).group(1)
     assert re.sub(r"\s+", " ", m) == ("a.n_chunks_total <= 2 && a.n_chunks_local == a.n_chunks_total && a.chunk_begin == 0 && np2 == a.n_cols && "
                                       "a.n_cols >= 128 && (a.n_cols & 63) == 0 && a.n_cols * a.n_chunks_total <= 65536")
@@ -804,10 +812,18 @@ def _batch_launches(c):
 
 
 def test_batch_selection_rule_matches_the_source():
-    src = open(os.path.join(ROOT, "lcpc_amd", "csrc", "batch_kernels.hip")).read()
-    assert int(re.search(r"const bool quad = \(u64\)a\.n_cols \* a\.n_chunks_local \* n_batch <= (\d+);", src).group(1)) == CM.K3B_QUAD_MAX
-    assert src.count("n_batch > 65535") == 5 and CM.K3B_MAX_BATCH == 65535          # each of the five launchers
-    assert "if (lw <= 9) {" in src and "blocks < 4096 ? blocks : 4096" in src
+    src = open(os.path.join(ROOT, "lcpc_amd", "csrc", "kernels.hip")).read()
+    assert [int(v) for v in re.findall(r"const bool quad = \(u64\)a\.n_cols \* a\.n_chunks_local \* n_batch <= (\d+);", src)] == [CM.K3B_QUAD_MAX]
+
+    # each of the five batch launchers reaches a refusal of n_batch > 65535: its own, or that of the implementation it shares with the
+    # single launcher (NAME_t<true>)
+    assert CM.K3B_MAX_BATCH == 65535
+    for entry in ("launch_leaf_chunks_batch", "launch_leaf_tree_batch", "launch_leaf_finish_batch", "launch_merkle_tree_from_batch",
+                  "launch_batch_place"):
+        b = _fn_body(src, "hipError_t %s(" % entry)
+        shared = re.search(r"return (\w+_t)<true>\(", b)
+        assert b.count("n_batch > 65535") == 1 if shared is None else _fn_body(src, "static hipError_t %s(" % shared.group(1)).count("n_batch > 65535") == 1, entry
+    assert src.count("if (lw <= 9) {") == 1 and "blocks < 4096 ? blocks : 4096" in src
     assert CM.leaf_quad_batch(256, 1, 256) and not CM.leaf_quad_batch(256, 1, 257) and CM.leaf_quad_batch(2048, 3, 1) == CM.leaf_quad(2048, 3)
 
 

@@ -93,6 +93,10 @@ def k2_thresholds():
                sliced_sl=_ints(r"spmm_t_sliced_kernel<NLV, (\d+)>", b), opw=one(r"spmm_t_kernel<NLV, (\d+)>", b),
                tail_max=one(r"tail <= (\d+)\)", b), rows_per_group=one(r"a\.n_rows & (\d+)\)", b) + 1)
     assert "nl == 8 && a.vals29 != nullptr && tail != 0 && tail <= " in b            # the tail kernel: Ft255 limb path only
+    # the batch launcher selects through the same body (the overload that takes the batch rows), each batch form beside its single form
+    assert _ints(r"spmm_t_sliced_kernel<NLV, (\d+), true>", b) == out["sliced_sl"] and _ints(r"spmm_t_kernel<NLV, (\d+), true>", b) == [out["opw"]]
+    bb = _body(k, "hipError_t launch_spmm_t_batch(int nl")
+    assert "return launch_spmm_t(nl, a, st, &b);" in bb and "hipLaunchKernelGGL" not in bb
     b = _body(k, "hipError_t launch_spmv(int nl")
     out["spmv_sl"] = one(r"constexpr int SL = (\d+);", b)
     b = _body(k, "__global__ void __launch_bounds__(256) spmv_kernel(")
