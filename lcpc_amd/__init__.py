@@ -51,6 +51,36 @@ def _elems(a, L):
     return a
 
 
+# the four moduli (lcpc-test-fields/src/lib.rs:13-59), for the plain-integer calls (include/lcpc_hip_ints.h): Python ints are reduced here
+FIELD_MODULUS = {FT63: 0x46d0760000000001, FT127: 0x6e754097ba20e0bf7f2bd90000000001,
+                 FT191: 0x453708aa3fbc8dda936888270ceecbcdd246820000000001,
+                 FT255: 0x663c799b6e4d2900fda9df04b9575969ef73c79086595f3002a4f20000000001}
+_INT_BYTES = {"u32": 4, "i32": 4, "u64": 8, "i64": 8}
+_INT_DTYPE_KIND = {"uint32": "u32", "int32": "i32", "uint64": "u64", "int64": "i64"}
+
+
+def _int_kind(dtype, shape, L, kind):
+    """(lcpci_kind, element count) of an integer array of `dtype` (numpy's or torch's, by name) and `shape`; kind=None goes by the
+    dtype, "wide" reads (n, L) 64-bit limbs, and a kind of the dtype's width re-reads its storage (int64 storage as "u64")."""
+    name = str(dtype).replace("torch.", "")
+    if name not in _INT_DTYPE_KIND:
+        raise ValueError("integer values must be uint32 / int32 / uint64 / int64, not %s" % name)
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if kind is None:
+        kind = _INT_DTYPE_KIND[name]
+    if kind not in _lib.INTS_KINDS:
+        raise ValueError("kind must be one of %s, not %r" % (sorted(_lib.INTS_KINDS), kind))
+    if kind == "wide":
+        if _INT_BYTES[_INT_DTYPE_KIND[name]] != 8 or len(shape) != 2 or shape[1] != L:
+            raise ValueError('kind="wide" takes an (n, L) array of 64-bit limbs')
+        n //= L
+    elif _INT_BYTES[kind] != _INT_BYTES[_INT_DTYPE_KIND[name]]:
+        raise ValueError("kind %r does not have the width of %s" % (kind, name))
+    return _lib.INTS_KINDS[kind], n
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -140,9 +170,37 @@ class _Encoding:
         self._check(_lib.lib().lcpc_random_coeffs_device(self._h, key, stream_id, n, C.c_void_p(out_ptr), C.c_void_p(stream)))
         return t
 
+    # plain integers <-> field elements on the host (include/lcpc_hip_ints.h): tensors, points, evaluations
+    def from_ints(self, values, kind=None):
+        """the (n, L) Montgomery limbs of `values` mod p.  values: a numpy array of uint32 / int32 / uint64 / int64 (kind="wide": (n, L)
+        uint64 limbs of unsigned 64 L-bit integers), or any sequence of Python ints of any size and sign -- those are reduced here and
+        sent as "wide".  A negative v is p - (|v| mod p)."""
+        if isinstance(values, np.ndarray) and values.dtype.kind in "iu":
+            a = np.ascontiguousarray(values)
+        else:
+            p = FIELD_MODULUS[self.field]
+            red = [int(v) % p for v in values]
+            a = np.array([[(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(self.L)] for v in red], np.uint64).reshape(len(red), self.L)
+            kind = "wide"
+        k, n = _int_kind(a.dtype, a.shape, self.L, kind)
+        out = np.zeros((n, self.L), np.uint64)
+        rc = _lib.lib().lcpci_from_ints(self.field, k, _ptr(a), n, _ptr(out))
+        if rc:
+            raise LcpcError(rc)
+        return out
+
+    def to_ints(self, elems):
+        """the canonical values of (n, L) Montgomery limbs as a list of Python ints in [0, p)"""
+        e = _elems(elems, self.L).reshape(-1, self.L)
+        out = np.zeros_like(e)
+        rc = _lib.lib().lcpci_to_canon(self.field, _ptr(e), e.shape[0], _ptr(out))
+        if rc:
+            raise LcpcError(rc)
+        return [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in out]
+
     def __del__(self):
         try:
-            _lib.lib().lcpc_ctx_destroy(self._h)      # commitments made with it keep the tables alive (refcount)
+            _lib.lib().lcpc_ctx_destroy(self._h)     # commitments made with it keep the tables alive (refcount)
         except Exception:
             pass
 
@@ -280,6 +338,31 @@ class LcCommit:
         root = (C.c_uint8 * enc.digest_len)() if sync else None
         cm._check(_lib.lib().lcpc_commit_device(cm._h, C.c_void_p(coeffs_ptr), n_coeffs, C.c_void_p(stream),
                                                 BORROW_COEFFS if borrow else 0, root))
+        return cm._refresh()
+
+    @classmethod
+    def commit_ints(cls, values, enc, kind=None, into=None, stream=0, sync=True):
+        """commit to plain integers (include/lcpc_hip_ints.h): element i of the polynomial is values[i] mod p; the integers cross the
+        bus as they are and are widened on the device.  A numpy array (uint32 / int32 / uint64 / int64, or (n, L) uint64 with
+        kind="wide") takes the host call, which is complete on return.  A torch tensor on the encoder's device takes the device call
+        (kind="u64" reads int64 storage as unsigned); sync=False only enqueues on `stream`, and the object keeps the tensor alive
+        until its next fill."""
+        cm = into if into is not None else cls(enc)
+        if isinstance(values, np.ndarray):
+            a = np.ascontiguousarray(values)
+            k, n = _int_kind(a.dtype, a.shape, enc.L, kind)
+            cm._check(_lib.lib().lcpci_commit_ints(cm._h, k, _ptr(a), n, None))
+            cm._coeffs_ref = None
+            return cm._refresh()
+        import torch
+        if not torch.is_tensor(values):
+            raise TypeError("values must be a numpy array or a torch tensor")
+        if values.device != torch.device("cuda", enc.params.device) or not values.is_contiguous():
+            raise ValueError("a tensor of integers must be contiguous and on the encoder's device")
+        k, n = _int_kind(values.dtype, tuple(values.shape), enc.L, kind)
+        root = (C.c_uint8 * enc.digest_len)() if sync else None
+        cm._check(_lib.lib().lcpci_commit_ints_device(cm._h, k, C.c_void_p(values.data_ptr()), n, C.c_void_p(stream), root))
+        cm._coeffs_ref = None if sync else values
         return cm._refresh()
 
     @classmethod

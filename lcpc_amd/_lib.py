@@ -131,6 +131,18 @@ COLUMNS_SYMBOLS = {
     "lcpcp_check_columns": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp]),
 }
 
+# the plain-integer extension (include/lcpc_hip_ints.h): again its own prefix, table and version
+INTS_VERSION = 1
+INTS_KINDS = {"u32": 0, "i32": 1, "u64": 2, "i64": 3, "wide": 4}      # lcpci_kind
+INTS_SYMBOLS = {
+    "lcpci_version": (_i32, []),
+    "lcpci_from_ints": (_i32, [_u32, _u32, _vp, _u64, _vp]),
+    "lcpci_to_canon": (_i32, [_u32, _vp, _u64, _vp]),
+    "lcpci_from_ints_device": (_i32, [_vp, _u32, _vp, _u64, _vp, _vp]),
+    "lcpci_commit_ints_device": (_i32, [_vp, _u32, _vp, _u64, _vp, _vp]),
+    "lcpci_commit_ints": (_i32, [_vp, _u32, _vp, _u64, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -180,5 +192,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcp_version() != COLUMNS_VERSION:
             raise RuntimeError("lcpc_amd: column-check extension version mismatch")
+        for name, (res, args) in INTS_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpci_version() != INTS_VERSION:
+            raise RuntimeError("lcpc_amd: integer extension version mismatch")
         _lib = L
     return _lib

@@ -507,7 +507,7 @@ void lcpc_commit_destroy(lcpc_commit_t* m) {
   m->sets.clear();
   m->sc.release();
   leave_slab(m);
-  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs); dev_free(m->d_chain);
+  dev_free(m->d_coeffs); dev_free(m->d_comm); dev_free(m->d_hashes); dev_free(m->d_cvs); dev_free(m->d_chain); dev_free(m->d_ints);
   for (auto& t : m->node_tabs) dev_free(t.d);
   dev_free(m->ws.d_tmp); dev_free(m->ws.d_t); dev_free(m->ws.d_mid); dev_free(m->d_gather); dev_free(m->d_xsend); dev_free(m->d_xrecv);
   for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
@@ -546,6 +546,22 @@ int lcpc::commit_device_locked(lcpc_commit_t* m, const uint64_t* coeffs_dev, uin
   const bool borrow = (flags & LCPC_COMMIT_BORROW_COEFFS) && n_rows * c->n_per_row == n_coeffs;
   if ((rc = ensure_commit_buffers(m, n_rows, !borrow, false))) return rc;
   if ((rc = encode_coeffs(m, reinterpret_cast<const uint32_t*>(coeffs_dev), n_coeffs, borrow, st))) return rc;
+  return commit_tail(m, st, root);
+}
+
+// plain integers in HBM (include/lcpc_hip_ints.h): K9 writes LcCommit.coeffs in its padded row layout, the tail of a ragged last row is
+// zeroed, and the encode reads coeffs where it lies -- no second copy, as the small host path
+int lcpc::commit_ints_device_locked(lcpc_commit_t* m, int kind, const void* vals_dev, uint64_t n_coeffs, hipStream_t st, uint8_t* root) {
+  const lcpc_ctx* c = m->enc;
+  const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
+  int rc = begin_commit(m, st, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
+  if (rc) return rc;
+  if ((rc = ensure_commit_buffers(m, n_rows, true, false))) return rc;
+  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
+  HIPCHK(m, launch_from_ints(c->NL, kind, vals_dev, n_coeffs, c->d_r2, m->d_coeffs, st));
+  if ((rc = zero_coeffs_tail(m, n_coeffs, st))) return rc;
+  if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, st))) return rc;
+  m->coeffs_view = m->d_coeffs;
   return commit_tail(m, st, root);
 }
 
@@ -651,20 +667,48 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
   std::lock_guard<std::mutex> g(m->mu);
   HIPCHK(m, hipSetDevice(c->prm.device));
+  return commit_host_locked(m, HostSource{coeffs, -1}, n_coeffs, root);
+  LCPC_CATCH(m)
+}
+
+}  // extern "C"
+
+// the widening step of a source of plain integers (K9, kernels.h launch_from_ints): elements [e0, e1) as uploaded at `up` -> their
+// place in LcCommit.coeffs.  Nothing to do for stored elements
+static int widen_source(lcpc_commit_t* m, const HostSource& src, const uint8_t* up, uint64_t e0, uint64_t e1, hipStream_t st) {
+  const lcpc_ctx* c = m->enc;
+  if (src.kind < 0 || e1 <= e0) return 0;
+  HIPCHK(m, launch_from_ints(c->NL, src.kind, up, e1 - e0, c->d_r2, m->d_coeffs + (size_t)e0 * c->NL, st));
+  return 0;
+}
+
+int lcpc::commit_host_locked(lcpc_commit_t* m, const HostSource& src, uint64_t n_coeffs, uint8_t* root) {
+  lcpc_ctx* c = m->enc;
+  const void* coeffs = src.p;
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
   int rc = begin_commit(m, nullptr, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
   if (rc) return rc;
   if ((rc = ensure_commit_buffers(m, n_rows, true, false))) return rc;
   const size_t eb = elem_bytes(c);
-  const size_t total_bytes = (size_t)n_coeffs * eb;
+  const size_t total_bytes = (size_t)n_coeffs * eb;          // of LcCommit.coeffs: what the choice of the path below goes by, whatever the source
+  // sb: bytes of one element as the source holds it; up_bytes: what crosses the bus.  The upload lands in coeffs itself where the two
+  // sizes agree (stored elements; integers as wide as an element, which K9 converts in place), else in d_ints
+  const size_t sb = src.kind < 0 ? eb : ints_elem_bytes(src.kind, c->L);
+  const size_t up_bytes = (size_t)n_coeffs * sb;
+  uint8_t* d_up = reinterpret_cast<uint8_t*>(m->d_coeffs);
+  if (sb != eb) {
+    if ((rc = ensure_dev(&m->err, &m->d_ints, &m->cap_ints, up_bytes))) return rc;
+    d_up = m->d_ints;
+  }
   // pageable source (a Rust Vec, malloc, numpy): staged through pinned bounce buffers by the host pool; small ones are not worth the ring
-  const bool pinned = c->sw_host_stage == 0 || (c->sw_host_stage < 0 && (total_bytes < ((size_t)4 << 20) || host_ptr_is_pinned(coeffs))) ||
+  const bool pinned = c->sw_host_stage == 0 || (c->sw_host_stage < 0 && (up_bytes < ((size_t)4 << 20) || host_ptr_is_pinned(coeffs))) ||
                       (c->sw_host_stage > 0 && host_ptr_is_device(coeffs));
   // Small inputs, Brakedown (whole-matrix transposes) and timing runs: one copy, then the resident path.
   if (c->prm.encoding != LCPC_ENC_LIGERO || total_bytes < ((size_t)64 << 20) || n_rows < 16 || m->timing) {
-    if ((rc = upload_host(m, m->d_coeffs, coeffs, total_bytes, total_bytes, nullptr, pinned))) return rc;
+    if ((rc = upload_host(m, d_up, coeffs, up_bytes, up_bytes, nullptr, pinned))) return rc;
     if ((rc = zero_coeffs_tail(m, n_coeffs, nullptr))) return rc;
     if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], nullptr));
+    if ((rc = widen_source(m, src, d_up, 0, n_coeffs, nullptr))) return rc;
     if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, nullptr))) return rc;
     m->coeffs_view = m->d_coeffs;
     if ((rc = commit_tail(m, nullptr, root))) return rc;
@@ -680,7 +724,7 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   for (auto& e : m->ev_batch)
     if (!e) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   // One exit: whatever fails from here on, the copies from the caller's buffer and the work behind them have left both streams
-  // before lcpc_commit returns -- as on success
+  // before the call returns -- as on success
   struct Drain {
     lcpc_commit_t* m;
     bool armed = true;
@@ -706,10 +750,11 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
     if (r0 >= n_rows) break;
     const uint64_t r1 = r0 + rows_per < n_rows ? r0 + rows_per : n_rows;
     const uint64_t e0 = r0 * c->n_per_row, e1 = r1 * c->n_per_row < n_coeffs ? r1 * c->n_per_row : n_coeffs;
-    if (e1 > e0 && (rc = upload_host(m, reinterpret_cast<uint8_t*>(m->d_coeffs) + (size_t)e0 * eb, reinterpret_cast<const uint8_t*>(coeffs) + (size_t)e0 * eb,
-                                     (size_t)(e1 - e0) * eb, total_bytes, m->s_copy, pinned))) return rc;
+    if (e1 > e0 && (rc = upload_host(m, d_up + (size_t)e0 * sb, reinterpret_cast<const uint8_t*>(coeffs) + (size_t)e0 * sb,
+                                     (size_t)(e1 - e0) * sb, up_bytes, m->s_copy, pinned))) return rc;
     HIPCHK(m, hipEventRecord(m->ev_batch[b], m->s_copy));
     HIPCHK(m, hipStreamWaitEvent(m->s_comp, m->ev_batch[b], 0));
+    if ((rc = widen_source(m, src, d_up + (size_t)e0 * sb, e0, e1, m->s_comp))) return rc;
     EncodeJob j;
     j.src = m->d_coeffs + (size_t)r0 * c->n_per_row * c->NL; j.src_stride = c->n_per_row; j.n_valid = c->n_per_row;
     j.dst = m->d_comm + (size_t)r0 * c->n_cols * c->NL; j.n_rows = r1 - r0; j.canon_out = c->comm_canon;
@@ -740,8 +785,9 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
   HIPCHK(m, hipStreamSynchronize(m->s_copy));              // (the tail memset when no batch followed it)
   drain.armed = false;
   return 0;
-  LCPC_CATCH(m)
 }
+
+extern "C" {
 
 int lcpc_commit_from_parts(lcpc_commit_t* m, const uint64_t* comm, const uint64_t* coeffs, uint64_t n_rows, uint8_t* root) {
   if (!m || !comm || n_rows == 0) return LCPC_ERR_ARG;

@@ -408,6 +408,8 @@ struct lcpc_commit_s {
   bool shard_encoded = false;      // split phases: the encode step of a sharded commit has been enqueued, hash / finish / merkle may follow
   hipStream_t s_copy = nullptr, s_comp = nullptr;   // lcpc_commit (host pointer): H2D of row batch b+1 overlaps the NTTs of batch b
   hipEvent_t ev_batch[16] = {nullptr};
+  uint8_t* d_ints = nullptr;       // host commit from plain integers narrower than an element (lcpci_commit_ints): the integers as uploaded,
+  uint64_t cap_ints = 0;           // widened from here into d_coeffs; capacity in bytes; kept across refills
   // Concurrency (include/lcpc_hip.h "Threads"): every fill (the commit entry points, from_parts, from_bincode) holds fill_mu
   // exclusively; every reader (prove, collapse, open, the getters) holds it shared for its whole duration.  A refill therefore waits
   // for the readers in flight, and no reader sees a half-filled object.  Lock order: fill_mu, then mu.
@@ -561,6 +563,16 @@ int merkleize_device(lcpc_commit_t* m, hipStream_t st);
 // lcpc_commit_device behind its argument checks and locks (the caller holds m->fill_mu exclusively and m->mu; the device is current)
 int commit_device_locked(lcpc_commit_t* m, const uint64_t* coeffs_dev, uint64_t n_coeffs, hipStream_t st, uint32_t flags, uint8_t* root);
 int encode_coeffs(lcpc_commit_t* m, const uint32_t* src, uint64_t n_src, bool borrow, hipStream_t st);
+// What a host commit reads: n stored elements (kind < 0: lcpc_commit), or n plain integers of lcpci_kind `kind` that the device widens
+// into LcCommit.coeffs behind their upload (lcpci_commit_ints).  One pipeline for both (commit.cpp commit_host_locked)
+struct HostSource {
+  const void* p = nullptr;
+  int kind = -1;
+};
+// lcpc_commit / lcpci_commit_ints behind their argument checks and locks (as commit_device_locked); complete on return
+int commit_host_locked(lcpc_commit_t* m, const HostSource& src, uint64_t n_coeffs, uint8_t* root);
+// lcpci_commit_ints_device likewise: widen into LcCommit.coeffs, encode from there
+int commit_ints_device_locked(lcpc_commit_t* m, int kind, const void* vals_dev, uint64_t n_coeffs, hipStream_t st, uint8_t* root);
 int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st);
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);
 int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);

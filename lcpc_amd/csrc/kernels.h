@@ -378,4 +378,14 @@ hipError_t launch_sdig_rs(int nl, const uint32_t* in, uint64_t in_stride, uint32
 hipError_t launch_pad_rows(int nl, const uint32_t* src, uint64_t src_stride, uint32_t* dst, uint64_t dst_stride,
                            uint64_t n_valid, uint64_t n_rows, hipStream_t st);
 
+// K9 (ints.hip): n plain integers of `kind` -> out[n][nl], the Montgomery forms of v mod p (r2 = R^2 mod p on the device).  The kinds
+// are lcpci_kind's values (include/lcpc_hip_ints.h); an element of the input is ints_elem_bytes wide and needs that alignment only
+// (WIDE: 8), `out` that of an element array (16 bytes; 8 where nl is 2 or 6).  One element per lane, the grid sized to n.  in == out
+// is allowed where the two element sizes are equal (a lane reads its element before it writes it).
+// n == 0 is hipSuccess, nothing launched; otherwise a bad nl or kind, a misaligned pointer or n >= 2^39 is hipErrorInvalidValue,
+// checked before the launch
+enum : int { INTS_U32 = 0, INTS_I32 = 1, INTS_U64 = 2, INTS_I64 = 3, INTS_WIDE = 4 };
+inline size_t ints_elem_bytes(int kind, int L) { return kind <= INTS_I32 ? 4 : kind <= INTS_I64 ? 8 : (size_t)8 * L; }
+hipError_t launch_from_ints(int nl, int kind, const void* in, uint64_t n, const uint32_t* r2, uint32_t* out, hipStream_t st);
+
 }  // namespace lcpc
