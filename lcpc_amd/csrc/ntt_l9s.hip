@@ -43,8 +43,9 @@ namespace {
 // (ln::mul_u on a.wq_w: 119 instructions) and a generic round does three lane-varying Montgomery multiplies (188 each) instead
 // of four; c2 comes out of a multiplier normalised.  Exact arithmetic mod p: the same fully reduced bits.
 // MID: the intermediate between the two passes is not the packed comm buffer but a.mid, which holds every element as the
-// LDS tile holds it -- 9 signed 29-bit limbs, normalised, |value| < 4p (invariant I of field_ln.h) -- laid out per row as
-// the successor's tiles: [tile of 1024 elements][limbs 0-3 x 1024 | limbs 4-7 x 1024 | limb 8 x 1024] (36 KiB per tile).
+// LDS tile holds it -- 9 signed 29-bit limbs, normalised; DIF form: |value| < 4p (invariant I of field_ln.h); pure form: |value| <
+// 12.04p, the I-only round's c1, c2, c3 as they leave the butterfly (below: the coset pass's round 0 is built for that) -- laid out per
+// row as the successor's tiles: [tile of 1024 elements][limbs 0-3 x 1024 | limbs 4-7 x 1024 | limb 8 x 1024] (36 KiB per tile).
 // The first pass then stores its tile as it stands (no clamp, no reduction, no 29 -> 32-bit packing: ~60 VALU per element)
 // and the last pass's tile load is a plain 36 KiB copy into LDS (no unpacking: ~17 per element), at 36 instead of 32 bytes
 // per element of intermediate traffic on a kernel that HBM does not bind.
@@ -531,8 +532,10 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
   }
 
   if constexpr (FIRST && MID) {
-    // every slot holds a normalised value with |value| < 4p (c0 clamped, c1 / c3 products, c2 a normalised sum of two
-    // products; after a lone radix-2 round: loads, normalised sums, products): stored as it is.  lb == 10 (the successor
+    // DIF form: every slot holds a normalised value with |value| < 4p (c0 clamped, c1 / c3 products, c2 a normalised sum of two
+    // products; after a lone radix-2 round: loads, normalised sums, products).  Pure form: the I-only round's outputs, normalised,
+    // c0 clamped, |c1| < 10.8p (12.04p behind an ln::mul2 round), |c2|, |c3| < 8.72p -- NOT invariant I; the coset pass clamps x0 and
+    // multiplies the rest by mul_u (tests/test_gpu_k1_passes.py holds the records to 12.04p).  Stored as it is.  lb == 10 (the successor
     // runs 10 stages), so slot (i, lp) is element (tile << LTJ | lp) of the successor's tile i
     u32* mrow = a.mid + (row << k) * 9;
 #pragma unroll

@@ -70,9 +70,9 @@ def coset_exp(k, lt, cls, r, m):
     return (k1 + (brev(m, 2 * r) << S)) << (lt - 2 - 2 * r)
 
 
-def run(x, k, lt, w, p, fourth):
-    """the two passes on a row x of n = 2^k residues, in place; fourth = w^(n/4).  Returns x (the reference's order: bit-reversed)."""
-    n, S, T = 1 << k, k - lt, 1 << lt
+def run_pure(x, k, lt, w, p, fourth):
+    """the pure first pass alone on a row x of n = 2^k residues, in place: a 2^S-point DIF on every column b (elements b + (i << lt))"""
+    S, T = k - lt, 1 << lt
     tab = Table(w, k, p)
     u0, nr4, sets, ru, _ = pure_shape(S)
     for b in range(T):                                   # column b: elements b + (i << lt)
@@ -103,6 +103,13 @@ def run(x, k, lt, w, p, fourth):
                     c = [x0 + x2 + x1 + x3, (x0 + x2 - x1 - x3) * tab(e2), (f + t) * tab(e0), (f - t) * tab(e3)]
                 for cc in range(4):
                     x[at(i0 + cc * d)] = c[cc] % p
+    return x
+
+
+def run_coset(x, k, lt, w, p, fourth):
+    """the coset-form last pass alone, in place on what run_pure left: tile t evaluates its 2^lt coefficients on w^rev_S(t) <w_{2^lt}>"""
+    S, T = k - lt, 1 << lt
+    tab = Table(w, k, p)
     for tile in range(1 << S):                           # tile: the contiguous elements (tile << lt) + e
         base = tile << lt
         for r in range(lt // 2):
@@ -118,3 +125,8 @@ def run(x, k, lt, w, p, fourth):
                 x[e0], x[e0 + d], x[e0 + 2 * d], x[e0 + 3 * d] = ((x0 + p2 + p1 + p3) % p, (x0 + p2 - p1 - p3) % p,
                                                                    (x0 - p2 + t) % p, (x0 - p2 - t) % p)
     return x
+
+
+def run(x, k, lt, w, p, fourth):
+    """the two passes on a row x of n = 2^k residues, in place; fourth = w^(n/4).  Returns x (the reference's order: bit-reversed)."""
+    return run_coset(run_pure(x, k, lt, w, p, fourth), k, lt, w, p, fourth)
