@@ -418,7 +418,10 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         const LN<9> b3 = ln::mul_u<FT>(ln::sub(x1, x3), wu + U_SLOT<FT>);                            // (-2p, 2.7p)
         LN<9> c2 = ln::add(b2, b3);
         // (pure form: clamped, (-4p, 5.4p) -> [0, p + 2^239), so that the I-only round after it adds four values below 2.7p)
-        if constexpr (NF) ln::clamp_apply<FT>(c2, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(c2.v[8])));
+        // (DIF form, a first pass that stores the limb intermediate: clamped as well.  The sum of two mul_u products lies in (-4p, 5.4p),
+        // which is fine for the rounds of this tile -- their sums are clamped -- but not for a record: invariant I, |value| < 4p, is
+        // what the successor's first round is built for, and a uniform round is this pass's last)
+        if constexpr (NF || (FIRST && MID)) ln::clamp_apply<FT>(c2, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(c2.v[8])));
         else ln::normalize<FT>(c2);
         planes_put<FT>(lds, T, SWZ(eu + 2 * dq), c2);
         planes_put<FT>(lds, T, SWZ(eu + 3 * dq), ln::mul_u<FT>(ln::sub(b2, b3), wu + 2 * U_SLOT<FT>));

@@ -430,6 +430,95 @@ GENERAL_REQUIRED = {"ntt_pass_kernel<4, 12, 1024>", "ntt_pass_kernel<2, 12, 1024
                     "ntt_pass_kernel<8, 11, 256>", "l9<10>", "l9<11>"}
 
 
+# ---- the saturating runs of tests/test_gpu_k1_saturated.py ---------------------------------------------------------------------------------
+SAT_WG_PER_CU = 8                                                   # 32 wave slots per CU / 4 waves: the most 256-thread workgroups a CU holds
+SAT_NOMINAL_CUS = 256                                               # the MI355X; the GPU module reads the real count from the device
+SAT_MAX_BYTES = 1 << 30                                             # device memory of one launch, all its buffers
+SAT_MAX_LOG_N = 20                                                  # (one row of a three-pass plan is 2048 workgroups already)
+
+
+def sat_tiles(cus):
+    """workgroups per launch that fill every CU to the bound and refill every slot at least once"""
+    return 2 * cus * SAT_WG_PER_CU
+
+
+def sat_rows(tiles_per_row, cus):
+    """the smallest row count that is odd, no multiple of 3 and reaches sat_tiles: q % n_rows and q / n_rows of the XCD-aware mappings
+    then stay off the powers of two, and off the period of the three reference rows"""
+    r = -(-sat_tiles(cus) // tiles_per_row)
+    while r % 2 == 0 or r % 3 == 0:
+        r += 1
+    return r
+
+
+def sat_plan_cases():
+    """the contexts of plan_cases() that get a saturating run: all but the three-pass ones; and Ft255 forced general at 2^19 columns,
+    the lazy-limb kernel on 2^11-element tiles (l9<11>), which plan_cases() has at 2^21 columns only"""
+    return [c for c in plan_cases() if c[2] <= SAT_MAX_LOG_N] + [("general-ft255-2^19", 3, 19, {"LCPC_NTT_GENERAL": "1"}, True)]
+
+
+def sat_tiles_per_row(fid, log_n, general):
+    """workgroups per row, counted in the kernel's own tile: 1024 elements for K1s / K1n, 2^log_tile for the general kernel (whose passes
+    launch n >> (s + log_tj) >= n >> log_tile workgroups per row)"""
+    plan = CM.ntt_plan(fid, log_n, general)
+    if plan[0]["kernel"] != "general":
+        return (1 << log_n) >> 10
+    return max(1, (1 << log_n) >> max(lt for _, _, _, lt in CM.general_passes(fid, log_n, general)))
+
+
+def sat_montword_splits(log_n):
+    """the passes test_montgomery_word_ft255_kernel runs, as lists of (log_tile, t0, s, log_tj)"""
+    k = log_n
+    return [[(lt, 0, k, 0)] for lt in (10, 11) if k <= lt] + [[(lt, 0, 1, lt - 1), (lt, 1, k - 1, 0)] for lt in (10, 11) if k - 1 <= lt <= k]
+
+
+def sat_case_bytes(fid, log_n, general, rows, gap=0, src_extra=0):
+    """the most device memory one launch of a saturating case holds: source, dst and copy_dst of rows x (n + gap) packed elements (the
+    source and copy_dst with src_extra more per row), and the limb intermediate (36 bytes per element) where the plan has one"""
+    n, eb = 1 << log_n, 8 * CM.FIELD_L[fid]
+    has_mid = fid == 3 and not general
+    return rows * ((n + gap) * eb + 2 * (n + src_extra) * eb + (n * 36 if has_mid else 0))
+
+
+def sat_reached_instantiations(cus=SAT_NOMINAL_CUS):
+    """every kernel instantiation the saturating runs launch, by the names of reached_instantiations()"""
+    names = set()
+    for _, fid, k, env, general in sat_plan_cases():
+        rows = sat_rows(sat_tiles_per_row(fid, k, general), cus)
+        for mb in ((0, 64) if fid == 3 and not general else (None,)):
+            names |= CM.ntt_instantiations(fid, CM.ntt_plan(fid, k, general, mb, n_rows=rows), k)
+        if general:
+            for t0, s, ltj, lt in CM.general_passes(fid, k, True):
+                names.add(general_instantiation(fid, lt, s, ltj, rows, k))
+    for k in MONTWORD_SIZES:
+        for passes in sat_montword_splits(k):
+            for lt, t0, s, ltj in passes:
+                names.add(general_instantiation(3, lt, s, ltj, sat_rows(max(1, (1 << k) >> lt), cus), k, montword=True))
+    return names
+
+
+def sat_required_instantiations():
+    """what the saturating runs must reach: the names of common.ntt_required_instantiations() and GENERAL_REQUIRED that exist up to
+    2^SAT_MAX_LOG_N columns -- no three-pass first pass -- with the block size the row count selects: a saturating launch has more than
+    256 tiles, so every ntt_pass_kernel<NL, 12, 1024> becomes <NL, 12, 256>"""
+    req = {x for x in CM.ntt_required_instantiations() if not x.startswith("3pass-")}
+    for fid in (0, 1, 2):                                           # K1n first passes shorter than the first two-pass size's: three-pass plans only
+        req -= {"K1n-ft%d-first-S%d" % (CM.FIELD_BITS[fid], s) for s in range(1, CM.FIRST_TWO_PASS[fid] - 10)}
+    return req | {x.replace(", 1024>", ", 256>") for x in GENERAL_REQUIRED}
+
+
+# what the saturating runs reach besides: the names the two lists above have no word for (Ft63's last pass, which has no uniform round
+# and so one form only; the multi-pass plans of the general kernel; its 2^11 tile for Ft127 and its 2^10 tile for Ft191)
+SAT_ALSO = {"K1n-ft63-last-blk0kept", "general-ft63", "general-ft127", "general-ft191", "general-ft255", "ntt_pass_kernel<4, 11, 256>",
+            "ntt_pass_kernel<6, 10, 256>"}
+
+
+def sat_commit_cases():
+    """(fid, log_n) of the commits at a saturating row count: the default plan of every field from its first two-pass size to
+    2^SAT_MAX_LOG_N columns, and the one-pass sizes 2^5 and 2^10"""
+    return [(fid, k) for fid in range(4) for k in [5, 10] + list(range(CM.FIRST_TWO_PASS[fid], SAT_MAX_LOG_N + 1))]
+
+
 def free_tiles(fid):
     """the tile sizes plan_passes uses for the field: its small and its big one"""
     nl = CM.NTT_NL[fid]

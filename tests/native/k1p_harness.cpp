@@ -35,7 +35,8 @@ using namespace lcpc;
 
 constexpr uint64_t CANARY_WORDS = 1024;                 // in front of and behind every body
 constexpr uint32_t CANARY = 0xA5A5A5A5u;
-constexpr uint64_t MAX_ROWS = 1024, MAX_ELEMS = (uint64_t)1 << 25;   // per buffer: 1 GiB of Ft255
+// per buffer: 1 GiB of Ft255; rows: a device filled with one-tile rows (tests/test_gpu_k1_saturated.py: 2 x CUs x 8 workgroups)
+constexpr uint64_t MAX_ROWS = 8192, MAX_ELEMS = (uint64_t)1 << 25;
 enum : uint64_t { F_COPY = 1, F_CANON = 2, F_MID = 4, F_INPLACE = 8, F_MONTWORD = 16 };
 constexpr uint64_t UNLIMITED = ~(uint64_t)0;
 

@@ -120,10 +120,11 @@ def _rows_of(buf, n_sub, stride, ln, NL):
 
 
 def run_step(O, ctxs, cx, i, inp, n_rows, canonical, mid=False, gap=0, n_valid=None, n_src_total=H.UNLIMITED, src_stride=None, copy=False,
-             inplace=False, what=()):
+             inplace=False, what=(), keep=None):
     """launch step i on `inp` and hold everything it wrote to the model.  inp: step 0: the job's source, (elements, L) uint64; later
     steps: (n_rows, n, L) stored values below the producer's bound, or (n_rows, n, 9) int32 limb records if the step reads mid.
-    -> the step's output in the form the next step reads (stored limbs, or limb records)"""
+    -> the step's output in the form the next step reads (stored limbs, or limb records).  keep: a dict that receives the launch as it
+    was made -- the source words, the strides, n_valid, n_src_total, the flags -- and the three buffers as they came back"""
     fid, k, L, NL = cx.fid, cx.log_n, CM.FIELD_L[cx.fid], cx.NL
     p, n = CM.field_p(fid), 1 << k
     st, last = cx.steps[i], i + 1 == len(cx.steps)
@@ -160,6 +161,9 @@ def run_step(O, ctxs, cx, i, inp, n_rows, canonical, mid=False, gap=0, n_valid=N
         res = M.reduce_once(flat, p).reshape(n_rows, n, L)
     dst, midb, cp = cx.run_step(i, src_words, n_rows=n_rows, src_stride=s_stride, dst_stride=dst_stride, n_valid=n_valid if i == 0 else None,
                                 n_src_total=n_src_total, flags=flags)
+    if keep is not None:
+        keep.update(step=i, src_words=src_words, src_stride=s_stride, dst_stride=dst_stride, n_valid=n_valid if i == 0 else ln,
+                    n_src_total=n_src_total, flags=flags, dst=dst, mid=midb, copy=cp, reads_mid=reads_mid, writes_mid=writes_mid)
     # ---- the model
     m_in = M.mont_mask_after(fid, k, cx.steps, i - 1, canonical)
     m_out = M.mont_mask_after(fid, k, cx.steps, i, canonical)

@@ -158,6 +158,56 @@ def test_case_list_reaches_every_instantiation():
             assert {m for kk, f, m in k1s if kk == k and m} == {"split", "mont"}
 
 
+def test_saturating_cases_fill_a_device_and_reach_every_instantiation():
+    """the case list of tests/test_gpu_k1_saturated.py on a nominal MI355X of 256 CUs: every context up to 2^20 columns and both
+    Montgomery-word sizes are there, every launch has 2 x 256 x 8 workgroups with a row count that is odd and no multiple of 3, no
+    launch holds 1 GiB, and the launches reach every instantiation those sizes have -- the general kernel in its BS = 256 form"""
+    cus = M.SAT_NOMINAL_CUS
+    assert M.sat_tiles(cus) == 4096
+    cases = M.sat_plan_cases()
+    ids = [c[0] for c in cases]
+    assert len(set(ids)) == len(ids)
+    assert not {c[0] for c in PLAN_CASES if c[2] <= 20} - set(ids)
+    assert not [c for c in PLAN_CASES if c[2] > 20 and not c[0].startswith("3pass-") and not c[4]]   # (only three-pass plans stay out)
+    for _, fid, k, env, general in cases:
+        tpr = M.sat_tiles_per_row(fid, k, general)
+        R = M.sat_rows(tpr, cus)
+        assert R % 2 == 1 and R % 3 != 0 and R * tpr >= M.sat_tiles(cus), (fid, k, R)
+        assert all(r % 2 == 0 or r % 3 == 0 for r in range(-(-M.sat_tiles(cus) // tpr), R)), (fid, k, R)         # the smallest such
+        for st in M.restated_steps(fid, k, general, env.get("LCPC_NTT_FORM")):
+            wg = R << (k - st.s - st.log_tj) if st.kind == "general" else R << (k - 10)    # workgroups of this step's launch
+            assert wg >= M.sat_tiles(cus), (fid, k, st)
+            if st.kind == "general":
+                assert ", 1024>" not in M.general_instantiation(fid, st.log_tile, st.s, st.log_tj, R, k)
+        # the strided run (5 elements between rows) and the fills (a source stride of n / 2 + 3 <= n + 3)
+        assert M.sat_case_bytes(fid, k, general, R, gap=5, src_extra=3) < M.SAT_MAX_BYTES, (fid, k, R)
+    for k in M.MONTWORD_SIZES:
+        assert M.sat_montword_splits(k)
+        for passes in M.sat_montword_splits(k):
+            assert sum(s for _, _, s, _ in passes) == k
+            for lt, t0, s, ltj in passes:
+                R = M.sat_rows(max(1, (1 << k) >> lt), cus)
+                assert R % 2 == 1 and R % 3 != 0 and R << (k - s - ltj) >= M.sat_tiles(cus)
+                assert 3 * R * (32 << k) < M.SAT_MAX_BYTES
+    for fid, k in M.sat_commit_cases():
+        R = M.sat_rows(M.sat_tiles_per_row(fid, k, False), cus)
+        assert R % 2 == 1 and R % 3 != 0 and R * max(1, (1 << k) >> 10) >= M.sat_tiles(cus)
+    assert {k for f, k in M.sat_commit_cases() if f == 3} == {5, 10} | set(range(11, 21))
+    # the instantiations: exactly the required ones of these sizes and the ones the lists have no name for
+    reached = M.sat_reached_instantiations(cus)
+    assert not M.sat_required_instantiations() - reached, sorted(M.sat_required_instantiations() - reached)
+    assert reached - M.sat_required_instantiations() == M.SAT_ALSO, sorted(reached - M.sat_required_instantiations())
+    assert not [x for x in reached if ", 1024>" in x]
+    assert {x for x in M.GENERAL_REQUIRED if ", 1024>" not in x} <= reached
+    # ... and with the three-pass cases, the free splits and the one-row general launches of test_gpu_k1_passes.py: everything
+    assert not (CM.ntt_required_instantiations() | M.GENERAL_REQUIRED) - (reached | M.reached_instantiations())
+
+
+def test_saturating_row_counts():
+    assert [M.sat_rows(t, 256) for t in (1, 2, 4, 8, 256, 512, 1024)] == [4097, 2051, 1025, 515, 17, 11, 5]
+    assert M.sat_rows(1, 304) == 4865 and M.sat_rows(1024, 304) == 5 and M.sat_rows(1, 1) == 17
+
+
 def test_free_splits_reach_the_paths_of_the_general_kernel():
     """what the free splits at 2^12 .. 2^14 columns reach, stated in tests/test_gpu_k1_passes.py's head"""
     want = {"s=1", "s odd", "s even", "lb < log_tj", "trivial last stages in a radix-4 round", "trivial last stage in the radix-2 tail"}
