@@ -81,6 +81,30 @@ def _int_kind(dtype, shape, L, kind):
     return _lib.INTS_KINDS[kind], n
 
 
+def _basis(basis):
+    if basis not in _lib.EVAL_BASES:
+        raise ValueError("basis must be one of %s, not %r" % (sorted(_lib.EVAL_BASES), basis))
+    return _lib.EVAL_BASES[basis]
+
+
+def _n_point(basis, n_rows, n_per_row):
+    """elements per point (include/lcpc_hip_eval.h): one for "powers", one per variable for the multilinear bases"""
+    return 1 if basis == "powers" else (n_rows * n_per_row).bit_length() - 1
+
+
+def tensors(field, point, n_rows, n_per_row, basis="powers"):
+    """lcpce_tensors (include/lcpc_hip_eval.h): the (outer (n_rows, L), inner (n_per_row, L)) tensors that open a polynomial of
+    n_rows x n_per_row coefficients at `point`.  basis="powers": point is one element x, outer[r] = x^(r n_per_row), inner[j] = x^j;
+    "ml_monomial" / "ml_lagrange": point is (n_vars, L), variable k = bit k of the coefficient index.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    p = _elems(point, L)
+    outer, inner = np.zeros((n_rows, L), np.uint64), np.zeros((n_per_row, L), np.uint64)
+    rc = _lib.lib().lcpce_tensors(field, _basis(basis), _ptr(p) if p.size else None, p.size // L, n_rows, n_per_row, _ptr(outer), _ptr(inner))
+    if rc:
+        raise LcpcError(rc)
+    return outer, inner
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -197,6 +221,11 @@ class _Encoding:
         if rc:
             raise LcpcError(rc)
         return [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in out]
+
+    def tensors(self, point, n_rows, basis="powers"):
+        """tensors(field, point, n_rows, n_per_row, basis) with the field and n_per_row of this encoder: what prove (outer) and
+        verify (outer, inner) take for a commitment of n_rows rows under it"""
+        return tensors(self.field, point, n_rows, self.n_per_row, basis)
 
     def __del__(self):
         try:
@@ -458,6 +487,64 @@ class LcCommit:
         out = np.zeros((k, self.n_per_row, self.enc.L), np.uint64)
         self._check(_lib.lib().lcpc_collapse(self._h, _ptr(t), k, _ptr(out)))
         return out[0] if k == 1 and np.ndim(tensors) <= 2 else out
+
+    # ---- evaluation (include/lcpc_hip_eval.h) ----
+    def _on_device(self, t):
+        import torch
+        if not torch.is_tensor(t):
+            return False
+        if t.device != torch.device("cuda", self.enc.params.device) or not t.is_contiguous() or t.element_size() != 8:
+            raise ValueError("a tensor of elements must be contiguous 64-bit limbs on the encoder's device")
+        return True
+
+    def eval(self, points, basis="powers"):
+        """the committed polynomial at `points`: (n_points, L) elements.  basis="powers": points is (n_points, L) (or one (L,) element)
+        and the value is sum_e coeffs[e] x^e; "ml_monomial" / "ml_lagrange": points is (n_points, n_vars, L), variable k = bit k of the
+        coefficient index.  A numpy array takes the host call (lcpce_eval: complete on return, any number of threads); a torch tensor
+        on the encoder's device takes lcpce_eval_device on torch's current stream and returns a tensor there, without a
+        synchronisation.  The limbs are those LcEvalProof.verify returns for the tensors of the same point."""
+        b, L = _basis(basis), self.enc.L
+        n_point = _n_point(basis, self.n_rows, self.n_per_row)
+        if self._on_device(points):
+            import torch
+            if points.numel() % (max(n_point, 1) * L):
+                raise LcpcError(ERR_ARG)
+            n_points = points.numel() // (n_point * L) if n_point else 1         # (no variables: the one empty point)
+            out = torch.empty((n_points, L), dtype=torch.int64, device=points.device)
+            st = torch.cuda.current_stream(points.device).cuda_stream
+            self._check(_lib.lib().lcpce_eval_device(self._h, b, C.c_void_p(points.data_ptr()), n_point, n_points, C.c_void_p(st),
+                                                     C.c_void_p(out.data_ptr())))
+            return out
+        p = _elems(points, L)
+        if p.size % (max(n_point, 1) * L):
+            raise LcpcError(ERR_ARG)
+        n_points = p.size // (n_point * L) if n_point else 1
+        out = np.zeros((n_points, L), np.uint64)
+        self._check(_lib.lib().lcpce_eval(self._h, b, _ptr(p), n_point, n_points, _ptr(out)))
+        return out
+
+    def eval_tensors(self, outer, inner):
+        """evaluation with the caller's own tensors: outer (k, n_rows, L) and inner (k, n_per_row, L) (or one pair without the
+        leading axis) -> (k, L) elements, sum_e coeffs[e] outer[e / n_per_row] inner[e % n_per_row].  numpy arrays are uploaded and
+        the result comes back as numpy; torch tensors on the encoder's device stay there (lcpce_eval_tensors_device on torch's
+        current stream, no synchronisation)."""
+        import torch
+        L = self.enc.L
+        dev = self._on_device(outer)
+        if dev != self._on_device(inner):
+            raise ValueError("outer and inner must both be numpy arrays or both device tensors")
+        if not dev:
+            device = torch.device("cuda", self.enc.params.device)
+            outer = torch.from_numpy(_elems(outer, L).view(np.int64)).to(device)
+            inner = torch.from_numpy(_elems(inner, L).view(np.int64)).to(device)
+        k = outer.numel() // (self.n_rows * L) if self.n_rows else 0
+        if k == 0 or k * self.n_rows * L != outer.numel() or k * self.n_per_row * L != inner.numel():
+            raise LcpcError(ERR_ARG)
+        out = torch.empty((k, L), dtype=torch.int64, device=outer.device)
+        st = torch.cuda.current_stream(outer.device).cuda_stream
+        self._check(_lib.lib().lcpce_eval_tensors_device(self._h, C.c_void_p(outer.data_ptr()), C.c_void_p(inner.data_ptr()), k,
+                                                         C.c_void_p(st), C.c_void_p(out.data_ptr())))
+        return out if dev else out.cpu().numpy().view(np.uint64)
 
     def open_columns(self, cols):
         cols = np.ascontiguousarray(cols, np.uint64)

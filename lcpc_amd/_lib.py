@@ -143,6 +143,19 @@ INTS_SYMBOLS = {
     "lcpci_commit_ints": (_i32, [_vp, _u32, _vp, _u64, _vp]),
 }
 
+# the evaluation extension (include/lcpc_hip_eval.h): again its own prefix, table and version
+EVAL_VERSION = 1
+EVAL_BASES = {"powers": 0, "ml_monomial": 1, "ml_lagrange": 2}      # lcpce_basis
+EVAL_SYMBOLS = {
+    "lcpce_version": (_i32, []),
+    "lcpce_tensors": (_i32, [_u32, _u32, _vp, _u32, _u64, _u64, _vp, _vp]),
+    "lcpce_tensors_device": (_i32, [_vp, _u32, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp]),
+    "lcpce_dot_device": (_i32, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "lcpce_eval_tensors_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "lcpce_eval_device": (_i32, [_vp, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "lcpce_eval": (_i32, [_vp, _u32, _vp, _u32, _u32, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -198,5 +211,11 @@ def lib():
             fn.argtypes = args
         if L.lcpci_version() != INTS_VERSION:
             raise RuntimeError("lcpc_amd: integer extension version mismatch")
+        for name, (res, args) in EVAL_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpce_version() != EVAL_VERSION:
+            raise RuntimeError("lcpc_amd: evaluation extension version mismatch")
         _lib = L
     return _lib

@@ -24,6 +24,8 @@ static void ctx_free(lcpc_ctx* c) {
   dev_free(c->d_wq_w); dev_free(c->d_rootsls); dev_free(c->d_rootslcs);
   dev_free(c->d_rootsl); dev_free(c->d_rootslc); dev_free(c->d_qpl); dev_free(c->d_roots); dev_free(c->d_r2);
   dev_free(c->ws.d_tmp); dev_free(c->ws.d_t); dev_free(c->ws.d_mid); dev_free(c->d_scratch);
+  dev_free(c->d_eval_tab);
+  if (c->ev_eval) (void)hipEventDestroy(c->ev_eval);
   c->verify_sets.clear();
   c->verify_batch_sets.clear();
   if (c->s_verify) (void)hipStreamDestroy(c->s_verify);

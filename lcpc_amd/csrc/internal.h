@@ -334,6 +334,12 @@ struct lcpc_ctx {
   lcpc::EncodeWs ws;
   uint32_t* d_scratch = nullptr;
   uint64_t scratch_cap = 0;
+  // lcpce_tensors_device / lcpce_dot_device (include/lcpc_hip_eval.h): the pair table of K10 or the chunk sums of K11, under `mu`.
+  // The calls only enqueue, on the caller's stream: ev_eval is recorded behind the kernel that last used the buffer, and the next
+  // call's stream waits for it
+  uint32_t* d_eval_tab = nullptr;
+  uint64_t eval_tab_cap = 0;
+  hipEvent_t ev_eval = nullptr;
   // RCCL communicator of a sharded encoder (lcpc_comm_init); opaque ncclComm_t
   void* comm = nullptr;
   std::mutex xchg_mu;              // serialises the submission of collectives on `comm` (several commitments, several host threads)

@@ -388,4 +388,32 @@ enum : int { INTS_U32 = 0, INTS_I32 = 1, INTS_U64 = 2, INTS_I64 = 3, INTS_WIDE =
 inline size_t ints_elem_bytes(int kind, int L) { return kind <= INTS_I32 ? 4 : kind <= INTS_I64 ? 8 : (size_t)8 * L; }
 hipError_t launch_from_ints(int nl, int kind, const void* in, uint64_t n, const uint32_t* r2, uint32_t* out, hipStream_t st);
 
+// K10 (eval.hip): the tensors of an opening from points.  The bases are lcpce_basis's values (include/lcpc_hip_eval.h); every basis is
+// out[i] = product over k < n_bits of (bit k of i * stride ? hi_k : lo_k).  `one` is R mod p as nl words in HOST memory (it travels
+// as a kernel argument); points, the table and the outputs are device arrays of elements, aligned as such (16 bytes; 8 where nl is
+// 2 or 6).  Points must be fully reduced; the outputs then are.
+// Step 1, one lane per point: tab[n_points][n_bits][2][nl] = the pairs (lo_k, hi_k) of every point, the points n_point elements
+// apart.  EVAL_POWERS: (1, x^(2^k)), n_point == 1; EVAL_ML_MONOMIAL: (1, z_k); EVAL_ML_LAGRANGE: (1 - z_k, z_k), n_point >= n_bits.
+// n_points == 0 or n_bits == 0 is hipSuccess, nothing launched; otherwise a bad nl or basis, n_bits > 64, an n_point that does not
+// fit, a NULL or misaligned pointer is hipErrorInvalidValue, checked before the launch
+enum : int { EVAL_POWERS = 0, EVAL_ML_MONOMIAL = 1, EVAL_ML_LAGRANGE = 2 };
+hipError_t launch_eval_pairs(int nl, int basis, const uint32_t* points, uint32_t n_point, uint32_t n_points, uint32_t n_bits,
+                             const uint32_t* one, uint32_t* tab, hipStream_t st);
+// Step 2, one output element per lane, the point as the grid's second dimension: out[n_points][n] from n_bits pairs of every point,
+// the points' pairs tab_bits pairs apart -- `tab` is step 1's table or, for a tensor over the variables from z_a on, that table from
+// its pair a (n_bits == 0: no table is read, every out[t][0] is 1).  n == 0 or n_points == 0 is hipSuccess, nothing launched; otherwise a bad nl or
+// basis, n_bits > 64 or > tab_bits, n_points > 65535, n >= 2^39, stride == 0, a largest index (n - 1) * stride that overflows 64 bits or has a bit
+// at or above n_bits, a NULL or misaligned pointer is hipErrorInvalidValue, checked before the launch
+hipError_t launch_eval_expand(int nl, int basis, const uint32_t* tab, uint32_t tab_bits, uint32_t n_bits, uint64_t n, uint64_t stride, uint32_t n_points,
+                              const uint32_t* one, uint32_t* out, hipStream_t st);
+// K11 (eval.hip): out[t] = sum_{i < n} a[t * a_stride + i] * b[t * b_stride + i] mod p for t < n_pairs; strides in elements, 0 shares
+// one vector.  Operands fully reduced Montgomery forms; so is the result (n == 0: zero).  parts == nullptr: one workgroup per pair.
+// Otherwise parts has room for field_dot_chunks(n, n_pairs) * n_pairs elements: a pair is cut into that many chunks, one workgroup
+// each, whose sums launch_field_sum adds in a second launch (one chunk: parts is not touched, one launch).  Same result either way.
+// n_pairs == 0 is hipSuccess, nothing launched; otherwise a bad nl, n_pairs > 65535, a NULL a / b / out or a misaligned pointer is
+// hipErrorInvalidValue, checked before any launch
+uint32_t field_dot_chunks(uint64_t n, uint32_t n_pairs);
+hipError_t launch_field_dot(int nl, const uint32_t* a, uint64_t a_stride, const uint32_t* b, uint64_t b_stride, uint64_t n,
+                            uint32_t n_pairs, uint32_t* out, uint32_t* parts, hipStream_t st);
+
 }  // namespace lcpc
