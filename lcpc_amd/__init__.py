@@ -105,6 +105,31 @@ def tensors(field, point, n_rows, n_per_row, basis="powers"):
     return outer, inner
 
 
+def _form(form):
+    if form not in _lib.FFT_FORMS:
+        raise ValueError("form must be one of %s, not %r" % (sorted(_lib.FFT_FORMS), form))
+    return _lib.FFT_FORMS[form]
+
+
+def _log_n(n):
+    if n < 1 or n & (n - 1):
+        raise ValueError("a transform takes a power-of-two number of elements, not %d" % n)
+    return n.bit_length() - 1
+
+
+def fft(field, x, form="fft_io"):
+    """lcpcf_fft (include/lcpc_hip_fft.h): fffft's FieldFFT of the (n, L) elements x, n a power of two, under the encoder's own root of
+    unity.  form: "fft_ii" / "fft_io" / "fft_oi" / "ifft_ii" / "ifft_io" / "ifft_oi", the two letters the order of input and output
+    (i natural, o bit-reversed).  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(x, L).reshape(-1, L)
+    out = np.zeros_like(a)
+    rc = _lib.lib().lcpcf_fft(field, _form(form), _ptr(a), _ptr(out), _log_n(a.shape[0]))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -226,6 +251,24 @@ class _Encoding:
         """tensors(field, point, n_rows, n_per_row, basis) with the field and n_per_row of this encoder: what prove (outer) and
         verify (outer, inner) take for a commitment of n_rows rows under it"""
         return tensors(self.field, point, n_rows, self.n_per_row, basis)
+
+    def fft(self, t, form="fft_io", out=None, stream=0):
+        """lcpcf_fft_device (include/lcpc_hip_fft.h): the transform of a torch tensor of 64-bit limbs on the encoder's device, (n, L)
+        or (n_vecs, n, L) with every vector transformed on its own; forms as lcpc_amd.fft.  out=None returns a new tensor, out=t runs
+        in place, any other tensor of t's shape must not overlap it.  Only enqueues on `stream`."""
+        import torch
+        if not torch.is_tensor(t) or t.device != torch.device("cuda", self.params.device) or not t.is_contiguous() or t.element_size() != 8:
+            raise ValueError("a tensor of elements must be contiguous 64-bit limbs on the encoder's device")
+        if t.dim() not in (2, 3) or t.shape[-1] != self.L:
+            raise ValueError("the transform takes (n, L) or (n_vecs, n, L) limbs")
+        if out is None:
+            out = torch.empty_like(t)
+        elif not torch.is_tensor(out) or out.shape != t.shape or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of the input's shape, dtype and device")
+        n_vecs = t.shape[0] if t.dim() == 3 else 1
+        self._check(_lib.lib().lcpcf_fft_device(self._h, _form(form), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                _log_n(t.shape[-2]), n_vecs, C.c_void_p(stream)))
+        return out
 
     def __del__(self):
         try:
@@ -392,6 +435,34 @@ class LcCommit:
         root = (C.c_uint8 * enc.digest_len)() if sync else None
         cm._check(_lib.lib().lcpci_commit_ints_device(cm._h, k, C.c_void_p(values.data_ptr()), n, C.c_void_p(stream), root))
         cm._coeffs_ref = None if sync else values
+        return cm._refresh()
+
+    @classmethod
+    def commit_evals(cls, evals, enc, order="natural", into=None, stream=0, sync=True):
+        """commit to the polynomial of degree < n that takes the values `evals` -- (n, L) elements, n a power of two -- on the subgroup
+        of order n (include/lcpc_hip_fft.h): order="natural" evals[i] = p(w^i), "bitrev" evals[rev(i)] = p(w^i), w the encoder's root
+        of unity.  The object ends up as LcCommit.commit of the interpolated coefficients leaves it.  A numpy array takes the host
+        call, which is complete on return.  A torch tensor on the encoder's device takes the device call and is only read;
+        sync=False only enqueues on `stream`, and the object keeps the tensor alive until its next fill."""
+        if order not in _lib.FFT_ORDERS:
+            raise ValueError("order must be one of %s, not %r" % (sorted(_lib.FFT_ORDERS), order))
+        cm = into if into is not None else cls(enc)
+        if isinstance(evals, np.ndarray):
+            a = _elems(evals, enc.L).reshape(-1, enc.L)
+            cm._check(_lib.lib().lcpcf_commit_evals(cm._h, _lib.FFT_ORDERS[order], _ptr(a), _log_n(a.shape[0]), None))
+            cm._coeffs_ref = None
+            return cm._refresh()
+        import torch
+        if not torch.is_tensor(evals):
+            raise TypeError("evals must be a numpy array or a torch tensor")
+        if evals.device != torch.device("cuda", enc.params.device) or not evals.is_contiguous() or evals.element_size() != 8:
+            raise ValueError("a tensor of elements must be contiguous 64-bit limbs on the encoder's device")
+        if evals.numel() % enc.L:
+            raise ValueError("element array size is not a multiple of L")
+        root = (C.c_uint8 * enc.digest_len)() if sync else None
+        cm._check(_lib.lib().lcpcf_commit_evals_device(cm._h, _lib.FFT_ORDERS[order], C.c_void_p(evals.data_ptr()),
+                                                       _log_n(evals.numel() // enc.L), C.c_void_p(stream), root))
+        cm._coeffs_ref = None if sync else evals
         return cm._refresh()
 
     @classmethod

@@ -156,6 +156,19 @@ EVAL_SYMBOLS = {
     "lcpce_eval": (_i32, [_vp, _u32, _vp, _u32, _u32, _vp]),
 }
 
+# the transform extension (include/lcpc_hip_fft.h): again its own prefix, table and version
+FFT_VERSION = 1
+FFT_FORMS = {"fft_ii": 0, "fft_io": 1, "fft_oi": 2, "ifft_ii": 3, "ifft_io": 4, "ifft_oi": 5}      # lcpcf_form
+FFT_ORDERS = {"natural": 0, "bitrev": 1}                                                          # lcpcf_order
+FFT_SYMBOLS = {
+    "lcpcf_version": (_i32, []),
+    "lcpcf_max_log_n": (_u32, [_u32]),
+    "lcpcf_fft": (_i32, [_u32, _u32, _vp, _vp, _u32]),
+    "lcpcf_fft_device": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _vp]),
+    "lcpcf_commit_evals_device": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp]),
+    "lcpcf_commit_evals": (_i32, [_vp, _u32, _vp, _u32, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -217,5 +230,11 @@ def lib():
             fn.argtypes = args
         if L.lcpce_version() != EVAL_VERSION:
             raise RuntimeError("lcpc_amd: evaluation extension version mismatch")
+        for name, (res, args) in FFT_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcf_version() != FFT_VERSION:
+            raise RuntimeError("lcpc_amd: transform extension version mismatch")
         _lib = L
     return _lib

@@ -673,6 +673,34 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
 
 }  // extern "C"
 
+// evaluations on the subgroup of 2^log_n points (include/lcpc_hip_fft.h): the inverse transform's first kernel reads the caller's
+// buffer and writes LcCommit.coeffs, the rest of it runs there in place (K12 / K13, fft.hip), and the encode reads coeffs where it
+// lies, as behind K9.  host: the evaluations are uploaded into coeffs first and the whole transform runs in place
+int lcpc::commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root) {
+  lcpc_ctx* c = m->enc;
+  const uint64_t n_coeffs = (uint64_t)1 << log_n;
+  const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
+  int rc = begin_commit(m, st, n_rows, 0, n_rows, 0, leaf_chunks(c, n_rows));
+  if (rc) return rc;
+  if ((rc = ensure_commit_buffers(m, n_rows, true, false))) return rc;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(evals);
+  if (host) {
+    const size_t bytes = (size_t)n_coeffs * elem_bytes(c);
+    const bool pinned = c->sw_host_stage == 0 || (c->sw_host_stage < 0 && (bytes < ((size_t)4 << 20) || host_ptr_is_pinned(evals))) ||
+                        (c->sw_host_stage > 0 && host_ptr_is_device(evals));
+    if ((rc = upload_host(m, m->d_coeffs, evals, bytes, bytes, st, pinned))) return rc;
+    src = m->d_coeffs;
+  }
+  if ((rc = zero_coeffs_tail(m, n_coeffs, st))) return rc;
+  if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
+  if ((rc = fft_enqueue(c, &m->err, form, src, m->d_coeffs, log_n, 1, st))) return rc;
+  if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, st))) return rc;
+  m->coeffs_view = m->d_coeffs;
+  if ((rc = commit_tail(m, st, root))) return rc;
+  if (host) HIPCHK(m, hipStreamSynchronize(st));     // the caller's (possibly pageable) buffer is no longer in use on return
+  return 0;
+}
+
 // the widening step of a source of plain integers (K9, kernels.h launch_from_ints): elements [e0, e1) as uploaded at `up` -> their
 // place in LcCommit.coeffs.  Nothing to do for stored elements
 static int widen_source(lcpc_commit_t* m, const HostSource& src, const uint8_t* up, uint64_t e0, uint64_t e1, hipStream_t st) {

@@ -286,6 +286,15 @@ struct lcpc_transcript {
   lcpc_transcript(const uint8_t* l, size_t n) : t(l, n) {}
 };
 
+namespace lcpc {
+struct FftTab {
+  uint32_t log_n = 0;
+  bool inverse = false;
+  uint32_t* d = nullptr;           // fft_tab_elems(log_n) elements (kernels.h launch_fft)
+  uint64_t stamp = 0;              // last use
+};
+}  // namespace lcpc
+
 struct lcpc_ctx {
   lcpc_params prm{};
   // A/B switches, read from the environment ONCE, when the context is created (never on a launch path: getenv next to a
@@ -340,6 +349,11 @@ struct lcpc_ctx {
   uint32_t* d_eval_tab = nullptr;
   uint64_t eval_tab_cap = 0;
   hipEvent_t ev_eval = nullptr;
+  // lcpcf_fft_device / lcpcf_commit_evals* (include/lcpc_hip_fft.h): the two-level twiddle tables of the last few (size, direction)
+  // pairs, under `mu`; made on first use (fft.cpp fft_enqueue), read-only afterwards, so streams need no order among each other --
+  // an evicted table is freed by hipFree, which waits for the kernels that still read it
+  lcpc::FftTab fft_tabs[4];
+  uint64_t fft_stamp = 0;
   // RCCL communicator of a sharded encoder (lcpc_comm_init); opaque ncclComm_t
   void* comm = nullptr;
   std::mutex xchg_mu;              // serialises the submission of collectives on `comm` (several commitments, several host threads)
@@ -579,6 +593,12 @@ struct HostSource {
 int commit_host_locked(lcpc_commit_t* m, const HostSource& src, uint64_t n_coeffs, uint8_t* root);
 // lcpci_commit_ints_device likewise: widen into LcCommit.coeffs, encode from there
 int commit_ints_device_locked(lcpc_commit_t* m, int kind, const void* vals_dev, uint64_t n_coeffs, hipStream_t st, uint8_t* root);
+// lcpcf_commit_evals_device / lcpcf_commit_evals (include/lcpc_hip_fft.h) behind their argument checks and locks: the inverse transform
+// (form: FFT_IFFT_II or FFT_IFFT_OI) of 2^log_n evaluations lands in LcCommit.coeffs and the pipeline runs from there.  host: `evals` is
+// host memory, uploaded into coeffs and transformed in place, and the call is complete on return
+int commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root);
+// K12 / K13 on `st` with the context's twiddle tables (fft.cpp; takes c->mu): in == out in place, otherwise disjoint
+int fft_enqueue(lcpc_ctx* c, ErrText* err, int form, const uint32_t* in, uint32_t* out, uint32_t log_n, uint32_t n_vecs, hipStream_t st);
 int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st);
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);
 int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);

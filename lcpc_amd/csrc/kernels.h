@@ -416,4 +416,26 @@ uint32_t field_dot_chunks(uint64_t n, uint32_t n_pairs);
 hipError_t launch_field_dot(int nl, const uint32_t* a, uint64_t a_stride, const uint32_t* b, uint64_t b_stride, uint64_t n,
                             uint32_t n_pairs, uint32_t* out, uint32_t* parts, hipStream_t st);
 
+// K12 / K13 (fft.hip): the transform of n_vecs whole vectors of n = 2^log_n elements, the vectors n elements apart.  The forms are
+// lcpcf_form's values (include/lcpc_hip_fft.h): X[k] = sum_j x[j] w^(jk), the inverse with w^-1 and n^-1; the two letters give the
+// order of input and output, I natural, O bit-reversed.
+// fft_plan: the stage split of a transform in decimation-in-frequency order, ceil(log_n / log_tile) passes of log_tile stages of
+// which the last takes the remainder; s[] has room for FFT_MAX_PASSES entries.  Returns the number of passes (0 for log_n == 0),
+// -1 for log_tile == 0, log_tile > FFT_MAX_LOG_TILE or log_n > FFT_MAX_LOG_N.  A pure host function: launch_fft runs exactly this plan
+// (the natural-output forms run it from its last pass to its first).
+// Twiddles come from a two-level table `tab` on the device, for the root v = w (forward) or w^-1 (inverse):
+//   tab[i] = v^i for i < 2^h, tab[2^h + i] = v^(i 2^h) for i < 2^(log_n - h), h = fft_tab_split(log_n); fft_tab_elems(log_n) elements
+// in all, at most 2^(ceil(log_n / 2) + 1).  n_inv: n^-1 mod p as nl words in HOST memory (a kernel argument), read by the inverse
+// forms only.  in == out runs in place; otherwise the two ranges must not overlap, and `in` is only read.  Inputs fully reduced; every
+// stored element then is.  *n_launches (may be null) receives the number of kernels launched: the passes, plus K13 for the II forms.
+// log_n == 0 copies (no launch).  A bad nl, form, log_tile or log_n, n_vecs == 0 or > 65535, n_vecs * n >= 2^39, a NULL or
+// misaligned pointer is hipErrorInvalidValue, checked before any launch
+enum : int { FFT_FFT_II = 0, FFT_FFT_IO = 1, FFT_FFT_OI = 2, FFT_IFFT_II = 3, FFT_IFFT_IO = 4, FFT_IFFT_OI = 5 };
+constexpr uint32_t FFT_MAX_LOG_TILE = 10, FFT_MAX_LOG_N = 32, FFT_MAX_PASSES = 32;
+inline uint32_t fft_tab_split(uint32_t log_n) { return log_n / 2; }
+inline uint64_t fft_tab_elems(uint32_t log_n) { return ((uint64_t)1 << fft_tab_split(log_n)) + ((uint64_t)1 << (log_n - fft_tab_split(log_n))); }
+int fft_plan(uint32_t log_n, uint32_t log_tile, uint32_t s[]);
+hipError_t launch_fft(int nl, int form, uint32_t log_n, uint32_t log_tile, uint32_t n_vecs, const uint32_t* in, uint32_t* out,
+                      const uint32_t* tab, const uint32_t* n_inv, hipStream_t st, uint32_t* n_launches);
+
 }  // namespace lcpc
