@@ -55,8 +55,8 @@
  *    log_n > min(S, 32); LCPC_ERR_STATE on a sharded encoder; both leave a committed object as it was.
  *  - the host form: one upload of the evaluations into coeffs, then the device form in place; complete on return.  Elements with
  *    a limb pattern >= p are LCPC_ERR_ARG.
- *  Out of scope: sharded encoders; batch forms of the commit; coset transforms; the values of a commitment on a subgroup (run
- *  the device transform on its coefficients).
+ *  Out of scope: sharded encoders; batch forms of the commit.  Coset transforms, the low-degree extension and the values of a
+ *  commitment on a domain are lcpc_hip_domain.h's.
  */
 #ifndef LCPC_HIP_FFT_H
 #define LCPC_HIP_FFT_H

@@ -130,6 +130,54 @@ def fft(field, x, form="fft_io"):
     return out
 
 
+def _order(order):
+    if order not in _lib.DOMAIN_ORDERS:
+        raise ValueError("order must be one of %s, not %r" % (sorted(_lib.DOMAIN_ORDERS), order))
+    return _lib.DOMAIN_ORDERS[order]
+
+
+def _shift(shift, L):
+    """one element: the L limbs of a shift, in host memory"""
+    s = np.ascontiguousarray(shift, dtype=np.uint64).reshape(-1)
+    if s.size != L:
+        raise ValueError("a shift is one element of %d limbs" % L)
+    return s
+
+
+def generator(field):
+    """lcpcd_generator (include/lcpc_hip_domain.h): ff's multiplicative_generator() of the field as (L,) Montgomery limbs -- the
+    coset shift everybody uses."""
+    out = np.zeros(FIELD_LIMBS[field], np.uint64)
+    rc = _lib.lib().lcpcd_generator(field, _ptr(out))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def coset_fft(field, x, shift, form="fft_io"):
+    """lcpcd_coset_fft (include/lcpc_hip_domain.h): the transform of the (n, L) elements x on the coset shift * H_n -- forward
+    X[k] = p(shift w^k), inverse back to the coefficients; forms as lcpc_amd.fft.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(x, L).reshape(-1, L)
+    out = np.zeros_like(a)
+    rc = _lib.lib().lcpcd_coset_fft(field, _form(form), _ptr(_shift(shift, L)), _ptr(a), _ptr(out), _log_n(a.shape[0]))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def extend(field, coeffs, shift, log_m, order="natural"):
+    """lcpcd_extend (include/lcpc_hip_domain.h): the values of the polynomial with the (n_coeffs, L) coefficients on the 2^log_m
+    points shift * w_m^k; order="natural" stores value k at [k], "bitrev" at [rev(k)].  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(coeffs, L).reshape(-1, L)
+    out = np.zeros((1 << log_m if log_m < 48 else 0, L), np.uint64)
+    rc = _lib.lib().lcpcd_extend(field, _ptr(_shift(shift, L)), _ptr(a), a.shape[0], log_m, _order(order), _ptr(out))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -269,6 +317,60 @@ class _Encoding:
         self._check(_lib.lib().lcpcf_fft_device(self._h, _form(form), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
                                                 _log_n(t.shape[-2]), n_vecs, C.c_void_p(stream)))
         return out
+
+    def _elem_tensor(self, t, what="the transform"):
+        import torch
+        if not torch.is_tensor(t) or t.device != torch.device("cuda", self.params.device) or not t.is_contiguous() or t.element_size() != 8:
+            raise ValueError("a tensor of elements must be contiguous 64-bit limbs on the encoder's device")
+        if t.dim() not in (2, 3) or t.shape[-1] != self.L:
+            raise ValueError("%s takes (n, L) or (n_vecs, n, L) limbs" % what)
+        return t.shape[0] if t.dim() == 3 else 1
+
+    def _out_tensor(self, t, out, shape):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=t.dtype, device=t.device)
+        if not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != t.dtype or out.device != t.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of shape %s with the input's dtype and device" % (tuple(shape),))
+        return out
+
+    def coset_fft(self, t, shift, form="fft_io", out=None, stream=0):
+        """lcpcd_coset_fft_device (include/lcpc_hip_domain.h): enc.fft on the coset shift * H_n; shift is one element of host limbs
+        (lcpc_amd.generator).  out=None returns a new tensor, out=t runs in place.  Only enqueues on `stream`."""
+        n_vecs = self._elem_tensor(t)
+        out = self._out_tensor(t, out, t.shape)
+        self._check(_lib.lib().lcpcd_coset_fft_device(self._h, _form(form), _ptr(_shift(shift, self.L)), C.c_void_p(t.data_ptr()),
+                                                      C.c_void_p(out.data_ptr()), _log_n(t.shape[-2]), n_vecs, C.c_void_p(stream)))
+        return out
+
+    def extend(self, coeffs, shift, log_m, order="natural", n_coeffs=None, out=None, stream=0):
+        """lcpcd_extend_device: the values on the 2^log_m points shift * w_m^k of the polynomials whose coefficients are the vectors
+        of `coeffs`, (n, L) or (n_vecs, n, L) with n a power of two; n_coeffs <= n says how many of each vector are read (the rest
+        counts as zero; n must then be the next power of two).  Returns (2^log_m, L) or (n_vecs, 2^log_m, L).  Only enqueues."""
+        n_vecs = self._elem_tensor(coeffs, "the extension")
+        n = coeffs.shape[-2]
+        _log_n(n)
+        if n_coeffs is None:
+            n_coeffs = n
+        if not 0 < n_coeffs <= n or 2 * n_coeffs <= n > 1:
+            raise ValueError("the coefficient vectors lie 2^ceil(log2 n_coeffs) elements apart")
+        out = self._out_tensor(coeffs, out, tuple(coeffs.shape[:-2]) + (1 << log_m if log_m < 40 else 0, self.L))
+        self._check(_lib.lib().lcpcd_extend_device(self._h, _ptr(_shift(shift, self.L)), C.c_void_p(coeffs.data_ptr()), n_coeffs, log_m,
+                                                   _order(order), C.c_void_p(out.data_ptr()), n_vecs, C.c_void_p(stream)))
+        return out
+
+    def lde(self, t, log_m, shift_out, shift_in=None, in_order="natural", out_order="natural", work=None, out=None, stream=0):
+        """lcpcd_lde_device: values on shift_in * H_n (shift_in=None: on H_n) -> values on shift_out * H_m, m = 2^log_m >= n, for (n, L)
+        or (n_vecs, n, L) columns.  Returns (out, work): work, of t's shape, holds the coefficients; work=t overwrites the input.
+        Only enqueues on `stream`."""
+        n_vecs = self._elem_tensor(t, "the low-degree extension")
+        work = self._out_tensor(t, work, t.shape)
+        out = self._out_tensor(t, out, tuple(t.shape[:-2]) + (1 << log_m if log_m < 40 else 0, self.L))
+        si = None if shift_in is None else _ptr(_shift(shift_in, self.L))
+        self._check(_lib.lib().lcpcd_lde_device(self._h, _order(in_order), si, C.c_void_p(t.data_ptr()), _log_n(t.shape[-2]),
+                                                _ptr(_shift(shift_out, self.L)), log_m, _order(out_order), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(work.data_ptr()), n_vecs, C.c_void_p(stream)))
+        return out, work
 
     def __del__(self):
         try:
@@ -464,6 +566,46 @@ class LcCommit:
                                                        _log_n(evals.numel() // enc.L), C.c_void_p(stream), root))
         cm._coeffs_ref = None if sync else evals
         return cm._refresh()
+
+    @classmethod
+    def commit_coset_evals(cls, evals, shift, enc, order="natural", into=None, stream=0, sync=True):
+        """commit_evals for values on the coset shift * H_n (include/lcpc_hip_domain.h): order="natural" evals[i] = p(shift w^i),
+        "bitrev" evals[rev(i)] = p(shift w^i); shift is one element of host limbs (lcpc_amd.generator).  numpy takes the host call,
+        a torch tensor on the encoder's device the device call, as commit_evals."""
+        o, sh = _order(order), _shift(shift, enc.L)
+        cm = into if into is not None else cls(enc)
+        if isinstance(evals, np.ndarray):
+            a = _elems(evals, enc.L).reshape(-1, enc.L)
+            cm._check(_lib.lib().lcpcd_commit_coset_evals(cm._h, o, _ptr(sh), _ptr(a), _log_n(a.shape[0]), None))
+            cm._coeffs_ref = None
+            return cm._refresh()
+        import torch
+        if not torch.is_tensor(evals):
+            raise TypeError("evals must be a numpy array or a torch tensor")
+        if evals.device != torch.device("cuda", enc.params.device) or not evals.is_contiguous() or evals.element_size() != 8:
+            raise ValueError("a tensor of elements must be contiguous 64-bit limbs on the encoder's device")
+        if evals.numel() % enc.L:
+            raise ValueError("element array size is not a multiple of L")
+        root = (C.c_uint8 * enc.digest_len)() if sync else None
+        cm._check(_lib.lib().lcpcd_commit_coset_evals_device(cm._h, o, _ptr(sh), C.c_void_p(evals.data_ptr()),
+                                                             _log_n(evals.numel() // enc.L), C.c_void_p(stream), root))
+        cm._coeffs_ref = None if sync else evals
+        return cm._refresh()
+
+    def values(self, shift, log_m, order="natural", out=None, stream=0):
+        """lcpcd_commit_values_device: the values of the committed polynomial sum_i coeffs[i] X^i on the 2^log_m points shift * w_m^k
+        as a (2^log_m, L) torch tensor on the encoder's device (out: written there).  2^log_m must be at least n_rows * n_per_row.
+        A reader of the object; only enqueues on `stream`."""
+        import torch
+        shape = (1 << log_m if log_m < 40 else 0, self.enc.L)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=torch.device("cuda", self.enc.params.device))
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.element_size() != 8 or not out.is_contiguous() or \
+                out.device != torch.device("cuda", self.enc.params.device):
+            raise ValueError("out must be a contiguous (2^log_m, L) tensor of 64-bit limbs on the encoder's device")
+        self._check(_lib.lib().lcpcd_commit_values_device(self._h, _ptr(_shift(shift, self.enc.L)), log_m, _order(order),
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
 
     @classmethod
     def from_parts(cls, enc, comm, coeffs, n_rows, into=None):

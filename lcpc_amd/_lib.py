@@ -169,6 +169,22 @@ FFT_SYMBOLS = {
     "lcpcf_commit_evals": (_i32, [_vp, _u32, _vp, _u32, _vp]),
 }
 
+# the domain extension (include/lcpc_hip_domain.h): again its own prefix, table and version; its forms are FFT_FORMS
+DOMAIN_VERSION = 1
+DOMAIN_ORDERS = {"natural": 0, "bitrev": 1}                                                       # lcpcd_order
+DOMAIN_SYMBOLS = {
+    "lcpcd_version": (_i32, []),
+    "lcpcd_generator": (_i32, [_u32, _vp]),
+    "lcpcd_coset_fft": (_i32, [_u32, _u32, _vp, _vp, _vp, _u32]),
+    "lcpcd_coset_fft_device": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "lcpcd_extend": (_i32, [_u32, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "lcpcd_extend_device": (_i32, [_vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32, _vp]),
+    "lcpcd_lde_device": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "lcpcd_commit_coset_evals_device": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "lcpcd_commit_coset_evals": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
+    "lcpcd_commit_values_device": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -236,5 +252,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcf_version() != FFT_VERSION:
             raise RuntimeError("lcpc_amd: transform extension version mismatch")
+        for name, (res, args) in DOMAIN_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcd_version() != DOMAIN_VERSION:
+            raise RuntimeError("lcpc_amd: domain extension version mismatch")
         _lib = L
     return _lib

@@ -675,8 +675,10 @@ int lcpc_commit(lcpc_commit_t* m, const uint64_t* coeffs, uint64_t n_coeffs, uin
 
 // evaluations on the subgroup of 2^log_n points (include/lcpc_hip_fft.h): the inverse transform's first kernel reads the caller's
 // buffer and writes LcCommit.coeffs, the rest of it runs there in place (K12 / K13, fft.hip), and the encode reads coeffs where it
-// lies, as behind K9.  host: the evaluations are uploaded into coeffs first and the whole transform runs in place
-int lcpc::commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root) {
+// lies, as behind K9.  host: the evaluations are uploaded into coeffs first and the whole transform runs in place.  With a shift the
+// evaluations lie on its coset and the inverse is K14's (include/lcpc_hip_domain.h)
+int lcpc::commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root,
+                              const uint64_t* shift) {
   lcpc_ctx* c = m->enc;
   const uint64_t n_coeffs = (uint64_t)1 << log_n;
   const uint64_t n_rows = (n_coeffs + c->n_per_row - 1) / c->n_per_row;
@@ -693,7 +695,7 @@ int lcpc::commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals,
   }
   if ((rc = zero_coeffs_tail(m, n_coeffs, st))) return rc;
   if (m->timing) HIPCHK(m, hipEventRecord(m->ev[0], st));
-  if ((rc = fft_enqueue(c, &m->err, form, src, m->d_coeffs, log_n, 1, st))) return rc;
+  if ((rc = shift ? coset_enqueue(c, &m->err, form, shift, src, m->d_coeffs, log_n, 1, st) : fft_enqueue(c, &m->err, form, src, m->d_coeffs, log_n, 1, st))) return rc;
   if ((rc = encode_commit(m, m->d_coeffs, ~(uint64_t)0, false, st))) return rc;
   m->coeffs_view = m->d_coeffs;
   if ((rc = commit_tail(m, st, root))) return rc;

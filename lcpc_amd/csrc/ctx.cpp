@@ -26,6 +26,7 @@ static void ctx_free(lcpc_ctx* c) {
   dev_free(c->ws.d_tmp); dev_free(c->ws.d_t); dev_free(c->ws.d_mid); dev_free(c->d_scratch);
   dev_free(c->d_eval_tab);
   for (auto& t : c->fft_tabs) dev_free(t.d);
+  for (auto& t : c->dom_tabs) dev_free(t.d);
   if (c->ev_eval) (void)hipEventDestroy(c->ev_eval);
   c->verify_sets.clear();
   c->verify_batch_sets.clear();

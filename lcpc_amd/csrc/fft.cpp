@@ -1,7 +1,8 @@
 // lcpc_amd/csrc/fft.cpp -- the transform extension of the C ABI (include/lcpc_hip_fft.h): the six FieldFFT forms on the host
-// (host_field.h, no HIP call) and on the device (K12 / K13, fft.hip) with the context's cache of two-level twiddle tables, and the
+// (fft_host.h, no HIP call) and on the device (K12 / K13, fft.hip) with the context's cache of two-level twiddle tables, and the
 // two commit entry points that read evaluations.  The commit pipeline itself is commit.cpp's (commit_evals_locked).
 #include "internal.h"
+#include "fft_host.h"
 #include "../../include/lcpc_hip_fft.h"
 
 using namespace lcpc;
@@ -13,107 +14,13 @@ static_assert(LCPCF_FFT_II == FFT_FFT_II && LCPCF_FFT_IO == FFT_FFT_IO && LCPCF_
 namespace {
 
 inline bool dev_aligned(const void* p, int L) { return reinterpret_cast<uintptr_t>(p) % (L % 2 ? 8 : 16) == 0; }
-inline bool form_inverse(uint32_t form) { return form >= LCPCF_IFFT_II; }
-inline bool form_ii(uint32_t form) { return form == LCPCF_FFT_II || form == LCPCF_IFFT_II; }
-inline bool form_dit(uint32_t form) { return form != LCPCF_FFT_IO && form != LCPCF_IFFT_IO; }      // the natural-output forms
 inline uint32_t dev_max_log_n(const FieldDesc& f) { return f.S < FFT_MAX_LOG_N ? f.S : FFT_MAX_LOG_N; }
 
-// two ranges of `bytes` bytes overlap without being the same range
-inline bool overlap(const void* a, const void* b, uint64_t bytes) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x != y && (x < y ? y - x < bytes : x - y < bytes);
-}
-
-bool all_reduced(const FieldDesc& f, const uint64_t* e, uint64_t n) {
-  for (uint64_t i = 0; i < n; i++)
-    if (h_ge_p(f, e + i * f.L)) return false;
-  return true;
-}
-
-void h_pow(const FieldDesc& f, uint64_t* o, const uint64_t* base, uint64_t e) {
-  uint64_t acc[MAXL], b[MAXL];
-  memcpy(acc, f.r, 8 * f.L);
-  memcpy(b, base, 8 * f.L);
-  for (; e; e >>= 1) {
-    if (e & 1) h_mul(f, acc, acc, b);
-    h_mul(f, b, b, b);
-  }
-  memcpy(o, acc, 8 * f.L);
-}
-
-// the root of the direction: w = ROOT_OF_UNITY^(2^(S - log_n)), or w^-1 = w^(n - 1)
-void root_of(const FieldDesc& f, uint32_t log_n, bool inverse, uint64_t* v) {
-  memcpy(v, f.rou, 8 * f.L);
-  for (unsigned i = log_n; i < f.S; i++) h_mul(f, v, v, v);
-  if (inverse) h_pow(f, v, v, ((uint64_t)1 << log_n) - 1);         // (log_n <= S < 64)
-}
-
-// n^-1 = ((p + 1) / 2)^log_n
-void n_inverse(const FieldDesc& f, uint32_t log_n, uint64_t* o) {
-  uint64_t half[MAXL] = {0, 0, 0, 0};
-  for (int i = 0; i < f.L; i++) half[i] = (f.p[i] >> 1) | (i + 1 < f.L ? f.p[i + 1] << 63 : 0);      // (p - 1) / 2
-  for (int i = 0; i < f.L && ++half[i] == 0; i++) {}
-  h_mul(f, half, half, f.r2);
-  h_pow(f, o, half, log_n);
-}
-
-// out[i] = v^i for i < n
-void powers(const FieldDesc& f, const uint64_t* v, uint64_t n, uint64_t* out) {
-  memcpy(out, f.r, 8 * f.L);
-  for (uint64_t i = 1; i < n; i++) h_mul(f, out + i * f.L, out + (i - 1) * f.L, v);
-}
-
-void host_fft(const FieldDesc& f, uint32_t form, uint64_t* a, uint32_t log_n) {
-  if (log_n == 0) return;
-  const int L = f.L;
-  const uint64_t n = (uint64_t)1 << log_n;
-  uint64_t v[MAXL];
-  root_of(f, log_n, form_inverse(form), v);
-  std::vector<uint64_t> tab((size_t)(n / 2) * L);
-  powers(f, v, n / 2, tab.data());
-  if (form_ii(form)) {
-    uint64_t t[MAXL];
-    for (uint64_t i = 0; i < n; i++) {
-      uint64_t j = 0;
-      for (uint32_t b = 0; b < log_n; b++) j |= ((i >> b) & 1) << (log_n - 1 - b);
-      if (i < j) {
-        memcpy(t, a + i * L, 8 * L); memcpy(a + i * L, a + j * L, 8 * L); memcpy(a + j * L, t, 8 * L);
-      }
-    }
-  }
-  const bool dit = form_dit(form);
-  for (uint32_t k = 0; k < log_n; k++) {
-    const uint32_t t = dit ? log_n - 1 - k : k;
-    const uint64_t h = n >> (t + 1);
-    for (uint64_t base = 0; base < n; base += 2 * h)
-      for (uint64_t j = 0; j < h; j++) {
-        uint64_t* x = a + (base + j) * L;
-        uint64_t* y = x + h * L;
-        const uint64_t* w = tab.data() + (size_t)(j << t) * L;
-        uint64_t s[MAXL];
-        if (dit) {
-          h_mul(f, y, y, w);
-          h_add(f, s, x, y);
-          h_sub(f, y, x, y);
-          memcpy(x, s, 8 * L);
-        } else {
-          h_add(f, s, x, y);
-          h_sub(f, y, x, y);
-          h_mul(f, y, y, w);
-          memcpy(x, s, 8 * L);
-        }
-      }
-  }
-  if (form_inverse(form)) {
-    uint64_t ni[MAXL];
-    n_inverse(f, log_n, ni);
-    for (uint64_t i = 0; i < n; i++) h_mul(f, a + i * L, a + i * L, ni);
-  }
-}
+}  // namespace
 
 // the context's table of (log_n, inverse), c->mu held: found, or built on the host, uploaded and put in place of the entry used
 // longest ago
-int fft_table(lcpc_ctx* c, ErrText* err, uint32_t log_n, bool inverse, const uint32_t** tab) {
+int lcpc::fft_table(lcpc_ctx* c, ErrText* err, uint32_t log_n, bool inverse, const uint32_t** tab) {
   FftTab* victim = &c->fft_tabs[0];
   for (auto& t : c->fft_tabs) {
     if (t.d && t.log_n == log_n && t.inverse == inverse) { t.stamp = ++c->fft_stamp; *tab = t.d; return 0; }
@@ -138,8 +45,6 @@ int fft_table(lcpc_ctx* c, ErrText* err, uint32_t log_n, bool inverse, const uin
   *tab = victim->d;
   return 0;
 }
-
-}  // namespace
 
 int lcpc::fft_enqueue(lcpc_ctx* c, ErrText* err, int form, const uint32_t* in, uint32_t* out, uint32_t log_n, uint32_t n_vecs, hipStream_t st) {
   std::lock_guard<std::mutex> g(c->mu);
@@ -168,7 +73,7 @@ int lcpcf_fft(uint32_t field, uint32_t form, const uint64_t* in, uint64_t* out, 
   const FieldDesc* f = field_desc((int)field);
   if (!f || form > LCPCF_IFFT_OI || !in || !out || log_n > f->S) return LCPC_ERR_ARG;
   const uint64_t n = (uint64_t)1 << log_n;
-  if (overlap(in, out, n * 8 * f->L) || !all_reduced(*f, in, n)) return LCPC_ERR_ARG;
+  if (ranges_overlap(in, out, n * 8 * f->L) || !elems_reduced(*f, in, n)) return LCPC_ERR_ARG;
   try {
     std::vector<uint64_t> a(in, in + (size_t)n * f->L);
     host_fft(*f, form, a.data(), log_n);
@@ -183,7 +88,7 @@ int lcpcf_fft_device(lcpc_ctx* c, uint32_t form, const uint64_t* in_dev, uint64_
   if (!c || form > LCPCF_IFFT_OI || !in_dev || !out_dev || n_vecs == 0 || n_vecs > 65535) return LCPC_ERR_ARG;
   if (!dev_aligned(in_dev, c->L) || !dev_aligned(out_dev, c->L) || log_n > dev_max_log_n(*c->f)) return LCPC_ERR_ARG;
   const uint64_t total = (uint64_t)n_vecs << log_n;
-  if (total >= ((uint64_t)1 << 39) || overlap(in_dev, out_dev, total * elem_bytes(c))) return LCPC_ERR_ARG;
+  if (total >= ((uint64_t)1 << 39) || ranges_overlap(in_dev, out_dev, total * elem_bytes(c))) return LCPC_ERR_ARG;
   LCPC_TRY
   HIPCHK(c, hipSetDevice(c->prm.device));
   return fft_enqueue(c, &c->err, (int)form, reinterpret_cast<const uint32_t*>(in_dev), reinterpret_cast<uint32_t*>(out_dev), log_n, n_vecs,
@@ -209,7 +114,7 @@ int lcpcf_commit_evals(lcpc_commit_t* m, uint32_t order, const uint64_t* evals_h
   const lcpc_ctx* c = m->enc;
   if (log_n > dev_max_log_n(*c->f)) return LCPC_ERR_ARG;
   if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
-  if (!all_reduced(*c->f, evals_host, (uint64_t)1 << log_n)) return LCPC_ERR_ARG;
+  if (!elems_reduced(*c->f, evals_host, (uint64_t)1 << log_n)) return LCPC_ERR_ARG;
   LCPC_TRY
   std::unique_lock<FillLock> fill(m->fill_mu);
   std::lock_guard<std::mutex> g(m->mu);

@@ -18,42 +18,14 @@
 // (one multiplication each), the twist is one more product of two table entries.  All arithmetic is field_dev.h's fe_mul / fe_add /
 // fe_sub on fully reduced elements, so every intermediate and every stored element is fully reduced.  All element indices are 64-bit.
 //
+// The pass's arguments, LDS layout and table look-up are fft_dev.h's, which K14 (domain.hip) shares.
+//
 // K13: out[rev(i)] = in[i], one element per lane; in place it swaps the pairs i < rev(i).  One side of it is scattered.
-#include "kernels.h"
-#include "field_dev.h"
+#include "fft_dev.h"
 
 namespace lcpc {
 
 namespace {
-
-struct FftPass {
-  const u32* src;
-  u32* dst;
-  const u32* tab;      // two-level table of the direction's root
-  u64 n_cols;          // n_vecs << (log_n - s)
-  u32 log_n, t0, s, h, log_c;
-  int dit, scale;
-};
-
-template <int NL> LCPC_DEV void lds_put(u32* base, u32 plane, u32 i, const Fe<NL>& v) {
-#pragma unroll
-  for (int l = 0; l < NL; l++) base[l * plane + i] = v.v[l];
-}
-template <int NL> LCPC_DEV Fe<NL> lds_get(const u32* base, u32 plane, u32 i) {
-  Fe<NL> v;
-#pragma unroll
-  for (int l = 0; l < NL; l++) v.v[l] = base[l * plane + i];
-  return v;
-}
-// where element (row m, column col) of a tile of 2^lc columns lies in a limb plane: the column is XORed with the row's low bits.  The
-// stages walk a row's columns with consecutive lanes and the transposing loads and stores of a pass with fewer low bits than
-// columns walk the rows of one column: both then hit different banks (unswizzled, the second is a stride of 2^lc words)
-LCPC_DEV u32 tile_at(u32 m, u32 col, u32 lc) { return (m << lc) | (col ^ (m & ((1u << lc) - 1))); }
-// v^e for e < 2^log_n from the two-level table
-template <int NL> LCPC_DEV Fe<NL> tab_pow(const u32* tab, u32 h, u64 e) {
-  const u64 lo = e & (((u64)1 << h) - 1), hi = e >> h;
-  return fe_mul<NL>(fe_load<NL>(tab + lo * NL), fe_load<NL>(tab + (((u64)1 << h) + hi) * NL));
-}
 
 template <int NL>
 __global__ void __launch_bounds__(1024) fft_pass_kernel(FftPass a, Fe<NL> n_inv) {
@@ -142,29 +114,11 @@ __global__ void __launch_bounds__(256) fft_bitrev_kernel(const u32* in, u32* out
   }
 }
 
-template <int NL> Fe<NL> fe_arg(const u32* w) {
-  Fe<NL> r;
-  for (int i = 0; i < NL; i++) r.v[i] = w ? w[i] : 0;
-  return r;
-}
-inline bool nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
-inline bool elem_aligned(const void* p, int nl) { return reinterpret_cast<uintptr_t>(p) % (nl % 4 == 0 ? 16 : 8) == 0; }
-
-// the tile of a workgroup holds at most 64 KiB of elements (two workgroups per CU beside their twiddles) and at most 256 columns
-inline uint32_t log_cols(int nl, uint32_t s) {
-  uint32_t cap = 0;
-  while (((size_t)8 * nl << cap) <= ((size_t)64 << 10)) cap++;      // largest cap with 4 nl 2^cap <= 64 KiB
-  const uint32_t lc = cap - s;
-  return lc < 8 ? lc : 8;
-}
-
 template <int NL>
 hipError_t pass_nl(const FftPass& a, const u32* n_inv, hipStream_t st) {
-  const size_t T = (size_t)1 << (a.s + a.log_c);
-  const size_t lds_bytes = (T + ((size_t)1 << (a.s - 1))) * NL * 4;
-  const uint64_t blocks = (a.n_cols + (((uint64_t)1 << a.log_c) - 1)) >> a.log_c;
-  unsigned nt = (unsigned)(T / 2);
-  nt = nt < 64 ? 64 : nt > 1024 ? 1024 : nt;
+  const size_t lds_bytes = pass_lds_bytes(NL, a);
+  const uint64_t blocks = pass_blocks(a);
+  const unsigned nt = pass_lanes(a);
   // (idempotent and cheap; set on every launch rather than cached in an unsynchronised static)
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_pass_kernel<NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
@@ -193,6 +147,12 @@ hipError_t bitrev_any(int nl, const u32* in, u32* out, u32 log_n, u64 total, hip
 }
 
 }  // namespace
+
+hipError_t launch_fft_bitrev(int nl, const uint32_t* in, uint32_t* out, uint32_t log_n, uint64_t total, hipStream_t st) {
+  if (!nl_ok(nl) || !in || !out || !elem_aligned(in, nl) || !elem_aligned(out, nl) || log_n == 0 || log_n > FFT_MAX_LOG_N) return hipErrorInvalidValue;
+  if (total == 0 || total >= ((uint64_t)1 << 39) || (total & (((uint64_t)1 << log_n) - 1))) return hipErrorInvalidValue;
+  return bitrev_any(nl, in, out, log_n, total, st);
+}
 
 int fft_plan(uint32_t log_n, uint32_t log_tile, uint32_t s[]) {
   if (log_tile == 0 || log_tile > FFT_MAX_LOG_TILE || log_n > FFT_MAX_LOG_N) return -1;

@@ -293,6 +293,14 @@ struct FftTab {
   uint32_t* d = nullptr;           // fft_tab_elems(log_n) elements (kernels.h launch_fft)
   uint64_t stamp = 0;              // last use
 };
+// the two-level table of the powers of a shift (kernels.h launch_coset_fft): its key is the shift's limbs, the size and the direction
+struct DomTab {
+  uint64_t shift[4] = {0, 0, 0, 0};
+  uint32_t log_n = 0;
+  bool inverse = false;
+  uint32_t* d = nullptr;           // fft_tab_elems(log_n) elements
+  uint64_t stamp = 0;
+};
 }  // namespace lcpc
 
 struct lcpc_ctx {
@@ -354,6 +362,9 @@ struct lcpc_ctx {
   // an evicted table is freed by hipFree, which waits for the kernels that still read it
   lcpc::FftTab fft_tabs[4];
   uint64_t fft_stamp = 0;
+  // the lcpcd_ device calls (include/lcpc_hip_domain.h): the shift tables of the last few (shift, size, direction) keys, under `mu`,
+  // by the same rules (domain.cpp dom_table); they share fft_stamp
+  lcpc::DomTab dom_tabs[8];
   // RCCL communicator of a sharded encoder (lcpc_comm_init); opaque ncclComm_t
   void* comm = nullptr;
   std::mutex xchg_mu;              // serialises the submission of collectives on `comm` (several commitments, several host threads)
@@ -596,9 +607,19 @@ int commit_ints_device_locked(lcpc_commit_t* m, int kind, const void* vals_dev, 
 // lcpcf_commit_evals_device / lcpcf_commit_evals (include/lcpc_hip_fft.h) behind their argument checks and locks: the inverse transform
 // (form: FFT_IFFT_II or FFT_IFFT_OI) of 2^log_n evaluations lands in LcCommit.coeffs and the pipeline runs from there.  host: `evals` is
 // host memory, uploaded into coeffs and transformed in place, and the call is complete on return
-int commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root);
+// shift (host limbs, checked by the caller) non-null: the values lie on the coset D(shift, 2^log_n) (include/lcpc_hip_domain.h)
+int commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint32_t log_n, bool host, hipStream_t st, uint8_t* root,
+                        const uint64_t* shift = nullptr);
 // K12 / K13 on `st` with the context's twiddle tables (fft.cpp; takes c->mu): in == out in place, otherwise disjoint
 int fft_enqueue(lcpc_ctx* c, ErrText* err, int form, const uint32_t* in, uint32_t* out, uint32_t log_n, uint32_t n_vecs, hipStream_t st);
+// the context's twiddle table of (log_n, direction), c->mu held: found, or built on the host, uploaded and cached (fft.cpp)
+int fft_table(lcpc_ctx* c, ErrText* err, uint32_t log_n, bool inverse, const uint32_t** tab);
+// K14 on `st` with the context's twiddle and shift tables (domain.cpp; both take c->mu).  shift: host limbs, nonzero and reduced.
+// coset_enqueue: in == out in place, otherwise disjoint.  extend_enqueue: n_vecs coefficient vectors -> their values on D(shift, 2^log_m)
+int coset_enqueue(lcpc_ctx* c, ErrText* err, int form, const uint64_t* shift, const uint32_t* in, uint32_t* out, uint32_t log_n,
+                  uint32_t n_vecs, hipStream_t st);
+int extend_enqueue(lcpc_ctx* c, ErrText* err, const uint64_t* shift, const uint32_t* coeffs, uint64_t n_coeffs, uint32_t log_m, bool natural,
+                   uint32_t* out, uint32_t n_vecs, hipStream_t st);
 int hash_chunks(lcpc_commit_t* m, uint64_t a, uint64_t b, uint32_t* out, hipStream_t st);
 int merkle_top(lcpc_commit_t* m, hipStream_t st, uint32_t levels_done = 0);
 int seal_commit(lcpc_commit_t* m, hipStream_t st, uint8_t* root);

@@ -437,5 +437,36 @@ inline uint64_t fft_tab_elems(uint32_t log_n) { return ((uint64_t)1 << fft_tab_s
 int fft_plan(uint32_t log_n, uint32_t log_tile, uint32_t s[]);
 hipError_t launch_fft(int nl, int form, uint32_t log_n, uint32_t log_tile, uint32_t n_vecs, const uint32_t* in, uint32_t* out,
                       const uint32_t* tab, const uint32_t* n_inv, hipStream_t st, uint32_t* n_launches);
+// K13 alone: out[v n + rev(i)] = in[v n + i] over total = n_vecs << log_n elements, log_n >= 1; in == out swaps in place
+hipError_t launch_fft_bitrev(int nl, const uint32_t* in, uint32_t* out, uint32_t log_n, uint64_t total, hipStream_t st);
+
+// K14 (domain.hip; include/lcpc_hip_domain.h): the coset forms of the transform above and the low-degree extension.
+// launch_coset_fft: X[k] = sum_j x[j] s^j w^(jk) and its inverse x[j] = s^-j n^-1 sum_k X[k] w^(-jk), launch_fft's forms, plan, vectors,
+// in-place rule and refusals.  tab as for launch_fft.  stab: the two-level table of the shift for this size and direction,
+//   stab[i] = t^i for i < 2^h, stab[2^h + i] = c t^(i 2^h) for i < 2^(log_n - h), h = fft_tab_split(log_n),
+// with t = s, c = 1 forward and t = s^-1, c = n^-1 inverse (there is no n_inv argument).  The scale is fused into the pass that loads
+// the input (forward) or stores the output (inverse): the launches are launch_fft's.
+// launch_extend: Y[k] = sum_{j < n_coeffs} x[j] s^j w_m^(jk) for k < m = 2^log_m, stored at out[k] (natural) or out[rev_m(k)].  Source
+// vectors lie 2^ext_src_log(n_coeffs) elements apart and are read up to n_coeffs; output vectors lie m apart; the two ranges must
+// not overlap.  It runs the plan of ext_log_n(n_coeffs, log_m) points on n_vecs << (log_m - that) blocks -- the launches of an FFT_IO of
+// that length, plus K13 in place for the natural order.  tab_m: the FORWARD table of launch_fft for log_m; stab: the forward shift table
+// for ext_log_n points.  hipErrorInvalidValue before any launch for n_coeffs == 0 or > m, log_m > FFT_MAX_LOG_N, n_vecs == 0,
+// n_vecs << (log_m - ext_src_log) > 65535, n_vecs * m >= 2^39, a NULL or misaligned pointer, overlapping ranges.  log_m == 0 copies.
+inline uint32_t ext_src_log(uint64_t n_coeffs) {
+  uint32_t l = 0;
+  while (l < 63 && ((uint64_t)1 << l) < n_coeffs) l++;
+  return l;
+}
+// the transform length of a block: the source length, but two points where one coefficient spreads over more than one value
+inline uint32_t ext_log_n(uint64_t n_coeffs, uint32_t log_m) {
+  const uint32_t l = ext_src_log(n_coeffs);
+  return l == 0 && log_m ? 1 : l;
+}
+// the source elements the extension may read: n_vecs vectors 2^ext_src_log apart, the last up to n_coeffs
+inline uint64_t ext_src_elems(uint64_t n_coeffs, uint32_t n_vecs) { return (((uint64_t)n_vecs - 1) << ext_src_log(n_coeffs)) + n_coeffs; }
+hipError_t launch_coset_fft(int nl, int form, uint32_t log_n, uint32_t log_tile, uint32_t n_vecs, const uint32_t* in, uint32_t* out,
+                            const uint32_t* tab, const uint32_t* stab, hipStream_t st, uint32_t* n_launches);
+hipError_t launch_extend(int nl, uint64_t n_coeffs, uint32_t log_m, int natural, uint32_t log_tile, uint32_t n_vecs, const uint32_t* coeffs,
+                         uint32_t* out, const uint32_t* tab_m, const uint32_t* stab, hipStream_t st, uint32_t* n_launches);
 
 }  // namespace lcpc
