@@ -229,6 +229,18 @@ template <class FT> LCPC_DEV LN<FT::N> mul_u(const LN<FT::N>& a, const u32* wt) 
   }
   return r;
 }
+// Ft255, the K1s kernels' form of the same multiply (ntt_l9s.hip): wmul_us, whose top limb is formed from the low words of its column
+// alone -- two instructions and a carry pair fewer, bit for bit mul_u's result (gen_wmul_asm.py build(short_tail);
+// tests/test_gen_short_tails.py runs both lists on integers)
+template <class FT> LCPC_DEV LN<FT::N> mul_us(const LN<FT::N>& a, const u32* wt) {
+  static_assert(FT::FID == FT255, "the short-tail statement exists for Ft255 only");
+  LN<FT::N> r;
+  u32 np2[9];
+#pragma unroll
+  for (int j = 0; j < 9; j++) np2[j] = 0u - 2u * FT::limb(j);
+  wmul_us(a.v, np2, wt, r.v);
+  return r;
+}
 // ---- carry-free lazy dot product (collapse, SpMV, SpMM) -----------------------------------------------------------------------------
 // acc += x * v with x, v as N unsigned W-bit limbs (x: a packed element < p split by from_packed; v: a matrix / tensor value in the
 // R'-Montgomery form, v R' mod p): N^2 v_mad_u64_u32 into 2N u64 columns, no carries.  A column receives <= N products

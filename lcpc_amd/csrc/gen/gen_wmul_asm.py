@@ -62,7 +62,10 @@ def fixed_regs(field):
     return VB - 2, VB - 4, VB - 6, VB - 2, VB - 7       # T shares A's pair (the chain starts after the quotient): 7 fixed registers
 
 
-def build(field):
+def build(field, short_tail=False):
+    """short_tail: the top limb takes the low 32 bits of its column only -- A.lo + C.lo + lo(Q * np2_top) by v_mul_lo_u32 and v_add3_u32
+    (the temp T is free by then) instead of the 64-bit add of column C, the mad and the closing move: two instructions and a carry pair
+    fewer, the same bits (mod 2^32 the two forms agree).  Ft255's wmul_us, the K1s kernels' multiply (ntt_l9s.hip)."""
     P, N, W, VB, s1, s2, MU = params(field)
     M = (1 << W) - 1
     sreg, S_MU, S_NP = sreg_map(field)
@@ -105,6 +108,10 @@ def build(field):
         if k < N - 2:
             for j in range(N):
                 ins.append("v_mad_i64_i32 %s, vcc, %s, %s, %s" % (acc(A), X(j), Wl(k, j), "0" if (k == 0 and j == 0) else acc(A)))
+        elif k == N - 1 and short_tail:
+            ins.append("v_mul_lo_u32 v%d, v%d, %s" % (T, Q, NP(k)))
+            ins.append("v_add3_u32 %s, v%d, v%d, v%d" % (R(k), A, C, T))
+            break
         else:
             src = Bv if k == N - 2 else C
             ins.append("v_add_co_u32 v%d, vcc, v%d, v%d" % (A, A, src))
@@ -118,15 +125,19 @@ def build(field):
     return ins
 
 
-def emit(field):
+def emit(field, short_tail=False):
     P, N, W, VB, s1, s2, MU = params(field)
     sreg, S_MU, S_NP = sreg_map(field)
-    ins = build(field)
+    ins = build(field, short_tail)
     A = fixed_regs(field)[0]
     T = min(fixed_regs(field))
     n_valu = sum(1 for i in ins if i.startswith("v_"))
     out = []
-    if field == "ft255":
+    if field == "ft255" and short_tail:
+        out.append("")
+        out.append("// the same multiply with the short tail (build(field, short_tail=True)): %d VALU instructions (%d mads), bit for bit wmul_u's result." % (n_valu, sum(1 for i in ins if i.startswith("v_mad"))))
+        out.append("LCPC_DEV void wmul_us(const u32* x, const u32* np2, const u32* w, u32* r) {")
+    elif field == "ft255":
         out.append("// GENERATED by lcpc_amd/csrc/gen/gen_wmul_asm.py -- do not edit.  %d VALU instructions (%d mads) per multiply." % (n_valu, sum(1 for i in ins if i.startswith("v_mad"))))
         out.append("// np2: the nine limbs of -2p (signed); w: wave-uniform pointer to the 81 dwords of one twiddle's shifted multiples.")
         out.append("#define WMUL_MU 0x%xu" % MU)
@@ -154,7 +165,7 @@ def emit(field):
 
 
 def main():
-    out = emit("ft255")
+    out = emit("ft255") + emit("ft255", short_tail=True)
     out.append("")
     out.append("// ---- the same multiply for the limb forms of field_ln.h (K1n, ntt_lns.hip); -2p and MU as scalar constants -------------------------")
     for f in ("ft63", "ft127", "ft191"):

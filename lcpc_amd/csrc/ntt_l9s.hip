@@ -23,7 +23,9 @@
 //   * the pure first pass's final round (I only) does the same for the packed intermediate: its quad is four elements of one column,
 //     clamped, packed and stored from the registers; and every round that stores from registers clamps each output once, straight
 //     from the butterfly's sums (ntt_ln_dev.h clamp_store; the bounds: field_ln.h clamp_apply);
-//   * (round 6) a wave holds priority 1 while it issues memory instructions and 0 inside the multiplier chains (field_dev.h mem_phase).
+//   * (round 6) a wave holds priority 1 while it issues memory instructions and 0 inside the multiplier chains (field_dev.h mem_phase);
+//   * every global address is a wave-uniform 64-bit base in scalar registers plus an unsigned 32-bit byte offset per lane (the kernel's
+//     "Global addresses"; ntt_ln_dev.h ubase / lane_at / pack_get_u): no 64-bit vector shifts or carry adds for addresses.
 // Exact modular arithmetic: any stage grouping gives the same fully-reduced bits as the reference's radix-2 loop.
 #include "kernels.h"
 #include "ntt_ln_dev.h"
@@ -40,7 +42,7 @@ namespace {
 // with w0 = w^e, w1 = w^(e + n/4) = I w0 (I = w^(n/4), the field's fixed primitive 4th root of unity) and w2 = w0^2.  Hence
 //   t = (x1 - x3) I;  c2 = ((x0 - x2) + t) w0;  c3 = ((x0 - x2) - t) w3,  w3 = w0 w2 = w^(3 e):
 // I is ONE constant for every lane of every transform, so its multiply takes the shifted-multiples form with scalar operands
-// (ln::mul_u on a.wq_w: 119 instructions) and a generic round does three lane-varying Montgomery multiplies (188 each) instead
+// (ln::mul_u on a.wq_w: 119 instructions; the code calls ln::mul_us, the same multiply with the two-instruction tail: two fewer) and a generic round does three lane-varying Montgomery multiplies (188 each) instead
 // of four; c2 comes out of a multiplier normalised.  Exact arithmetic mod p: the same fully reduced bits.
 // MID: the intermediate between the two passes is not the packed comm buffer but a.mid, which holds every element as the
 // LDS tile holds it -- 9 signed 29-bit limbs, normalised; DIF form: |value| < 4p (invariant I of field_ln.h); pure form: |value| <
@@ -75,14 +77,14 @@ namespace {
 // (-3.01p, 2.01p) for limbs in (-2^30, 2^30) -- still |value| < 4p, invariant I; the rounds that depend on more say so.
 template <bool M2> struct Tw { LN<9> b0, b1; };
 template <> struct Tw<false> { LN<9> b0; };
-template <bool M2, u32 NV> LCPC_DEV Tw<M2> tw_get(const u32* blk, u32 period, u32 variant, u32 jl) {
-  using FT = LnField<FT255>;
+// variant uv + lv: uv wave-uniform, lv by lane (ntt_ln_dev.h pack_get_u: scalar bases, 32-bit lane offsets)
+template <bool M2, u32 NV> LCPC_DEV Tw<M2> tw_get(const u32* blk, u32 period, u32 uv, u32 lv, u32 jl) {
   Tw<M2> t;
   if constexpr (M2) {
-    t.b0 = pack_get<FT, 2 * NV>(blk, period, variant, jl);
-    t.b1 = pack_get<FT, 2 * NV>(blk, period, NV + variant, jl);
+    t.b0 = pack_get_u<2 * NV>(blk, period, uv, lv, jl);
+    t.b1 = pack_get_u<2 * NV>(blk, period, NV + uv, lv, jl);
   } else {
-    t.b0 = pack_get<FT, NV>(blk, period, variant, jl);
+    t.b0 = pack_get_u<NV>(blk, period, uv, lv, jl);
   }
   return t;
 }
@@ -159,13 +161,19 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     else return (tile << S) | e;
   };
   const bool canon = a.roots29c != nullptr && ((u32)row & a.canon_row_mask) == 0;     // (wave-uniform)
-  for (u32 i = tid; i < 64 * 12; i += 256) nqp[i] = 0u - a.qp29[i];
-  const u32* src = a.src + row * a.src_stride * NL;
+  for (u32 i = tid; i < 64 * 12; i += 256) nqp[i] = 0u - *lane_at(ubase(a.qp29), i * 4u);
+  // Global addresses (ntt_ln_dev.h ubase / lane_at): the row, the tile of a last pass and the pack class are the workgroup's own --
+  // 64-bit, scalar -- and a lane adds an unsigned 32-bit byte offset.  The largest a lane forms: first pass, an element of its row,
+  // gindex(e) * 32 < 2^k * 32 <= 2^31 (k <= 26, the three-pass plans; launch_ntt_pass_l9s refuses more); last pass, an element of its
+  // tile, < 32 KiB (36 KiB in the limb intermediate); the limb intermediate's store, < 2^S tiles of 36 KiB <= 36 MiB.
+  const u64 src_row = row * a.src_stride;                    // (flat element index of the row's start)
+  const u32* src = ubase(a.src + (src_row + (FIRST ? 0u : (u64)tile << S)) * NL);
+  const u32 n_val = (u32)(a.n_valid < ((u64)1 << k) ? a.n_valid : (u64)1 << k);      // (column indices are < 2^k: their comparisons stay 32-bit)
   constexpr bool DIRECT = !(LAST && MID);                    // the first round takes its inputs from the loads (below)
   LN<9> xin[4];
   if constexpr (LAST && MID) {
     // the tile as the first pass left it: [limbs 0-3][limbs 4-7][limb 8] planes, the LDS layout itself
-    const uint4* t4 = reinterpret_cast<const uint4*>(a.mid + (row << k) * 9 + (size_t)tile * (9 * T));
+    const uint4* t4 = reinterpret_cast<const uint4*>(ubase(a.mid + (row << k) * 9 + (size_t)tile * (9 * T)));   // (u32 indices below: < 36 KiB)
     uint4* l4 = reinterpret_cast<uint4*>(lds);
     if constexpr (SWZD) {
       // (the swizzled tile: planes 0 and 1 move whole uint4s, the limb-8 plane word by word -- (e + j) -> SWZ(e) ^ j for e = 0 mod 4)
@@ -187,27 +195,30 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
 #pragma unroll
   for (u32 it = 0; it < 4; it++) {
     const u32 e = tid + 256u * it;
-    const u32 g = gindex(e);
     Fe<NL> v;
     if constexpr (FIRST) {        // zero padding, the ragged tail of the caller's vector and the coeffs copy exist here only
-      v = (g < a.n_valid && row * a.src_stride + g < a.n_src_total) ? fe_load<NL>(src + (size_t)g * NL) : fe_zero<NL>();
-      if (a.copy_dst != nullptr && g < a.n_valid) fe_store<NL>(a.copy_dst + (row * a.src_stride + g) * NL, v);
+      const u32 g = gindex(e);
+      // (columns of this row that the caller's vector holds: n_valid, less where the flat vector ends inside the row or before it)
+      const u64 left = a.n_src_total > src_row ? a.n_src_total - src_row : 0;
+      const u32 n_src = left < n_val ? (u32)left : n_val;
+      v = g < n_src ? fe_load<NL>(lane_at(src, g * (NL * 4u))) : fe_zero<NL>();
+      if (a.copy_dst != nullptr && g < n_val) fe_store<NL>(lane_at(ubase(a.copy_dst + src_row * NL), g * (NL * 4u)), v);
     } else {
-      v = fe_load<NL>(src + (size_t)g * NL);                 // < 2^256 (the first pass's store), not necessarily < p
+      v = fe_load<NL>(lane_at(ubase(src + 256u * it * NL), tid * (NL * 4u)));   // < 2^256 (the first pass's store), not necessarily < p
     }
     xin[it] = ln::from_packed<FT>(v);
   }
   __builtin_amdgcn_sched_barrier(0);                         // (the first round's twiddle loads stay behind the conversions: registers)
   }
   // (pack classes: DIF first pass and coset last pass one per tile position; DIF last pass and pure first pass one)
-  const u32* cls_pack = pack + (size_t)(FIRST != NF ? tile : 0u) * pi.class_words;
+  const u32* cls_pack = ubase(pack + (size_t)(FIRST != NF ? tile : 0u) * pi.class_words);
   // tiles that hold elements of "block 0" (never multiplied so far).  a.blk0_gone: an earlier pass had a uniform round and
   // converted what was left of block 0 before it (below): nothing is in Montgomery form any more
   const bool blk0_tile = (FIRST || tile == 0) && a.blk0_gone == 0;   // (pure first pass: every tile holds its columns' block 0)
   LN<9> k32;                                                 // 2^5 = 2^261 R^-1: ln::mul by it converts (Montgomery form -> canonical)
 #pragma unroll
   for (int i = 0; i < 9; i++) k32.v[i] = i == 0 ? 32u : 0u;
-  const bool zero_hi = FIRST && a.n_valid <= (1ull << (k - 1));
+  const bool zero_hi = FIRST && n_val <= (1u << (k - 1));
   // the limb intermediate's tile sits in LDS; otherwise only the q*p table does, which no first round reads (their pure sums are
   // sums of loads: normalised, not clamped): the barrier at the end of that round serves
   if constexpr (!DIRECT) __syncthreads();
@@ -221,7 +232,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     for (u32 pp = 0; pp < 2; pp++) {
       const u32 e1 = tid + 256u * pp;                        // slots with the top stage bit clear are [0, half)
       // pure form: w_{2^S}^i for the pair's i = e1 >> LBT, whatever the tile and lp
-      const Tw<M2> w = NF ? tw_get<M2, 2>(blk, 1u << (S - 1), canon ? 1u : 0u, e1 >> LBT) : tw_get<M2, 2>(blk, SH::period2, canon ? 1u : 0u, e1);
+      const Tw<M2> w = NF ? tw_get<M2, 2>(blk, 1u << (S - 1), 0, canon ? 1u : 0u, e1 >> LBT) : tw_get<M2, 2>(blk, SH::period2, 0, canon ? 1u : 0u, e1);
       const LN<9> x = DIRECT ? xin[pp] : planes_get<FT>(lds, T, SWZ(e1));
       if (pp == 0) mem_phase(false);
       // pure form, S = 1 and 3: no later round reads the pack, so the sum half is converted here as well (RC < 0, ntt_ln_dev.h)
@@ -281,13 +292,13 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         const u32* wu = cls_pack + pi.u_off + ((u32)r * 4 + sb) * (3 * U_SLOT<FT>);
         mem_phase(false);
         if (!from_regs) ln::clamp_apply<FT>(x0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x0.v[8])));
-        p2 = ln::mul_u<FT>(x2, wu + U_SLOT<FT>);
-        p1 = ln::mul_u<FT>(x1, wu);
-        p3 = ln::mul_u<FT>(x3, wu + 2 * U_SLOT<FT>);
+        p2 = ln::mul_us<FT>(x2, wu + U_SLOT<FT>);
+        p1 = ln::mul_us<FT>(x1, wu);
+        p3 = ln::mul_us<FT>(x3, wu + 2 * U_SLOT<FT>);
       } else {
         const u32* blk = cls_pack + pi.round_off[r];
-        const Tw<M2> w1 = tw_get<M2, 3>(blk, coset_sets(r), 0, m), w2 = tw_get<M2, 3>(blk, coset_sets(r), 1, m);
-        const Tw<M2> w3 = tw_get<M2, 3>(blk, coset_sets(r), 2, m);
+        const Tw<M2> w1 = tw_get<M2, 3>(blk, coset_sets(r), 0, 0, m), w2 = tw_get<M2, 3>(blk, coset_sets(r), 1, 0, m);
+        const Tw<M2> w3 = tw_get<M2, 3>(blk, coset_sets(r), 2, 0, m);
         mem_phase(false);
         ln::clamp_apply<FT>(x0, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x0.v[8])));
         p2 = tw_mul<M2>(x2, w2);
@@ -297,7 +308,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       const LN<9> s02 = ln::add(x0, p2), d02 = ln::sub(x0, p2), s13 = ln::add(p1, p3);
       LN<9> y0 = ln::add(s02, s13), y1 = ln::sub(s02, s13);
       if (r < 4) ln::normalize<FT>(y0);
-      const LN<9> t = ln::mul_u<FT>(ln::sub(p1, p3), a.wq_w);
+      const LN<9> t = ln::mul_us<FT>(ln::sub(p1, p3), a.wq_w);
       LN<9> y2 = ln::add(d02, t), y3 = ln::sub(d02, t);
       if (r == 0) { ln::normalize<FT>(y1); ln::normalize<FT>(y2); ln::normalize<FT>(y3); }
       mem_phase(true);
@@ -311,11 +322,11 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         // D == 1: four consecutive elements of the row, |value| < 4.6p (M2: 9.04p), NOT normalised: y0's limbs lie in [0, 2^31 - 4] (a
         // clamped x0 plus three normalised products), those of y1, y2, y3 in (-2^30, 2^30) -- the two classes ln::clamp_apply takes as
         // they are (the bound the x0 of rounds 1 .. 4 goes by, above).  Clamp, pack, the rare conditional subtract, store
-        u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
-        clamp_store<FT, true>(dstq, y0, nqp);
-        clamp_store<FT, true>(dstq + (size_t)1 * NL, y1, nqp);
-        clamp_store<FT, true>(dstq + (size_t)2 * NL, y2, nqp);
-        clamp_store<FT, true>(dstq + (size_t)3 * NL, y3, nqp);
+        u32* dstq = a.dst + (row * a.dst_stride + ((u64)tile << S)) * NL;          // (the tile; each element of the quad takes a scalar base of its own)
+        clamp_store<FT, true>(lane_at(ubase(dstq + 0 * NL), e0 * (NL * 4u)), y0, nqp);
+        clamp_store<FT, true>(lane_at(ubase(dstq + 1 * NL), e0 * (NL * 4u)), y1, nqp);
+        clamp_store<FT, true>(lane_at(ubase(dstq + 2 * NL), e0 * (NL * 4u)), y2, nqp);
+        clamp_store<FT, true>(lane_at(ubase(dstq + 3 * NL), e0 * (NL * 4u)), y3, nqp);
       }
     }
     return;
@@ -355,7 +366,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       const LN<9> b0 = ln::add(x0, x2), b1 = ln::add(x1, x3);
       LN<9> c0 = ln::add(b0, b1), c1 = ln::sub(b0, b1);
       const LN<9> b2 = ln::sub(x0, x2);
-      const LN<9> t = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);                                    // normalised, (-2p, 2.7p)
+      const LN<9> t = ln::mul_us<FT>(ln::sub(x1, x3), a.wq_w);                                    // normalised, (-2p, 2.7p)
       LN<9> c2 = ln::add(b2, t), c3 = ln::sub(b2, t);
       if constexpr (!MID && SH::NR4 >= 1) {                  // (S == 1 has no such round: its instantiation keeps a single exit)
         if (RC < 0 && SH::U0 == 0 && canon) {
@@ -368,11 +379,11 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         // and met the barrier behind its puts: one barrier then, one now)
         if constexpr (SH::U0 == 0 && SH::NR4 == 1) __syncthreads();
         mem_phase(true);
-        u32* dstq = a.dst + row * a.dst_stride * NL;
-        clamp_store<FT, false>(dstq + (size_t)gindex(e0) * NL, c0, nqp);            // [0, p + 2^239) < 2^256: what the successor reads
-        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + dq) * NL, c1, nqp);
-        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + 2 * dq) * NL, c2, nqp);
-        clamp_store<FT, false>(dstq + (size_t)gindex(e0 + 3 * dq) * NL, c3, nqp);
+        u32* dstq = ubase(a.dst + row * a.dst_stride * NL);
+        clamp_store<FT, false>(lane_at(dstq, gindex(e0) * (NL * 4u)), c0, nqp);     // [0, p + 2^239) < 2^256: what the successor reads
+        clamp_store<FT, false>(lane_at(dstq, gindex(e0 + dq) * (NL * 4u)), c1, nqp);
+        clamp_store<FT, false>(lane_at(dstq, gindex(e0 + 2 * dq) * (NL * 4u)), c2, nqp);
+        clamp_store<FT, false>(lane_at(dstq, gindex(e0 + 3 * dq) * (NL * 4u)), c3, nqp);
         return;
       }
       ln::normalize<FT>(c1); ln::normalize<FT>(c2); ln::normalize<FT>(c3);
@@ -413,9 +424,9 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         planes_put<FT>(lds, T, SWZ(eu), c0);
         LN<9> d1 = ln::sub(b0, b1);
         ln::normalize<FT>(d1);                                                                 // mul_u wants sum |limb| < 9 * 2^29
-        planes_put<FT>(lds, T, SWZ(eu + dq), ln::mul_u<FT>(d1, wu + 2 * U_SLOT<FT>));
-        const LN<9> b2 = ln::mul_u<FT>(ln::sub(x0, x2), wu);
-        const LN<9> b3 = ln::mul_u<FT>(ln::sub(x1, x3), wu + U_SLOT<FT>);                            // (-2p, 2.7p)
+        planes_put<FT>(lds, T, SWZ(eu + dq), ln::mul_us<FT>(d1, wu + 2 * U_SLOT<FT>));
+        const LN<9> b2 = ln::mul_us<FT>(ln::sub(x0, x2), wu);
+        const LN<9> b3 = ln::mul_us<FT>(ln::sub(x1, x3), wu + U_SLOT<FT>);                            // (-2p, 2.7p)
         LN<9> c2 = ln::add(b2, b3);
         // (pure form: clamped, (-4p, 5.4p) -> [0, p + 2^239), so that the I-only round after it adds four values below 2.7p)
         // (DIF form, a first pass that stores the limb intermediate: clamped as well.  The sum of two mul_u products lies in (-4p, 5.4p),
@@ -424,7 +435,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         if constexpr (NF || (FIRST && MID)) ln::clamp_apply<FT>(c2, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(c2.v[8])));
         else ln::normalize<FT>(c2);
         planes_put<FT>(lds, T, SWZ(eu + 2 * dq), c2);
-        planes_put<FT>(lds, T, SWZ(eu + 3 * dq), ln::mul_u<FT>(ln::sub(b2, b3), wu + 2 * U_SLOT<FT>));
+        planes_put<FT>(lds, T, SWZ(eu + 3 * dq), ln::mul_us<FT>(ln::sub(b2, b3), wu + 2 * U_SLOT<FT>));
         mem_phase(true);
         __syncthreads();
         continue;
@@ -434,10 +445,10 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       // zero-padded first round (rate <= 1/2): x2 = x3 = 0, the stage-0 butterflies are (x, x w); inputs < p; everything
       // is block 0, so with canonical output the three multiplies leaving it (w0, w3, and w2 for c1) take the converting set
       const u32 vb = canon ? 3u : 0u;
-      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, vb + 0, jl), w3 = tw_get<M2, 6>(blk, period, vb + 1, jl), w2 = tw_get<M2, 6>(blk, period, vb + 2, jl);
+      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, 0, vb, jl), w3 = tw_get<M2, 6>(blk, period, 1, vb, jl), w2 = tw_get<M2, 6>(blk, period, 2, vb, jl);
       mem_phase(false);
       const bool cv0 = NF && canon && r == RC;               // pure form: the round that converts the pure sum as well (below)
-      if (a.n_valid <= (1ull << (k - 2))) {                  // rate <= 1/4: x1 is zero too
+      if (n_val <= (1u << (k - 2))) {                  // rate <= 1/4: x1 is zero too
         const LN<9> x0 = DIRECT ? xin[0] : planes_get<FT>(lds, T, SWZ(e0));
         if constexpr (DIRECT) planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(x0, k32) : x0);
         planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(x0, w2));
@@ -449,7 +460,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         ln::normalize<FT>(c0);
         planes_put<FT>(lds, T, SWZ(e0), cv0 ? ln::mul<FT>(c0, k32) : c0);
         planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(ln::sub(x0, x1), w2));
-        const LN<9> t = ln::mul_u<FT>(x1, a.wq_w);                                                // x1 I (plain constant: t keeps x1's form); (-2p, 2.7p)
+        const LN<9> t = ln::mul_us<FT>(x1, a.wq_w);                                                // x1 I (plain constant: t keeps x1's form); (-2p, 2.7p)
         planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(x0, t), w0));                   // in: limbs (-2^29, 2^30), |value| < 3.7p
         planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(x0, t), w3));
       }
@@ -470,17 +481,17 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
       LN<9> c1 = ln::sub(b0, b1);
       const LN<9> b2 = ln::sub(x0, x2);
       // w^(n/4) is the one twiddle every lane shares: its multiply takes the shifted-multiples form (scalar operands)
-      const LN<9> b3 = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);
+      const LN<9> b3 = ln::mul_us<FT>(ln::sub(x1, x3), a.wq_w);
       LN<9> c2 = ln::add(b2, b3);
       LN<9> c3 = ln::sub(b2, b3);
       // dq == 1 here: the quad is four CONSECUTIVE elements of the row, 128 bytes -- reduced and stored from the registers (no LDS round
       // trip, no barrier; -0.2 ... -0.8 % by shape).  -> [0, p): ntt_ln_dev.h clamp_store
       mem_phase(true);
-      u32* dstq = a.dst + row * a.dst_stride * NL + (size_t)((tile << S) | e0) * NL;
-      clamp_store<FT, true>(dstq, c0, nqp);
-      clamp_store<FT, true>(dstq + (size_t)1 * NL, c1, nqp);
-      clamp_store<FT, true>(dstq + (size_t)2 * NL, c2, nqp);
-      clamp_store<FT, true>(dstq + (size_t)3 * NL, c3, nqp);
+      u32* dstq = a.dst + (row * a.dst_stride + ((u64)tile << S)) * NL;          // (the tile; each element of the quad takes a scalar base of its own)
+      clamp_store<FT, true>(lane_at(ubase(dstq + 0 * NL), e0 * (NL * 4u)), c0, nqp);
+      clamp_store<FT, true>(lane_at(ubase(dstq + 1 * NL), e0 * (NL * 4u)), c1, nqp);
+      clamp_store<FT, true>(lane_at(ubase(dstq + 2 * NL), e0 * (NL * 4u)), c2, nqp);
+      clamp_store<FT, true>(lane_at(ubase(dstq + 3 * NL), e0 * (NL * 4u)), c3, nqp);
       return;
     } else {
       // clamp the pure sum at once: c0 leaves the registers before the multiplier chains start (holding it and its
@@ -509,22 +520,22 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
         // the same butterfly as below on 18 words per twiddle: w3's are asked for behind the first product, under whose chain they
         // arrive, and the two differences are taken before it, so that x0 .. x3 are dead when the first chain starts (all three pairs
         // up front spill at 128 VGPRs)
-        const Tw<M2> w2 = tw_get<M2, 6>(blk, period, vb + 2, jl), w0 = tw_get<M2, 6>(blk, period, vb + 0, jl);
+        const Tw<M2> w2 = tw_get<M2, 6>(blk, period, 2, vb, jl), w0 = tw_get<M2, 6>(blk, period, 0, vb, jl);
         const LN<9> d1 = ln::sub(b0, b1);
         const LN<9> d13 = ln::sub(x1, x3), e2 = ln::sub(x0, x2);
         planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(d1, w2));                                   // normalised, (-3.01p, 2.01p)
         __builtin_amdgcn_sched_barrier(0);
-        const Tw<M2> w3 = tw_get<M2, 6>(blk, period, vb + 1, jl);
-        const LN<9> t = ln::mul_u<FT>(d13, a.wq_w);                                                // normalised, (-2p, 2.7p)
+        const Tw<M2> w3 = tw_get<M2, 6>(blk, period, 1, vb, jl);
+        const LN<9> t = ln::mul_us<FT>(d13, a.wq_w);                                                // normalised, (-2p, 2.7p)
         planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(e2, t), w0));
         planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(e2, t), w3));
       } else {
-      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, vb + 0, jl), w3 = tw_get<M2, 6>(blk, period, vb + 1, jl);
-      const Tw<M2> w2 = tw_get<M2, 6>(blk, period, vb + 2, jl);
+      const Tw<M2> w0 = tw_get<M2, 6>(blk, period, 0, vb, jl), w3 = tw_get<M2, 6>(blk, period, 1, vb, jl);
+      const Tw<M2> w2 = tw_get<M2, 6>(blk, period, 2, vb, jl);
       const LN<9> d1 = ln::sub(b0, b1);                                                       // limbs (-2^30, 2^30), |value| < 16p
       planes_put<FT>(lds, T, SWZ(e0 + dq), tw_mul<M2>(d1, w2));                                     // normalised, (-1.2p, 0.2p]
       // t = (x1 - x3) I by the plain constant: in block 0 it stays in the form of its inputs and the two products below convert
-      const LN<9> t = ln::mul_u<FT>(ln::sub(x1, x3), a.wq_w);                                     // normalised, (-2p, 2.7p)
+      const LN<9> t = ln::mul_us<FT>(ln::sub(x1, x3), a.wq_w);                                     // normalised, (-2p, 2.7p)
       const LN<9> e2 = ln::sub(x0, x2);                                                       // limbs (-2^29, 2^29), |value| < 8p
       planes_put<FT>(lds, T, SWZ(e0 + 2 * dq), tw_mul<M2>(ln::add(e2, t), w0));                     // in: limbs (-2^29, 2^30), |value| < 10.7p
       planes_put<FT>(lds, T, SWZ(e0 + 3 * dq), tw_mul<M2>(ln::sub(e2, t), w3));
@@ -540,22 +551,28 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     // c0 clamped, |c1| < 10.8p (12.04p behind an ln::mul2 round), |c2|, |c3| < 8.72p -- NOT invariant I; the coset pass clamps x0 and
     // multiplies the rest by mul_u (tests/test_gpu_k1_passes.py holds the records to 12.04p).  Stored as it is.  lb == 10 (the successor
     // runs 10 stages), so slot (i, lp) is element (tile << LTJ | lp) of the successor's tile i
-    u32* mrow = a.mid + (row << k) * 9;
+    u32* mrow = ubase(a.mid + (row << k) * 9);
+    // (the lane offsets are formed afresh from the thread index: shared with the tile load's, they would sit in registers across
+    // every round -- scratch at 128 VGPRs for S = 9)
+    u32 tid_st = tid;
+    asm volatile("" : "+v"(tid_st));
 #pragma unroll
-    for (u32 e = tid; e < T; e += 256) {
+    for (u32 e = tid_st; e < T; e += 256) {
       const u32 e2 = (tile << LTJ) | (e & ((1u << LBT) - 1));
-      u32* t = mrow + (size_t)(e >> LBT) * (9 * T);
+      const u32 t = (e >> LBT) * (9 * T * 4u);                // byte offset of the successor's tile in this row: < 2^S * 36 KiB
       const LN<9> x = planes_get<FT>(lds, T, SWZ(e));
-      *reinterpret_cast<uint4*>(t + (size_t)e2 * 4) = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-      *reinterpret_cast<uint4*>(t + (size_t)(T + e2) * 4) = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-      t[(size_t)8 * T + e2] = x.v[8];
+      *reinterpret_cast<uint4*>(lane_at(mrow, t + e2 * 16u)) = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+      *reinterpret_cast<uint4*>(lane_at(mrow, t + (T + e2) * 16u)) = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+      *lane_at(mrow, t + (8 * T + e2) * 4u) = x.v[8];
     }
     return;
   }
   if constexpr (FIRST) {           // (a last pass has stored from its final round and returned)
-  u32* dst = a.dst + row * a.dst_stride * NL;
+  u32* dst = ubase(a.dst + row * a.dst_stride * NL);
+  u32 tid_st = tid;                                          // (as for the limb intermediate's store above)
+  asm volatile("" : "+v"(tid_st));
 #pragma unroll
-  for (u32 e = tid; e < T; e += 256) {
+  for (u32 e = tid_st; e < T; e += 256) {
     const u32 g = gindex(e);
     LN<9> x = planes_get<FT>(lds, T, SWZ(e));                                        // normalised, |value| < 16p
     ln::clamp_apply<FT>(x, ln::clamp_row<FT>(nqp, ln::clamp_q<FT>(x.v[8])));        // [0, p + 2^239) < 2^256: what the successor reads as limbs anyway
@@ -564,7 +581,7 @@ __global__ void __launch_bounds__(256, 4) ntt_pass_l9s_kernel(NttPassArgs a, con
     Fe<NL> v;
 #pragma unroll
     for (int i = 0; i < 8; i++) v.v[i] = w[i];
-    fe_store<NL>(dst + (size_t)g * NL, v);
+    fe_store<NL>(lane_at(dst, g * (NL * 4u)), v);
   }
   }
 }
@@ -610,6 +627,9 @@ hipError_t launch_ntt_pass_l9s(const NttPassArgs& a, bool first, const uint32_t*
   // two-pass plans: s + 10 stages in all; three-pass plans: s + 20 (the first pass works at element stride 2^20)
   if (a.t0 != 0 || a.s + a.log_tj != 10 || (a.s + 10 != a.log_n && a.s + 20 != a.log_n)) return hipErrorInvalidValue;
   if (a.form && a.s + 10 != a.log_n) return hipErrorInvalidValue;      // (the pure / coset form: two-pass plans only)
+  // a first pass addresses its row by 32-bit byte offsets from the row's start (the kernel's "Global addresses"): 2^26 columns x 32 B
+  // = 2^31 is the largest plan there is (ntt_l9s3_supported); a wider row would wrap
+  if (a.log_n > 26) return hipErrorInvalidValue;
   if (a.tile_group && ((1u << (a.log_n - 10)) >> a.tile_group) < 8) return hipErrorInvalidValue;
   switch (a.s) {
 #define X(SV) case SV: return launch_t<SV, 10 - SV, true>(a, pack, pi, st);

@@ -45,6 +45,22 @@ template <class FT> constexpr u32 U_SLOT = (FT::N * FT::N + 31) & ~31u;
 // block at its 16-byte alignment
 template <class FT> constexpr u32 U_ALIGN = FT::N == 9 ? 4u : 16u;
 
+// ---- global addresses of a K1s pass: a wave-uniform 64-bit base held in scalar registers plus an UNSIGNED 32-bit byte offset per
+//      lane -- the saddr + voffset form of global_load / global_store, so that no address costs a 64-bit vector shift or carry add
+//      (VOP3, 4.3 cycles each).  ubase(): p is uniform by construction (kernel arguments, blockIdx, compile-time constants); the
+//      readfirstlane pair says so and keeps the compiler from folding the uniform part back into a shared per-lane 64-bit sum.
+//      lane_at(): the caller states the largest offset it forms.  Everything row-, tile- or class-sized stays on the 64-bit side: a
+//      commitment matrix exceeds 4 GiB at the headline (2^18 columns x 512 rows x 32 B).
+template <class T> LCPC_DEV T* ubase(T* p) {
+  const u64 v = reinterpret_cast<u64>(p);
+  const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
+  // (rebuilt from integers, the pointer would be a generic one -- flat instructions, which have no scalar base: it names global memory)
+  typedef __attribute__((address_space(1))) T* GP;
+  return (T*)(GP)(((u64)hi << 32) | lo);
+}
+LCPC_DEV const u32* lane_at(const u32* base, u32 byte_off) { return reinterpret_cast<const u32*>(reinterpret_cast<const char*>(base) + byte_off); }
+LCPC_DEV u32* lane_at(u32* base, u32 byte_off) { return reinterpret_cast<u32*>(reinterpret_cast<char*>(base) + byte_off); }
+
 // ---- an array of `cnt` elements in planes: limbs 0-3 as uint4 (N >= 5), then a uint2 plane (N = 3: limbs 0-1; N = 7: limbs 4-5)
 //      or a second uint4 plane (N = 9: limbs 4-7), then the top limb as u32.  The LDS tile (cnt = the tile size: unit-stride
 //      lanes are conflict-free in every plane; the q*p table follows it) and K1n's twiddle packs (cnt = variants x period).  cnt: a
@@ -139,6 +155,22 @@ template <class FT, u32 NV> LCPC_DEV LN<FT::N> pack_get(const u32* blk, u32 peri
   } else {
     return planes_get<FT>(blk, NV * period, variant * period + jl);
   }
+}
+// the same entry for the K1s pass kernels, whose block pointer and period are wave-uniform by construction (class = the workgroup's
+// tile or none, round and period compile-time): entry (uv + lv) with uv the wave-uniform part of the variant (which twiddle of the
+// triple, which table of an ln::mul2 pair) and lv the part that may differ by lane (plain or converting set).  Each of the three loads
+// takes a scalar base of its own (ubase) and the lanes add (2 lv period + jl) * 16 resp. (lv period + jl) * 4 bytes: lv < 6 and
+// jl < period <= 512, so a lane offset stays below 104 KiB -- 32 bits whatever the plan, since a class block does not grow with the
+// transform (<= 2^20 columns in two passes, <= 2^26 in three: the same rounds, the same periods).
+// == pack_get<FT, NV>(blk, period, uv + lv, jl), which serves a block pointer of any kind (tests/native/k1_harness.cpp)
+template <u32 NV> LCPC_DEV LN<9> pack_get_u(const u32* blk, u32 period, u32 uv, u32 lv, u32 jl) {
+  const u32 o16 = (lv * 2 * period + jl) << 4, o4 = (lv * period + jl) << 2;
+  const uint4 a = *reinterpret_cast<const uint4*>(lane_at(ubase(blk + (size_t)(uv * 2 + 0) * period * 4), o16));
+  const uint4 b = *reinterpret_cast<const uint4*>(lane_at(ubase(blk + (size_t)(uv * 2 + 1) * period * 4), o16));
+  const u32 c = *lane_at(ubase(blk + (size_t)NV * 2 * period * 4 + (size_t)uv * period), o4);
+  LN<9> t;
+  t.v[0] = a.x; t.v[1] = a.y; t.v[2] = a.z; t.v[3] = a.w; t.v[4] = b.x; t.v[5] = b.y; t.v[6] = b.z; t.v[7] = b.w; t.v[8] = c;
+  return t;
 }
 template <class FT, u32 NV> LCPC_DEV void pack_put(u32* blk, u32 period, u32 variant, u32 jl, const LN<FT::N>& x) {
   if constexpr (FT::N == 9) {
