@@ -178,6 +178,63 @@ def extend(field, coeffs, shift, log_m, order="natural"):
     return out
 
 
+def _op(op):
+    if op not in _lib.QUOT_OPS:
+        raise ValueError("op must be one of %s, not %r" % (sorted(_lib.QUOT_OPS), op))
+    return _lib.QUOT_OPS[op]
+
+
+def batch_inverse(field, x):
+    """lcpcq_batch_inverse (include/lcpc_hip_quot.h): the inverses of the (n, L) elements x, zero for a zero.  A host call: no
+    device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(x, L).reshape(-1, L)
+    out = np.zeros_like(a)
+    rc = _lib.lib().lcpcq_batch_inverse(field, _ptr(a), _ptr(out), a.shape[0])
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def pointwise(field, op, a, b):
+    """lcpcq_pointwise: a[i] op b[i] over two (n, L) element arrays, op "add" / "sub" / "mul" / "div" (a[i] / b[i], zero where b[i]
+    is zero).  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    x, y = _elems(a, L).reshape(-1, L), _elems(b, L).reshape(-1, L)
+    if x.shape != y.shape:
+        raise ValueError("a and b hold the same number of elements")
+    out = np.zeros_like(x)
+    rc = _lib.lib().lcpcq_pointwise(field, _op(op), _ptr(x), _ptr(y), _ptr(out), x.shape[0])
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def divide_linear(field, vals, shift, z, y, order="natural"):
+    """lcpcq_divide_linear: (vals[k] - y) / (shift w_m^k - z) over the (m, L) values of a column on shift * H_m (shift=None: on H_m);
+    z and y are one element each.  order as lcpc_amd.extend.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(vals, L).reshape(-1, L)
+    out = np.zeros_like(a)
+    s = None if shift is None else _ptr(_shift(shift, L))
+    rc = _lib.lib().lcpcq_divide_linear(field, s, _order(order), _ptr(a), _log_n(a.shape[0]), _ptr(_shift(z, L)), _ptr(_shift(y, L)), _ptr(out))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def divide_vanishing(field, vals, shift, log_n, order="natural"):
+    """lcpcq_divide_vanishing: vals[k] / ((shift w_m^k)^n - 1), n = 2^log_n, over the (m, L) values of a column on shift * H_m, a
+    coset off the subgroup.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(vals, L).reshape(-1, L)
+    out = np.zeros_like(a)
+    rc = _lib.lib().lcpcq_divide_vanishing(field, _ptr(_shift(shift, L)), _order(order), _ptr(a), _log_n(a.shape[0]), log_n, _ptr(out))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -371,6 +428,50 @@ class _Encoding:
                                                 _ptr(_shift(shift_out, self.L)), log_m, _order(out_order), C.c_void_p(out.data_ptr()),
                                                 C.c_void_p(work.data_ptr()), n_vecs, C.c_void_p(stream)))
         return out, work
+
+    def batch_inverse(self, t, out=None, stream=0):
+        """lcpcq_batch_inverse_device (include/lcpc_hip_quot.h): the inverse of every element of an (n, L) or (n_vecs, n, L) tensor on
+        the encoder's device, zero for a zero.  out=None returns a new tensor, out=t runs in place.  Only enqueues on `stream`."""
+        n_vecs = self._elem_tensor(t, "the inversion")
+        out = self._out_tensor(t, out, t.shape)
+        self._check(_lib.lib().lcpcq_batch_inverse_device(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                          n_vecs * t.shape[-2], C.c_void_p(stream)))
+        return out
+
+    def pointwise(self, op, a, b, out=None, stream=0):
+        """lcpcq_pointwise_device: a[i] op b[i] over two tensors of one shape, op "add" / "sub" / "mul" / "div" (zero where b[i] is
+        zero).  out may be a or b.  Only enqueues on `stream`."""
+        n_vecs = self._elem_tensor(a, "a pointwise operation")
+        if self._elem_tensor(b, "a pointwise operation") != n_vecs or a.shape != b.shape:
+            raise ValueError("a and b are tensors of one shape")
+        out = self._out_tensor(a, out, a.shape)
+        self._check(_lib.lib().lcpcq_pointwise_device(self._h, _op(op), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                                      C.c_void_p(out.data_ptr()), n_vecs * a.shape[-2], C.c_void_p(stream)))
+        return out
+
+    def divide_linear(self, vals, shift, z, y, order="natural", out=None, stream=0):
+        """lcpcq_divide_linear_device: (vals_v[k] - y_v) / (shift w_m^k - z) over (m, L) or (n_vecs, m, L) values on shift * H_m
+        (shift=None: on H_m).  shift and z are host limbs; y is a tensor of n_vecs elements on the device, where LcCommit.eval leaves
+        them.  Only enqueues on `stream`."""
+        import torch
+        n_vecs = self._elem_tensor(vals, "the division")
+        if not torch.is_tensor(y) or y.device != vals.device or not y.is_contiguous() or y.element_size() != 8 or y.numel() != n_vecs * self.L:
+            raise ValueError("y holds one element per vector, contiguous 64-bit limbs on the encoder's device")
+        out = self._out_tensor(vals, out, vals.shape)
+        s = None if shift is None else _ptr(_shift(shift, self.L))
+        self._check(_lib.lib().lcpcq_divide_linear_device(self._h, s, _order(order), C.c_void_p(vals.data_ptr()), _log_n(vals.shape[-2]), n_vecs,
+                                                          _ptr(_shift(z, self.L)), C.c_void_p(y.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                          C.c_void_p(stream)))
+        return out
+
+    def divide_vanishing(self, vals, shift, log_n, order="natural", out=None, stream=0):
+        """lcpcq_divide_vanishing_device: vals_v[k] / ((shift w_m^k)^n - 1), n = 2^log_n, over (m, L) or (n_vecs, m, L) values on the
+        coset shift * H_m.  Only enqueues on `stream`."""
+        n_vecs = self._elem_tensor(vals, "the division")
+        out = self._out_tensor(vals, out, vals.shape)
+        self._check(_lib.lib().lcpcq_divide_vanishing_device(self._h, _ptr(_shift(shift, self.L)), _order(order), C.c_void_p(vals.data_ptr()),
+                                                             _log_n(vals.shape[-2]), log_n, n_vecs, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
 
     def __del__(self):
         try:

@@ -185,6 +185,21 @@ DOMAIN_SYMBOLS = {
     "lcpcd_commit_values_device": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
 }
 
+# the quotient extension (include/lcpc_hip_quot.h): again its own prefix, table and version; its orders are DOMAIN_ORDERS
+QUOT_VERSION = 1
+QUOT_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3}                                               # lcpcq_op
+QUOT_SYMBOLS = {
+    "lcpcq_version": (_i32, []),
+    "lcpcq_batch_inverse": (_i32, [_u32, _vp, _vp, _u64]),
+    "lcpcq_batch_inverse_device": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "lcpcq_pointwise": (_i32, [_u32, _u32, _vp, _vp, _vp, _u64]),
+    "lcpcq_pointwise_device": (_i32, [_vp, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "lcpcq_divide_linear": (_i32, [_u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "lcpcq_divide_linear_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "lcpcq_divide_vanishing": (_i32, [_u32, _vp, _u32, _vp, _u32, _u32, _vp]),
+    "lcpcq_divide_vanishing_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -258,5 +273,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcd_version() != DOMAIN_VERSION:
             raise RuntimeError("lcpc_amd: domain extension version mismatch")
+        for name, (res, args) in QUOT_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcq_version() != QUOT_VERSION:
+            raise RuntimeError("lcpc_amd: quotient extension version mismatch")
         _lib = L
     return _lib

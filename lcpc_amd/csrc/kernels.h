@@ -469,4 +469,25 @@ hipError_t launch_coset_fft(int nl, int form, uint32_t log_n, uint32_t log_tile,
 hipError_t launch_extend(int nl, uint64_t n_coeffs, uint32_t log_m, int natural, uint32_t log_tile, uint32_t n_vecs, const uint32_t* coeffs,
                          uint32_t* out, const uint32_t* tab_m, const uint32_t* stab, hipStream_t st, uint32_t* n_launches);
 
+// K15 / K16 (quot.hip; include/lcpc_hip_quot.h): inverses, pointwise arithmetic and quotients on a domain.  One launch each.  A
+// workgroup inverts a tile of quot_tile(nl) elements with one exponentiation per lane of ONE wave (quot.hip describes it).  Inputs fully
+// reduced; every stored element then is.  An input may BE the output; ranges that overlap otherwise, a bad nl, op or kind, a NULL or
+// misaligned pointer, n == 0 or n >= 2^39 are hipErrorInvalidValue, checked before the launch.
+// launch_batch_inverse: out[i] = in[i]^-1, zero for zero.
+// launch_pointwise: out[i] = a[i] op b[i]; QUOT_DIV is a[i] b[i]^-1, zero where b[i] is zero.
+// launch_domain_quotient: n_vecs vectors of m = 2^log_m values at x_k = s w_m^k, value k at [k] or (bitrev) at [rev_m(k)];
+//   QUOT_LINEAR: out_v[k] = (in_v[k] - y[v]) / (x_k - z), s = *shift (NULL: one), z: nl words in HOST memory, y: n_vecs elements on the
+//   device that must not meet the output.  The caller guarantees that z is no point of the domain.
+//   QUOT_VANISH: out_v[k] = in_v[k] / (x_k^n - 1), n = 2^log_n <= m; `shift` holds s^n (not NULL), z and y are not read.  The caller
+//   guarantees s^m != 1.
+//   tab_m: the FORWARD table of launch_fft for log_m (not read for log_m == 0); shift and z are kernel arguments.  Further refusals:
+//   log_m > FFT_MAX_LOG_N, n_vecs == 0 or > 65535, n_vecs * m >= 2^39, log_n > log_m.
+enum : int { QUOT_ADD = 0, QUOT_SUB = 1, QUOT_MUL = 2, QUOT_DIV = 3 };
+enum : int { QUOT_LINEAR = 0, QUOT_VANISH = 1 };
+constexpr uint32_t quot_tile(int nl) { return nl >= 6 ? 2048 : 4096; }      // elements of a workgroup's tile
+hipError_t launch_batch_inverse(int nl, const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t st);
+hipError_t launch_pointwise(int nl, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint64_t n, hipStream_t st);
+hipError_t launch_domain_quotient(int nl, int kind, int bitrev, uint32_t log_m, uint32_t log_n, uint32_t n_vecs, const uint32_t* in, uint32_t* out,
+                                  const uint32_t* tab_m, const uint32_t* shift, const uint32_t* z, const uint32_t* y, hipStream_t st);
+
 }  // namespace lcpc
