@@ -185,7 +185,6 @@ static void chain_dispatch(int nl, bool canon, const F& f) {
     case 8: if (canon) f.template operator()<8, true>(); else f.template operator()<8, false>(); break;
   }
 }
-inline bool chain_nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
 
 template <class D> struct ChainLeafLaunch {
   const LeafArgs& a; dim3 grid; hipStream_t st;
@@ -207,14 +206,14 @@ template <class D> struct ChainLeafRangeLaunch {
 
 template <class D> hipError_t chain_leaves(int nl, const LeafArgs& a, hipStream_t st) {
   if (a.n_cols == 0) return hipSuccess;
-  if (!chain_nl_ok(nl)) return hipErrorInvalidValue;
+  if (!nl_ok(nl)) return hipErrorInvalidValue;
   chain_dispatch(nl, a.canon_in != 0, ChainLeafLaunch<D>{a, dim3((unsigned)((a.n_cols + 255) / 256)), st});
   return hipGetLastError();
 }
 
 template <class D> hipError_t chain_leaves_batch(int nl, const LeafArgs& a, u32 n_batch, u64 comm_stride, u64 out_stride, hipStream_t st) {
   if (n_batch > 65535) return hipErrorInvalidValue;          // grid.y
-  if (!chain_nl_ok(nl)) return hipErrorInvalidValue;
+  if (!nl_ok(nl)) return hipErrorInvalidValue;
   if (nl == 8 && !a.canon_in) return hipErrorInvalidValue;
   if (a.n_cols == 0 || n_batch == 0) return hipSuccess;
   chain_dispatch(nl, a.canon_in != 0, ChainLeafBatchLaunch<D>{a, dim3((unsigned)((a.n_cols + 255) / 256), n_batch), comm_stride, out_stride, st});
@@ -222,7 +221,7 @@ template <class D> hipError_t chain_leaves_batch(int nl, const LeafArgs& a, u32 
 }
 
 template <class D> hipError_t chain_leaves_range(int nl, const LeafArgs& a, u64 b0, u64 b1, u32* state, hipStream_t st) {
-  if (!chain_nl_ok(nl)) return hipErrorInvalidValue;
+  if (!nl_ok(nl)) return hipErrorInvalidValue;
   if (b0 > b1 || b1 > D::n_blocks(D::PREFIX + (u64)(nl / 2) * a.n_rows_total)) return hipErrorInvalidValue;
   if (a.n_cols == 0 || b0 == b1) return hipSuccess;
   chain_dispatch(nl, a.canon_in != 0,

@@ -1,61 +1,30 @@
 // lcpc_amd/csrc/domain.cpp -- the domain extension of the C ABI (include/lcpc_hip_domain.h): coset transforms and the extension on
-// the host (fft_host.h, no HIP call) and on the device (K14, domain.hip) with the context's cache of shift tables, the low-degree
-// extension built from the two, the commit entry points that read values on a coset (commit.cpp commit_evals_locked) and the reader
-// that writes a commitment's values on a domain.
+// the host (fft_host.h, no HIP call) and on the device (K14, domain.hip) with the context's cache of shift tables (fft.cpp
+// cached_table), the low-degree extension built from the two, the commit entry points that read values on a coset (fft.cpp
+// commit_evals_entry) and the reader that writes a commitment's values on a domain.
 #include "internal.h"
 #include "fft_host.h"
 #include "../../include/lcpc_hip_domain.h"
+#include "../../include/lcpc_hip_fft.h"
 
 using namespace lcpc;
 
+static_assert((int)LCPCD_NATURAL == (int)LCPCF_NATURAL && (int)LCPCD_BITREV == (int)LCPCF_BITREV,
+              "commit_evals_entry (fft.cpp) reads both extensions' orders");
 static_assert(LCPCD_FFT_II == FFT_FFT_II && LCPCD_FFT_IO == FFT_FFT_IO && LCPCD_FFT_OI == FFT_FFT_OI && LCPCD_IFFT_II == FFT_IFFT_II &&
                   LCPCD_IFFT_IO == FFT_IFFT_IO && LCPCD_IFFT_OI == FFT_IFFT_OI,
               "lcpcd_form and the launcher's forms are one numbering");
 
 namespace {
 
-inline bool dev_aligned(const void* p, int L) { return reinterpret_cast<uintptr_t>(p) % (L % 2 ? 8 : 16) == 0; }
-inline uint32_t dev_max_log_n(const FieldDesc& f) { return f.S < FFT_MAX_LOG_N ? f.S : FFT_MAX_LOG_N; }
-// two ranges of na and nb bytes have a byte in common
-inline bool ranges_meet(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
-
-// the context's shift table of (shift, log_n, direction), c->mu held, by fft_table's rules: found, or built on the host, uploaded
-// and put in place of the entry used longest ago.  Forward: t = shift; inverse: t = shift^-1 with n^-1 in the upper level
+// the context's shift table of (shift, log_n, direction), c->mu held: cached_table (fft.cpp) on t = shift forward, t = shift^-1 with
+// n^-1 in the upper level inverse
 int dom_table(lcpc_ctx* c, ErrText* err, const uint64_t* shift, uint32_t log_n, bool inverse, const uint32_t** tab) {
-  const FieldDesc& f = *c->f;
-  DomTab* victim = &c->dom_tabs[0];
-  for (auto& t : c->dom_tabs) {
-    if (t.d && t.log_n == log_n && t.inverse == inverse && !memcmp(t.shift, shift, 8 * f.L)) { t.stamp = ++c->fft_stamp; *tab = t.d; return 0; }
-    if (!t.d ? victim->d != nullptr : (victim->d && t.stamp < victim->stamp)) victim = &t;
-  }
-  const uint32_t h = fft_tab_split(log_n);
-  const uint64_t n_lo = (uint64_t)1 << h, n_hi = (uint64_t)1 << (log_n - h);
-  std::vector<uint64_t> host((size_t)(n_lo + n_hi) * f.L);
-  uint64_t t[MAXL];
-  if (inverse) h_inv(f, t, shift); else memcpy(t, shift, 8 * f.L);
-  powers(f, t, n_lo, host.data());
-  h_pow(f, t, t, n_lo);
-  uint64_t* hi = host.data() + (size_t)n_lo * f.L;
-  powers(f, t, n_hi, hi);
-  if (inverse) {
-    uint64_t ni[MAXL];
-    n_inverse(f, log_n, ni);
-    for (uint64_t i = 0; i < n_hi; i++) h_mul(f, hi + i * f.L, hi + i * f.L, ni);
-  }
-  dev_free(victim->d);                 // (waits for whatever still reads it)
-  victim->d = nullptr;
-  int rc = dev_alloc(err, &victim->d, host.size() * 8);
-  if (rc) return rc;
-  hipError_t e = hipMemcpy(victim->d, host.data(), host.size() * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { dev_free(victim->d); victim->d = nullptr; return fail_hip(err, e, "hipMemcpy (shift table)"); }
-  memset(victim->shift, 0, sizeof victim->shift);
-  memcpy(victim->shift, shift, 8 * f.L);
-  victim->log_n = log_n; victim->inverse = inverse; victim->stamp = ++c->fft_stamp;
-  *tab = victim->d;
-  return 0;
+  return cached_table(c, err, c->dom_tabs, 8, shift, log_n, inverse,
+                      [](const FieldDesc& f, const uint64_t* shift, uint32_t log_n, bool inverse, uint64_t* v, uint64_t* factor) {
+                        if (inverse) { h_inv(f, v, shift); n_inverse(f, log_n, factor); } else memcpy(v, shift, 8 * f.L);
+                        return inverse;
+                      }, tab);
 }
 
 // what lcpcd_extend_device refuses beyond pointers, order and shift; *total: elements of the output
@@ -145,10 +114,8 @@ int lcpcd_extend(uint32_t field, const uint64_t* shift, const uint64_t* coeffs, 
 
 int lcpcd_coset_fft_device(lcpc_ctx* c, uint32_t form, const uint64_t* shift, const uint64_t* in_dev, uint64_t* out_dev, uint32_t log_n,
                            uint32_t n_vecs, void* stream) {
-  if (!c || form > LCPCD_IFFT_OI || !shift_ok(*c->f, shift) || !in_dev || !out_dev || n_vecs == 0 || n_vecs > 65535) return LCPC_ERR_ARG;
-  if (!dev_aligned(in_dev, c->L) || !dev_aligned(out_dev, c->L) || log_n > dev_max_log_n(*c->f)) return LCPC_ERR_ARG;
-  const uint64_t total = (uint64_t)n_vecs << log_n;
-  if (total >= ((uint64_t)1 << 39) || ranges_overlap(in_dev, out_dev, total * elem_bytes(c))) return LCPC_ERR_ARG;
+  uint64_t total = 0;
+  if (!c || form > LCPCD_IFFT_OI || !shift_ok(*c->f, shift) || !dev_vectors_ok(c, in_dev, out_dev, log_n, n_vecs, &total)) return LCPC_ERR_ARG;
   LCPC_TRY
   HIPCHK(c, hipSetDevice(c->prm.device));
   return coset_enqueue(c, &c->err, (int)form, shift, reinterpret_cast<const uint32_t*>(in_dev), reinterpret_cast<uint32_t*>(out_dev), log_n,
@@ -196,30 +163,11 @@ int lcpcd_lde_device(lcpc_ctx* c, uint32_t in_order, const uint64_t* shift_in, c
 
 int lcpcd_commit_coset_evals_device(lcpc_commit_t* m, uint32_t order, const uint64_t* shift, const uint64_t* evals_dev, uint32_t log_n,
                                     void* stream, uint8_t* root) {
-  if (!m || !evals_dev || order > LCPCD_BITREV) return LCPC_ERR_ARG;
-  const lcpc_ctx* c = m->enc;
-  if (!shift_ok(*c->f, shift) || !dev_aligned(evals_dev, c->L) || log_n > dev_max_log_n(*c->f)) return LCPC_ERR_ARG;
-  if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
-  LCPC_TRY
-  std::unique_lock<FillLock> fill(m->fill_mu);      // a fill: waits for the readers in flight (internal.h)
-  std::lock_guard<std::mutex> g(m->mu);
-  HIPCHK(m, hipSetDevice(c->prm.device));
-  return commit_evals_locked(m, order == LCPCD_NATURAL ? FFT_IFFT_II : FFT_IFFT_OI, evals_dev, log_n, false, (hipStream_t)stream, root, shift);
-  LCPC_CATCH(m)
+  return commit_evals_entry(m, order, true, shift, evals_dev, log_n, false, (hipStream_t)stream, root);
 }
 
 int lcpcd_commit_coset_evals(lcpc_commit_t* m, uint32_t order, const uint64_t* shift, const uint64_t* evals_host, uint32_t log_n, uint8_t* root) {
-  if (!m || !evals_host || order > LCPCD_BITREV) return LCPC_ERR_ARG;
-  const lcpc_ctx* c = m->enc;
-  if (!shift_ok(*c->f, shift) || log_n > dev_max_log_n(*c->f)) return LCPC_ERR_ARG;
-  if (c->prm.shard_count > 1) return LCPC_ERR_STATE;
-  if (!elems_reduced(*c->f, evals_host, (uint64_t)1 << log_n)) return LCPC_ERR_ARG;
-  LCPC_TRY
-  std::unique_lock<FillLock> fill(m->fill_mu);
-  std::lock_guard<std::mutex> g(m->mu);
-  HIPCHK(m, hipSetDevice(c->prm.device));
-  return commit_evals_locked(m, order == LCPCD_NATURAL ? FFT_IFFT_II : FFT_IFFT_OI, evals_host, log_n, true, nullptr, root, shift);
-  LCPC_CATCH(m)
+  return commit_evals_entry(m, order, true, shift, evals_host, log_n, true, nullptr, root);
 }
 
 int lcpcd_commit_values_device(lcpc_commit_t* m, const uint64_t* shift, uint32_t log_m, uint32_t order, uint64_t* out_dev, void* stream) {

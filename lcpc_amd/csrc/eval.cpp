@@ -17,7 +17,6 @@ constexpr uint32_t MAX_POINTS = 65535;      // the expansion's second grid dimen
 inline unsigned bit_len(uint64_t v) { return v ? 64u - (unsigned)__builtin_clzll(v) : 0u; }
 inline bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline bool dev_aligned(const void* p, int L) { return reinterpret_cast<uintptr_t>(p) % (L % 2 ? 8 : 16) == 0; }
 
 // What a basis makes of a shape: the pairs per point in K10's table, and which of them each tensor reads
 struct Shape {

@@ -107,8 +107,6 @@ template <int NL> Fe<NL> fe_arg(const u32* w) {
   for (int i = 0; i < NL; i++) r.v[i] = w[i];
   return r;
 }
-inline bool nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
-inline bool elem_aligned(const void* p, int nl) { return reinterpret_cast<uintptr_t>(p) % (nl % 4 == 0 ? 16 : 8) == 0; }
 
 template <int NL>
 void pairs_nl(const u32* points, u32 n_point, u32 n_points, int basis, u32 n_bits, const u32* one, u32* tab, hipStream_t st) {

@@ -1,7 +1,8 @@
 // lcpc_amd/csrc/fft_host.h -- the transforms on the host, on one thread, over host_field.h alone (no HIP): the six FieldFFT forms of
 // include/lcpc_hip_fft.h, and over them the coset forms and the extension of include/lcpc_hip_domain.h.  Also what the device side
-// builds its tables from: the root of a size and direction, n^-1, powers, the inverse of an element.  fft.cpp and domain.cpp hold the
-// entry points; tools/check_domain_host.cpp compiles this header without the HIP runtime.
+// builds its tables from: the root of a size and direction, n^-1, powers, the inverse of an element, and the two-level table itself
+// (two_level_table).  fft.cpp and domain.cpp hold the entry points; tools/check_domain_host.cpp compiles this header without the HIP
+// runtime.
 #pragma once
 #include <vector>
 
@@ -80,6 +81,18 @@ inline void n_inverse(const FieldDesc& f, uint32_t log_n, uint64_t* o) {
 inline void powers(const FieldDesc& f, const uint64_t* v, uint64_t n, uint64_t* out) {
   memcpy(out, f.r, 8 * f.L);
   for (uint64_t i = 1; i < n; i++) h_mul(f, out + i * f.L, out + (i - 1) * f.L, v);
+}
+
+// the two-level table of the powers of v that the device kernels read (kernels.h launch_fft, launch_coset_fft): out[i] = v^i for
+// i < n_lo, out[n_lo + i] = c v^(i n_lo) for i < n_hi; c null: one.  v^e for e < n_lo n_hi is then one product of two entries
+inline void two_level_table(const FieldDesc& f, const uint64_t* v, uint64_t n_lo, uint64_t n_hi, const uint64_t* c, uint64_t* out) {
+  uint64_t step[MAXL];
+  powers(f, v, n_lo, out);
+  h_pow(f, step, v, n_lo);
+  uint64_t* hi = out + n_lo * f.L;
+  powers(f, step, n_hi, hi);
+  if (c)
+    for (uint64_t i = 0; i < n_hi; i++) h_mul(f, hi + i * f.L, hi + i * f.L, c);
 }
 
 inline void host_fft(const FieldDesc& f, uint32_t form, uint64_t* a, uint32_t log_n) {

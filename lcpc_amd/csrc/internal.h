@@ -287,19 +287,14 @@ struct lcpc_transcript {
 };
 
 namespace lcpc {
+// a cached two-level table on the device (fft.cpp cached_table): the twiddles of a size and direction (kernels.h launch_fft), or the
+// powers of a shift (launch_coset_fft), whose key has the shift's limbs as well -- a twiddle table's are all zero, which no shift is
 struct FftTab {
-  uint32_t log_n = 0;
-  bool inverse = false;
-  uint32_t* d = nullptr;           // fft_tab_elems(log_n) elements (kernels.h launch_fft)
-  uint64_t stamp = 0;              // last use
-};
-// the two-level table of the powers of a shift (kernels.h launch_coset_fft): its key is the shift's limbs, the size and the direction
-struct DomTab {
   uint64_t shift[4] = {0, 0, 0, 0};
   uint32_t log_n = 0;
   bool inverse = false;
   uint32_t* d = nullptr;           // fft_tab_elems(log_n) elements
-  uint64_t stamp = 0;
+  uint64_t stamp = 0;              // last use
 };
 }  // namespace lcpc
 
@@ -363,8 +358,8 @@ struct lcpc_ctx {
   lcpc::FftTab fft_tabs[4];
   uint64_t fft_stamp = 0;
   // the lcpcd_ device calls (include/lcpc_hip_domain.h): the shift tables of the last few (shift, size, direction) keys, under `mu`,
-  // by the same rules (domain.cpp dom_table); they share fft_stamp
-  lcpc::DomTab dom_tabs[8];
+  // by the same routine (domain.cpp dom_table); they share fft_stamp
+  lcpc::FftTab dom_tabs[8];
   // RCCL communicator of a sharded encoder (lcpc_comm_init); opaque ncclComm_t
   void* comm = nullptr;
   std::mutex xchg_mu;              // serialises the submission of collectives on `comm` (several commitments, several host threads)
@@ -505,6 +500,24 @@ template <typename T> int ensure_dev(ErrText* err, T** p, uint64_t* cap, uint64_
 }
 
 inline size_t elem_bytes(const lcpc_ctx* c) { return (size_t)8 * c->L; }
+// what the device entry points of the extensions (eval.cpp, fft.cpp, domain.cpp, quot.cpp) ask of their arguments: an element pointer
+// aligned for the kernels' widest load, a transform no longer than the field's 2-adicity and the launchers allow
+inline bool dev_aligned(const void* p, int L) { return reinterpret_cast<uintptr_t>(p) % (L % 2 ? 8 : 16) == 0; }
+inline uint32_t dev_max_log_n(const FieldDesc& f) { return f.S < FFT_MAX_LOG_N ? f.S : FFT_MAX_LOG_N; }
+// two ranges of na and nb bytes have a byte in common
+inline bool ranges_meet(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+// n_vecs vectors of 2^log_n elements, in and out, on the device: 1 .. 65535 vectors, aligned, log_n <= dev_max_log_n, fewer than 2^39
+// elements (*total), in == out or disjoint
+inline bool dev_vectors_ok(const lcpc_ctx* c, const uint64_t* in_dev, const uint64_t* out_dev, uint32_t log_n, uint32_t n_vecs, uint64_t* total) {
+  if (!in_dev || !out_dev || n_vecs == 0 || n_vecs > 65535) return false;
+  if (!dev_aligned(in_dev, c->L) || !dev_aligned(out_dev, c->L) || log_n > dev_max_log_n(*c->f)) return false;
+  *total = (uint64_t)n_vecs << log_n;
+  if (*total >= ((uint64_t)1 << 39)) return false;
+  return in_dev == out_dev || !ranges_meet(in_dev, *total * elem_bytes(c), out_dev, *total * elem_bytes(c));
+}
 inline bool is_sha3(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_SHA3_256; }
 inline bool is_blake2b(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_BLAKE2B; }
 inline bool is_keccak256(const lcpc_ctx* c) { return c->prm.hash == LCPC_HASH_KECCAK256; }
@@ -612,7 +625,17 @@ int commit_evals_locked(lcpc_commit_t* m, int form, const uint64_t* evals, uint3
                         const uint64_t* shift = nullptr);
 // K12 / K13 on `st` with the context's twiddle tables (fft.cpp; takes c->mu): in == out in place, otherwise disjoint
 int fft_enqueue(lcpc_ctx* c, ErrText* err, int form, const uint32_t* in, uint32_t* out, uint32_t log_n, uint32_t n_vecs, hipStream_t st);
-// the context's twiddle table of (log_n, direction), c->mu held: found, or built on the host, uploaded and cached (fft.cpp)
+// the four commit-from-evaluations entry points (lcpcf_commit_evals*, lcpcd_commit_coset_evals*) whole, argument checks and locks
+// included (fft.cpp).  host: `evals` is host memory and st unused; coset: shift must be a shift (fft_host.h shift_ok), else it is unused
+int commit_evals_entry(lcpc_commit_t* m, uint32_t order, bool coset, const uint64_t* shift, const uint64_t* evals, uint32_t log_n, bool host,
+                       hipStream_t st, uint8_t* root);
+// The context's cached two-level tables, c->mu held (fft.cpp): the table of key (shift, log_n, inverse) among tabs[n_tabs] -- found, or
+// built on the host (fft_host.h two_level_table), uploaded and put in place of the entry used longest ago.  shift null: the all-zero key.
+// base names what a miss builds from: the base element v and, where it returns true, the factor c of the upper level
+using TabBase = bool (*)(const FieldDesc& f, const uint64_t* shift, uint32_t log_n, bool inverse, uint64_t* v, uint64_t* c);
+int cached_table(lcpc_ctx* c, ErrText* err, FftTab* tabs, int n_tabs, const uint64_t* shift, uint32_t log_n, bool inverse, TabBase base,
+                 const uint32_t** tab);
+// the context's twiddle table of (log_n, direction): cached_table on the direction's root
 int fft_table(lcpc_ctx* c, ErrText* err, uint32_t log_n, bool inverse, const uint32_t** tab);
 // K14 on `st` with the context's twiddle and shift tables (domain.cpp; both take c->mu).  shift: host limbs, nonzero and reduced.
 // coset_enqueue: in == out in place, otherwise disjoint.  extend_enqueue: n_vecs coefficient vectors -> their values on D(shift, 2^log_m)

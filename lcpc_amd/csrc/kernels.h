@@ -6,6 +6,11 @@
 
 namespace lcpc {
 
+// an element width the launchers know (NL = 2, 4, 6 or 8 words), and what those of eval.hip, fft.hip, domain.hip and quot.hip ask of an
+// element pointer: aligned for the widest load of an element
+inline bool nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
+inline bool elem_aligned(const void* p, int nl) { return reinterpret_cast<uintptr_t>(p) % (nl % 4 == 0 ? 16 : 8) == 0; }
+
 struct NttPassArgs {
   const uint32_t* src;     // row-major, src_stride elements per row
   uint32_t* dst;           // row-major, dst_stride elements per row (may alias src when strides match)
@@ -429,7 +434,7 @@ hipError_t launch_field_dot(int nl, const uint32_t* a, uint64_t a_stride, const 
 // forms only.  in == out runs in place; otherwise the two ranges must not overlap, and `in` is only read.  Inputs fully reduced; every
 // stored element then is.  *n_launches (may be null) receives the number of kernels launched: the passes, plus K13 for the II forms.
 // log_n == 0 copies (no launch).  A bad nl, form, log_tile or log_n, n_vecs == 0 or > 65535, n_vecs * n >= 2^39, a NULL or
-// misaligned pointer is hipErrorInvalidValue, checked before any launch
+// misaligned pointer, ranges that overlap without being the same is hipErrorInvalidValue, checked before any launch
 enum : int { FFT_FFT_II = 0, FFT_FFT_IO = 1, FFT_FFT_OI = 2, FFT_IFFT_II = 3, FFT_IFFT_IO = 4, FFT_IFFT_OI = 5 };
 constexpr uint32_t FFT_MAX_LOG_TILE = 10, FFT_MAX_LOG_N = 32, FFT_MAX_PASSES = 32;
 inline uint32_t fft_tab_split(uint32_t log_n) { return log_n / 2; }

@@ -15,21 +15,12 @@ static_assert(LCPCQ_ADD == QUOT_ADD && LCPCQ_SUB == QUOT_SUB && LCPCQ_MUL == QUO
 
 namespace {
 
-inline bool dev_aligned(const void* p, int L) { return reinterpret_cast<uintptr_t>(p) % (L % 2 ? 8 : 16) == 0; }
-inline uint32_t dev_max_log_n(const FieldDesc& f) { return f.S < FFT_MAX_LOG_N ? f.S : FFT_MAX_LOG_N; }
-inline bool ranges_meet(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
 inline bool elem_ok(const FieldDesc& f, const uint64_t* e) { return e && !h_ge_p(f, e); }
 inline const uint32_t* words(const uint64_t* p) { return reinterpret_cast<const uint32_t*>(p); }
 
 // what the two device divisions refuse alike; *total: elements of the output
 bool divide_dims_ok(const lcpc_ctx* c, uint32_t order, const uint64_t* in_dev, uint64_t* out_dev, uint32_t log_m, uint32_t n_vecs, uint64_t* total) {
-  if (order > LCPCD_BITREV || !in_dev || !out_dev || n_vecs == 0 || n_vecs > 65535) return false;
-  if (!dev_aligned(in_dev, c->L) || !dev_aligned(out_dev, c->L) || log_m > dev_max_log_n(*c->f)) return false;
-  *total = (uint64_t)n_vecs << log_m;
-  return *total < ((uint64_t)1 << 39) && !ranges_overlap(in_dev, out_dev, *total * elem_bytes(c));
+  return order <= LCPCD_BITREV && dev_vectors_ok(c, in_dev, out_dev, log_m, n_vecs, total);
 }
 
 // K16 on `st` with the context's forward table of 2^log_m points (takes c->mu)

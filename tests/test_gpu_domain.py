@@ -127,6 +127,26 @@ def test_shift_table_cache():
             assert np.array_equal(got, DC.host_coset_fft(fid, form, sl, xs[log_n], log_n)), (log_n, form)
 
 
+@pytest.mark.parametrize("fid", (3, 0))
+def test_twiddle_and_shift_caches_interleaved(fid):
+    """plain and coset transforms alternated on one fresh encoder, six sizes in both directions: twelve twiddle keys through four
+    entries and twelve shift keys through eight, on the stamp the two caches share; then the first keys again.  Every result is the
+    host form's"""
+    L = O.limbs(fid)
+    enc = LigeroEncoding.new_from_dims(fid, 64, 128)        # a context of its own: two empty caches
+    sl = DC.shift_limbs(fid, FC.rng("caches", fid).randrange(2, FC.field(fid).p))
+    log_ns = (1, 2, 3, 4, 5, 6)
+    xs = {log_n: FC.mont(fid, FC.random_vector(fid, log_n, "caches")) for log_n in log_ns}
+    keys = [(log_n, form) for log_n in log_ns for form in ("fft_io", "ifft_oi")]
+    for log_n, form in keys + keys[:3]:
+        d_x = to_dev(xs[log_n])
+        got = to_host(enc.fft(d_x, form))
+        assert np.array_equal(got, FC.host_fft(fid, form, xs[log_n], log_n)), (log_n, form, "plain")
+        got = to_host(enc.coset_fft(d_x, sl, form))
+        assert np.array_equal(got, DC.host_coset_fft(fid, form, sl, xs[log_n], log_n)), (log_n, form, "coset")
+        assert got.shape == (1 << log_n, L)
+
+
 # ---- the low-degree extension ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fid", DC.FIELDS)
 def test_lde(fid):

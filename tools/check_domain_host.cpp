@@ -4,7 +4,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ilcpc_amd/csrc tools/check_domain_host.cpp \
 //       lcpc_amd/csrc/encoding.cpp lcpc_amd/csrc/host_crypto.cpp -lpthread -o check_domain_host && ./check_domain_host
 // Checks: coset forward then inverse is the identity in every pairing of forms; shift 1 is the plain transform; block c of the
-// bit-reversed extension is the FFT_IO coset transform with the shift s w_m^rev_b(c); the natural extension is its permutation.
+// bit-reversed extension is the FFT_IO coset transform with the shift s w_m^rev_b(c); the natural extension is its permutation; the
+// two-level tables of the device caches (two_level_table), with and without a factor, hold the powers they stand for.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -73,6 +74,34 @@ int main() {
             host_coset_fft(f, HF_FFT_IO, sc, blk.data(), log_n);
             CHECK(!memcmp(blk.data(), rev_out.data() + c * n * L, n * L * 8));
           }
+        }
+      }
+    }
+  }
+  // the two-level tables the device reads: a twiddle table (no factor) and a shift table (factor n^-1), each in a buffer of exactly
+  // n_lo + n_hi elements, against the plain powers: v^e = tab[e mod n_lo] * tab[n_lo + e / n_lo] (times the factor)
+  for (int fid = 0; fid < 4; fid++) {
+    const FieldDesc& f = *field_desc(fid);
+    const int L = f.L;
+    uint64_t s[MAXL];
+    rand_elem(f, s);
+    for (uint32_t log_n : {0u, 1u, 5u}) {
+      const uint32_t h = log_n / 2;
+      const size_t n = (size_t)1 << log_n, n_lo = (size_t)1 << h, n_hi = (size_t)1 << (log_n - h);
+      uint64_t w[MAXL], ni[MAXL];
+      root_of(f, log_n, false, w);
+      n_inverse(f, log_n, ni);
+      for (int shifted = 0; shifted < 2; shifted++) {
+        const uint64_t* v = shifted ? s : w;
+        std::vector<uint64_t> tab((n_lo + n_hi) * L), pw(n * L);
+        two_level_table(f, v, n_lo, n_hi, shifted ? ni : nullptr, tab.data());
+        powers(f, v, n, pw.data());
+        for (size_t e = 0; e < n; e++) {
+          uint64_t got[MAXL], want[MAXL];
+          h_mul(f, got, tab.data() + (e % n_lo) * L, tab.data() + (n_lo + e / n_lo) * L);
+          memcpy(want, pw.data() + e * L, 8 * L);
+          if (shifted) h_mul(f, want, want, ni);
+          CHECK(!memcmp(got, want, 8 * L));
         }
       }
     }
