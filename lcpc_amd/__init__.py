@@ -234,6 +234,40 @@ def divide_vanishing(field, vals, shift, log_n, order="natural"):
         raise LcpcError(rc)
     return out
 
+def _scan_op(op):
+    if op not in _lib.SCAN_OPS:
+        raise ValueError("op must be one of %s, not %r" % (sorted(_lib.SCAN_OPS), op))
+    return _lib.SCAN_OPS[op]
+
+
+def scan(field, x, op, exclusive=False, init=None):
+    """lcpcs_scan (include/lcpc_hip_scan.h): the prefix sums (op "sum") or products ("product") of the (n, L) elements x, starting
+    from init (one element; None: the identity) -- out[k] takes in x[0..k], or x[0..k-1] with exclusive=True.  Returns (out, total),
+    total the one element init (+) all of x.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(x, L).reshape(-1, L)
+    out, total = np.zeros_like(a), np.zeros(L, np.uint64)
+    c = None if init is None else _ptr(_shift(init, L))
+    rc = _lib.lib().lcpcs_scan(field, _scan_op(op), int(bool(exclusive)), _ptr(a), _ptr(out), a.shape[0], c, _ptr(total))
+    if rc:
+        raise LcpcError(rc)
+    return out, total
+
+
+def scan_ratio(field, num, den, op, exclusive=False, init=None):
+    """lcpcs_scan_ratio: lcpc_amd.scan of the terms num[k] / den[k], zero where den[k] is zero.  op "product" with exclusive=True is
+    the accumulator of a permutation argument (total is one for a valid one), op "sum" a log-derivative sum.  A host call."""
+    L = FIELD_LIMBS[field]
+    x, y = _elems(num, L).reshape(-1, L), _elems(den, L).reshape(-1, L)
+    if x.shape != y.shape:
+        raise ValueError("num and den hold the same number of elements")
+    out, total = np.zeros_like(x), np.zeros(L, np.uint64)
+    c = None if init is None else _ptr(_shift(init, L))
+    rc = _lib.lib().lcpcs_scan_ratio(field, _scan_op(op), int(bool(exclusive)), _ptr(x), _ptr(y), _ptr(out), x.shape[0], c, _ptr(total))
+    if rc:
+        raise LcpcError(rc)
+    return out, total
+
 
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
@@ -472,6 +506,47 @@ class _Encoding:
         self._check(_lib.lib().lcpcq_divide_vanishing_device(self._h, _ptr(_shift(shift, self.L)), _order(order), C.c_void_p(vals.data_ptr()),
                                                              _log_n(vals.shape[-2]), log_n, n_vecs, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
+
+    def _scan_ends(self, t, n_vecs, op, init, total, stream):
+        """what enc.scan and enc.scan_ratio share: the op, init and total as tensors of n_vecs elements, and the work buffer"""
+        import torch
+        for name, e in (("init", init), ("total", total)):
+            if e is not None and (not torch.is_tensor(e) or e.device != t.device or not e.is_contiguous() or e.dtype != t.dtype or
+                                  e.numel() != n_vecs * self.L):
+                raise ValueError("%s holds one element per vector, contiguous limbs of the input's dtype on the encoder's device" % name)
+        need = _lib.lib().lcpcs_scan_work_bytes(self._h, t.shape[-2], n_vecs)
+        work = torch.empty(max(need, 16) // 8, dtype=torch.int64, device=t.device)
+        if stream:                                   # freed on return, while the scan may still run on a stream torch does not know
+            work.record_stream(torch.cuda.ExternalStream(stream, device=t.device))
+        return _scan_op(op), None if init is None else C.c_void_p(init.data_ptr()), None if total is None else C.c_void_p(total.data_ptr()), work, need
+
+    def scan(self, x, op, exclusive=False, init=None, out=None, total=None, stream=None):
+        """lcpcs_scan_device (include/lcpc_hip_scan.h): the prefix sums (op "sum") or products ("product") of every vector of an (n, L)
+        or (n_vecs, n, L) tensor, each starting from its element of init (None: the identity); exclusive=True leaves init itself at
+        [0].  total, a tensor of n_vecs elements, receives init (+) the whole vector, and may be the init of the next call.  out=None
+        returns a new tensor, out=x runs in place.  The work buffer is a torch allocation.  Returns out, or (out, total) when total is
+        given.  Only enqueues on `stream`."""
+        stream = stream or 0
+        n_vecs = self._elem_tensor(x, "the scan")
+        out = self._out_tensor(x, out, x.shape)
+        o, c, tot, work, need = self._scan_ends(x, n_vecs, op, init, total, stream)
+        self._check(_lib.lib().lcpcs_scan_device(self._h, o, int(bool(exclusive)), C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), x.shape[-2],
+                                                 n_vecs, c, tot, C.c_void_p(work.data_ptr()), need, C.c_void_p(stream)))
+        return out if total is None else (out, total)
+
+    def scan_ratio(self, num, den, op, exclusive=False, init=None, out=None, total=None, stream=None):
+        """lcpcs_scan_ratio_device: enc.scan of the terms num[k] / den[k] (zero where den[k] is zero) of two tensors of one shape; out
+        may be num or den.  op "product" with exclusive=True is the accumulator of a permutation argument, whose total is one."""
+        stream = stream or 0
+        n_vecs = self._elem_tensor(num, "the scan")
+        if self._elem_tensor(den, "the scan") != n_vecs or num.shape != den.shape:
+            raise ValueError("num and den are tensors of one shape")
+        out = self._out_tensor(num, out, num.shape)
+        o, c, tot, work, need = self._scan_ends(num, n_vecs, op, init, total, stream)
+        self._check(_lib.lib().lcpcs_scan_ratio_device(self._h, o, int(bool(exclusive)), C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()),
+                                                       C.c_void_p(out.data_ptr()), num.shape[-2], n_vecs, c, tot, C.c_void_p(work.data_ptr()),
+                                                       need, C.c_void_p(stream)))
+        return out if total is None else (out, total)
 
     def __del__(self):
         try:

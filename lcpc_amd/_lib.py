@@ -200,6 +200,19 @@ QUOT_SYMBOLS = {
     "lcpcq_divide_vanishing_device": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp]),
 }
 
+# the scan extension (include/lcpc_hip_scan.h): again its own prefix, table and version
+SCAN_VERSION = 1
+SCAN_OPS = {"sum": 0, "product": 1}                                                               # lcpcs_op
+SCAN_MODES = {"inclusive": 0, "exclusive": 1}                                                     # lcpcs_mode
+SCAN_SYMBOLS = {
+    "lcpcs_version": (_i32, []),
+    "lcpcs_scan": (_i32, [_u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "lcpcs_scan_ratio": (_i32, [_u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "lcpcs_scan_work_bytes": (_u64, [_vp, _u64, _u32]),
+    "lcpcs_scan_device": (_i32, [_vp, _u32, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "lcpcs_scan_ratio_device": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -279,5 +292,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcq_version() != QUOT_VERSION:
             raise RuntimeError("lcpc_amd: quotient extension version mismatch")
+        for name, (res, args) in SCAN_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcs_version() != SCAN_VERSION:
+            raise RuntimeError("lcpc_amd: scan extension version mismatch")
         _lib = L
     return _lib

@@ -495,4 +495,35 @@ hipError_t launch_pointwise(int nl, int op, const uint32_t* a, const uint32_t* b
 hipError_t launch_domain_quotient(int nl, int kind, int bitrev, uint32_t log_m, uint32_t log_n, uint32_t n_vecs, const uint32_t* in, uint32_t* out,
                                   const uint32_t* tab_m, const uint32_t* shift, const uint32_t* z, const uint32_t* y, hipStream_t st);
 
+// K17 (scan.hip; include/lcpc_hip_scan.h): prefix sums and products of n_vecs vectors of n elements, the vectors n elements apart,
+// each scanned on its own.  out_v[k] = c_v (+) in_v[0] (+) ... (+) in_v[k] (SCAN_INCLUSIVE) or ... (+) in_v[k - 1] (SCAN_EXCLUSIVE),
+// total[v] = c_v (+) all of in_v, with c_v = init[v], or the identity where init is NULL; total may be NULL.  `one` is R mod p as nl
+// words in HOST memory (a kernel argument).  A workgroup owns a tile of scan_tile(nl) consecutive elements, scan_lane_elems(nl)
+// consecutive ones per lane.  A vector of one tile is ONE launch (K17c seeded with c_v; work is not touched).  Otherwise K17a writes
+// the tile totals to work[v * tiles + t]; K17b turns them into the tiles' exclusive prefixes in place and writes total -- it is this
+// very scan, exclusive and in place, of n_vecs runs of `tiles` elements, with the rest of `work` as its workspace: one launch while
+// tiles <= scan_mid_chunk(nl), three up to its square --; K17c applies them.  Three launches up to scan_tile(nl)^2 elements per
+// vector, five beyond.  No workgroup waits for another.  in == out runs in place (both modes); *n_launches (may be null) receives
+// the number of kernels.  work has room for work_elems >= scan_work_elems(nl, n, n_vecs) elements: the totals of every level, the
+// last (one per vector) included.  Inputs fully reduced; every stored element then is.
+// hipErrorInvalidValue before any launch: a bad nl, op or mode, n == 0, n_vecs == 0 or > 65535, n * n_vecs >= 2^39, a NULL in, out,
+// one or work, a misaligned pointer, too small a work_elems, in and out overlapping without being the same, init, total or work
+// meeting another buffer or each other; and a vector of SCAN_MAX_TILES tiles or more (2^35 elements, 2^36 for nl <= 4 -- more than
+// any device holds): the tiles of a vector are the grid's x dimension, which times the 256 lanes must stay below 2^32
+enum : int { SCAN_SUM = 0, SCAN_PRODUCT = 1 };
+enum : int { SCAN_INCLUSIVE = 0, SCAN_EXCLUSIVE = 1 };
+constexpr uint32_t SCAN_LANES = 256;
+constexpr uint64_t SCAN_MAX_TILES = (uint64_t)1 << 24;
+constexpr uint32_t scan_lane_elems(int nl) { return nl >= 6 ? 8 : 16; }
+constexpr uint32_t scan_tile(int nl) { return SCAN_LANES * scan_lane_elems(nl); }
+constexpr uint32_t scan_mid_chunk(int nl) { return scan_tile(nl); }
+inline uint64_t scan_tiles(int nl, uint64_t n) { return (n + scan_tile(nl) - 1) / scan_tile(nl); }
+inline uint64_t scan_work_elems(int nl, uint64_t n, uint32_t n_vecs) {
+  uint64_t t = n, sum = 0;
+  do { t = scan_tiles(nl, t); sum += t; } while (t > 1);
+  return sum * n_vecs;
+}
+hipError_t launch_scan(int nl, int op, int mode, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t n_vecs, const uint32_t* init,
+                       uint32_t* total, const uint32_t* one, uint32_t* work, uint64_t work_elems, hipStream_t st, uint32_t* n_launches);
+
 }  // namespace lcpc
