@@ -269,6 +269,63 @@ def scan_ratio(field, num, den, op, exclusive=False, init=None):
     return out, total
 
 
+def _sc_order(order):
+    if order not in _lib.SUMCHECK_ORDERS:
+        raise ValueError("order must be one of %s, not %r" % (sorted(_lib.SUMCHECK_ORDERS), order))
+    return _lib.SUMCHECK_ORDERS[order]
+
+
+def _sc_terms(terms, L):
+    """a list of (coeff_or_None, [table indices]) -> (lcpcm_term array, n_terms, the coefficients as (n_terms, L) limbs or None when
+    every one is None, the degree).  A coefficient left None beside given ones has no limbs to stand for it: give all or none"""
+    terms = list(terms)
+    if not 1 <= len(terms) <= _lib.SUMCHECK_MAX_TERMS:
+        raise ValueError("a composition has 1 .. %d terms" % _lib.SUMCHECK_MAX_TERMS)
+    arr = (_lib.LcpcmTerm * len(terms))()
+    coeffs = []
+    for m, (c, idx) in enumerate(terms):
+        idx = list(idx)
+        if not 1 <= len(idx) <= _lib.SUMCHECK_MAX_FACTORS:
+            raise ValueError("a term has 1 .. %d factors" % _lib.SUMCHECK_MAX_FACTORS)
+        arr[m].n_factors = len(idx)
+        for k, t in enumerate(idx):
+            arr[m].table[k] = t
+        coeffs.append(c)
+    given = [c is not None for c in coeffs]
+    if any(given) and not all(given):
+        raise ValueError("give a coefficient for every term or for none")
+    cs = np.stack([_shift(c, L) for c in coeffs]) if all(given) else None
+    return arr, len(terms), cs, max(t.n_factors for t in arr)
+
+
+def sumcheck_bind(field, table, r, order="low"):
+    """lcpcm_bind (include/lcpc_hip_sumcheck.h): binds one variable of the (n, L) table to r -- out[i] = lo + r (hi - lo) with
+    (lo, hi) = (t[2i], t[2i+1]) (order "low") or (t[i], t[i + n/2]) ("high").  Returns the (n / 2, L) table.  A host call: no device."""
+    L = FIELD_LIMBS[field]
+    a = _elems(table, L).reshape(-1, L)
+    out = np.zeros((a.shape[0] // 2, L), np.uint64)
+    rc = _lib.lib().lcpcm_bind(field, _sc_order(order), _ptr(a), _ptr(out), a.shape[0], _ptr(_shift(r, L)))
+    if rc:
+        raise LcpcError(rc)
+    return out
+
+
+def sumcheck_round(field, tables, terms, order="low"):
+    """lcpcm_round: the round polynomial of sum_i sum_m c_m prod_k tables[idx_mk] at t = 0 .. d, as (d + 1, L) limbs.  tables: a list of
+    (n, L) tables of one length; terms: a list of (coeff_or_None, [table indices]).  A host call."""
+    L = FIELD_LIMBS[field]
+    tabs = [_elems(t, L).reshape(-1, L) for t in tables]
+    if not tabs or any(t.shape != tabs[0].shape for t in tabs):
+        raise ValueError("the tables hold one number of elements")
+    arr, n_terms, cs, d = _sc_terms(terms, L)
+    ptrs = (C.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
+    evals = np.zeros((d + 1, L), np.uint64)
+    rc = _lib.lib().lcpcm_round(field, _sc_order(order), ptrs, len(tabs), arr, n_terms, None if cs is None else _ptr(cs), tabs[0].shape[0], _ptr(evals))
+    if rc:
+        raise LcpcError(rc)
+    return evals
+
+
 class Transcript:
     """merlin::Transcript (the `tr: &mut Transcript` of prove/verify)."""
 
@@ -547,6 +604,87 @@ class _Encoding:
                                                        C.c_void_p(out.data_ptr()), num.shape[-2], n_vecs, c, tot, C.c_void_p(work.data_ptr()),
                                                        need, C.c_void_p(stream)))
         return out if total is None else (out, total)
+
+    def _sc_tables(self, tables, what):
+        """the tables of a sumcheck call: a list of (n, L) tensors of one length -> (pointer array, n)"""
+        tables = list(tables)
+        if not tables:
+            raise ValueError("%s takes at least one table" % what)
+        for t in tables:
+            if self._elem_tensor(t, what) != 1 or t.dim() != 2 or t.shape != tables[0].shape or t.dtype != tables[0].dtype:
+                raise ValueError("%s takes (n, L) tables of one length and dtype" % what)
+        return (C.c_void_p * len(tables))(*[t.data_ptr() for t in tables]), tables[0].shape[0]
+
+    def _sc_out(self, tables, out):
+        """out=None: new tensors of half the length; otherwise a list of as many tensors; out[j] is tables[j] binds in place -- the
+        result is then the first half of that tensor, which is what is returned for it"""
+        import torch
+        h = tables[0].shape[0] // 2
+        if out is None:
+            outs = [torch.empty((h, self.L), dtype=t.dtype, device=t.device) for t in tables]
+            return outs, outs
+        out = list(out)
+        if len(out) != len(tables):
+            raise ValueError("out holds one tensor per table")
+        ret = []
+        for o, t in zip(out, tables):
+            if o is t:
+                ret.append(t[:h])
+                continue
+            if not torch.is_tensor(o) or tuple(o.shape) != (h, self.L) or o.dtype != t.dtype or o.device != t.device or not o.is_contiguous():
+                raise ValueError("an output is the table itself or a contiguous (n / 2, L) tensor of its dtype and device")
+            ret.append(o)
+        return out, ret
+
+    def _sc_work(self, n, n_terms, like, stream):
+        import torch
+        need = _lib.lib().lcpcm_round_work_bytes(self._h, n, n_terms)
+        work = torch.empty(max(need, 16) // 8, dtype=torch.int64, device=like.device)
+        if stream:                                   # freed on return, while the round may still run on a stream torch does not know
+            work.record_stream(torch.cuda.ExternalStream(stream, device=like.device))
+        return work, need
+
+    def sumcheck_bind(self, tables, r, order="low", out=None, stream=None):
+        """lcpcm_bind_device (include/lcpc_hip_sumcheck.h): binds one variable of every (n, L) tensor of the list `tables` to r (one
+        element of host limbs) in one launch.  out=None returns new (n / 2, L) tensors, out=tables binds in place (order "high" only)
+        and returns views of the first halves.  Only enqueues on `stream`."""
+        stream = stream or 0
+        tables = list(tables)
+        ins, n = self._sc_tables(tables, "the bind")
+        outs, ret = self._sc_out(tables, out)
+        op = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        self._check(_lib.lib().lcpcm_bind_device(self._h, _sc_order(order), ins, op, len(tables), n, _ptr(_shift(r, self.L)), C.c_void_p(stream)))
+        return ret
+
+    def sumcheck_round(self, tables, terms, order="low", evals=None, stream=None):
+        """lcpcm_round_device: the round polynomial of the composition `terms` (a list of (coeff_or_None, [table indices])) over the
+        tensors `tables` at t = 0 .. d, as a (d + 1, L) tensor (evals=None: a new one).  The work buffer is a torch allocation.  Only
+        enqueues on `stream`."""
+        stream = stream or 0
+        tables = list(tables)
+        ins, n = self._sc_tables(tables, "the round")
+        arr, n_terms, cs, d = _sc_terms(terms, self.L)
+        evals = self._out_tensor(tables[0], evals, (d + 1, self.L))
+        work, need = self._sc_work(n, n_terms, tables[0], stream)
+        self._check(_lib.lib().lcpcm_round_device(self._h, _sc_order(order), ins, len(tables), arr, n_terms, None if cs is None else _ptr(cs), n,
+                                                  C.c_void_p(evals.data_ptr()), C.c_void_p(work.data_ptr()), need, C.c_void_p(stream)))
+        return evals
+
+    def sumcheck_bind_round(self, tables, terms, r, order="low", out=None, evals=None, stream=None):
+        """lcpcm_bind_round_device: enc.sumcheck_bind by r followed by enc.sumcheck_round on the bound tables, in one pass over the
+        tables (n >= 4).  Returns (bound tables, evals), byte for byte those of the two calls."""
+        stream = stream or 0
+        tables = list(tables)
+        ins, n = self._sc_tables(tables, "the bind")
+        outs, ret = self._sc_out(tables, out)
+        op = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        arr, n_terms, cs, d = _sc_terms(terms, self.L)
+        evals = self._out_tensor(tables[0], evals, (d + 1, self.L))
+        work, need = self._sc_work(n, n_terms, tables[0], stream)
+        self._check(_lib.lib().lcpcm_bind_round_device(self._h, _sc_order(order), ins, op, len(tables), arr, n_terms, None if cs is None else _ptr(cs), n,
+                                                       _ptr(_shift(r, self.L)), C.c_void_p(evals.data_ptr()), C.c_void_p(work.data_ptr()), need,
+                                                       C.c_void_p(stream)))
+        return ret, evals
 
     def __del__(self):
         try:

@@ -213,6 +213,26 @@ SCAN_SYMBOLS = {
     "lcpcs_scan_ratio_device": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
 }
 
+# the sumcheck extension (include/lcpc_hip_sumcheck.h): again its own prefix, table and version
+SUMCHECK_VERSION = 1
+SUMCHECK_ORDERS = {"low": 0, "high": 1}                                                           # lcpcm_order
+SUMCHECK_MAX_TABLES, SUMCHECK_MAX_TERMS, SUMCHECK_MAX_FACTORS = 8, 4, 4
+
+
+class LcpcmTerm(C.Structure):
+    _fields_ = [("n_factors", C.c_uint32), ("table", C.c_uint32 * SUMCHECK_MAX_FACTORS)]
+
+
+SUMCHECK_SYMBOLS = {
+    "lcpcm_version": (_i32, []),
+    "lcpcm_bind": (_i32, [_u32, _u32, _vp, _vp, _u64, _vp]),
+    "lcpcm_round": (_i32, [_u32, _u32, _vp, _u32, _vp, _u32, _vp, _u64, _vp]),
+    "lcpcm_round_work_bytes": (_u64, [_vp, _u64, _u32]),
+    "lcpcm_bind_device": (_i32, [_vp, _u32, _vp, _vp, _u32, _u64, _vp, _vp]),
+    "lcpcm_round_device": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "lcpcm_bind_round_device": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+}
+
 
 def build(force=False):
     """compile lcpc_amd/lib/liblcpc_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -298,5 +318,11 @@ def lib():
             fn.argtypes = args
         if L.lcpcs_version() != SCAN_VERSION:
             raise RuntimeError("lcpc_amd: scan extension version mismatch")
+        for name, (res, args) in SUMCHECK_SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.lcpcm_version() != SUMCHECK_VERSION:
+            raise RuntimeError("lcpc_amd: sumcheck extension version mismatch")
         _lib = L
     return _lib

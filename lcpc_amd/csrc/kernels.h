@@ -526,4 +526,111 @@ inline uint64_t scan_work_elems(int nl, uint64_t n, uint32_t n_vecs) {
 hipError_t launch_scan(int nl, int op, int mode, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t n_vecs, const uint32_t* init,
                        uint32_t* total, const uint32_t* one, uint32_t* work, uint64_t work_elems, hipStream_t st, uint32_t* n_launches);
 
+// K18 / K19 (sumcheck.hip; include/lcpc_hip_sumcheck.h): the round sums of a composition of tables and the binding of a variable.  A
+// table is n = 2^v elements; pair i < n / 2 is (t[2i], t[2i+1]) (SUMCHECK_LOW_FIRST) or (t[i], t[i + n/2]) (SUMCHECK_HIGH_FIRST), and
+// ext(t, i, x) = lo + x (hi - lo).  `in`, `out`, `tables` are HOST arrays of n_tables device pointers; r, coeffs ([n_terms][nl], null: all
+// one) and one (R mod p) are nl-word elements in HOST memory that travel as kernel arguments.
+// launch_sumcheck_bind (K19): out[j][i] = ext(in[j], i, r), i < n / 2, one launch, the table as the grid's second dimension.
+// launch_sumcheck_round (K18): evals[x] = sum_i sum_m c_m prod_k ext(tables[terms[m].table[k]], i, x), x = 0 .. d = max n_factors.  A
+// workgroup of SUMCHECK_LANES lanes takes tiles of sumcheck_tile_pairs pairs in a grid-stride loop over sumcheck_groups(pairs,
+// max_groups) workgroups and leaves its sums, one per term and x, in work[(group * n_terms + m) * (d + 1) + x]; a second launch of d + 1
+// workgroups adds them and applies c_m.  One workgroup does both itself: one launch, work untouched.
+// launch_sumcheck_bind_round (K18f), n >= 4: lane i < n / 4 binds its two pairs of every table, stores them, and adds the round of the
+// BOUND tables (n / 2 elements, pair i) to its sums: the stores of the bind and the evals of the round on its output, bit for bit.
+// *n_launches (may be null) receives the kernels launched.  Inputs fully reduced; every stored element then is.  No workgroup waits
+// for another.
+// hipErrorInvalidValue before any launch, for everything sumcheck_job_ok refuses: a bad nl or order; n no power of two, below 2 (4 for
+// the fused form) or >= 2^39; n_tables, n_terms, an n_factors of 0 or above its limit, a table index >= n_tables; a NULL or misaligned
+// pointer (coeffs may be null); max_groups == 0; work_elems < sumcheck_work_elems(pairs, n_terms, max_groups); an output that meets an
+// input without BEING it under SUMCHECK_HIGH_FIRST with the same table number (and that input listed once); outputs meeting each
+// other; evals or work meeting anything else.
+enum : int { SUMCHECK_LOW_FIRST = 0, SUMCHECK_HIGH_FIRST = 1 };
+constexpr uint32_t SUMCHECK_MAX_TABLES = 8, SUMCHECK_MAX_TERMS = 4, SUMCHECK_MAX_FACTORS = 4;
+constexpr uint32_t SUMCHECK_LANES = 256;
+constexpr uint32_t SUMCHECK_GROUPS = 1024;          // the product's max_groups: four workgroups for each of 256 compute units
+struct SumcheckTerm { uint32_t n_factors; uint32_t table[SUMCHECK_MAX_FACTORS]; };
+constexpr uint32_t sumcheck_tile_pairs(int) { return SUMCHECK_LANES; }      // one pair per lane and stride, every field
+inline uint32_t sumcheck_groups(uint64_t pairs, uint32_t max_groups) {
+  const uint64_t tiles = (pairs + SUMCHECK_LANES - 1) / SUMCHECK_LANES;
+  return (uint32_t)(tiles < max_groups ? tiles : max_groups);
+}
+// (every workgroup has room for MAX_FACTORS + 1 sums per term, whatever the degree)
+inline uint64_t sumcheck_work_elems(uint64_t pairs, uint32_t n_terms, uint32_t max_groups) {
+  return (uint64_t)sumcheck_groups(pairs, max_groups) * n_terms * (SUMCHECK_MAX_FACTORS + 1);
+}
+// the degree of a composition, 0 where it is refused
+inline uint32_t sumcheck_degree(uint32_t n_tables, const SumcheckTerm* terms, uint32_t n_terms) {
+  if (n_tables == 0 || n_tables > SUMCHECK_MAX_TABLES || !terms || n_terms == 0 || n_terms > SUMCHECK_MAX_TERMS) return 0;
+  uint32_t d = 0;
+  for (uint32_t m = 0; m < n_terms; m++) {
+    if (terms[m].n_factors == 0 || terms[m].n_factors > SUMCHECK_MAX_FACTORS) return 0;
+    for (uint32_t k = 0; k < terms[m].n_factors; k++)
+      if (terms[m].table[k] >= n_tables) return 0;
+    if (terms[m].n_factors > d) d = terms[m].n_factors;
+  }
+  return d;
+}
+// one call of the three launchers: bind (out used), round (terms, evals, work used) or both (the fused form).  A pure host function
+// that reads none of the buffers: the launchers and the entry points of sumcheck.cpp settle their refusals with it
+struct SumcheckJob {
+  int nl, order;
+  bool bind, round;
+  const uint32_t* const* in;
+  uint32_t* const* out;
+  uint32_t n_tables;
+  const SumcheckTerm* terms;
+  uint32_t n_terms;
+  uint64_t n;
+  const uint32_t* evals;
+  const uint32_t* work;
+  uint64_t work_elems;
+  uint32_t max_groups;
+};
+inline uint64_t sumcheck_pairs(const SumcheckJob& j) { return j.bind && j.round ? j.n / 4 : j.n / 2; }
+inline bool sumcheck_job_ok(const SumcheckJob& j) {
+  auto meet = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+  };
+  if (!nl_ok(j.nl) || (j.order != SUMCHECK_LOW_FIRST && j.order != SUMCHECK_HIGH_FIRST) || !j.in) return false;
+  if (j.n_tables == 0 || j.n_tables > SUMCHECK_MAX_TABLES) return false;
+  if (j.n < (j.bind && j.round ? 4u : 2u) || j.n >= ((uint64_t)1 << 39) || (j.n & (j.n - 1))) return false;
+  const uint64_t eb = (uint64_t)j.nl * 4, in_b = j.n * eb, out_b = in_b / 2;
+  for (uint32_t t = 0; t < j.n_tables; t++)
+    if (!j.in[t] || !elem_aligned(j.in[t], j.nl)) return false;
+  uint64_t ev_b = 0, work_b = 0;
+  if (j.round) {
+    const uint32_t d = sumcheck_degree(j.n_tables, j.terms, j.n_terms);
+    if (d == 0 || !j.evals || !j.work || !elem_aligned(j.evals, j.nl) || !elem_aligned(j.work, j.nl) || j.max_groups == 0) return false;
+    const uint64_t need = sumcheck_work_elems(sumcheck_pairs(j), j.n_terms, j.max_groups);
+    if (j.work_elems < need) return false;
+    ev_b = (d + 1) * eb; work_b = need * eb;
+    if (meet(j.evals, ev_b, j.work, work_b)) return false;
+    for (uint32_t t = 0; t < j.n_tables; t++)
+      if (meet(j.evals, ev_b, j.in[t], in_b) || meet(j.work, work_b, j.in[t], in_b)) return false;
+  }
+  if (j.bind) {
+    if (!j.out) return false;
+    for (uint32_t t = 0; t < j.n_tables; t++) {
+      if (!j.out[t] || !elem_aligned(j.out[t], j.nl)) return false;
+      if (j.round && (meet(j.evals, ev_b, j.out[t], out_b) || meet(j.work, work_b, j.out[t], out_b))) return false;
+      for (uint32_t u = 0; u < j.n_tables; u++) {
+        if (u != t && meet(j.out[t], out_b, j.out[u], out_b)) return false;
+        if (!meet(j.out[t], out_b, j.in[u], in_b)) continue;
+        if (j.order != SUMCHECK_HIGH_FIRST || u != t || j.out[t] != j.in[t]) return false;     // in place: this table's own input only
+      }
+    }
+  }
+  return true;
+}
+hipError_t launch_sumcheck_bind(int nl, int order, const uint32_t* const* in, uint32_t* const* out, uint32_t n_tables, uint64_t n,
+                                const uint32_t* r, hipStream_t st);
+hipError_t launch_sumcheck_round(int nl, int order, const uint32_t* const* tables, uint32_t n_tables, const SumcheckTerm* terms, uint32_t n_terms,
+                                 const uint32_t* coeffs, const uint32_t* one, uint64_t n, uint32_t* evals, uint32_t* work, uint64_t work_elems,
+                                 uint32_t max_groups, hipStream_t st, uint32_t* n_launches);
+hipError_t launch_sumcheck_bind_round(int nl, int order, const uint32_t* const* in, uint32_t* const* out, uint32_t n_tables,
+                                      const SumcheckTerm* terms, uint32_t n_terms, const uint32_t* coeffs, const uint32_t* one, uint64_t n,
+                                      const uint32_t* r, uint32_t* evals, uint32_t* work, uint64_t work_elems, uint32_t max_groups,
+                                      hipStream_t st, uint32_t* n_launches);
+
 }  // namespace lcpc
