@@ -9,22 +9,14 @@ import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_fe_harness.so")
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+
+LIB_PATH = K.lib_path("fe")
 NL = {0: 2, 1: 4, 2: 6, 3: 8}
 SENTINEL = 0xA5C3F00D
 WT_STRIDE = 96
 OP_ADD, OP_SUB, OP_MUL, OP_CANON = 0, 1, 2, 3
-
-
-class BadArgs(ValueError):
-    pass
-
-
-class HipError(RuntimeError):
-    def __init__(self, what, code):
-        RuntimeError.__init__(self, "%s: hipError_t %d" % (what, code))
-        self.code = code
 
 
 _vp, _u64, _u32, _i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -46,39 +38,12 @@ SYMBOLS = {
     "feh_canon_r29": [_vp, _vp, _u32, _u32],
     "feh_host_op": [_i32, _i32, _vp, _vp, _vp, _u64],
 }
-_lib = None
-
-
 def available():
     return os.path.exists(LIB_PATH)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not available():
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
-
-
-def _check(what, rc):
-    if rc == -1:
-        raise BadArgs(what)
-    if rc:
-        raise HipError(what, rc)
+    return K.load("fe", SYMBOLS)
 
 
 # ---- Python ints <-> device words ---------------------------------------------------------------------------------------------------

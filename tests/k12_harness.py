@@ -2,21 +2,19 @@
 whole-vector transform (K12 / K13, launch_fft of lcpc_amd/csrc/kernels.h) with a tile size and a twiddle table of the test's choice,
 the product's own stage split (fft_plan), and the launcher's refusals.  The two-level table is built here in Python bignum from the
 layout kernels.h documents, so the kernels are held to a table the product's host code had no part in.  Errors as in
-tests/k2_harness.py, whose classes these are."""
+tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import fft_cases as FC
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k12_harness.so")
+LIB_PATH = K.lib_path("k12")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 FORMS = FC.FORMS                                    # the launcher's form numbers are lcpcf_form's
-CANARY = FC.CANARY
-PAD = 8                                             # canary elements in front of and behind an output
+CANARY, PAD = K.CANARY, K.PAD                      # the canary elements around an output: harness_kit.padded
 
 _vp, _u64, _u32, _i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SYMBOLS = {
@@ -29,24 +27,10 @@ SYMBOLS = {
     "k12h_fft": (_i32, [_i32, _i32, _u32, _u32, _u32, _vp, _vp, _u64, _u64, _i32, _vp, _u64, _vp, _vp]),
     "k12h_refusal": (_i32, [_i32, _i32, _u32, _u32, _u32, _u32, _u32]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("k12", SYMBOLS)
 
 
 def max_log_tile():
@@ -87,14 +71,14 @@ def run(fid, form, log_n, log_tile, x, in_place=False):
     inverse = form.startswith("ifft")
     tab = table(fid, log_n, inverse)
     n_inv = FC.mont(fid, [pow(1 << log_n, -1, F.p)])
-    buf = np.full((PAD + x.shape[0] * x.shape[1] + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded(x.shape[0] * x.shape[1], F.L)
     keep = x.copy()
     launches = C.c_uint32(0xFFFFFFFF)
     _check("k12h_fft", lib().k12h_fft(2 * F.L, FORMS.index(form), log_n, log_tile, n_vecs, _ptr(x), _ptr(buf), buf.size * 2, PAD * F.L * 2,
                                       int(in_place), _ptr(tab), tab.shape[0], _ptr(n_inv), C.byref(launches)))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
+    out = K.inner(buf)
     assert (x == keep).all()
-    return buf[PAD:-PAD].reshape(x.shape).copy(), launches.value
+    return out.reshape(x.shape).copy(), launches.value
 
 
 def refusal(nl, form, log_n, log_tile, n_vecs, null_mask=0, misalign=0):

@@ -1,22 +1,20 @@
 """ctypes side of tests/native/k14_harness.cpp (lcpc_amd/lib/liblcpc_k14_harness.so, built by lcpc_amd/csrc/Makefile): the coset
 transform and the extension (K14, launch_coset_fft / launch_extend of lcpc_amd/csrc/kernels.h) with a tile size and with twiddle and
 shift tables of the test's choice, and the launchers' refusals.  The tables are built here in Python bignum from the layout kernels.h
-documents, so the kernels are held to tables the product's host code had no part in.  Errors as in tests/k2_harness.py."""
+documents, so the kernels are held to tables the product's host code had no part in.  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import fft_cases as FC
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 import k12_harness as K12
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k14_harness.so")
+LIB_PATH = K.lib_path("k14")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 FORMS = FC.FORMS
-CANARY = FC.CANARY
-PAD = 8                                             # canary elements in front of and behind an output
+CANARY, PAD = K.CANARY, K.PAD                      # the canary elements around an output: harness_kit.padded
 
 _vp, _u64, _u32, _i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SYMBOLS = {
@@ -28,24 +26,10 @@ SYMBOLS = {
     "k14h_coset_refusal": (_i32, [_i32, _i32, _u32, _u32, _u32, _u32, _u32, _i32]),
     "k14h_extend_refusal": (_i32, [_i32, _u64, _u32, _i32, _u32, _u32, _u32, _u32, _i32]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("k14", SYMBOLS)
 
 
 def ext_log_n(n_coeffs, log_m):
@@ -77,14 +61,14 @@ def run_coset(fid, form, log_n, log_tile, x, s, in_place=False):
     x = np.ascontiguousarray(x, np.uint64).reshape(-1, 1 << log_n, F.L)
     inverse = form.startswith("ifft")
     tab, stab = K12.table(fid, log_n, inverse), shift_table(fid, s, log_n, inverse)
-    buf = np.full((PAD + x.shape[0] * x.shape[1] + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded(x.shape[0] * x.shape[1], F.L)
     keep = x.copy()
     launches = C.c_uint32(0xFFFFFFFF)
     _check("k14h_coset_fft", lib().k14h_coset_fft(2 * F.L, FORMS.index(form), log_n, log_tile, x.shape[0], _ptr(x), _ptr(buf), buf.size * 2,
                                                   PAD * F.L * 2, int(in_place), _ptr(tab), _ptr(stab), tab.shape[0], C.byref(launches)))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
+    out = K.inner(buf)
     assert (x == keep).all(), "the input of the transform was written"
-    return buf[PAD:-PAD].reshape(x.shape).copy(), launches.value
+    return out.reshape(x.shape).copy(), launches.value
 
 
 def run_extend(fid, coeffs, n_coeffs, log_m, order, log_tile, s):
@@ -99,14 +83,14 @@ def run_extend(fid, coeffs, n_coeffs, log_m, order, log_tile, s):
     keep = flat.copy()
     log_n = ext_log_n(n_coeffs, log_m)
     tab, stab = K12.table(fid, log_m, False), shift_table(fid, s, log_n, False)
-    buf = np.full((PAD + (n_vecs << log_m) + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded((n_vecs << log_m), F.L)
     launches = C.c_uint32(0xFFFFFFFF)
     _check("k14h_extend", lib().k14h_extend(2 * F.L, n_coeffs, log_m, int(order == "natural"), log_tile, n_vecs, _ptr(flat), flat.size * 2,
                                             _ptr(buf), buf.size * 2, PAD * F.L * 2, _ptr(tab), tab.shape[0], _ptr(stab), stab.shape[0],
                                             C.byref(launches)))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
+    out = K.inner(buf)
     assert (flat == keep).all(), "the coefficients were written"
-    return buf[PAD:-PAD].reshape(n_vecs, 1 << log_m, F.L).copy(), launches.value
+    return out.reshape(n_vecs, 1 << log_m, F.L).copy(), launches.value
 
 
 def coset_refusal(nl, form, log_n, log_tile, n_vecs, null_mask=0, misalign=0, overlap=0):

@@ -1,21 +1,19 @@
 """ctypes side of tests/native/k15_harness.cpp (lcpc_amd/lib/liblcpc_k15_harness.so, built by lcpc_amd/csrc/Makefile): the inverse,
 pointwise and domain-quotient launchers (K15 / K16, launch_batch_inverse / launch_pointwise / launch_domain_quotient of
 lcpc_amd/csrc/kernels.h) with canaries around the output, a twiddle table built here in Python bignum (tests/k12_harness.py's
-builder), and the launchers' refusals.  Errors as in tests/k2_harness.py."""
+builder), and the launchers' refusals.  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import fft_cases as FC
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 import k12_harness as K12
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k15_harness.so")
+LIB_PATH = K.lib_path("k15")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
-CANARY = FC.CANARY
-PAD = 8                                             # canary elements in front of and behind an output
+CANARY, PAD = K.CANARY, K.PAD                      # the canary elements around an output: harness_kit.padded
 OPS = {"inverse": -1, "add": 0, "sub": 1, "mul": 2, "div": 3}
 KINDS = {"linear": 0, "vanishing": 1}
 
@@ -29,24 +27,10 @@ SYMBOLS = {
     "k15h_pointwise_refusal": (_i32, [_i32, _i32, _u64, _u32, _u32, _i32]),
     "k15h_quotient_refusal": (_i32, [_i32, _i32, _u32, _u32, _u32, _u32, _u32, _i32]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("k15", SYMBOLS)
 
 
 def tile(nl):
@@ -66,12 +50,12 @@ def run_pointwise(fid, op, a, b, in_place=0):
     b = np.ascontiguousarray(b, np.uint64).reshape(-1, F.L)
     a = None if a is None else np.ascontiguousarray(a, np.uint64).reshape(-1, F.L)
     keep_a, keep_b = None if a is None else a.copy(), b.copy()
-    buf = np.full((PAD + b.shape[0] + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded(b.shape[0], F.L)
     _check("k15h_pointwise", lib().k15h_pointwise(2 * F.L, OPS[op], None if a is None else _ptr(a), _ptr(b), b.shape[0], _ptr(buf), buf.size * 2,
                                                   PAD * F.L * 2, in_place))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
+    out = K.inner(buf)
     assert (b == keep_b).all() and (a is None or (a == keep_a).all()), "an operand was written"
-    return buf[PAD:-PAD].copy()
+    return out.copy()
 
 
 def run_quotient(fid, kind, order, log_m, log_n, vals, s, z=0, y=(), in_place=False):
@@ -86,13 +70,13 @@ def run_quotient(fid, kind, order, log_m, log_n, vals, s, z=0, y=(), in_place=Fa
     else:
         sl = None if s is None else FC.mont(fid, [s])
     zl, yl = FC.mont(fid, [z]), FC.mont(fid, list(y) or [0])
-    buf = np.full((PAD + v.shape[0] * v.shape[1] + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded(v.shape[0] * v.shape[1], F.L)
     _check("k15h_domain_quotient", lib().k15h_domain_quotient(2 * F.L, KINDS[kind], int(order == "bitrev"), log_m, log_n, v.shape[0], _ptr(v), _ptr(buf),
                                                               buf.size * 2, PAD * F.L * 2, int(in_place), _ptr(tab), tab.shape[0],
                                                               None if sl is None else _ptr(sl), _ptr(zl), _ptr(yl)))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
+    out = K.inner(buf)
     assert (v == keep).all(), "the input was written"
-    return buf[PAD:-PAD].reshape(v.shape).copy()
+    return out.reshape(v.shape).copy()
 
 
 def pointwise_refusal(nl, op, n, null_mask=0, misalign=0, overlap=0):

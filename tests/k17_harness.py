@@ -1,19 +1,17 @@
 """ctypes side of tests/native/k17_harness.cpp (lcpc_amd/lib/liblcpc_k17_harness.so, built by lcpc_amd/csrc/Makefile): the scan
 launcher (K17, launch_scan of lcpc_amd/csrc/kernels.h) with canaries around the output, the totals and the workspace, K17b alone on
-a caller's tile totals, and the launcher's refusals.  Errors as in tests/k2_harness.py."""
+a caller's tile totals, and the launcher's refusals.  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import fft_cases as FC
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k17_harness.so")
+LIB_PATH = K.lib_path("k17")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
-CANARY = FC.CANARY
-PAD = 8                                             # canary elements in front of and behind the output, the totals and the workspace
+CANARY, PAD = K.CANARY, K.PAD                      # the canary elements around an output: harness_kit.padded
 OPS = {"sum": 0, "product": 1}
 MODES = {"inclusive": 0, "exclusive": 1}
 
@@ -29,24 +27,10 @@ SYMBOLS = {
     "k17h_scan_totals": (_i32, [_i32, _i32, _vp, _u64, _u32, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64]),
     "k17h_scan_refusal": (_i32, [_i32, _i32, _i32, _u64, _u32, _u32, _u32, _i32, _i32]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("k17", SYMBOLS)
 
 
 def tile(nl):
@@ -80,9 +64,9 @@ def run_scan(fid, op, mode, x, init=None, in_place=False, totals_only=False):
     keep = v.copy()
     one = FC.mont(fid, [1])
     ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(n_vecs, F.L)
-    buf = np.full((PAD + n_vecs * n + PAD, F.L), CANARY, np.uint64)
-    tot = np.full((PAD + n_vecs + PAD, F.L), CANARY, np.uint64)
-    work = np.full((PAD + work_elems(nl, n, n_vecs) + PAD, F.L), CANARY, np.uint64)
+    buf = K.padded(n_vecs * n, F.L)
+    tot = K.padded(n_vecs, F.L)
+    work = K.padded(work_elems(nl, n, n_vecs), F.L)
     launches = C.c_uint32(0)
     off = PAD * nl
     if totals_only:
@@ -92,11 +76,10 @@ def run_scan(fid, op, mode, x, init=None, in_place=False, totals_only=False):
         _check("k17h_scan", lib().k17h_scan(nl, OPS[op], MODES[mode], _ptr(v), n, n_vecs, _ptr(buf), buf.size * 2, off, int(in_place),
                                            None if ini is None else _ptr(ini), _ptr(tot), tot.size * 2, off, _ptr(one), _ptr(work),
                                            work.size * 2, off, C.byref(launches)))
-    assert (buf[:PAD] == CANARY).all() and (buf[-PAD:] == CANARY).all(), "elements around the output were written"
-    assert (tot[:PAD] == CANARY).all() and (tot[-PAD:] == CANARY).all(), "elements around the totals were written"
-    assert (work[:PAD] == CANARY).all() and (work[-PAD:] == CANARY).all(), "elements around the workspace were written"
+    out, totals = K.inner(buf), K.inner(tot, "the totals")
+    K.inner(work, "the workspace")
     assert (v == keep).all(), "the input was written"
-    return buf[PAD:-PAD].reshape(x.shape).copy(), tot[PAD:-PAD].copy(), launches.value
+    return out.reshape(x.shape).copy(), totals.copy(), launches.value
 
 
 def scan_refusal(nl, op, mode, n, n_vecs=1, null_mask=0, misalign=0, overlap=0, short_work=0):

@@ -1,20 +1,18 @@
 """ctypes side of tests/native/k18_harness.cpp (lcpc_amd/lib/liblcpc_k18_harness.so, built by lcpc_amd/csrc/Makefile): the sumcheck
 launchers (K18 / K19 of lcpc_amd/csrc/kernels.h) with a max_groups of the caller's choice, canaries around every output, the evals
-and the workspace, and the launchers' refusals.  Errors as in tests/k2_harness.py."""
+and the workspace, and the launchers' refusals.  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import fft_cases as FC
 import sumcheck_cases as MC
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k18_harness.so")
+LIB_PATH = K.lib_path("k18")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
-CANARY = FC.CANARY
-PAD = 8                                             # canary elements in front of and behind every output, the evals and the workspace
+CANARY, PAD = K.CANARY, K.PAD                      # the canary elements around an output: harness_kit.padded
 ORDERS = {"low": 0, "high": 1}
 MODES = {"bind": 0, "round": 1, "fused": 2}
 
@@ -28,24 +26,10 @@ SYMBOLS = {
     "k18h_run": (_i32, [_i32, _i32, _i32, _vp, _u64, _u32, _vp, _u64, _u64, _i32, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _vp]),
     "k18h_refusal": (_i32, [_i32, _i32, _i32, _u64, _u32, _vp, _u32, _u32, _u32, _i32, _i32, _u32]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("k18", SYMBOLS)
 
 
 def tile_pairs(nl):
@@ -92,10 +76,10 @@ def run(mode, fid, order, tabs, terms=None, r=None, max_groups=None, in_place=Fa
     span = n if in_place else n // 2
     slot = PAD + span + PAD
     out = np.full((n_tables, slot, F.L), CANARY, np.uint64)
-    ev = np.full((PAD + 5 + PAD, F.L), CANARY, np.uint64)
+    ev = K.padded(5, F.L)
     pairs = n // 4 if mode == "fused" else n // 2
     need = work_elems(pairs, len(terms), max_groups) if rnd else 0
-    work = np.full((PAD + need + PAD, F.L), CANARY, np.uint64)
+    work = K.padded(need, F.L)
     launches = C.c_uint32(0)
     off = PAD * nl
     _check("k18h_run", lib().k18h_run(MODES[mode], nl, ORDERS[order], _ptr(tabs), n, n_tables, _ptr(out), slot * nl, off, int(in_place),
@@ -103,7 +87,7 @@ def run(mode, fid, order, tabs, terms=None, r=None, max_groups=None, in_place=Fa
                                      None if rl is None else _ptr(rl), _ptr(ev), ev.size * 2, off, _ptr(work), work.size * 2, off, max_groups,
                                      C.byref(launches)))
     assert (tabs == keep).all(), "an input was written"
-    assert (work[:PAD] == CANARY).all() and (work[PAD + need:] == CANARY).all(), "elements around the workspace were written"
+    K.inner(work, "the workspace")
     bound = evals = None
     if bind:
         assert (out[:, :PAD] == CANARY).all() and (out[:, PAD + span:] == CANARY).all(), "elements around an output were written"

@@ -2,16 +2,16 @@
 context made by lcpc_ctx_create, and read-only copies of what its row NTT (K1) reads -- the plan, the twiddle / clamp / fourth-root tables
 at their full stride, the lane-varying entries of a pass's pack as the product's pack_get loads them, and the packs' shifted-multiples
 tables.  The LCPC_NTT_* switches are read when a context is created: `Ctx(..., env=...)` sets them around that call and takes them back.
-Errors as in tests/k2_harness.py; BadArgs means the harness refused the request before it touched the device."""
+Errors as in tests/harness_kit.py; BadArgs means the harness refused the request before it touched the device."""
 import ctypes as C
 import os
 
 import numpy as np
 
-from k2_harness import BadArgs, HipError, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k1_harness.so")
+LIB_PATH = K.lib_path("k1")
 K1H_BAD_ARGS = -1000
 TABLES = ["d_roots", "d_rootsl", "d_rootslc", "d_rootsls", "d_rootslcs", "d_qpl", "d_wq_w"]      # the harness's table numbers
 KINDS = ["general", "K1s", "K1n"]
@@ -30,26 +30,13 @@ SYMBOLS = {
     "k1h_uniform": [_vp, _u32, _vp, _u32, _vp, _u64],
     "k1h_last_error": [_vp],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        L.k1h_close.restype = None
-        L.k1h_last_error.restype = C.c_char_p
-        _lib = L
-    return _lib
+    L = K.load("k1", SYMBOLS)
+    L.k1h_close.restype = None
+    L.k1h_last_error.restype = C.c_char_p
+    return L
 
 
 def _check(what, rc, h=None):

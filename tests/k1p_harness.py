@@ -1,7 +1,7 @@
 """ctypes side of tests/native/k1p_harness.cpp (lcpc_amd/lib/liblcpc_k1p_harness.so, built by lcpc_amd/csrc/Makefile): a real Ligero
 context made by lcpc_ctx_create, ONE pass kernel of its row-NTT plan per call through the product's launcher, the general kernel on a
 free split of the stages, and the launchers' documented refusals.  The LCPC_NTT_* switches are read when a context is created:
-`Ctx(..., env=...)` sets them around that call and takes them back.  Errors as in tests/k2_harness.py; BadArgs means the harness
+`Ctx(..., env=...)` sets them around that call and takes them back.  Errors as in tests/harness_kit.py; BadArgs means the harness
 refused the request before it touched the device.
 
 Every buffer a pass may write comes back whole as a `Buf`: the canary words in front of and behind it and the body, gaps between rows
@@ -11,10 +11,10 @@ import os
 
 import numpy as np
 
-from k2_harness import BadArgs, HipError, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k1p_harness.so")
+LIB_PATH = K.lib_path("k1p")
 K1P_BAD_ARGS = -1000
 KINDS = ["general", "K1s", "K1n"]
 SWITCHES = ("LCPC_NTT_GENERAL", "LCPC_NTT_FORM", "LCPC_NTT_MUL", "LCPC_NTT_MID_MAX_MB", "LCPC_DEBUG_TIMING")
@@ -38,27 +38,14 @@ SYMBOLS = {
     "k1p_run_general": [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _u64],
     "k1p_refused": [_vp, _u32, _vp, _u32],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        L.k1p_close.restype = None
-        L.k1p_last_error.restype = C.c_char_p
-        L.k1p_canary_words.restype = _u64
-        _lib = L
-    return _lib
+    L = K.load("k1p", SYMBOLS)
+    L.k1p_close.restype = None
+    L.k1p_last_error.restype = C.c_char_p
+    L.k1p_canary_words.restype = _u64
+    return L
 
 
 def _check(what, rc, h=None):

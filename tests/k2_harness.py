@@ -3,24 +3,15 @@ launchers of lcpc_amd/csrc/kernels.h on matrices and operands a test builds.  El
 (Montgomery) limbs, like everywhere at the C ABI; in / out buffers are modified in place.  Every call returns after the device has
 finished and raises on any hipError_t; BadArgs means the harness refused the call before touching the device."""
 import ctypes as C
-import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k2_harness.so")
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+
+LIB_PATH = K.lib_path("k2")
 NL = {0: 2, 1: 4, 2: 6, 3: 8}
 HIP_ERROR_INVALID_VALUE = 1
-
-
-class BadArgs(ValueError):
-    pass
-
-
-class HipError(RuntimeError):
-    def __init__(self, what, code):
-        RuntimeError.__init__(self, "%s: hipError_t %d" % (what, code))
-        self.code = code
 
 
 _vp, _u64, _u32, _i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -35,41 +26,16 @@ SYMBOLS = {
     "k2h_transpose_from_t": [_i32, _vp, _u64, _u64, _vp, _u64],
     "k2h_pad_rows": [_i32, _vp, _u64, _vp, _u64, _u64, _u64],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+    return K.load("k2", SYMBOLS)
 
 
 def _elems(a, fid, n=None):
     assert a.dtype == np.uint64 and a.flags.c_contiguous and a.shape[-1] * 2 == NL[fid], (a.dtype, a.shape)
     assert n is None or a.size == n * a.shape[-1], (a.shape, n)
     return _ptr(a)
-
-
-def _check(what, rc):
-    if rc == -1:
-        raise BadArgs(what)
-    if rc:
-        raise HipError(what, rc)
 
 
 def field_consts(fid):

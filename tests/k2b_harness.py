@@ -2,16 +2,16 @@
 of the position-major Brakedown launchers of lcpc_amd/csrc/kernels.h (launch_transpose_to_t_batch, launch_spmm_t_batch,
 launch_sdig_rs_t_batch) on matrices and operands a test builds.  A batch buffer is an (n_batch, stride_elems, L) uint64 array: member
 i's elements first, whatever the test put behind them (a sentinel) up to the stride; in / out buffers are modified in place.  The
-launchers take member strides in 32-bit words: stride_elems * 2 L here.  Errors as in tests/k2_harness.py, whose classes these are."""
+launchers take member strides in 32-bit words: stride_elems * 2 L here.  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from k2_harness import NL, BadArgs, Csr, HipError, _check, _elems, _ptr, field_consts  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+from k2_harness import NL, Csr, _elems, field_consts  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k2b_harness.so")
+LIB_PATH = K.lib_path("k2b")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 TRANSPOSE, SPMM, SDIG_RS = 0, 1, 2
 
@@ -23,24 +23,10 @@ SYMBOLS = {
     "k2bh_transpose_to_t": [_i32, _vp, _u64, _u64, _u64, _u64, _vp, _u64, _u32, _u64, _vp, _i32],
     "k2bh_refusal": [_i32, _i32, _u32, _u64, _u64, _i32],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
+    return K.load("k2b", SYMBOLS)
 
 
 def _members(a, fid):

@@ -1,7 +1,7 @@
 """ctypes side of tests/native/k5_harness.cpp (lcpc_amd/lib/liblcpc_k5_harness.so, built by lcpc_amd/csrc/Makefile): the prover's kernels
 (K5 / K6 of lcpc_amd/csrc/kernels.h: collapse in both forms, to_r29, the split sum, to_mont / to_canon, the column and path gathers in
 both forms, assemble_columns) on operands a test builds, and the case builders with their Python-int expectations.  Elements cross as
-uint64 arrays of stored (Montgomery) limbs, last axis L.  Errors as in tests/k2_harness.py, whose classes these are.
+uint64 arrays of stored (Montgomery) limbs, last axis L.  Errors as in tests/harness_kit.py.
 
 Every builder lays its inputs out with POISON (all-ones limbs, not a reduced element) in every gap and its outputs pre-filled with
 SENTINEL, and gives the whole expected output array: what the kernel must write, and SENTINEL everywhere else.  The members of a batch
@@ -9,17 +9,17 @@ carry distinct data and sit in memory in an order unlike their batch order, so a
 expectation wrong in a named way ("swap": members 0 and 1 exchanged; "no_j0": the collapse reads column j - j0; "no_slice": the second
 slice of a column gather reads the first slice's column numbers); tests/test_k5_cases.py holds every batched case to changing under it."""
 import ctypes as C
-import os
 import random
 from operator import mul
 
 import numpy as np
 
 from common import FIELD_L, field_p, maxc, maxt, to_int, to_limbs  # noqa: F401
-from k2_harness import NL, BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+from k2_harness import NL  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k5_harness.so")
+LIB_PATH = K.lib_path("k5")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 POISON = (1 << 64) - 1                  # all-ones limbs in every gap of an input: must never be read
 SENTINEL = 0x5A5A5A5A5A5A5A5A           # what every output holds before the launch
@@ -43,24 +43,10 @@ SYMBOLS = {
     "k5h_refuse_convert": [_i32, _i32, _u64],
     "k5h_refuse_assemble_columns": [_i32, _u32, _u64],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
+    return K.load("k5", SYMBOLS)
 
 
 def pack(vals, L):

@@ -1,17 +1,17 @@
 """ctypes side of tests/native/k7_harness.cpp (lcpc_amd/lib/liblcpc_k7_harness.so, built by lcpc_amd/csrc/Makefile): the column check of
 the batched verify (K7b, launch_verify_columns_batch of lcpc_amd/csrc/kernels.h) on operands a test builds, and the case builder with
 its Python-int expectations.  Elements cross as uint64 arrays of stored (Montgomery) limbs, last axis L.  Errors as in
-tests/k2_harness.py, whose classes these are."""
+tests/harness_kit.py."""
 import ctypes as C
-import os
 import random
 
 import numpy as np
 
-from k2_harness import NL, BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+from k2_harness import NL  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k7_harness.so")
+LIB_PATH = K.lib_path("k7")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 DEGREE_BIT, EVAL_BIT = 1, 2
 POISON = (1 << 64) - 1           # all-ones limbs: not a reduced element; must never be read
@@ -22,24 +22,10 @@ SYMBOLS = {
     "k7h_verify_columns": [_i32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32],
     "k7h_refusal": [_i32, _u32, _u32, _u32, _i32],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
+    return K.load("k7", SYMBOLS)
 
 
 class Case:

@@ -1,19 +1,18 @@
 """ctypes side of tests/native/k8_harness.cpp (lcpc_amd/lib/liblcpc_k8_harness.so, built by lcpc_amd/csrc/Makefile): the Merkle path
 folds of the batched verify and the column check (K8b, launch_fold_paths_b3 / launch_chain_fold_paths of lcpc_amd/csrc/kernels.h) on
 operands a test builds, and the case builder with its expectations: hashlib for SHA3-256, SHA-256 and BLAKE2b-512, and the Keccak-256
-and BLAKE3 references of the digest suites (tests/digest_ref.py ref_digest).  Errors as in tests/k2_harness.py, whose classes these are."""
+and BLAKE3 references of the digest suites (tests/digest_ref.py ref_digest).  Errors as in tests/harness_kit.py."""
 import ctypes as C
-import os
 import random
 
 import numpy as np
 
 import digest_more  # noqa: F401  (teaches digest_ref.ref_digest Keccak-256 and SHA-256)
 import digest_ref as DR
-from k2_harness import BadArgs, HipError, _check, _ptr  # noqa: F401
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_k8_harness.so")
+LIB_PATH = K.lib_path("k8")
 HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
 PATH_BIT = 4
 DIGESTS = ["blake3", "sha3_256", "keccak256", "sha256", "blake2b"]      # the harness's digest numbers
@@ -26,24 +25,10 @@ SYMBOLS = {
     "k8h_fold_paths": [_i32, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _u32],
     "k8h_refusal": [_i32, _u32, _u32, _u32, _u32],
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, args in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = _i32, args
-        _lib = L
-    return _lib
+    return K.load("k8", SYMBOLS)
 
 
 # ---- the reference -------------------------------------------------------------------------------------------------------------

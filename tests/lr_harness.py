@@ -4,26 +4,17 @@ lcpc_amd/csrc/kernels.h) on buffers a test builds.  Elements cross as (.., L) ui
 and the hashes as flat uint32 arrays that are modified in place.  Every call returns after the device has finished and raises on any
 hipError_t; BadArgs means the harness refused the call before touching the device."""
 import ctypes as C
-import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_lr_harness.so")
+import harness_kit as K
+from harness_kit import BadArgs, HipError, check as _check, ptr as _ptr  # noqa: F401
+
+LIB_PATH = K.lib_path("lr")
 NL = {0: 2, 1: 4, 2: 6, 3: 8}
 FAMILY = {"sha3_256": 0, "keccak256": 1, "sha256": 2, "blake2b": 3}
 # per digest: 64-bit words of zero prefix, 64-bit words per block, 32-bit words of chaining state per column, 32-bit words per digest
 SHAPE = {"sha3_256": (4, 17, 50, 8), "keccak256": (4, 17, 50, 8), "sha256": (4, 8, 8, 8), "blake2b": (8, 16, 16, 16)}
-
-
-class BadArgs(ValueError):
-    pass
-
-
-class HipError(RuntimeError):
-    def __init__(self, what, code):
-        RuntimeError.__init__(self, "%s: hipError_t %d" % (what, code))
-        self.code = code
 
 
 _vp, _u64, _i32, _u32 = C.c_void_p, C.c_uint64, C.c_int, C.c_uint32
@@ -34,24 +25,10 @@ SYMBOLS = {
     "lrh_leaves": (_i32, [_i32, _i32, _vp, _u64, _u64, _u64, _u64, _u64, _i32, _u32, _u64, _u64, _vp, _u64, _u64]),
     "lrh_merkle_tree": (_i32, [_i32, _u64, _u32, _u64, _vp, _u64, _u64, _vp, _u64, _u64]),
 }
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s is missing -- `make -C lcpc_amd/csrc` (or __graft_entry__.build()) builds it beside the product" % LIB_PATH)
-        try:
-            import torch  # noqa: F401  (its bundled HIP runtime must be the first one loaded: lcpc_amd/_lib.py)
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = L
-    return _lib
+    return K.load("lr", SYMBOLS)
 
 
 def leaf_blocks(digest, fid, n_rows):
@@ -73,13 +50,6 @@ def leaf_range(digest, fid, comm, row_stride, col_stride, n_cols, n_rows_total, 
         raise BadArgs("lrh_leaf_range")
     if rc:
         raise HipError("lrh_leaf_range", rc)
-
-
-def _check(what, rc):
-    if rc == -1:
-        raise BadArgs(what)
-    if rc:
-        raise HipError(what, rc)
 
 
 def leaves(digest, fid, comm, row_stride, col_stride, n_cols, n_rows_total, canon_in, out, out_off, n_batch=0, comm_stride=0, out_stride=0):

@@ -8,34 +8,16 @@
 //
 // One thin kernel per primitive: lane i loads operand(s) i, calls the primitive once, stores result i; blocks of 256 lanes.  Every
 // wrapper takes HOST pointers, copies in, launches on the null stream, synchronises and copies the output buffers back whole (out_n >= n
-// elements, so the caller sees what was written past element n - 1 too).  The return value is the first hipError_t, or FEH_BAD_ARGS for
+// elements, so the caller sees what was written past element n - 1 too).  The return value is the first hipError_t, or H_BAD_ARGS for
 // a call the harness refuses (nothing is launched then): a field or word count it has no instantiation for, a count out of range, or an
 // operand whose table index (clamp_q, ln::clamp) would leave the 64-entry table.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "harness.h"
 #include "../../lcpc_amd/csrc/field_ln.h"
 #include "../../lcpc_amd/csrc/host_field.h"
-
-#define FEH_EXPORT extern "C" __attribute__((visibility("default")))
-#define FEH_BAD_ARGS (-1)
 
 using namespace lcpc;
 
 namespace {
-
-struct DevBuf {
-  u32* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t put(const void* src, size_t bytes) {
-    hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t get(void* dst, size_t bytes) const { return bytes ? hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-};
-
-#define FEH_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 constexpr u32 MAX_N = 1u << 20;          // lanes per launch
 constexpr u32 MAX_WIDE_K = 1u << 12;     // terms per lane of wide_dot (every caller reduces after 8)
@@ -43,7 +25,6 @@ constexpr u32 MAX_LAZY_K = 60;           // field_ln.h: one Montgomery reduction
 constexpr u32 MAX_LAZY_C = 6;            //             a normalise at least every 6 terms
 constexpr u32 WT_STRIDE = 96;            // words per shifted-multiples table (ctx.cpp wmul_table: N^2 <= 81 words, padded)
 
-bool nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
 bool counts_ok(u32 n, u32 out_n) { return n <= MAX_N && out_n >= n && out_n <= MAX_N + 1; }
 dim3 grid(u32 n) { return dim3((n + 255) / 256 ? (n + 255) / 256 : 1); }
 __device__ __forceinline__ u32 lane_id() { return blockIdx.x * 256u + threadIdx.x; }
@@ -188,10 +169,10 @@ template <class FT> bool tops_ok(const u32* l, u32 n) {
 template <class F> int run_out(u32* out, u32 out_n, int ow, F launch) {
   DevBuf d_out;
   const size_t bytes = (size_t)out_n * ow * 4;
-  FEH_TRY(d_out.put(out, bytes));
+  H_TRY(d_out.put(out, bytes));
   launch(d_out.p);
-  FEH_TRY(hipGetLastError());
-  FEH_TRY(hipDeviceSynchronize());
+  H_TRY(hipGetLastError());
+  H_TRY(hipDeviceSynchronize());
   return (int)d_out.get(out, bytes);
 }
 
@@ -201,7 +182,7 @@ template <class F> int run_out(u32* out, u32 out_n, int ow, F launch) {
     case 4: { constexpr int NLV = 4; BODY; } break; \
     case 6: { constexpr int NLV = 6; BODY; } break; \
     case 8: { constexpr int NLV = 8; BODY; } break; \
-    default: return FEH_BAD_ARGS; \
+    default: return H_BAD_ARGS; \
   }
 #define FEH_FT_SWITCH(fid, BODY) \
   switch (fid) { \
@@ -209,7 +190,7 @@ template <class F> int run_out(u32* out, u32 out_n, int ow, F launch) {
     case FT127: { using FT = LnField<FT127>; BODY; } break; \
     case FT191: { using FT = LnField<FT191>; BODY; } break; \
     case FT255: { using FT = LnField<FT255>; BODY; } break; \
-    default: return FEH_BAD_ARGS; \
+    default: return H_BAD_ARGS; \
   }
 // the fields with a shifted-multiples multiply and a limb dot product
 #define FEH_FT_SWITCH3(fid, BODY) \
@@ -217,13 +198,13 @@ template <class F> int run_out(u32* out, u32 out_n, int ow, F launch) {
     case FT127: { using FT = LnField<FT127>; BODY; } break; \
     case FT191: { using FT = LnField<FT191>; BODY; } break; \
     case FT255: { using FT = LnField<FT255>; BODY; } break; \
-    default: return FEH_BAD_ARGS; \
+    default: return H_BAD_ARGS; \
   }
 
 template <int NL> int binop(int op, const u32* a, const u32* b, u32* out, u32 n, u32 out_n) {
   DevBuf d_a, d_b;
-  FEH_TRY(d_a.put(a, (size_t)n * NL * 4));
-  FEH_TRY(d_b.put(b, (size_t)n * NL * 4));
+  H_TRY(d_a.put(a, (size_t)n * NL * 4));
+  H_TRY(d_b.put(b, (size_t)n * NL * 4));
   return run_out(out, out_n, NL, [&](u32* d_out) {
     if (op == OP_ADD) hipLaunchKernelGGL((k_binop<NL, OP_ADD>), grid(n), dim3(256), 0, nullptr, d_a.p, d_b.p, d_out, n);
     else if (op == OP_SUB) hipLaunchKernelGGL((k_binop<NL, OP_SUB>), grid(n), dim3(256), 0, nullptr, d_a.p, d_b.p, d_out, n);
@@ -233,16 +214,16 @@ template <int NL> int binop(int op, const u32* a, const u32* b, u32* out, u32 n,
 
 template <class FT> int lazy_dot(const u32* x, const u32* v, u32 k, u32 c, u32* out, u32 n, u32 out_n) {
   DevBuf d_x, d_v;
-  FEH_TRY(d_x.put(x, (size_t)n * k * FT::NL * 4));
-  FEH_TRY(d_v.put(v, (size_t)n * k * FT::N * 4));
+  H_TRY(d_x.put(x, (size_t)n * k * FT::NL * 4));
+  H_TRY(d_v.put(v, (size_t)n * k * FT::N * 4));
   return run_out(out, out_n, FT::NL, [&](u32* d_out) {
     hipLaunchKernelGGL((k_lazy_dot<FT>), grid(n), dim3(256), 0, nullptr, d_x.p, d_v.p, k, c, d_out, n);
   });
 }
 template <class FT> int mul_u(const u32* a, const u32* wt, u32 n_tabs, u32* out, u32 n, u32 out_n) {
   DevBuf d_a, d_w;
-  FEH_TRY(d_a.put(a, (size_t)n * FT::N * 4));
-  FEH_TRY(d_w.put(wt, (size_t)n_tabs * WT_STRIDE * 4));
+  H_TRY(d_a.put(a, (size_t)n * FT::N * 4));
+  H_TRY(d_w.put(wt, (size_t)n_tabs * WT_STRIDE * 4));
   return run_out(out, out_n, FT::N, [&](u32* d_out) {
     hipLaunchKernelGGL((k_mul_u<FT>), grid(n), dim3(256), 0, nullptr, d_a.p, d_w.p, n_tabs, d_out, n);
   });
@@ -250,156 +231,153 @@ template <class FT> int mul_u(const u32* a, const u32* wt, u32 n_tabs, u32* out,
 
 }  // namespace
 
-FEH_EXPORT int feh_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
+H_DEVICE_COUNT(feh_)
 
 // ---- packed layer: elements are nl words ----------------------------------------------------------------------------------------
 // op: 0 fe_add, 1 fe_sub, 2 fe_mul
-FEH_EXPORT int feh_binop(int op, int nl, const u32* a, const u32* b, u32* out, u32 n, u32 out_n) {
-  if (op < OP_ADD || op > OP_MUL || !counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_binop(int op, int nl, const u32* a, const u32* b, u32* out, u32 n, u32 out_n) {
+  if (op < OP_ADD || op > OP_MUL || !counts_ok(n, out_n)) return H_BAD_ARGS;
   FEH_NL_SWITCH(nl, return binop<NLV>(op, a, b, out, n, out_n));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
-FEH_EXPORT int feh_canon(int nl, const u32* a, u32* out, u32 n, u32 out_n) {
-  if (!nl_ok(nl) || !counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_canon(int nl, const u32* a, u32* out, u32 n, u32 out_n) {
+  if (!nl_ok(nl) || !counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_a;
-  FEH_TRY(d_a.put(a, (size_t)n * nl * 4));
+  H_TRY(d_a.put(a, (size_t)n * nl * 4));
   FEH_NL_SWITCH(nl, return run_out(out, out_n, NLV, [&](u32* d_out) {
     hipLaunchKernelGGL((k_canon<NLV>), grid(n), dim3(256), 0, nullptr, d_a.p, d_out, n);
   }));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 // top: n words for the (t, top) form, null for the one-argument form
-FEH_EXPORT int feh_reduce_once(int nl, const u32* t, const u32* top, u32* out, u32 n, u32 out_n) {
-  if (!nl_ok(nl) || !counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_reduce_once(int nl, const u32* t, const u32* top, u32* out, u32 n, u32 out_n) {
+  if (!nl_ok(nl) || !counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_t, d_top;
-  FEH_TRY(d_t.put(t, (size_t)n * nl * 4));
-  if (top) FEH_TRY(d_top.put(top, (size_t)n * 4));
+  H_TRY(d_t.put(t, (size_t)n * nl * 4));
+  if (top) H_TRY(d_top.put(top, (size_t)n * 4));
   FEH_NL_SWITCH(nl, return run_out(out, out_n, NLV, [&](u32* d_out) {
     hipLaunchKernelGGL((k_reduce_once<NLV>), grid(n), dim3(256), 0, nullptr, d_t.p, top ? d_top.p : nullptr, d_out, n);
   }));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 // a, b: n * k elements, lane i takes pairs [i k, (i + 1) k): k wide_mac, one wide_reduce
-FEH_EXPORT int feh_wide_dot(int nl, const u32* a, const u32* b, u32 k, u32* out, u32 n, u32 out_n) {
-  if (!nl_ok(nl) || !counts_ok(n, out_n) || k > MAX_WIDE_K) return FEH_BAD_ARGS;
+H_EXPORT int feh_wide_dot(int nl, const u32* a, const u32* b, u32 k, u32* out, u32 n, u32 out_n) {
+  if (!nl_ok(nl) || !counts_ok(n, out_n) || k > MAX_WIDE_K) return H_BAD_ARGS;
   DevBuf d_a, d_b;
-  FEH_TRY(d_a.put(a, (size_t)n * k * nl * 4));
-  FEH_TRY(d_b.put(b, (size_t)n * k * nl * 4));
+  H_TRY(d_a.put(a, (size_t)n * k * nl * 4));
+  H_TRY(d_b.put(b, (size_t)n * k * nl * 4));
   FEH_NL_SWITCH(nl, return run_out(out, out_n, NLV, [&](u32* d_out) {
     hipLaunchKernelGGL((k_wide_dot<NLV>), grid(n), dim3(256), 0, nullptr, d_a.p, d_b.p, k, d_out, n);
   }));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 
 // ---- limb layer: fid selects LnField<fid>; a limb-form element is N words, a packed one NL ---------------------------------------
-FEH_EXPORT int feh_from_packed(int fid, const u32* a, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_from_packed(int fid, const u32* a, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_a;
   FEH_FT_SWITCH(fid, {
-    FEH_TRY(d_a.put(a, (size_t)n * FT::NL * 4));
+    H_TRY(d_a.put(a, (size_t)n * FT::NL * 4));
     return run_out(out, out_n, FT::N, [&](u32* d_out) { hipLaunchKernelGGL((k_from_packed<FT>), grid(n), dim3(256), 0, nullptr, d_a.p, d_out, n); });
   });
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
-FEH_EXPORT int feh_to_packed(int fid, const u32* l, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_to_packed(int fid, const u32* l, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_l;
   FEH_FT_SWITCH(fid, {
-    FEH_TRY(d_l.put(l, (size_t)n * FT::N * 4));
+    H_TRY(d_l.put(l, (size_t)n * FT::N * 4));
     return run_out(out, out_n, FT::NL, [&](u32* d_out) { hipLaunchKernelGGL((k_to_packed<FT>), grid(n), dim3(256), 0, nullptr, d_l.p, d_out, n); });
   });
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
-FEH_EXPORT int feh_normalize(int fid, const u32* l, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_normalize(int fid, const u32* l, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_l;
   FEH_FT_SWITCH(fid, {
-    FEH_TRY(d_l.put(l, (size_t)n * FT::N * 4));
+    H_TRY(d_l.put(l, (size_t)n * FT::N * 4));
     return run_out(out, out_n, FT::N, [&](u32* d_out) { hipLaunchKernelGGL((k_normalize<FT>), grid(n), dim3(256), 0, nullptr, d_l.p, d_out, n); });
   });
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 // clamp_q on the top limb, clamp_row from nqp (64 rows of STRIDE words: the limb-wise negated (i - QOFF) p table), clamp_apply; q_out
 // (out_n words) receives clamp_q's index
-FEH_EXPORT int feh_clamp_qa(int fid, const u32* l, const u32* nqp, u32* out, u32* q_out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_clamp_qa(int fid, const u32* l, const u32* nqp, u32* out, u32* q_out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_l, d_t, d_q;
   FEH_FT_SWITCH(fid, {
-    if (!tops_ok<FT>(l, n)) return FEH_BAD_ARGS;
-    FEH_TRY(d_l.put(l, (size_t)n * FT::N * 4));
-    FEH_TRY(d_t.put(nqp, (size_t)64 * FT::STRIDE * 4));
-    FEH_TRY(d_q.put(q_out, (size_t)out_n * 4));
+    if (!tops_ok<FT>(l, n)) return H_BAD_ARGS;
+    H_TRY(d_l.put(l, (size_t)n * FT::N * 4));
+    H_TRY(d_t.put(nqp, (size_t)64 * FT::STRIDE * 4));
+    H_TRY(d_q.put(q_out, (size_t)out_n * 4));
     const int rc = run_out(out, out_n, FT::N, [&](u32* d_out) {
       hipLaunchKernelGGL((k_clamp_qa<FT>), grid(n), dim3(256), 0, nullptr, d_l.p, d_t.p, d_out, d_q.p, n);
     });
     return rc ? rc : (int)d_q.get(q_out, (size_t)out_n * 4);
   });
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
-FEH_EXPORT int feh_mul(int fid, const u32* a, const u32* w, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_mul(int fid, const u32* a, const u32* w, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_a, d_w;
   FEH_FT_SWITCH(fid, {
-    FEH_TRY(d_a.put(a, (size_t)n * FT::N * 4));
-    FEH_TRY(d_w.put(w, (size_t)n * FT::N * 4));
+    H_TRY(d_a.put(a, (size_t)n * FT::N * 4));
+    H_TRY(d_w.put(w, (size_t)n * FT::N * 4));
     return run_out(out, out_n, FT::N, [&](u32* d_out) { hipLaunchKernelGGL((k_mul<FT>), grid(n), dim3(256), 0, nullptr, d_a.p, d_w.p, d_out, n); });
   });
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 // wt: n_tabs tables of 96 words (the first N^2 used); the lanes of block b (256 lanes) multiply by table b mod n_tabs.  Ft127 / Ft191 /
 // Ft255 (has_mul_u)
-FEH_EXPORT int feh_mul_u(int fid, const u32* a, const u32* wt, u32 n_tabs, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n) || !n_tabs || n_tabs > 4096) return FEH_BAD_ARGS;
+H_EXPORT int feh_mul_u(int fid, const u32* a, const u32* wt, u32 n_tabs, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n) || !n_tabs || n_tabs > 4096) return H_BAD_ARGS;
   FEH_FT_SWITCH3(fid, return mul_u<FT>(a, wt, n_tabs, out, n, out_n));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 // x: n * k packed elements, v: n * k limb-form values; lane i takes pairs [i k, (i + 1) k): lazy_mac each, lazy_normalize every c terms,
 // one lazy_reduce.  Ft127 / Ft191 / Ft255 (the fields whose kernels use it)
-FEH_EXPORT int feh_lazy_dot(int fid, const u32* x, const u32* v, u32 k, u32 c, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n) || k > MAX_LAZY_K || !c || c > MAX_LAZY_C) return FEH_BAD_ARGS;
+H_EXPORT int feh_lazy_dot(int fid, const u32* x, const u32* v, u32 k, u32 c, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n) || k > MAX_LAZY_K || !c || c > MAX_LAZY_C) return H_BAD_ARGS;
   FEH_FT_SWITCH3(fid, return lazy_dot<FT>(x, v, k, c, out, n, out_n));
-  return FEH_BAD_ARGS;
+  return H_BAD_ARGS;
 }
 
 // ---- Ft255 only: qp is the (i - QOFF) p table itself, 64 rows of 12 words ------------------------------------------------------------
 // which: 0 ln::clamp (out: 9 words per element), 1 ln::to_packed_reduced (out: 8 words)
-FEH_EXPORT int feh_clamp9(int which, const u32* l, const u32* qp, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n) || (which != 0 && which != 1) || !tops_ok<LnField<FT255>>(l, n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_clamp9(int which, const u32* l, const u32* qp, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n) || (which != 0 && which != 1) || !tops_ok<LnField<FT255>>(l, n)) return H_BAD_ARGS;
   DevBuf d_l, d_t;
-  FEH_TRY(d_l.put(l, (size_t)n * 9 * 4));
-  FEH_TRY(d_t.put(qp, (size_t)64 * 12 * 4));
+  H_TRY(d_l.put(l, (size_t)n * 9 * 4));
+  H_TRY(d_t.put(qp, (size_t)64 * 12 * 4));
   return run_out(out, out_n, which ? 8 : 9, [&](u32* d_out) {
     if (which) hipLaunchKernelGGL(k_to_packed_reduced, grid(n), dim3(256), 0, nullptr, d_l.p, d_t.p, d_out, n);
     else hipLaunchKernelGGL(k_clamp9, grid(n), dim3(256), 0, nullptr, d_l.p, d_t.p, d_out, n);
   });
 }
 // a: packed, b: 9 limbs
-FEH_EXPORT int feh_mul_r29(const u32* a, const u32* b, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_mul_r29(const u32* a, const u32* b, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_a, d_b;
-  FEH_TRY(d_a.put(a, (size_t)n * 8 * 4));
-  FEH_TRY(d_b.put(b, (size_t)n * 9 * 4));
+  H_TRY(d_a.put(a, (size_t)n * 8 * 4));
+  H_TRY(d_b.put(b, (size_t)n * 9 * 4));
   return run_out(out, out_n, 8, [&](u32* d_out) { hipLaunchKernelGGL(k_mul_r29, grid(n), dim3(256), 0, nullptr, d_a.p, d_b.p, d_out, n); });
 }
-FEH_EXPORT int feh_canon_r29(const u32* a, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return FEH_BAD_ARGS;
+H_EXPORT int feh_canon_r29(const u32* a, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_a;
-  FEH_TRY(d_a.put(a, (size_t)n * 8 * 4));
+  H_TRY(d_a.put(a, (size_t)n * 8 * 4));
   return run_out(out, out_n, 8, [&](u32* d_out) { hipLaunchKernelGGL(k_canon_r29, grid(n), dim3(256), 0, nullptr, d_a.p, d_out, n); });
 }
 
 // ---- host_field.h: op 0 h_add, 1 h_sub, 2 h_mul, 3 h_canon (b unused) over n elements of L u64 limbs; no device involved -----------
-FEH_EXPORT int feh_host_op(int op, int fid, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n) {
+H_EXPORT int feh_host_op(int op, int fid, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n) {
   const FieldDesc* f = field_desc(fid);
-  if (!f || op < OP_ADD || op > OP_CANON) return FEH_BAD_ARGS;
+  if (!f || op < OP_ADD || op > OP_CANON) return H_BAD_ARGS;
   for (uint64_t i = 0; i < n; i++) {
     const uint64_t *x = a + i * f->L, *y = b ? b + i * f->L : nullptr;
     uint64_t* o = out + i * f->L;
     if (op == OP_CANON) h_canon(*f, o, x);
-    else if (!y) return FEH_BAD_ARGS;
+    else if (!y) return H_BAD_ARGS;
     else if (op == OP_ADD) h_add(*f, o, x, y);
     else if (op == OP_SUB) h_sub(*f, o, x, y);
     else h_mul(*f, o, x, y);

@@ -3,58 +3,22 @@
 // library, which gains nothing by it (tests/k17_harness.py, tests/test_gpu_k17_kernels.py).
 //
 // They take HOST pointers and the sizes of the buffers behind them, check that every element the launcher may touch stays inside them
-// (a refused call returns K17H_BAD_ARGS and launches nothing), allocate device buffers, copy in, launch on the null stream,
+// (a refused call returns H_BAD_ARGS and launches nothing), allocate device buffers, copy in, launch on the null stream,
 // synchronise and copy the WHOLE output, total and work buffers back, the words around them included, and the input as the kernels
 // left it.  k17h_scan_refusal hands the launcher arguments it must settle BEFORE any launch, with never-read buffers: it touches no
 // device.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "harness.h"
 #include "../../lcpc_amd/csrc/kernels.h"
 
-#define K17H_EXPORT extern "C" __attribute__((visibility("default")))
-#define K17H_BAD_ARGS (-1)
-
-namespace {
-
-struct DevBuf {
-  uint32_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t put(const void* src, size_t bytes) {
-    hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t get(void* dst, size_t bytes) const { return bytes ? hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-};
-
-#define K17H_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-constexpr uint64_t MAX_WORDS = (uint64_t)1 << 28;   // what a test may ask for here (the launcher takes more)
-bool nl_ok(int nl) { return nl == 2 || nl == 4 || nl == 6 || nl == 8; }
-bool off_ok(uint64_t off_words, int nl) { return (off_words * 4) % (nl % 4 == 0 ? 16 : 8) == 0; }
-// `words` words from off on lie inside a buffer of buf_words
-bool span_ok(uint64_t words, uint64_t buf_words, uint64_t off, int nl) {
-  return words <= MAX_WORDS && buf_words <= MAX_WORDS && off <= buf_words && words <= buf_words - off && off_ok(off, nl);
-}
-
-}  // namespace
-
-K17H_EXPORT int k17h_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-K17H_EXPORT int k17h_cu_count() {
-  hipDeviceProp_t prop;
-  return hipGetDeviceProperties(&prop, 0) == hipSuccess ? prop.multiProcessorCount : 0;
-}
+H_DEVICE_COUNT(k17h_)
+H_CU_COUNT(k17h_)
 
 // the elements of a workgroup's tile, the consecutive elements of a lane, the totals K17b takes per recursion level, and the elements
 // of the workspace
-K17H_EXPORT uint32_t k17h_tile(int nl) { return nl_ok(nl) ? lcpc::scan_tile(nl) : 0; }
-K17H_EXPORT uint32_t k17h_lane_elems(int nl) { return nl_ok(nl) ? lcpc::scan_lane_elems(nl) : 0; }
-K17H_EXPORT uint32_t k17h_mid_chunk(int nl) { return nl_ok(nl) ? lcpc::scan_mid_chunk(nl) : 0; }
-K17H_EXPORT uint64_t k17h_work_elems(int nl, uint64_t n, uint32_t n_vecs) {
+H_EXPORT uint32_t k17h_tile(int nl) { return nl_ok(nl) ? lcpc::scan_tile(nl) : 0; }
+H_EXPORT uint32_t k17h_lane_elems(int nl) { return nl_ok(nl) ? lcpc::scan_lane_elems(nl) : 0; }
+H_EXPORT uint32_t k17h_mid_chunk(int nl) { return nl_ok(nl) ? lcpc::scan_mid_chunk(nl) : 0; }
+H_EXPORT uint64_t k17h_work_elems(int nl, uint64_t n, uint32_t n_vecs) {
   return nl_ok(nl) && n && n < ((uint64_t)1 << 39) && n_vecs && n_vecs <= 65535 ? lcpc::scan_work_elems(nl, n, n_vecs) : 0;
 }
 
@@ -63,54 +27,54 @@ K17H_EXPORT uint64_t k17h_work_elems(int nl, uint64_t n, uint32_t n_vecs) {
 // n_vecs elements or NULL.  total: NULL, or total_words words of which n_vecs elements from total_off on receive the totals.  work:
 // work_words words of which the scan_work_elems elements from work_off on are the workspace.  one: R mod p.  Everything else in out, total
 // and work must come back as it went in.  *n_launches (may be NULL): the kernels launched
-K17H_EXPORT int k17h_scan(int nl, int op, int mode, uint32_t* in, uint64_t n, uint32_t n_vecs, uint32_t* out, uint64_t out_words, uint64_t out_off,
-                          int in_place, const uint32_t* init, uint32_t* total, uint64_t total_words, uint64_t total_off, const uint32_t* one,
-                          uint32_t* work, uint64_t work_words, uint64_t work_off, uint32_t* n_launches) {
-  if (!nl_ok(nl) || !in || !out || !one || !work || n == 0 || n_vecs == 0 || n_vecs > 65535 || n > MAX_WORDS / nl / n_vecs) return K17H_BAD_ARGS;
+H_EXPORT int k17h_scan(int nl, int op, int mode, uint32_t* in, uint64_t n, uint32_t n_vecs, uint32_t* out, uint64_t out_words, uint64_t out_off,
+                       int in_place, const uint32_t* init, uint32_t* total, uint64_t total_words, uint64_t total_off, const uint32_t* one,
+                       uint32_t* work, uint64_t work_words, uint64_t work_off, uint32_t* n_launches) {
+  if (!nl_ok(nl) || !in || !out || !one || !work || n == 0 || n_vecs == 0 || n_vecs > 65535 || n > MAX_WORDS / nl / n_vecs) return H_BAD_ARGS;
   const uint64_t words = n * n_vecs * nl, ends = (uint64_t)n_vecs * nl, need = lcpc::scan_work_elems(nl, n, n_vecs);
-  if (!span_ok(words, out_words, out_off, nl) || (total && !span_ok(ends, total_words, total_off, nl))) return K17H_BAD_ARGS;
-  if (!span_ok(need * nl, work_words, work_off, nl)) return K17H_BAD_ARGS;
+  if (!span_ok(words, out_words, out_off, nl) || (total && !span_ok(ends, total_words, total_off, nl))) return H_BAD_ARGS;
+  if (!span_ok(need * nl, work_words, work_off, nl)) return H_BAD_ARGS;
   DevBuf d_in, d_out, d_init, d_total, d_work;
-  K17H_TRY(d_out.put(out, out_words * 4));
-  K17H_TRY(d_work.put(work, work_words * 4));
-  if (init) K17H_TRY(d_init.put(init, ends * 4));
-  if (total) K17H_TRY(d_total.put(total, total_words * 4));
+  H_TRY(d_out.put(out, out_words * 4));
+  H_TRY(d_work.put(work, work_words * 4));
+  if (init) H_TRY(d_init.put(init, ends * 4));
+  if (total) H_TRY(d_total.put(total, total_words * 4));
   const uint32_t* src;
   if (in_place) {
-    K17H_TRY(hipMemcpy(d_out.p + out_off, in, words * 4, hipMemcpyHostToDevice));
+    H_TRY(hipMemcpy(d_out.p + out_off, in, words * 4, hipMemcpyHostToDevice));
     src = d_out.p + out_off;
   } else {
-    K17H_TRY(d_in.put(in, words * 4));
+    H_TRY(d_in.put(in, words * 4));
     src = d_in.p;
   }
-  K17H_TRY(lcpc::launch_scan(nl, op, mode, src, d_out.p + out_off, n, n_vecs, d_init.p, total ? d_total.p + total_off : nullptr, one,
+  H_TRY(lcpc::launch_scan(nl, op, mode, src, d_out.p + out_off, n, n_vecs, d_init.p, total ? d_total.p + total_off : nullptr, one,
                              d_work.p + work_off, need, nullptr, n_launches));
-  K17H_TRY(hipDeviceSynchronize());
-  if (!in_place) K17H_TRY(d_in.get(in, words * 4));
-  if (total) K17H_TRY(d_total.get(total, total_words * 4));
-  K17H_TRY(d_work.get(work, work_words * 4));
+  H_TRY(hipDeviceSynchronize());
+  if (!in_place) H_TRY(d_in.get(in, words * 4));
+  if (total) H_TRY(d_total.get(total, total_words * 4));
+  H_TRY(d_work.get(work, work_words * 4));
   return (int)d_out.get(out, out_words * 4);
 }
 
 // K17b alone: what the scan does with the tile totals of n_vecs vectors, n_totals each -- their exclusive scan in place, seeded with
 // init, and the totals of the vectors.  The buffers as for k17h_scan, `totals` in the place of out
-K17H_EXPORT int k17h_scan_totals(int nl, int op, uint32_t* totals_in, uint64_t n_totals, uint32_t n_vecs, uint32_t* totals, uint64_t totals_words,
-                                 uint64_t totals_off, const uint32_t* init, uint32_t* total, uint64_t total_words, uint64_t total_off,
-                                 const uint32_t* one, uint32_t* work, uint64_t work_words, uint64_t work_off) {
+H_EXPORT int k17h_scan_totals(int nl, int op, uint32_t* totals_in, uint64_t n_totals, uint32_t n_vecs, uint32_t* totals, uint64_t totals_words,
+                              uint64_t totals_off, const uint32_t* init, uint32_t* total, uint64_t total_words, uint64_t total_off,
+                              const uint32_t* one, uint32_t* work, uint64_t work_words, uint64_t work_off) {
   return k17h_scan(nl, op, lcpc::SCAN_EXCLUSIVE, totals_in, n_totals, n_vecs, totals, totals_words, totals_off, 1, init, total, total_words, total_off,
                    one, work, work_words, work_off, nullptr);
 }
 
-// What launch_scan answers to a job it must settle before any launch -- so this refuses (K17H_BAD_ARGS) every job a correct launcher
+// What launch_scan answers to a job it must settle before any launch -- so this refuses (H_BAD_ARGS) every job a correct launcher
 // would launch.  null_mask / misalign: bit 0 in, 1 out, 2 work, 3 init, 4 total, 5 one (NULL only).  overlap: 1 out starts one element
 // behind in; 2 init is the output's first element; 3 total lies in the input; 4 work starts at the output's last element; 5 init is total.
 // short_work: work_elems is one less than needed.  The pointers point at words nothing reads.  Returns the launcher's hipError_t
-K17H_EXPORT int k17h_scan_refusal(int nl, int op, int mode, uint64_t n, uint32_t n_vecs, uint32_t null_mask, uint32_t misalign, int overlap,
-                                  int short_work) {
+H_EXPORT int k17h_scan_refusal(int nl, int op, int mode, uint64_t n, uint32_t n_vecs, uint32_t null_mask, uint32_t misalign, int overlap,
+                               int short_work) {
   bool settled = !nl_ok(nl) || op < 0 || op > 1 || mode < 0 || mode > 1 || n == 0 || n >= ((uint64_t)1 << 39) || n_vecs == 0 || n_vecs > 65535;
   if (!settled) settled = n * n_vecs >= ((uint64_t)1 << 39) || lcpc::scan_tiles(nl, n) >= lcpc::SCAN_MAX_TILES || (null_mask & 39u) || (misalign & ~null_mask & 31u) || short_work || (overlap >= 2 && overlap <= 5) ||
                           (overlap == 1 && n * n_vecs > 1);
-  if (!settled || overlap < 0 || overlap > 5) return K17H_BAD_ARGS;
+  if (!settled || overlap < 0 || overlap > 5) return H_BAD_ARGS;
   // the buffers lie far apart in an address range that is never touched: 2^50 bytes per buffer
   auto arg = [&](unsigned bit) -> uint32_t* {
     if ((null_mask >> bit) & 1u) return nullptr;

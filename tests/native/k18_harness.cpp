@@ -4,56 +4,26 @@
 // (tests/k18_harness.py, tests/test_gpu_k18_kernels.py).
 //
 // k18h_run takes HOST pointers and the sizes of the buffers behind them, checks that every element the launcher may touch stays
-// inside them (a refused call returns K18H_BAD_ARGS and launches nothing), allocates device buffers, copies in, launches on the null
+// inside them (a refused call returns H_BAD_ARGS and launches nothing), allocates device buffers, copies in, launches on the null
 // stream with the caller's max_groups, synchronises and copies the WHOLE output, evals and work buffers back, the words around them
 // included, and the input as the kernels left it.  k18h_refusal hands a launcher a job it must settle BEFORE any launch, with
 // never-read buffers: it touches no device.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "harness.h"
 #include "../../lcpc_amd/csrc/kernels.h"
-
-#define K18H_EXPORT extern "C" __attribute__((visibility("default")))
-#define K18H_BAD_ARGS (-1)
 
 namespace {
 
-struct DevBuf {
-  uint32_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t put(const void* src, size_t bytes) {
-    hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t get(void* dst, size_t bytes) const { return bytes ? hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-};
-
-#define K18H_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-constexpr uint64_t MAX_WORDS = (uint64_t)1 << 28;   // what a test may ask for here (the launchers take more)
-bool off_ok(uint64_t off_words, int nl) { return (off_words * 4) % (nl % 4 == 0 ? 16 : 8) == 0; }
-// `words` words from off on lie inside a buffer of buf_words
-bool span_ok(uint64_t words, uint64_t buf_words, uint64_t off, int nl) {
-  return words <= MAX_WORDS && buf_words <= MAX_WORDS && off <= buf_words && words <= buf_words - off && off_ok(off, nl);
-}
 enum { MODE_BIND = 0, MODE_ROUND = 1, MODE_FUSED = 2 };
 
 }  // namespace
 
-K18H_EXPORT int k18h_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-K18H_EXPORT int k18h_cu_count() {
-  hipDeviceProp_t prop;
-  return hipGetDeviceProperties(&prop, 0) == hipSuccess ? prop.multiProcessorCount : 0;
-}
+H_DEVICE_COUNT(k18h_)
+H_CU_COUNT(k18h_)
 
 // the pairs a workgroup takes per stride (P), the product's max_groups, and the elements of the workspace of a round over `pairs` pairs
-K18H_EXPORT uint32_t k18h_tile_pairs(int nl) { return lcpc::nl_ok(nl) ? lcpc::sumcheck_tile_pairs(nl) : 0; }
-K18H_EXPORT uint32_t k18h_default_groups() { return lcpc::SUMCHECK_GROUPS; }
-K18H_EXPORT uint64_t k18h_work_elems(uint64_t pairs, uint32_t n_terms, uint32_t max_groups) {
+H_EXPORT uint32_t k18h_tile_pairs(int nl) { return lcpc::nl_ok(nl) ? lcpc::sumcheck_tile_pairs(nl) : 0; }
+H_EXPORT uint32_t k18h_default_groups() { return lcpc::SUMCHECK_GROUPS; }
+H_EXPORT uint64_t k18h_work_elems(uint64_t pairs, uint32_t n_terms, uint32_t max_groups) {
   return pairs && n_terms && n_terms <= lcpc::SUMCHECK_MAX_TERMS && max_groups ? lcpc::sumcheck_work_elems(pairs, n_terms, max_groups) : 0;
 }
 
@@ -64,37 +34,37 @@ K18H_EXPORT uint64_t k18h_work_elems(uint64_t pairs, uint32_t n_terms, uint32_t 
 // evals_words words of which the d + 1 elements from evals_off on receive the result; work: work_words words of which the
 // sumcheck_work_elems elements from work_off on are the workspace.  Everything else in out, evals and work must come back as it went
 // in.  *n_launches (may be NULL): the kernels launched
-K18H_EXPORT int k18h_run(int mode, int nl, int order, uint32_t* in, uint64_t n, uint32_t n_tables, uint32_t* out, uint64_t slot_words,
-                         uint64_t out_off, int in_place, const uint32_t* terms, uint32_t n_terms, const uint32_t* coeffs, const uint32_t* one,
-                         const uint32_t* r, uint32_t* evals, uint64_t evals_words, uint64_t evals_off, uint32_t* work, uint64_t work_words,
-                         uint64_t work_off, uint32_t max_groups, uint32_t* n_launches) {
+H_EXPORT int k18h_run(int mode, int nl, int order, uint32_t* in, uint64_t n, uint32_t n_tables, uint32_t* out, uint64_t slot_words,
+                      uint64_t out_off, int in_place, const uint32_t* terms, uint32_t n_terms, const uint32_t* coeffs, const uint32_t* one,
+                      const uint32_t* r, uint32_t* evals, uint64_t evals_words, uint64_t evals_off, uint32_t* work, uint64_t work_words,
+                      uint64_t work_off, uint32_t max_groups, uint32_t* n_launches) {
   const bool bind = mode != MODE_ROUND, round = mode != MODE_BIND;
-  if (mode < MODE_BIND || mode > MODE_FUSED || !lcpc::nl_ok(nl) || !in || n_tables == 0 || n_tables > lcpc::SUMCHECK_MAX_TABLES) return K18H_BAD_ARGS;
-  if (n < (mode == MODE_FUSED ? 4u : 2u) || (n & (n - 1)) || n > MAX_WORDS / nl / n_tables) return K18H_BAD_ARGS;
-  if (in_place && (!bind || order != lcpc::SUMCHECK_HIGH_FIRST)) return K18H_BAD_ARGS;
+  if (mode < MODE_BIND || mode > MODE_FUSED || !lcpc::nl_ok(nl) || !in || n_tables == 0 || n_tables > lcpc::SUMCHECK_MAX_TABLES) return H_BAD_ARGS;
+  if (n < (mode == MODE_FUSED ? 4u : 2u) || (n & (n - 1)) || n > MAX_WORDS / nl / n_tables) return H_BAD_ARGS;
+  if (in_place && (!bind || order != lcpc::SUMCHECK_HIGH_FIRST)) return H_BAD_ARGS;
   const uint64_t words = n * nl;
   const lcpc::SumcheckTerm* tm = reinterpret_cast<const lcpc::SumcheckTerm*>(terms);
   uint64_t need = 0;
   if (bind && (!out || !r || slot_words > MAX_WORDS / n_tables || !span_ok(in_place ? words : words / 2, slot_words, out_off, nl) || !off_ok(slot_words, nl)))
-    return K18H_BAD_ARGS;
+    return H_BAD_ARGS;
   if (round) {
-    if (!evals || !work || !one || max_groups == 0 || lcpc::sumcheck_degree(n_tables, tm, n_terms) == 0) return K18H_BAD_ARGS;
+    if (!evals || !work || !one || max_groups == 0 || lcpc::sumcheck_degree(n_tables, tm, n_terms) == 0) return H_BAD_ARGS;
     need = lcpc::sumcheck_work_elems(mode == MODE_FUSED ? n / 4 : n / 2, n_terms, max_groups);
-    if (!span_ok((lcpc::SUMCHECK_MAX_FACTORS + 1) * nl, evals_words, evals_off, nl) || !span_ok(need * nl, work_words, work_off, nl)) return K18H_BAD_ARGS;
+    if (!span_ok((lcpc::SUMCHECK_MAX_FACTORS + 1) * nl, evals_words, evals_off, nl) || !span_ok(need * nl, work_words, work_off, nl)) return H_BAD_ARGS;
   }
   DevBuf d_in, d_out, d_evals, d_work;
   const uint32_t* ins[lcpc::SUMCHECK_MAX_TABLES];
   uint32_t* outs[lcpc::SUMCHECK_MAX_TABLES];
-  if (bind) K18H_TRY(d_out.put(out, n_tables * slot_words * 4));
+  if (bind) H_TRY(d_out.put(out, n_tables * slot_words * 4));
   if (round) {
-    K18H_TRY(d_evals.put(evals, evals_words * 4));
-    K18H_TRY(d_work.put(work, work_words * 4));
+    H_TRY(d_evals.put(evals, evals_words * 4));
+    H_TRY(d_work.put(work, work_words * 4));
   }
-  if (!in_place) K18H_TRY(d_in.put(in, n_tables * words * 4));
+  if (!in_place) H_TRY(d_in.put(in, n_tables * words * 4));
   for (uint32_t j = 0; j < n_tables; j++) {
     outs[j] = bind ? d_out.p + j * slot_words + out_off : nullptr;
     if (in_place) {
-      K18H_TRY(hipMemcpy(outs[j], in + j * words, words * 4, hipMemcpyHostToDevice));
+      H_TRY(hipMemcpy(outs[j], in + j * words, words * 4, hipMemcpyHostToDevice));
       ins[j] = outs[j];
     } else {
       ins[j] = d_in.p + j * words;
@@ -102,33 +72,33 @@ K18H_EXPORT int k18h_run(int mode, int nl, int order, uint32_t* in, uint64_t n, 
   }
   if (n_launches) *n_launches = 0;
   if (mode == MODE_BIND) {
-    K18H_TRY(lcpc::launch_sumcheck_bind(nl, order, ins, outs, n_tables, n, r, nullptr));
+    H_TRY(lcpc::launch_sumcheck_bind(nl, order, ins, outs, n_tables, n, r, nullptr));
     if (n_launches) *n_launches = 1;
   } else if (mode == MODE_ROUND) {
-    K18H_TRY(lcpc::launch_sumcheck_round(nl, order, ins, n_tables, tm, n_terms, coeffs, one, n, d_evals.p + evals_off, d_work.p + work_off, need, max_groups,
+    H_TRY(lcpc::launch_sumcheck_round(nl, order, ins, n_tables, tm, n_terms, coeffs, one, n, d_evals.p + evals_off, d_work.p + work_off, need, max_groups,
                                          nullptr, n_launches));
   } else {
-    K18H_TRY(lcpc::launch_sumcheck_bind_round(nl, order, ins, outs, n_tables, tm, n_terms, coeffs, one, n, r, d_evals.p + evals_off, d_work.p + work_off, need,
+    H_TRY(lcpc::launch_sumcheck_bind_round(nl, order, ins, outs, n_tables, tm, n_terms, coeffs, one, n, r, d_evals.p + evals_off, d_work.p + work_off, need,
                                               max_groups, nullptr, n_launches));
   }
-  K18H_TRY(hipDeviceSynchronize());
-  if (!in_place) K18H_TRY(d_in.get(in, n_tables * words * 4));
+  H_TRY(hipDeviceSynchronize());
+  if (!in_place) H_TRY(d_in.get(in, n_tables * words * 4));
   if (round) {
-    K18H_TRY(d_evals.get(evals, evals_words * 4));
-    K18H_TRY(d_work.get(work, work_words * 4));
+    H_TRY(d_evals.get(evals, evals_words * 4));
+    H_TRY(d_work.get(work, work_words * 4));
   }
   return bind ? (int)d_out.get(out, n_tables * slot_words * 4) : 0;
 }
 
-// What a launcher answers to a job it must settle before any launch -- so this refuses (K18H_BAD_ARGS) every job a correct launcher
+// What a launcher answers to a job it must settle before any launch -- so this refuses (H_BAD_ARGS) every job a correct launcher
 // would launch.  null_mask / misalign: bit 0 the array `in`, 1 in[0], 2 the array `out`, 3 out[0], 4 evals, 5 work, 6 one, 7 r, 8 terms
 // (misalign: bits 1, 3, 4, 5).  overlap: 1 out[0] is in[0] (in place); 2 out[0] starts one element behind in[0]; 3 out[1] is out[0];
 // 4 evals lies in in[0]; 5 work starts at out[0]; 6 evals is work; 7 out[0] is in[1]; 8 in[1] is in[0] and out[0] too; 9 out[0] is the upper half
 // of in[0]; 10 evals lies in out[0].  short_work: work_elems is one less than needed.  The pointers point at words nothing reads.  Returns the
 // launcher's hipError_t
-K18H_EXPORT int k18h_refusal(int mode, int nl, int order, uint64_t n, uint32_t n_tables, const uint32_t* terms, uint32_t n_terms, uint32_t null_mask,
-                             uint32_t misalign, int overlap, int short_work, uint32_t max_groups) {
-  if (mode < MODE_BIND || mode > MODE_FUSED || overlap < 0 || overlap > 10) return K18H_BAD_ARGS;
+H_EXPORT int k18h_refusal(int mode, int nl, int order, uint64_t n, uint32_t n_tables, const uint32_t* terms, uint32_t n_terms, uint32_t null_mask,
+                          uint32_t misalign, int overlap, int short_work, uint32_t max_groups) {
+  if (mode < MODE_BIND || mode > MODE_FUSED || overlap < 0 || overlap > 10) return H_BAD_ARGS;
   const bool bind = mode != MODE_ROUND, round = mode != MODE_BIND;
   // the buffers lie far apart in an address range that is never touched: 2^44 bytes per buffer
   auto far = [&](unsigned slot, unsigned bit) -> uint32_t* {
@@ -165,7 +135,7 @@ K18H_EXPORT int k18h_refusal(int mode, int nl, int order, uint64_t n, uint32_t n
                                need, max_groups};
   // the job is one the launcher settles on the host: by its own test of the shape, or by a missing one / r
   const bool settled = !lcpc::sumcheck_job_ok(j) || (round && !onep) || (bind && !rp);
-  if (!settled) return K18H_BAD_ARGS;
+  if (!settled) return H_BAD_ARGS;
   if (mode == MODE_BIND) return (int)lcpc::launch_sumcheck_bind(nl, order, j.in, j.out, n_tables, n, rp, nullptr);
   if (mode == MODE_ROUND) return (int)lcpc::launch_sumcheck_round(nl, order, j.in, n_tables, tm, n_terms, nullptr, onep, n, evals, work, need, max_groups, nullptr, nullptr);
   return (int)lcpc::launch_sumcheck_bind_round(nl, order, j.in, j.out, n_tables, tm, n_terms, nullptr, onep, n, rp, evals, work, need, max_groups, nullptr, nullptr);

@@ -18,27 +18,19 @@
 //   pure first pass  the same at LBT = 0 and one class; its one uniform round: table (jl0 * 3 + v)
 //   coset last pass  rounds 2 .. 4: (w, w^2, w^3) x 4^r sub-blocks; rounds 0, 1: table ((r * 4 + m) * 3 + v), m < 4^r
 // A split pack (NttPackInfo.mul2) has twice the variants: b0 of variant v at v, b1 at NV + v; all of them are dumped.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <vector>
 
+#include "harness.h"
 #include "../../lcpc_amd/csrc/internal.h"
 #include "../../lcpc_amd/csrc/ntt_ln_dev.h"
 
-#define K1H_EXPORT extern "C" __attribute__((visibility("default")))
+// the entry points also return lcpc status codes: a hipError_t comes back as 1000 + e, a refused call as -1000
 #define K1H_BAD_ARGS (-1000)
-#define K1H_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
+#define K1H_TRY(expr) H_TRY_OFF(expr, 1000)
 
 namespace {
 
 using namespace lcpc;
-
-struct DevBuf {
-  uint32_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc((void**)&p, bytes ? bytes : 16); }
-};
 
 // one lane-varying slot of a class block
 struct Slot { uint32_t slot, off, nv, period; };       // round_off index, word offset in the class, variants stored (NV or 2 NV), positions
@@ -189,13 +181,10 @@ const lcpc_ctx* ctx_of(const void* h) {
 
 }  // namespace
 
-K1H_EXPORT int k1h_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
+H_DEVICE_COUNT(k1h_)
 
 // a Ligero context of `fid` with new_from_dims(n_per_row, n_cols) at rate rho_num / rho_den: the status of lcpc_ctx_create
-K1H_EXPORT int k1h_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint32_t rho_num, uint32_t rho_den, void** out) {
+H_EXPORT int k1h_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint32_t rho_num, uint32_t rho_den, void** out) {
   if (!out) return K1H_BAD_ARGS;
   *out = nullptr;
   if (fid > 3 || !n_per_row || n_per_row >= n_cols || (n_cols & (n_cols - 1)) || n_cols > ((uint64_t)1 << 22)) return K1H_BAD_ARGS;
@@ -208,12 +197,12 @@ K1H_EXPORT int k1h_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint3
   if (rc == 0) *out = c;
   return rc;
 }
-K1H_EXPORT void k1h_close(void* h) {
+H_EXPORT void k1h_close(void* h) {
   if (h) lcpc_ctx_destroy(static_cast<lcpc_ctx*>(h));
 }
 
 // out[8]: NL, N, W, STRIDE, log_n, passes of the plan, comm_canon, U_SLOT words
-K1H_EXPORT int k1h_info(const void* h, uint32_t* out, uint32_t out_words) {
+H_EXPORT int k1h_info(const void* h, uint32_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < 8) return K1H_BAD_ARGS;
   const int N = ntt_lns_limbs(c->NL);
@@ -222,7 +211,7 @@ K1H_EXPORT int k1h_info(const void* h, uint32_t* out, uint32_t out_words) {
   return 0;
 }
 // out[7]: entries of d_roots, d_rootsl, d_rootslc, d_rootsls, d_rootslcs, d_qpl, d_wq_w (0: the context has no such table)
-K1H_EXPORT int k1h_tables(const void* h, uint64_t* out, uint32_t out_words) {
+H_EXPORT int k1h_tables(const void* h, uint64_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < T_COUNT) return K1H_BAD_ARGS;
   for (int t = 0; t < T_COUNT; t++) {
@@ -233,7 +222,7 @@ K1H_EXPORT int k1h_tables(const void* h, uint64_t* out, uint32_t out_words) {
 }
 // one pass of the plan, out[24]: kind (0 general, 1 K1s, 2 K1n), first, log_n, t0, s, log_tj, form, round_off[8], class_words, u_off,
 // mul2, tile classes (0: no pack), log_tile, lane-varying records per class, shifted-multiples tables per class, 0, 0
-K1H_EXPORT int k1h_plan(const void* h, uint32_t pass, uint32_t* out, uint32_t out_words) {
+H_EXPORT int k1h_plan(const void* h, uint32_t pass, uint32_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < 24 || pass >= c->ntt.size()) return K1H_BAD_ARGS;
   const NttStep& p = c->ntt[pass];
@@ -252,7 +241,7 @@ K1H_EXPORT int k1h_plan(const void* h, uint32_t pass, uint32_t* out, uint32_t ou
 }
 // entries [first, first + count) of table `which` (0 d_roots, 1 d_rootsl, 2 d_rootslc, 3 d_rootsls, 4 d_rootslcs, 5 d_qpl, 6 d_wq_w) at
 // their full stride, pad words included, into out
-K1H_EXPORT int k1h_table(const void* h, int which, uint64_t first, uint64_t count, uint32_t* out, uint64_t out_words) {
+H_EXPORT int k1h_table(const void* h, int which, uint64_t first, uint64_t count, uint32_t* out, uint64_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || which < 0 || which >= T_COUNT) return K1H_BAD_ARGS;
   uint64_t entries;
@@ -265,7 +254,7 @@ K1H_EXPORT int k1h_table(const void* h, int which, uint64_t first, uint64_t coun
 }
 // every lane-varying entry of pass `pass` for the classes listed: records (class, slot, variant, jl, N limbs), 4 + N words each, class
 // by class in the order of the list, inside a class by slot, variant, jl.  out_words must hold n_cls x records-per-class of them
-K1H_EXPORT int k1h_pack_entries(const void* h, uint32_t pass, const uint32_t* classes, uint32_t n_cls, uint32_t* out, uint64_t out_words) {
+H_EXPORT int k1h_pack_entries(const void* h, uint32_t pass, const uint32_t* classes, uint32_t n_cls, uint32_t* out, uint64_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !classes || !out || !n_cls || pass >= c->ntt.size()) return K1H_BAD_ARGS;
   const NttStep& p = c->ntt[pass];
@@ -303,7 +292,7 @@ K1H_EXPORT int k1h_pack_entries(const void* h, uint32_t pass, const uint32_t* cl
 // every shifted-multiples table of pass `pass` for the classes listed: records (class, round, position, v, U_SLOT raw words), 4 +
 // U_SLOT words each.  round: the uniform round's number among the pass's uniform rounds (DIF / K1n), 0 (pure) or the round r (coset);
 // position: jl0 < 4, or the coset sub-block m
-K1H_EXPORT int k1h_uniform(const void* h, uint32_t pass, const uint32_t* classes, uint32_t n_cls, uint32_t* out, uint64_t out_words) {
+H_EXPORT int k1h_uniform(const void* h, uint32_t pass, const uint32_t* classes, uint32_t n_cls, uint32_t* out, uint64_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !classes || !out || !n_cls || pass >= c->ntt.size()) return K1H_BAD_ARGS;
   const NttStep& p = c->ntt[pass];
@@ -330,4 +319,4 @@ K1H_EXPORT int k1h_uniform(const void* h, uint32_t pass, const uint32_t* classes
   }
   return 0;
 }
-K1H_EXPORT const char* k1h_last_error(const void* h) { return h ? lcpc_last_error(static_cast<const lcpc_ctx*>(h)) : ""; }
+H_EXPORT const char* k1h_last_error(const void* h) { return h ? lcpc_last_error(static_cast<const lcpc_ctx*>(h)) : ""; }

@@ -16,18 +16,17 @@
 // returned whole, gaps between rows included.  Host buffers come with their sizes; a request that is out of range or inconsistent is
 // refused (K1P_BAD_ARGS) before the device is touched, and the sizes the caller states must be exactly the ones computed here.  The
 // source is uploaded into an allocation of exactly the words the pass may read.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
 
+#include "harness.h"
 #include "../../lcpc_amd/csrc/internal.h"
 
-#define K1P_EXPORT extern "C" __attribute__((visibility("default")))
+// the entry points also return lcpc status codes: a hipError_t comes back as 1000 + e, a refused call as -1000
 #define K1P_BAD_ARGS (-1000)
-#define K1P_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
+#define K1P_TRY(expr) H_TRY_OFF(expr, 1000)
 
 namespace {
 
@@ -40,10 +39,11 @@ constexpr uint64_t MAX_ROWS = 8192, MAX_ELEMS = (uint64_t)1 << 25;
 enum : uint64_t { F_COPY = 1, F_CANON = 2, F_MID = 4, F_INPLACE = 8, F_MONTWORD = 16 };
 constexpr uint64_t UNLIMITED = ~(uint64_t)0;
 
-struct DevBuf {
+// not harness.h's DevBuf: [canary | body | canary] in one allocation, fetched whole
+struct CanaryBuf {
   uint32_t* p = nullptr;
-  uint64_t body = 0;                                     // words between the canaries
-  ~DevBuf() { if (p) (void)hipFree(p); }
+  uint64_t body = 0;                                    // words between the canaries
+  ~CanaryBuf() { if (p) (void)hipFree(p); }
   hipError_t alloc_plain(uint64_t words) { return hipMalloc((void**)&p, words ? words * 4 : 16); }
   hipError_t alloc_canary(uint64_t words) {
     body = words;
@@ -142,14 +142,11 @@ bool general_tile_ok(int nl, uint64_t log_tile) {
 
 }  // namespace
 
-K1P_EXPORT int k1p_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-K1P_EXPORT uint64_t k1p_canary_words() { return CANARY_WORDS; }
+H_DEVICE_COUNT(k1p_)
+H_EXPORT uint64_t k1p_canary_words() { return CANARY_WORDS; }
 
 // a Ligero context of `fid` with new_from_dims(n_per_row, n_cols) at rate rho_num / rho_den: the status of lcpc_ctx_create
-K1P_EXPORT int k1p_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint32_t rho_num, uint32_t rho_den, void** out) {
+H_EXPORT int k1p_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint32_t rho_num, uint32_t rho_den, void** out) {
   if (!out) return K1P_BAD_ARGS;
   *out = nullptr;
   if (fid > 3 || !n_per_row || n_per_row >= n_cols || (n_cols & (n_cols - 1)) || n_cols > ((uint64_t)1 << 22)) return K1P_BAD_ARGS;
@@ -162,13 +159,13 @@ K1P_EXPORT int k1p_open(uint32_t fid, uint64_t n_per_row, uint64_t n_cols, uint3
   if (rc == 0) *out = c;
   return rc;
 }
-K1P_EXPORT void k1p_close(void* h) {
+H_EXPORT void k1p_close(void* h) {
   if (h) lcpc_ctx_destroy(static_cast<lcpc_ctx*>(h));
 }
-K1P_EXPORT const char* k1p_last_error(const void* h) { return h ? lcpc_last_error(static_cast<const lcpc_ctx*>(h)) : ""; }
+H_EXPORT const char* k1p_last_error(const void* h) { return h ? lcpc_last_error(static_cast<const lcpc_ctx*>(h)) : ""; }
 
 // out[8]: NL, N, W, STRIDE, log_n, steps of the plan, comm_canon, the lazy-limb tables exist (d_rootsl and d_qpl)
-K1P_EXPORT int k1p_info(const void* h, uint32_t* out, uint32_t out_words) {
+H_EXPORT int k1p_info(const void* h, uint32_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < 8) return K1P_BAD_ARGS;
   out[0] = (uint32_t)c->NL; out[1] = (uint32_t)ntt_lns_limbs(c->NL); out[2] = (uint32_t)ntt_lns_limb_bits(c->NL);
@@ -179,7 +176,7 @@ K1P_EXPORT int k1p_info(const void* h, uint32_t* out, uint32_t out_words) {
 // one step of the plan c->ntt, out[16]: kind (0 general, 1 K1s, 2 K1n), first, log_n, t0, s, log_tj, log_tile, form, pack_info.mul2,
 // mont_prefix, blk0_gone, canon_row_mask, tile_group, pack classes (0: no pack), the step has a converting table (canonical output can
 // be asked for), 0
-K1P_EXPORT int k1p_plan(const void* h, uint32_t step, uint32_t* out, uint32_t out_words) {
+H_EXPORT int k1p_plan(const void* h, uint32_t step, uint32_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < 16 || step >= c->ntt.size()) return K1P_BAD_ARGS;
   const NttStep& p = c->ntt[step];
@@ -201,8 +198,8 @@ K1P_EXPORT int k1p_plan(const void* h, uint32_t step, uint32_t* out, uint32_t ou
 // src_stride + len elements, or -- the K1s last pass with the limb intermediate -- n_sub x len records of 9 words in the tile layout of
 // ntt_l9s.hip.  dst / mid / copy: canary + body + canary words, body = n_sub dst_stride NL / n_sub len 9 / n_rows src_stride NL (a buffer
 // that was not asked for: null, 0 words).  All sizes must be exact.
-K1P_EXPORT int k1p_run_step(const void* h, uint32_t step, const uint64_t* req, uint32_t req_words, const uint32_t* src, uint64_t src_words,
-                            uint32_t* dst, uint64_t dst_words, uint32_t* mid, uint64_t mid_words, uint32_t* copy, uint64_t copy_words) {
+H_EXPORT int k1p_run_step(const void* h, uint32_t step, const uint64_t* req, uint32_t req_words, const uint32_t* src, uint64_t src_words,
+                          uint32_t* dst, uint64_t dst_words, uint32_t* mid, uint64_t mid_words, uint32_t* copy, uint64_t copy_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !req || req_words != 6 || !src || !dst) return K1P_BAD_ARGS;
   const Req r = req_of(req);
@@ -214,7 +211,7 @@ K1P_EXPORT int k1p_run_step(const void* h, uint32_t step, const uint64_t* req, u
   if (r.has(F_COPY) ? (!copy || copy_words != z.copy_words + C2) : (copy || copy_words)) return K1P_BAD_ARGS;
   const NttStep& p = c->ntt[step];
   K1P_TRY(hipSetDevice(c->prm.device));
-  DevBuf d_src, d_dst, d_mid, d_copy;
+  CanaryBuf d_src, d_dst, d_mid, d_copy;
   K1P_TRY(d_dst.alloc_canary(z.dst_words));
   if (r.has(F_MID)) K1P_TRY(d_mid.alloc_canary(z.mid_words));
   if (r.has(F_COPY)) K1P_TRY(d_copy.alloc_canary(z.copy_words));
@@ -244,8 +241,8 @@ K1P_EXPORT int k1p_run_step(const void* h, uint32_t step, const uint64_t* req, u
 // Every pass of the general kernel applies n_valid / n_src_total / copy_dst, so they are free here whatever t0 is; in place needs whole
 // rows (n_valid = the row length, n_src_total unlimited, equal strides) and no copy_dst.  mont_prefix is plan_passes' (canonical output,
 // t0 + s = log_n).  src: the first min(n_src_total, (n_rows - 1) src_stride + n_valid) elements.
-K1P_EXPORT int k1p_run_general(const void* h, const uint64_t* req, uint32_t req_words, const uint32_t* src, uint64_t src_words, uint32_t* dst,
-                               uint64_t dst_words, uint32_t* copy, uint64_t copy_words) {
+H_EXPORT int k1p_run_general(const void* h, const uint64_t* req, uint32_t req_words, const uint32_t* src, uint64_t src_words, uint32_t* dst,
+                             uint64_t dst_words, uint32_t* copy, uint64_t copy_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !req || req_words != 10 || !src || !dst) return K1P_BAD_ARGS;
   const Req r = req_of(req);
@@ -266,7 +263,7 @@ K1P_EXPORT int k1p_run_general(const void* h, const uint64_t* req, uint32_t req_
   if (src_words != want_src || dst_words != want_dst + C2) return K1P_BAD_ARGS;
   if (r.has(F_COPY) ? (!copy || copy_words != want_copy + C2) : (copy || copy_words)) return K1P_BAD_ARGS;
   K1P_TRY(hipSetDevice(c->prm.device));
-  DevBuf d_src, d_dst, d_copy;
+  CanaryBuf d_src, d_dst, d_copy;
   K1P_TRY(d_dst.alloc_canary(want_dst));
   if (r.has(F_COPY)) K1P_TRY(d_copy.alloc_canary(want_copy));
   const uint32_t* a_src;
@@ -304,7 +301,7 @@ K1P_EXPORT int k1p_run_general(const void* h, const uint64_t* req, uint32_t req_
 //   4  K1s first pass of the pure form with S = 2, 7 or 9 and pack_info.mul2 (ntt_l9s_mul2_supported names no such pass)
 //   5  K1n last pass with a tile_group
 // BAD_ARGS if the context has no such pass.
-K1P_EXPORT int k1p_refused(const void* h, uint32_t which, uint32_t* out, uint32_t out_words) {
+H_EXPORT int k1p_refused(const void* h, uint32_t which, uint32_t* out, uint32_t out_words) {
   const lcpc_ctx* c = ctx_of(h);
   if (!c || !out || out_words < 2 || which > 5 || c->ntt.empty()) return K1P_BAD_ARGS;
   const uint32_t last = (uint32_t)c->ntt.size() - 1;
@@ -325,7 +322,7 @@ K1P_EXPORT int k1p_refused(const void* h, uint32_t which, uint32_t* out, uint32_
   Sizes z;
   if (!step_sizes(c, step, r, z)) return K1P_BAD_ARGS;
   K1P_TRY(hipSetDevice(c->prm.device));
-  DevBuf d_src, d_dst, d_copy;
+  CanaryBuf d_src, d_dst, d_copy;
   K1P_TRY(d_dst.alloc_canary(z.dst_words));
   K1P_TRY(d_copy.alloc_canary(z.copy_words));
   K1P_TRY(d_src.alloc_plain(z.src_words));
@@ -348,7 +345,7 @@ K1P_EXPORT int k1p_refused(const void* h, uint32_t which, uint32_t* out, uint32_
   }
   K1P_TRY(hipDeviceSynchronize());
   bool intact = true;
-  for (const DevBuf* b : {&d_dst, &d_copy}) {
+  for (const CanaryBuf* b : {&d_dst, &d_copy}) {
     const uint64_t words = b->body + 2 * CANARY_WORDS;
     std::unique_ptr<uint32_t[]> host(new uint32_t[words]);
     K1P_TRY(b->fetch(host.get()));

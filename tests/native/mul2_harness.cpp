@@ -4,15 +4,9 @@
 // lcpc_amd/lib/liblcpc_mul2_harness.so; it includes the product's header and links nothing of the product.
 //
 // Every wrapper takes HOST pointers to n elements of 9 words, copies in, launches on the null stream (blocks of 256 lanes, lanes >= n
-// idle), synchronises and copies out_n >= n elements back.  Returns the first hipError_t, or M2H_BAD_ARGS for a count out of range.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// idle), synchronises and copies out_n >= n elements back.  Returns the first hipError_t, or H_BAD_ARGS for a count out of range.
+#include "harness.h"
 #include "../../lcpc_amd/csrc/field_ln.h"
-
-#define M2H_EXPORT extern "C" __attribute__((visibility("default")))
-#define M2H_BAD_ARGS (-1)
-#define M2H_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 using namespace lcpc;
 
@@ -20,17 +14,6 @@ namespace {
 
 using FT = LnField<FT255>;
 constexpr u32 MAX_N = 1u << 20;
-
-struct DevBuf {
-  u32* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t put(const void* src, size_t bytes) {
-    hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t get(void* dst, size_t bytes) const { return bytes ? hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-};
 
 __device__ __forceinline__ LN<9> limbs_get(const u32* p, size_t i) {
   LN<9> r;
@@ -60,33 +43,30 @@ dim3 grid(u32 n) { return dim3((n + 255) / 256 ? (n + 255) / 256 : 1); }
 
 }  // namespace
 
-M2H_EXPORT int m2h_device_count() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
+H_DEVICE_COUNT(m2h_)
 // out[i] = ln::mul2(x[i], b0[i], b1[i]); out holds out_n elements, those past n - 1 come back as they went in
-M2H_EXPORT int m2h_mul2(const u32* x, const u32* b0, const u32* b1, u32* out, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return M2H_BAD_ARGS;
+H_EXPORT int m2h_mul2(const u32* x, const u32* b0, const u32* b1, u32* out, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_x, d_0, d_1, d_o;
-  M2H_TRY(d_x.put(x, (size_t)n * 36));
-  M2H_TRY(d_0.put(b0, (size_t)n * 36));
-  M2H_TRY(d_1.put(b1, (size_t)n * 36));
-  M2H_TRY(d_o.put(out, (size_t)out_n * 36));
+  H_TRY(d_x.put(x, (size_t)n * 36));
+  H_TRY(d_0.put(b0, (size_t)n * 36));
+  H_TRY(d_1.put(b1, (size_t)n * 36));
+  H_TRY(d_o.put(out, (size_t)out_n * 36));
   hipLaunchKernelGGL(k_mul2, grid(n), dim3(256), 0, nullptr, d_x.p, d_0.p, d_1.p, d_o.p, n);
-  M2H_TRY(hipGetLastError());
-  M2H_TRY(hipDeviceSynchronize());
+  H_TRY(hipGetLastError());
+  H_TRY(hipDeviceSynchronize());
   return (int)d_o.get(out, (size_t)out_n * 36);
 }
 // (o0[i], o1[i]) = ln::mul2_pair(e[i])
-M2H_EXPORT int m2h_pair(const u32* e, u32* o0, u32* o1, u32 n, u32 out_n) {
-  if (!counts_ok(n, out_n)) return M2H_BAD_ARGS;
+H_EXPORT int m2h_pair(const u32* e, u32* o0, u32* o1, u32 n, u32 out_n) {
+  if (!counts_ok(n, out_n)) return H_BAD_ARGS;
   DevBuf d_e, d_0, d_1;
-  M2H_TRY(d_e.put(e, (size_t)n * 36));
-  M2H_TRY(d_0.put(o0, (size_t)out_n * 36));
-  M2H_TRY(d_1.put(o1, (size_t)out_n * 36));
+  H_TRY(d_e.put(e, (size_t)n * 36));
+  H_TRY(d_0.put(o0, (size_t)out_n * 36));
+  H_TRY(d_1.put(o1, (size_t)out_n * 36));
   hipLaunchKernelGGL(k_pair, grid(n), dim3(256), 0, nullptr, d_e.p, d_0.p, d_1.p, n);
-  M2H_TRY(hipGetLastError());
-  M2H_TRY(hipDeviceSynchronize());
-  M2H_TRY(d_0.get(o0, (size_t)out_n * 36));
+  H_TRY(hipGetLastError());
+  H_TRY(hipDeviceSynchronize());
+  H_TRY(d_0.get(o0, (size_t)out_n * 36));
   return (int)d_1.get(o1, (size_t)out_n * 36);
 }

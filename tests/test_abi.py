@@ -267,7 +267,26 @@ def test_product_library_has_no_test_hooks():
     assert syms(hooks) == syms(_lib.LIB_PATH)
 
 
-def _harness_is_a_separate_library(module, prefix, source, make_var):
+# every native test harness that links the product (tests/native/<stem>_harness.cpp, tests/<stem>_harness.py) and the prefix of its exports
+HARNESSES = {"k1": "k1h_", "k1p": "k1p_", "k2": "k2h_", "k2b": "k2bh_", "k3": "k3h_", "k5": "k5h_", "k7": "k7h_", "k8": "k8h_", "k12": "k12h_",
+             "k14": "k14h_", "k15": "k15h_", "k17": "k17h_", "k18": "k18h_", "lr": "lrh_", "fe": "feh_"}
+# the exceptions to _harness_is_a_separate_library: the assertion each does not meet, and why
+NOT_LINKED = {"mul2": "liblcpc_hip.so is not NEEDED: it instantiates ln::mul2 from field_ln.h alone and links nothing of the product, by design"}
+_make_all = []
+
+
+def make_builds(module, source):
+    """(`make all` builds lib/liblcpc_<module>.so from `source`, its stem is one of the Makefile's HARNESSES) -- asked of make itself"""
+    import subprocess
+    if not _make_all:
+        out = subprocess.check_output(["make", "-n", "-B", "-p", "-C", os.path.join(ROOT, "lcpc_amd", "csrc"), "all"], text=True)
+        _make_all.append((out.splitlines(), re.search(r"^HARNESSES = (.*)$", out, re.M).group(1).split()))
+    lines, stems = _make_all[0]
+    return any(" -o ../lib/liblcpc_%s.so ../../%s" % (module, source) in l for l in lines), module[:-len("_harness")] in stems
+
+
+def _harness_is_a_separate_library(module, prefix, source, make_var=None):
+    """(make_var named the harness's own Makefile variable while it had one; the callers in the other test modules still pass it)"""
     import importlib
     import subprocess
     import sys
@@ -284,8 +303,7 @@ def _harness_is_a_separate_library(module, prefix, source, make_var):
                      if " T lcpc_" in l)
     assert product == header_symbols() and len(product) == 58
     assert prefix.encode() not in open(_lib.LIB_PATH, "rb").read()
-    mk = open(os.path.join(ROOT, "lcpc_amd", "csrc", "Makefile")).read()
-    assert source in mk and "$(%s)" % make_var in mk.split("\nall:")[1].split("\n")[0]
+    assert make_builds(module, source) == (True, True)
 
 
 def test_k2_harness_is_a_separate_library():
@@ -299,3 +317,31 @@ def test_k3_harness_is_a_separate_library():
     """the same separation for lib/liblcpc_k3_harness.so (tests/native/k3_harness.cpp, the fourth artefact): k3h_* only, linked against
     the product, of which the product carries no trace"""
     _harness_is_a_separate_library("k3_harness", "k3h_", "tests/native/k3_harness.cpp", "K3H_OUT")
+
+
+@pytest.mark.parametrize("stem", sorted(HARNESSES))
+def test_harness_is_a_separate_library(stem):
+    """the same for every harness of the Makefile's HARNESSES, whether or not a test module of its own asks as well"""
+    _harness_is_a_separate_library(stem + "_harness", HARNESSES[stem], "tests/native/%s_harness.cpp" % stem)
+
+
+def test_every_native_harness_is_held_to_the_separation():
+    """a harness is in HARNESSES above or a stated exception; the one exception meets everything but the link: its exports are the
+    table of tests/test_gpu_ntt_mul2.py, it defines no product symbol, `make all` builds it outside the HARNESSES list"""
+    import glob
+    import subprocess
+    import sys
+    stems = sorted(os.path.basename(p)[:-len("_harness.cpp")] for p in glob.glob(os.path.join(ROOT, "tests", "native", "*_harness.cpp")))
+    assert stems == sorted(list(HARNESSES) + list(NOT_LINKED))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import harness_kit
+    import test_gpu_ntt_mul2 as M2
+    path = harness_kit.lib_path("mul2")
+    defined = [l.split() for l in subprocess.check_output(["nm", "-D", "--defined-only", path], text=True).splitlines()]
+    funcs = sorted(l[-1] for l in defined if l[-2] in "TtWw")
+    assert funcs == sorted(M2.M2H_SYMBOLS) and all(f.startswith("m2h_") for f in funcs)
+    assert not any("lcpc" in l[-1] for l in defined)
+    needed = re.findall(r"NEEDED.*\[(.*?)\]", subprocess.run(["readelf", "-d", path], capture_output=True, text=True).stdout)
+    assert not any("lcpc" in n for n in needed), NOT_LINKED["mul2"]
+    assert b"m2h_" not in open(_lib.LIB_PATH, "rb").read()
+    assert make_builds("mul2_harness", "tests/native/mul2_harness.cpp") == (True, False)

@@ -88,5 +88,5 @@ def test_k8_harness_is_a_library_of_its_own():
     _harness_is_a_separate_library("k8_harness", "k8h_", "tests/native/k8_harness.cpp", "K8H_OUT")
     import k8_harness
     assert sorted(k8_harness.SYMBOLS) == ["k8h_device_count", "k8h_fold_paths", "k8h_refusal"] and k8_harness.LIB_PATH == HARNESS
-    mk = open(os.path.join(ROOT, "lcpc_amd", "csrc", "Makefile")).read()
-    assert "$(K8H_OUT)" in mk.split("\nclean:")[1]
+    clean = subprocess.check_output(["make", "-n", "-C", os.path.join(ROOT, "lcpc_amd", "csrc"), "clean"], text=True)
+    assert "../lib/liblcpc_k8_harness.so" in clean.split()

@@ -21,6 +21,7 @@ import random
 import numpy as np
 import pytest
 
+import harness_kit as K
 from common import field_p, ntt_maxlimb, stage_input_rows
 from lcpc_amd import LcCommit, LigeroEncoding
 
@@ -153,17 +154,11 @@ W, N = 29, 9
 M = (1 << W) - 1
 
 
+M2H_SYMBOLS = {"m2h_device_count": [], "m2h_mul2": [C.c_void_p] * 4 + [C.c_uint32] * 2, "m2h_pair": [C.c_void_p] * 3 + [C.c_uint32] * 2}
+
+
 def _h():
-    path = os.path.join(ROOT, "lcpc_amd", "lib", "liblcpc_mul2_harness.so")
-    assert os.path.exists(path), "lcpc_amd/csrc/Makefile builds it beside the product"
-    try:
-        import torch  # noqa: F401  (its HIP runtime must be the one loaded first, as in lcpc_amd/_lib.py)
-    except ImportError:
-        pass
-    L = C.CDLL(path)
-    L.m2h_mul2.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 2
-    L.m2h_pair.argtypes = [C.c_void_p] * 3 + [C.c_uint32] * 2
-    return L
+    return K.load("mul2", M2H_SYMBOLS)
 
 
 def _arr(elems):

@@ -8,7 +8,7 @@ import pytest
 import fft_cases as FC
 import k18_harness as K18
 import sumcheck_cases as MC
-from k2_harness import BadArgs
+from k18_harness import BadArgs
 
 INVALID = K18.HIP_ERROR_INVALID_VALUE
 

@@ -229,7 +229,8 @@ def test_k1p_harness_is_a_library_of_its_own():
     hooks, like the product whose context it reads"""
     from test_abi import _harness_is_a_separate_library
     _harness_is_a_separate_library("k1p_harness", "k1p_", "tests/native/k1p_harness.cpp", "K1PH_OUT")
-    mk = open(os.path.join(os.path.dirname(HERE), "lcpc_amd", "csrc", "Makefile")).read()
-    assert "$(K1PH_OUT)" in mk.split("\nclean:")[1]
-    rule = mk.split("\n$(K1PH_OUT):")[1].split("\n$(")[0]
+    import subprocess
+    make = lambda target: subprocess.check_output(["make", "-n", "-B", "-C", os.path.join(os.path.dirname(HERE), "lcpc_amd", "csrc"), target], text=True)
+    assert "../lib/liblcpc_k1p_harness.so" in make("clean").split()
+    rule, = [l for l in make("all").splitlines() if " -o ../lib/liblcpc_k1p_harness.so " in l]
     assert "LCPC_TEST_HOOKS" not in rule and "-llcpc_hip" in rule
